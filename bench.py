@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: TF-bins/s of ssq_stft (n_fft=1024, hop=256, fp32) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --total-batch B] [--gather]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --total-batch B] [--gather] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 One "step" = one pass of the fused ssq_stft hot path over one batch of synthetic signals of 2^20 samples resident
@@ -18,6 +18,11 @@ relays their JSON line and exit code.
 Outside the timed region the bench checks what it timed: three signals of the batch are copied back and compared
 bitwise with the single-signal path of the same library, and signal 0 with the committed BASELINE-config-2
 checksums (tests/golden/c2_summary.npz) -> "validated".
+
+`--dump-outputs DIR` writes what the last timed step left in Tx (rank 0's signals) as .npy files, float32 with a
+trailing (real, imag) axis: whole signals 0, B/2 and B-1 as far as they fit, and a fixed seeded sample of single bins
+over the whole batch, under 64 MiB in all (see dump_plan).  The inputs are seeded, so two builds run with the same
+arguments can be compared file by file.
 
 torch is plumbing only (process group, barrier, torch.cuda.synchronize, the buffer handed to RCCL); the
 stream, the HIP events and the kernels all come from libssq_hip.so through its C-ABI.
@@ -64,7 +69,13 @@ def parse_args(argv=None):
                          "~30 ms of this kernel after any gap run 5-8 %% slower than its steady state (clock ramp)")
     ap.add_argument("--no-c5", action="store_true", help="skip the fp64 BASELINE-config-5 secondary legs (17 - 170 GB)")
     ap.add_argument("--gather", action="store_true", help="also time the optional RCCL all_gather of the Tx shards")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's Tx of the last step (whole signals + a seeded sample) "
+                         "as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------- launcher ----
@@ -353,6 +364,37 @@ def roofline_of(leg, kern_ms, traffic, kernel_name):
             "alg_bytes_per_launch": alg}
 
 
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: everything written, headers included
+DUMP_SAMPLE_BINS = 1 << 19         # single bins sampled over the whole batch (value + index: 16 bytes each)
+
+
+def dump_plan(B, n_freqs, n_frames, seed=0):
+    """What --dump-outputs takes of a [B, n_freqs, n_frames] Tx: (whole signals, sorted flat bin indices).
+    Signals 0, B/2, B-1 as many as fit beside the sample; the sample depends on the shape and the seed only."""
+    total = B * n_freqs * n_frames
+    flat = np.sort(np.random.default_rng(seed).choice(total, size=min(total, DUMP_SAMPLE_BINS), replace=False))
+    room = DUMP_LIMIT_BYTES - 16 * flat.size - 4 * 4096            # 4 KiB per .npy header, generously
+    whole = sorted({0, B // 2, B - 1})[: max(0, room // (n_freqs * n_frames * 2 * 4))]
+    return whole, flat
+
+
+def dump_outputs(out_dir, out_t, leg):
+    """Write the Tx of the last step (fp32 `out_t`, [B, n_freqs, n_frames] complex) as float32 (..., 2) arrays, and
+    the positions they were taken from as float64."""
+    import torch
+    whole, flat = dump_plan(leg.B, leg.n_freqs, leg.n_frames)
+    tx = out_t.view(leg.B, leg.n_freqs, leg.n_frames, 2)
+    arrays = {"Tx_sample": out_t.view(-1, 2)[torch.from_numpy(flat).to(out_t.device)].cpu().numpy(),
+              "Tx_sample_index": flat.astype(np.float64)}
+    if whole:
+        arrays["Tx_signals"] = tx[whole].cpu().numpy()
+        arrays["Tx_signals_index"] = np.asarray(whole, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 FP_PEAK_TFLOPS = {"f32": 157.3, "f64": 78.6}            # MI355X_MICROARCH.md: vector fp32 / fp64
 
 
@@ -526,6 +568,9 @@ def main():
         tt = torch.tensor([wall], device="cuda", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall = float(tt.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, out_t, leg)
 
     # Secondary legs (N = 1 only) run AFTER the headline's timed region (round 2 ran them before it, which lengthened the
     # undisclosed warm-up): the only load in front of the K timed steps is the disclosed run-in (settle_ms) + W steps.
@@ -665,6 +710,8 @@ def main():
             line["validation"] = validation
         if gather is not None:
             line["gather"] = gather
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if sec is not None:
             line["secondary"] = sec
     ok = validation is None or validation.get("ok_all_ranks", validation["ok"])
