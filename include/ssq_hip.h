@@ -228,6 +228,32 @@ int ssq_cwt_plan_exec_ssq(ssq_cwt_plan* plan, const void* d_x, int64_t batch,
                           void* d_Tx, void* d_dbg_Wx, void* d_dbg_dWx, void* d_dbg_wk,
                           void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- ridge extraction: ssqueezepy.extract_ridges (old/ssqueezepy/ridge_extraction.py:11-233) -------------------
+ * Tf: [batch][n_freqs][n_time], complex (interleaved) when is_complex, in `dtype` (the energy / cost / DP type, :121).
+ * param_dtype: the dtype of scales, eps and penalty (:113-116) -- SSQ_F64 only for complex128 upstream, so
+ * (SSQ_F64, SSQ_F32) is the fp64-cost / fp32-parameter case of real float64 input; (SSQ_F32, SSQ_F64) is rejected.
+ * metric: [n_freqs] in param_dtype, log(scales) for 'cwt' else scales (:118-120), from which the kernels form
+ * P[i, j] = penalty * (m_i - m_j)**2 (:89).  scales: [n_freqs] in param_dtype (ridge_f = scales[idx], :138), may be
+ * NULL when ridge_f is.  Outputs [batch][n_time][n_ridges]: ridge_idxs int64, ridge_f / ridge_e in param_dtype
+ * (either may be NULL); cost_out [batch][n_ridges][n_freqs][n_time] in dtype, the cost each ridge tracked (:133),
+ * NULL normally.  bw: the band zeroed around each ridge with Python slice rules (:141-143).  The backward trace is
+ * upstream's serial one (:206-215); the `parallel` kernel (:217-232) races on ties and is not mirrored.
+ * 1 <= n_freqs <= 32767, n_time >= 1, 1 <= batch <= 65535, n_ridges >= 1, bw >= 0.  Device pointers, async on
+ * `stream`. */
+int64_t ssq_ridges_workspace_bytes(int dtype, int64_t batch, int64_t n_freqs, int64_t n_time);
+int ssq_ridges_exec(int dtype, int param_dtype, int is_complex, const void* d_Tf, int64_t batch, int64_t n_freqs,
+                    int64_t n_time, const void* d_metric, const void* d_scales, double penalty, int64_t n_ridges,
+                    double bw, int64_t* d_ridge_idxs, void* d_ridge_f, void* d_ridge_e, void* d_cost_out,
+                    void* d_workspace, int64_t workspace_bytes, void* stream);
+/* the same on host arrays (synchronous) */
+int ssq_extract_ridges_host(int dtype, int param_dtype, int is_complex, const void* Tf, int64_t batch, int64_t n_freqs,
+                            int64_t n_time, const void* metric, const void* scales, double penalty, int64_t n_ridges,
+                            double bw, int64_t* ridge_idxs, void* ridge_f, void* ridge_e, void* cost_out);
+/* fw_bw_ridge_tracking (:92-111) alone on a caller's cost [batch][n_freqs][n_time] in dtype: ridge_idxs [batch][n_time]
+ * int64, pen_out [batch][n_freqs][n_time] the forward accumulated cost (:149-175), may be NULL.  Host arrays. */
+int ssq_ridge_track_host(int dtype, int param_dtype, const void* cost, int64_t batch, int64_t n_freqs, int64_t n_time,
+                         const void* metric, double penalty, int64_t* ridge_idxs, void* pen_out);
+
 /* ---- multi-GPU: the optional final gather of the batch-sharded results over xGMI ------------------------------
  * Signals are independent (the reference's batch is a Python loop over channels, tests/stft_ssq_test.py:230), so the
  * data path has no collective; a consumer that wants every rank to hold all shards calls ssq_gather_shards after its

@@ -92,6 +92,12 @@ _SIGNATURES = {
     "ssq_cwt_plan_exec_cwt": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, i64, vp]),
     "ssq_cwt_plan_exec_ssq": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                         vp, vp, vp, vp, vp, i64, vp]),
+    "ssq_ridges_workspace_bytes": (i64, [C.c_int, i64, i64, i64]),
+    "ssq_ridges_exec": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, i64, i64, i64, vp, vp, C.c_double, i64, C.c_double,
+                                  vp, vp, vp, vp, vp, i64, vp]),
+    "ssq_extract_ridges_host": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, i64, i64, i64, vp, vp, C.c_double, i64,
+                                          C.c_double, vp, vp, vp, vp]),
+    "ssq_ridge_track_host": (C.c_int, [C.c_int, C.c_int, vp, i64, i64, i64, vp, C.c_double, vp, vp]),
     "ssq_rccl_available": (C.c_int, []),
     "ssq_rccl_unique_id": (C.c_int, [vp]),
     "ssq_rccl_comm_init": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.c_int]),

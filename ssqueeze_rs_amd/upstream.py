@@ -11,12 +11,16 @@ Supported subset (anything else raises ValueError naming the option):
   * `window`: ndarray (upstream's default DPSS / named windows come from scipy.signal, which callers can pass in);
   * `scales`: explicit exponentially spaced ndarray ('log' scaletype; the automatic 'log-piecewise' bounds are not built);
   * wavelets 'gmw' (gamma, beta; bandpass norm, order 0) and 'morlet' (mu) -- names, or (name, {params});
-  * difftype 'trig'; squeezing 'sum' / 'lebesgue'; padtype 'reflect' / 'zero'; full inverses (no component curves).
+  * difftype 'trig'; squeezing 'sum' / 'lebesgue'; padtype 'reflect' / 'zero'; full inverses (no component curves);
+  * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
+    serial backward trace (`parallel` is accepted and ignored).
 dtype: float64 in -> complex128 (upstream's 'float64'); float32 in -> complex64 (upstream's default 'float32').
 
 Parity: unpinned against upstream itself (it does not import here: numba missing); tests compare with the numba-free
 restatement oracle/upstream_oracle.py and pin upstream's own reconstruction thresholds
-(old/tests/reconstruction_test.py:111-123, :160-206).
+(old/tests/reconstruction_test.py:111-123, :160-206).  Ridges: unpinned likewise; tests compare with the numba-free
+restatement tests/helpers/ridge_oracle.py (the forward DP bitwise) and pin upstream's one stated fact,
+old/tests/ridge_extraction_test.py:17-26 (`test_basic`).
 """
 from __future__ import annotations
 
@@ -343,3 +347,55 @@ def icwt(Wx, wavelet="gmw", scales="log-piecewise", nv=None, one_int=True, x_len
         raise AssertionError("%s != %s" % (len(s), Wx.shape[0]))
     x = _issq(Wx, (2.0 / adm_ssq(wavelet)) * np.log(2 ** (1 / _nv)), None if l1_norm else 1.0 / np.sqrt(s))
     return x + x_mean
+
+
+# ---------------------------------------------------------------------------------------------- ridge extraction ----
+def extract_ridges(Tf, scales, penalty=2., n_ridges=1, bw=15, transform='cwt', get_params=False, parallel=True):
+    """ssqueezepy.extract_ridges (old/ssqueezepy/ridge_extraction.py:11-146) -> ridge_idxs [N, n_ridges] int64, or
+    (ridge_idxs, ridge_f, ridge_e) with get_params.  Extension: a 3-D `Tf` [B, F, N] is a batch (outputs get a leading
+    B).  dtypes as upstream (:113-121): the parameter dtype (scales, eps, penalty, ridge_f, ridge_e) is float64 only
+    for complex128 `Tf`; the cost and DP run in the dtype of |Tf|**2 (fp64 for float64 or integer `Tf`).  The metric
+    log(scales) / scales (:118-120) is formed here in NumPy; everything per element runs in HIP kernels.  The backward
+    trace is upstream's serial one (:206-215): `parallel` is accepted and ignored (its prange kernel, :217-232, races
+    when two rows match)."""
+    lib = _lib.load()
+    Tf = np.asarray(Tf)
+    if Tf.ndim not in (2, 3):
+        raise ValueError("`Tf` must be 2D [F, N] or 3D [B, F, N]")
+    batched = Tf.ndim == 3
+    Tb = Tf if batched else Tf[None]
+    B, F, N = Tb.shape
+    if Tf.dtype == np.complex128:
+        code, pcode, cplx, src = SSQ_F64, SSQ_F64, 1, Tb
+    elif Tf.dtype == np.complex64:
+        code, pcode, cplx, src = SSQ_F32, SSQ_F32, 1, Tb
+    elif Tf.dtype == np.float32:
+        code, pcode, cplx, src = SSQ_F32, SSQ_F32, 0, Tb
+    elif Tf.dtype == np.float64 or Tf.dtype.kind in "biu":    # integers: |x|**2 is exact in fp64 for |x| < 2**26
+        code, pcode, cplx, src = SSQ_F64, SSQ_F32, 0, Tb.astype(np.float64, copy=False)
+    else:
+        raise TypeError(f"`Tf` dtype {Tf.dtype}: complex64/128, float32/64 or integer are supported")
+    pdt = np.float64 if pcode == SSQ_F64 else np.float32
+    s = np.asarray(scales, dtype=pdt)
+    if s.ndim > 2 or (s.ndim == 2 and s.shape[1] != 1) or s.size != F:
+        raise ValueError(f"`scales` must have shape ({F},) or ({F}, 1) to match `Tf`, got {s.shape}")
+    if int(n_ridges) != n_ridges or n_ridges < 1:
+        raise ValueError("`n_ridges` must be an integer >= 1")
+    if not np.isfinite(bw) or bw < 0:
+        raise ValueError("`bw` must be finite and >= 0")
+    scales_orig = np.ascontiguousarray(s.reshape(-1))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        metric = np.ascontiguousarray((np.log(scales_orig) if transform == 'cwt' else scales_orig).reshape(-1))
+    pen = float(np.asarray(penalty, dtype=pdt))
+    n_ridges = int(n_ridges)
+    _lib.require_gpu()
+    src = np.ascontiguousarray(src)
+    ridge_idxs = np.empty((B, N, n_ridges), dtype=np.int64)
+    ridge_f = np.empty((B, N, n_ridges), dtype=pdt) if get_params else None
+    ridge_e = np.empty((B, N, n_ridges), dtype=pdt) if get_params else None
+    _call(lib.ssq_extract_ridges_host(code, pcode, cplx, _ptr(src), B, F, N, _ptr(metric), _ptr(scales_orig), pen,
+                                      n_ridges, float(bw), _ptr(ridge_idxs), _ptr(ridge_f), _ptr(ridge_e), None))
+    if not batched:
+        ridge_idxs = ridge_idxs[0]
+        ridge_f, ridge_e = (ridge_f[0], ridge_e[0]) if get_params else (None, None)
+    return (ridge_idxs, ridge_f, ridge_e) if get_params else ridge_idxs
