@@ -12,14 +12,6 @@
 namespace ssq {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
-const char* tune_env(const char* name) {
-#ifdef SSQ_TUNING
-  return std::getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
 }  // namespace ssq
 
 using namespace ssq;
@@ -227,11 +219,3 @@ int ssq_graph_destroy(void* graph_exec) {
 }
 
 }  // extern "C"
-
-extern "C" int ssq_build_has_tuning(void) {
-#ifdef SSQ_TUNING
-  return 1;
-#else
-  return 0;
-#endif
-}

@@ -80,40 +80,15 @@ struct ssq_cwt_plan {
   // ssq path of two-step plans: Tx is cleared on a side stream while the transforms run
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool can_fuse_ssq() const { return two_step && !naive && na <= 32767; }
-  // SSQ_CWT_FUSED=1 selects the fused step B / mode Z (phase transform + bin in the store phase, Wx + 16-bit row index
-  // out, dWx never in memory: 37 % less traffic between the transforms and the reassignment).  Measured on C4
-  // (profiles/r02_ab_cwt_fused.txt): 8.64 ms against 8.16 ms for the unfused narrow step B with two blocks per CU --
-  // the tile kernel's phases add, so the extra store-phase arithmetic costs more than the bytes it saves.  Default off.
-  bool fused_ssq() const {
-    if (!can_fuse_ssq()) return false;
-    const char* e = tune_env("SSQ_CWT_FUSED");
-    return e && std::atoi(e) != 0;
-  }
+  bool clear_tx_aside() const { return two_step && !naive && na <= 32767; }
 };
 
 namespace {
 
 const long double kPI = 3.14159265358979323846264338327950288L;
 constexpr long long kZoomTabQ = 4096;   // twiddle table extent of the single-pass (mode Z) transforms (tile kernel: LOGM <= 12)
-// longest single-pass (mode Z) transform actually used (SSQ_CWT_ZMAXQ, a power of two <= 4096; read at plan creation)
-long long zoom_max_q() {
-  long long q = 2048;
-  if (const char* e = tune_env("SSQ_CWT_ZMAXQ")) {
-    const long long v = std::atoll(e);
-    if (v >= 16 && v <= kZoomTabQ && (v & (v - 1)) == 0) q = v;
-  }
-  return q;
-}
-
-// SSQ_CWT_GROUP (read per call): n > 0 reassigns every n scales right behind their transforms (while their Wx / dWx are
-// still in the Infinity Cache) instead of once per call; default 0: measured 5 % slower on C4, profiles/r02_ab_cwt_group.txt
-int ssq_group_env(int dflt) {
-  const char* e = tune_env("SSQ_CWT_GROUP");
-  if (!e) return dflt;
-  const int v = std::atoi(e);
-  return v < 0 ? dflt : v;
-}
+// longest single-pass (mode Z) transform actually used (4096: no gain with the time-tile path)
+constexpr long long kZoomMaxQ = 2048;
 
 // Smallest w beyond which the wavelet table entry is exactly zero in T (the table is evaluated in fp64 and
 // rounded once to T: csrc/cwt_kernels.hip::wavelet_table_kernel), with margin.
@@ -355,8 +330,8 @@ WsLayout ws_layout(const ssq_cwt_plan* pl) {
                        : (pl->two_step ? (long long)pl->chunk * 2 * pl->P * csz : 0));
   L.w = off;                   // (all scales time-tiled: Wx / dWx never exist in memory, nothing is reserved)
   if (!pl->all_tiled) off += align((long long)pl->na * pl->N * csz);
-  L.dw = off;                  // fused ssq path: the 16-bit row indices K live here instead of dWx
-  if (!pl->all_tiled) off += align((long long)pl->na * pl->N * csz);   // dWx (unfused path) or row indices (fused path)
+  L.dw = off;
+  if (!pl->all_tiled) off += align((long long)pl->na * pl->N * csz);   // dWx
   L.xc = off;                  // register-core path: the transposed, residue-twiddled spectrum
   if (pl->reg) off += align(((long long)pl->reg_D << 20) * csz);
   L.os_xs = off;               // time-tiled path: the tiles' spectra
@@ -457,15 +432,10 @@ int run_forward(const ssq_cwt_plan* pl, CwtDev<T> p, const T* d_x, hipStream_t s
 }
 
 // per-scale wavelet multiply + inverse FFT + normalise + unpad  (cwt.rs:228-310, :108-129)
-// `after(s0, s1)` runs behind every group of scales whose outputs are complete (the ssq path reassigns there); with
-// group > 0 the band-limited runs are cut into launches of at most `group` scales so that a group fits the cache.
-struct NoAfter {
-  int operator()(int, int) const { return 0; }
-};
 // Scales with skip[s] != 0 are left out (the ssq path computes them by time tiles, cwt_os.hip).
-template <typename T, typename After = NoAfter>
+template <typename T>
 int run_inverse(const ssq_cwt_plan* pl, CwtDev<T> p, cpx<T>* Wx, cpx<T>* dWx, bool l1_norm, bool rpadded,
-                hipStream_t st, After after = After(), int group = 0, const char* skip = nullptr) {
+                hipStream_t st, const char* skip = nullptr) {
   p.Wx = Wx;
   p.dWx = dWx;
   p.n_kinds = dWx ? 2 : 1;
@@ -478,7 +448,6 @@ int run_inverse(const ssq_cwt_plan* pl, CwtDev<T> p, cpx<T>* Wx, cpx<T>* dWx, bo
       p.scale0 = c0;
       p.n_transforms = ns * p.n_kinds;
       SSQ_HIP(launch_cwt_big_inv<T>(p, p.ybuf + (long long)pl->chunk * 2 * pl->P, st));
-      if (int rc = after(c0, c0 + ns)) return rc;
     }
     return 0;
   }
@@ -486,14 +455,14 @@ int run_inverse(const ssq_cwt_plan* pl, CwtDev<T> p, cpx<T>* Wx, cpx<T>* dWx, bo
     p.scale0 = 0;
     p.n_transforms = pl->na * p.n_kinds;
     SSQ_HIP(launch_cwt_naive_inv<T>(p, p.n_transforms, st));
-    return after(0, pl->na);
+    return 0;
   }
   if (!pl->two_step) {
     p.scale0 = 0;
     p.n_transforms = pl->na * p.n_kinds;
     p.tw_m = (const cpx<T>*)pl->d_tw1;
     SSQ_HIP(launch_cwt_tile<T>(CWT_INV_S, p, st));
-    return after(0, pl->na);
+    return 0;
   }
   // runs of consecutive scales on the same path: band-limited ones (mode Z, grouped by Q) in one launch per run,
   // the others through the two-step transform in chunks whose ybuf stays inside the Infinity Cache
@@ -513,14 +482,9 @@ int run_inverse(const ssq_cwt_plan* pl, CwtDev<T> p, cpx<T>* Wx, cpx<T>* dWx, bo
       z.tw_m = (const cpx<T>*)pl->d_twz + pl->twz_off[lq];
       z.tw_compact = sizeof(T) == 8 ? 1 : 0;
       z.tw_f2 = (const cpx<T>*)pl->d_f2z[lq];
-      const int step = group > 0 ? group : s1 - s0;
-      for (int c0 = s0; c0 < s1; c0 += step) {
-        const int ns = (s1 - c0 < step) ? s1 - c0 : step;
-        z.scale0 = c0;
-        z.n_transforms = ns * p.n_kinds;
-        SSQ_HIP(launch_cwt_tile<T>(CWT_INV_Z, z, st));
-        if (int rc = after(c0, c0 + ns)) return rc;
-      }
+      z.scale0 = s0;
+      z.n_transforms = (s1 - s0) * p.n_kinds;
+      SSQ_HIP(launch_cwt_tile<T>(CWT_INV_Z, z, st));
     } else {
       for (int c0 = s0; c0 < s1; c0 += pl->chunk) {
         const int ns = (s1 - c0 < pl->chunk) ? s1 - c0 : pl->chunk;
@@ -546,49 +510,6 @@ int run_inverse(const ssq_cwt_plan* pl, CwtDev<T> p, cpx<T>* Wx, cpx<T>* dWx, bo
           p.tw_m = (const cpx<T>*)pl->d_tw2;
           SSQ_HIP(launch_cwt_tile<T>(CWT_INV_B, p, st));
         }
-        if (int rc = after(c0, c0 + ns)) return rc;
-      }
-    }
-    s0 = s1;
-  }
-  return 0;
-}
-
-// ssq path of two-step plans: step A as above, then the FUSED step B / mode Z (Wx + row index out, dWx stays on chip)
-template <typename T>
-int run_inverse_ssq(const ssq_cwt_plan* pl, CwtDev<T> p, const CwtSsqDev<T>& q, cpx<T>* Wx, short* K, cpx<T>* dWx_dbg,
-                    hipStream_t st) {
-  p.Wx = Wx;
-  p.K = K;
-  p.dWx = dWx_dbg;
-  p.n_kinds = 2;
-  p.rpadded = 0;
-  p.cols = pl->N;
-  p.out_scale = (const T*)pl->d_scale_l1;                 // ssq_cwt is always L1 (ssq_cwt.rs:405)
-  int s0 = 0;
-  while (s0 < pl->na) {
-    const int lq = pl->zoom_logq[(size_t)s0];
-    int s1 = s0 + 1;
-    while (s1 < pl->na && pl->zoom_logq[(size_t)s1] == lq) ++s1;
-    if (lq > 0) {
-      CwtDev<T> z = p;
-      z.scale0 = s0;
-      z.n_transforms = (s1 - s0) * 2;
-      z.log_p2 = lq;
-      z.log_p1 = pl->logP - lq;
-      z.tw_m = (const cpx<T>*)pl->d_twz + pl->twz_off[lq];
-      z.tw_compact = sizeof(T) == 8 ? 1 : 0;
-      z.tw_f2 = (const cpx<T>*)pl->d_f2z[lq];
-      SSQ_HIP(launch_cwt_tile_ssq<T>(CWT_INV_Z, z, q, st));
-    } else {
-      for (int c0 = s0; c0 < s1; c0 += pl->chunk) {
-        const int ns = (s1 - c0 < pl->chunk) ? s1 - c0 : pl->chunk;
-        p.scale0 = c0;
-        p.n_transforms = ns * 2;
-        p.tw_m = (const cpx<T>*)pl->d_tw1;
-        SSQ_HIP(launch_cwt_tile<T>(CWT_INV_A, p, st));
-        p.tw_m = (const cpx<T>*)pl->d_tw2;
-        SSQ_HIP(launch_cwt_tile_ssq<T>(CWT_INV_B, p, q, st));
       }
     }
     s0 = s1;
@@ -642,7 +563,7 @@ int exec_cwt_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, bool l1, 
     if (int rc = run_forward<T>(pl, p, (const T*)d_x + b * pl->N, st)) return rc;
     cpx<T>* W = (cpx<T>*)d_Wx + b * pl->na * cols;
     cpx<T>* dW = d_dWx ? (cpx<T>*)d_dWx + b * pl->na * cols : nullptr;
-    if (int rc = run_inverse<T>(pl, p, W, dW, l1, rpadded, st, NoAfter(), 0, tiles ? mask.data() : nullptr)) return rc;
+    if (int rc = run_inverse<T>(pl, p, W, dW, l1, rpadded, st, tiles ? mask.data() : nullptr)) return rc;
     if constexpr (sizeof(T) == 4) {
       if (tiles) {
         CwtOsDev o;
@@ -734,46 +655,13 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
   if (ups && gamma < 0) q.gamma = (T)(10.0 * (sizeof(T) == 8 ? 2.2204460492503131e-16 : 1.1920928955078125e-07));
   q.leb_val = (T)(1.0 / (double)n);
   const long long plane = (long long)n * pl->N;
-  if (pl->fused_ssq() && !pl->all_tiled && !ups) {
-    if (!pl->side) {
-      SSQ_HIP(hipStreamCreateWithFlags(&pl->side, hipStreamNonBlocking));
-      SSQ_HIP(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
-      SSQ_HIP(hipEventCreateWithFlags(&pl->ev_join, hipEventDisableTiming));
-    }
-    for (long long b = 0; b < batch; ++b) {
-      CwtDev<T> p = base_dev<T>(pl, ws);
-      cpx<T>* W = (cpx<T>*)(ws + L.w);
-      short* K = (short*)(ws + L.dw);
-      q.Wx = W;
-      q.dWx = nullptr;
-      q.Tx = (cpx<T>*)d_Tx + b * plane;
-      q.wk = d_dbg_wk ? (cpx<T>*)d_dbg_wk + b * plane : nullptr;
-      // fork: clear this signal's Tx (2.15 GB at C4) beside the transforms instead of in front of the reassignment
-      SSQ_HIP(hipEventRecord(pl->ev_fork, st));
-      SSQ_HIP(hipStreamWaitEvent(pl->side, pl->ev_fork, 0));
-      SSQ_HIP(hipMemsetAsync(q.Tx, 0, (size_t)plane * sizeof(cpx<T>), pl->side));
-      SSQ_HIP(hipEventRecord(pl->ev_join, pl->side));
-      if (int rc = run_forward<T>(pl, p, (const T*)d_x + b * pl->N, st)) return rc;
-      if (int rc = run_inverse_ssq<T>(pl, p, q, W, K, d_dbg_dWx ? (cpx<T>*)d_dbg_dWx + b * plane : nullptr, st)) return rc;
-      SSQ_HIP(hipStreamWaitEvent(st, pl->ev_join, 0));            // join
-      SSQ_HIP(launch_cwt_reassign_k<T>(q, K, st));
-      if (d_dbg_Wx)
-        SSQ_HIP(hipMemcpyAsync((cpx<T>*)d_dbg_Wx + b * plane, W, (size_t)plane * sizeof(cpx<T>),
-                               hipMemcpyDeviceToDevice, st));
-    }
-    return 0;
-  }
-  const int group = (pl->can_fuse_ssq() && !pl->all_tiled && !ups) ? ssq_group_env(0) : 0;
-  // reassignment with a written-rows bitmap (first run of a row: plain store).  SSQ_CWT_SWEEP: 0 = read-modify-write
-  // of a cleared Tx; 1 (default) = bitmap, Tx cleared beside the transforms; 2 = bitmap and the kernel writes the
-  // untouched rows as zeros itself, no clear (measured slower on C4: the clear overlaps the transforms, the zero rows
-  // would not -- profiles/r02_ab_cwt_sweep.txt)
-  const char* sweep_env = tune_env("SSQ_CWT_SWEEP");
-  const int sweep_mode = sweep_env ? std::atoi(sweep_env) : 1;
-  const bool os = sizeof(T) == 4 && group == 0 && (pl->os_s1 > pl->os_s0 || pl->os_z1 > pl->os_z0);   // time-tile family
-  const bool sweep = !ups && !os && group == 0 && cwt_reassign_can_sweep<T>(n) && sweep_mode != 0;
-  const bool self_zero = sweep && (sweep_mode == 2 || !pl->can_fuse_ssq());
-  const bool side_clear = pl->can_fuse_ssq() && !self_zero;   // clear Tx beside the transforms
+  // reassignment with a written-rows bitmap (first run of a row: plain store), Tx cleared beside the transforms (a
+  // read-modify-write of a cleared Tx, or the kernel writing the untouched rows as zeros itself instead of the clear,
+  // measured slower on C4: profiles/r02_ab_cwt_sweep.txt)
+  const bool os = sizeof(T) == 4 && (pl->os_s1 > pl->os_s0 || pl->os_z1 > pl->os_z0);   // time-tile family
+  const bool sweep = !ups && !os && cwt_reassign_can_sweep<T>(n);
+  const bool self_zero = sweep && !pl->clear_tx_aside();
+  const bool side_clear = pl->clear_tx_aside() && !self_zero;   // clear Tx beside the transforms
   if (side_clear && !pl->side) {
     SSQ_HIP(hipStreamCreateWithFlags(&pl->side, hipStreamNonBlocking));
     SSQ_HIP(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
@@ -794,23 +682,11 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
     q.Wx = W;
     q.dWx = dW;
     q.wk = d_dbg_wk ? (cpx<T>*)d_dbg_wk + b * plane : nullptr;
-    if (group > 0) {
-      // reassign each group of scales right behind its transforms, while its Wx / dWx are still in the Infinity Cache
-      bool joined = false;
-      auto after = [&](int s0, int s1) -> int {
-        if (!joined) SSQ_HIP(hipStreamWaitEvent(st, pl->ev_join, 0));
-        joined = true;
-        q.s_begin = s0;
-        q.s_end = s1;
-        SSQ_HIP(launch_cwt_reassign<T>(q, st, false));
-        return 0;
-      };
-      if (int rc = run_inverse<T>(pl, p, W, dW, true, false, st, after, group)) return rc;   // always L1 (:405)
-    } else if (os) {
+    if (os) {
       if constexpr (sizeof(T) == 4) {
         // every other scale through the transforms into the workspaces ...
         if (!pl->all_tiled) {
-          if (int rc = run_inverse<T>(pl, p, W, dW, true, false, st, NoAfter(), 0, pl->os_mask.data())) return rc;
+          if (int rc = run_inverse<T>(pl, p, W, dW, true, false, st, pl->os_mask.data())) return rc;   // always L1 (:405)
           if (d_dbg_Wx)
             SSQ_HIP(hipMemcpyAsync((cpx<T>*)d_dbg_Wx + b * plane, W, (size_t)plane * sizeof(cpx<T>),
                                    hipMemcpyDeviceToDevice, st));
@@ -823,7 +699,7 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
         // are plain stores (behind the tile kernels each would be a dependent read-modify-write chain per column)
         int lead = 0;
         while (lead < n && !pl->os_mask[(size_t)lead]) ++lead;
-        const bool lead_sweep = lead > 0 && lead < n && cwt_reassign_can_sweep<T>(n) && sweep_mode != 0;
+        const bool lead_sweep = lead > 0 && lead < n && cwt_reassign_can_sweep<T>(n);
         if (lead_sweep) {
           q.s_begin = 0;
           q.s_end = lead;
@@ -985,7 +861,6 @@ int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int 
     // step doubles them (C5: 4096 -> 2048 points, 32 -> 64 B; C4: 2048 -> 1024, 64 -> 128 B): one C5 signal 106 -> 91 ms,
     // C4 fp64 19.0 -> 17.2 ms (profiles/r03_ab_cwt_f64_split.txt)
     if (dtype == SSQ_F64) pl->log_p2 = (lp + 1) / 2;
-    if (const char* e = tune_env("SSQ_CWT_P2UP")) pl->log_p2 = (lp + std::atoi(e)) / 2;   // tuning switch
     pl->log_p1 = lp - pl->log_p2;
   }
   // SSQ_CWT_REG=0 keeps the tile kernels for the two-step scales (A/B and tests)
@@ -996,7 +871,6 @@ int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int 
   }
   const long long csz = dtype == SSQ_F32 ? 8 : 16;
   long long chunk_mb = 128;                                      // ybuf of a chunk stays inside the 256 MB Infinity Cache
-  if (const char* e = tune_env("SSQ_CWT_CHUNK_MB")) chunk_mb = std::atoll(e) > 0 ? std::atoll(e) : chunk_mb;   // tuning switch
   long long ch = (chunk_mb << 20) / (2 * pl->P * csz);
   if (ch < 1) ch = 1;
   if (ch > (na > 0 ? na : 1)) ch = (na > 0 ? na : 1);
@@ -1014,7 +888,7 @@ int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int 
       if (!(a > 0.0) || !std::isfinite(a)) continue;
       const double kb = wmax / (a * h) + 2.0;                        // psih_i[k] == 0 for k >= kb
       if (kb < (double)(pl->P / 2 + 1)) pl->band[(size_t)i] = (int)kb + 1;
-      if (kb > (double)zoom_max_q() || pl->big) continue;
+      if (kb > (double)kZoomMaxQ || pl->big) continue;
       int lq = 4;
       while ((double)(1LL << lq) < kb) ++lq;
       pl->zoom_logq[(size_t)i] = lq;
@@ -1047,30 +921,24 @@ int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int 
       if (best1 - best0 >= 8 && n_signal >= 64LL * kOsL) {
         pl->os_s0 = best0;
         pl->os_s1 = best1;
-        // the scales whose wavelet fits HALF the halo take the 4096-point tiles (SSQ_CWT_OS_ROWS=8: all on 8192 points)
-        const char* er = tune_env("SSQ_CWT_OS_ROWS");
+        // the scales whose wavelet fits HALF the halo take the 4096-point tiles (profiles/r02_ab_cwt_os_rows.txt)
         int mid = best0;
-        if (!(er && std::atoi(er) == 8))
-          while (mid < best1 && scales[mid] <= 0.5 * a_hi) ++mid;
+        while (mid < best1 && scales[mid] <= 0.5 * a_hi) ++mid;
         if (mid - best0 < 8) mid = best0;
         pl->os_mid = mid;
         pl->os_d1 = best1;
         // behind them the long wavelets that are band-limited below 1 / 64 cycles per sample: 16-fold decimated tiles
-        // (halo 16 * 2048 samples; psih_s[k] == 0 from band[s] <= P / 32 on); SSQ_CWT_OS_DEC=0 keeps the transforms
-        const char* ed = tune_env("SSQ_CWT_OS_DEC");
-        if (!(ed && std::atoi(ed) == 0)) {
-          int d1 = best1;
-          while (d1 < (int)na && scales[d1] <= a_hi * (double)(1 << kOsLogDec) && pl->zoom_logq[(size_t)d1] == 0 &&
-                 (long long)pl->band[(size_t)d1] <= pl->P / 32)
-            ++d1;
-          if (d1 - best1 >= 4) pl->os_d1 = d1;
-        }
+        // (halo 16 * 2048 samples; psih_s[k] == 0 from band[s] <= P / 32 on; profiles/r02_ab_cwt_os_dec.txt)
+        int d1 = best1;
+        while (d1 < (int)na && scales[d1] <= a_hi * (double)(1 << kOsLogDec) && pl->zoom_logq[(size_t)d1] == 0 &&
+               (long long)pl->band[(size_t)d1] <= pl->P / 32)
+          ++d1;
+        if (d1 - best1 >= 4) pl->os_d1 = d1;
         // in front of them the finest scales, whose psih is NOT negligible at Nyquist, on tiles of the analytic signal
         // (register-core plans compute it with one extra transform); the continued spectrum must vanish by 2 pi:
-        // Morlet a >= 1.97, GMW a >= 0.64.  SSQ_CWT_OS_ANALYTIC=0 keeps the register-core transforms for them
-        const char* ea = tune_env("SSQ_CWT_OS_ANALYTIC");
+        // Morlet a >= 1.97, GMW a >= 0.64 (profiles/r02_ab_cwt_os_analytic.txt)
         pl->os_a0 = best0;
-        if (pl->reg && !(ea && std::atoi(ea) == 0)) {
+        if (pl->reg) {
           const double a_ext = wavelet == SSQ_WAVELET_MORLET ? 1.97 : 0.64;
           int a0 = best0;
           while (a0 > 0 && scales[a0 - 1] >= a_ext && pl->zoom_logq[(size_t)(a0 - 1)] == 0) --a0;
@@ -1080,12 +948,11 @@ int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int 
     }
   }
   // full-circle phase blocks for the band-limited scales: 2 N <= P (the kept samples lie inside the middle half of the
-  // padded length, which is what the tile kernel emits), spectrum below 2048 bins; SSQ_CWT_OS_FULL=0 keeps mode Z + the column reassignment for them
+  // padded length, which is what the tile kernel emits), spectrum below 2048 bins (profiles/r02_ab_cwt_os_full.txt)
   {
     const char* e = os_env;
-    const char* ef = tune_env("SSQ_CWT_OS_FULL");
-    if (!ups && dtype == SSQ_F32 && pl->two_step && !(e && std::atoi(e) == 0) && !(ef && std::atoi(ef) == 0) &&
-        2 * pl->N <= pl->P && n_signal >= 64LL * kOsL) {
+    if (!ups && dtype == SSQ_F32 && pl->two_step && !(e && std::atoi(e) == 0) && 2 * pl->N <= pl->P &&
+        n_signal >= 64LL * kOsL) {
       bool ascending = true;
       for (int64_t i = 1; i < na; ++i) ascending = ascending && scales[i] >= scales[i - 1];
       int z0 = pl->os_d1;
@@ -1188,8 +1055,7 @@ int ssq_cwt_plan_exec_ssq(ssq_cwt_plan* pl, const void* d_x, int64_t batch, int 
 // ---- D2H of signal b on a second stream while signal b+1 computes -----------------------------------------------
 namespace {
 
-// the four TEST hooks plan creation reads from the environment are part of the key (tests flip them between calls);
-// tuning switches exist only in -DSSQ_TUNING builds (ssq_common.h::tune_env) and are not
+// the four TEST hooks plan creation reads from the environment are part of the key (tests flip them between calls)
 std::string plan_env() {
   std::string k;
   for (const char* v : {"SSQ_CWT_NOPRUNE", "SSQ_CWT_FORCE_BIG", "SSQ_CWT_REG", "SSQ_CWT_OS"}) {

@@ -6,9 +6,6 @@
 
 namespace ssq {
 
-#ifndef SSQ_CWT_FAST_BIN
-#define SSQ_CWT_FAST_BIN 1      // fp32: hardware rcp / sqrt / log2 (1 ulp) in the phase transform and the bin formula
-#endif
 // ------------------------------------------------ phase transform + reassignment ----
 // ssq_cwt.rs:15-47 (phase_cwt) and :116-222 (ssqueeze).
 // Phase transform and bin of one (scale, time) element: returns the Tx row (after flipud) or -1.
@@ -36,21 +33,13 @@ __device__ __forceinline__ int reassign_bin(const CwtSsqDev<T>& p, cpx<T> Wv, cp
     // pre-scaled ratio: the reference's GMW is un-normalised (peak ~4e17), so |Wx|^2 and
     // b*c - a*d overflow fp32 long before the ratio does.  The scale factor and the quotient use the hardware
     // reciprocal (1 ulp): IEEE divisions here made the kernel's arithmetic as long as its memory time
+    // (profiles/r02_ab_cwt_fastbin.txt); so do the square root and, below, the log2 of the bin formula
     const T mx = fmaxf(fabsf(Wv.x), fabsf(Wv.y));
-#if SSQ_CWT_FAST_BIN
     const T sc = __builtin_amdgcn_rcpf(mx);
-#else
-    const T sc = (T)1 / mx;
-#endif
     const T cs = Wv.x * sc, ds = Wv.y * sc;
     const T den = Wv.x * cs + Wv.y * ds;               // |Wx|^2 / mx
-#if SSQ_CWT_FAST_BIN
     small = !(mx * __builtin_amdgcn_sqrtf(cs * cs + ds * ds) >= p.gamma);
     w = fabsf((dW.y * cs - dW.x * ds) * __builtin_amdgcn_rcpf(den * two_pi));
-#else
-    small = !(mx * sqrtf(cs * cs + ds * ds) >= p.gamma);
-    w = fabsf((dW.y * cs - dW.x * ds) / (den * two_pi));
-#endif
   } else {
     const T den = Wv.x * Wv.x + Wv.y * Wv.y;
     small = hypot(Wv.x, Wv.y) < p.gamma;               // Complex::norm()  ssq_cwt.rs:29
@@ -60,13 +49,10 @@ __device__ __forceinline__ int reassign_bin(const CwtSsqDev<T>& p, cpx<T> Wv, cp
   int kk = -1;
   if (!(isinf(w) || w != w)) {                         // ssq_cwt.rs:167
     T v;
-#if SSQ_CWT_FAST_BIN
     if constexpr (sizeof(T) == 4) {
       const T lw = p.is_log ? __builtin_amdgcn_logf(w) : w;   // v_log_f32 = log2, 1 ulp (w is finite, positive or zero here)
       v = (lw - p.bin_min) * p.inv_bin_step;
-    } else
-#endif
-    {
+    } else {
       if (p.is_log) v = (log2(w) - p.bin_min) / p.bin_step;    // ssq_cwt.rs:175-176
       else v = (w - p.bin_min) / p.bin_step;                   // ssq_cwt.rs:187
     }

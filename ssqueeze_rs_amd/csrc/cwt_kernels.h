@@ -33,7 +33,6 @@ struct CwtDev {
   const int* band;       // [na] psih_s[k] == 0 for k >= band[s] (<= P/2 + 1)
   cpx<T>* Wx;            // [na][cols]
   cpx<T>* dWx;           // [na][cols] or NULL
-  short* K;              // fused ssq kernels: [na][N] Tx row of every (scale, time) element, -1 = skipped
   long long n_signal;
   long long P;           // padded length (power of two)
   long long n1;          // (P - N)/2                                 (cwt.rs:98)
@@ -110,17 +109,6 @@ template <typename T>
 bool cwt_reassign_can_sweep(int na);
 template <typename T>
 hipError_t launch_cwt_reassign_sweep(const CwtSsqDev<T>& p, hipStream_t stream, bool zero_fill);
-
-// Fused synchrosqueezing variants of inverse step B / mode Z (two-step plans): one block runs BOTH transforms (Wx and
-// dWx, ssq_cwt.rs:387-402) of one scale for its rows, applies the phase transform (ssq_cwt.rs:15-47) and the bin
-// formula (:160-196) in the store phase and writes Wx plus a 16-bit row index -- dWx never reaches memory.
-// p.n_transforms = 2 * scales of the launch; q carries the binning parameters and the optional (w, k) hook buffer.
-template <typename T>
-hipError_t launch_cwt_tile_ssq(int mode, const CwtDev<T>& p, const CwtSsqDev<T>& q, hipStream_t stream);
-// Tx from (Wx, K): one thread per time column, scales ascending, runs of equal rows summed in registers.
-// Tx must be zero on entry (the caller clears it on a side stream while the transforms run).
-template <typename T>
-hipError_t launch_cwt_reassign_k(const CwtSsqDev<T>& p, const short* K, hipStream_t stream);
 
 // ---- cwt_reg.hip: fp32 inverse transforms of P = 2^20 / 2^21 on the per-wave register FFT core ----
 struct CwtRegDev {

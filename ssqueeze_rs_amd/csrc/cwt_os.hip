@@ -23,9 +23,8 @@
 
 namespace ssq {
 
-#ifndef SSQ_OS_WAVES_PER_SIMD
-#define SSQ_OS_WAVES_PER_SIMD 4     // 4: 128 VGPRs (two 8-wave blocks per CU); 2: 256 VGPRs, no spills, one 8-wave block per CU
-#endif
+// 4: 128 VGPRs (two 8-wave blocks per CU); 2 (256 VGPRs, no spills, one 8-wave block per CU): profiles/r02_ab_cwt_os_waves.txt
+constexpr int kOsWavesPerSimd = 4;
 
 namespace {
 
@@ -84,7 +83,7 @@ __device__ __forceinline__ void os_dft(cpx<float> (&v)[R]) {
 // the input that cut is already in the signal, the filter stays smooth -- hence short in time -- and the finest scales,
 // whose psih is NOT negligible at Nyquist, become tile-able as well.
 template <int R, int LOGM, bool CPLX = false>
-__global__ __launch_bounds__(OsCfg<R>::THREADS, SSQ_OS_WAVES_PER_SIMD) void cwt_os_kernel(CwtOsDev p) {
+__global__ __launch_bounds__(OsCfg<R>::THREADS, kOsWavesPerSimd) void cwt_os_kernel(CwtOsDev p) {
   using K = OsCfg<R>;
   constexpr int F = K::F, L = K::L, HALO = K::HALO, THREADS = K::THREADS, PT = K::PT, LOGR = K::LOGR;
   constexpr int H2 = CPLX ? R : R / 2;                         // live rows of the spectrum
@@ -125,9 +124,6 @@ __global__ __launch_bounds__(OsCfg<R>::THREADS, SSQ_OS_WAVES_PER_SIMD) void cwt_
 
   // W_F^(c j), j < R, for the columns c = tid + THREADS * u this thread transforms (forward sign): 1, w, w^2 ...
   constexpr int CPT = 1024 / THREADS;                          // columns per thread in the length-R transforms: 1 or 2
-#ifndef SSQ_OS_WJ_KEEP
-#define SSQ_OS_WJ_KEEP 0     // 1: the R powers live in registers across all scales (2 R CPT of the 128 the kernel may use)
-#endif
   cpx<float> wj[CPT][R];
 #pragma unroll
   for (int u = 0; u < CPT; ++u) {
@@ -221,7 +217,6 @@ __global__ __launch_bounds__(OsCfg<R>::THREADS, SSQ_OS_WAVES_PER_SIMD) void cwt_
       asm volatile("s_mov_b32 %0, 0" : "=s"(z));
       xs_it += z;
     }
-#if !SSQ_OS_WJ_KEEP
     {
       // the twiddle powers are rebuilt per scale (one cached table read and R - 2 products per column) instead of
       // living in 2 R CPT registers through the wave transform and the epilogue, where the kernel spills: the opaque
@@ -237,7 +232,6 @@ __global__ __launch_bounds__(OsCfg<R>::THREADS, SSQ_OS_WAVES_PER_SIMD) void cwt_
         for (int j = 2; j < R; ++j) wj[u][j] = cmul(wj[u][j - 1], wj[u][1]);
       }
     }
-#endif
 #pragma unroll
     for (int u = 0; u < CPT; ++u) {
       const int c = tid + THREADS * u;

@@ -19,19 +19,6 @@
 
 namespace ssq {
 
-// ablation bits of a diagnostic build (python -m ssqueeze_rs_amd.build --variant X -DSSQ_REG_ABL=n; results wrong by
-// construction): R1 1 no loads, 2 no stores, 4 no FFT; R2 8 no loads, 16 no stores, 32 no FFT.  profiles/r02_abl_cwt_reg.txt
-#ifndef SSQ_REG_ABL
-#define SSQ_REG_ABL 0
-#endif
-#define REG_ABL(bit) ((SSQ_REG_ABL & (bit)) != 0)
-#ifndef SSQ_R2_XCDPAIR
-#define SSQ_R2_XCDPAIR 1
-#endif
-#ifndef SSQ_R2_EARLY
-#define SSQ_R2_EARLY 0      // 1: issue the next tile's 16 loads at the top of the tile (32 more registers across the FFT): +1.7 % on C4
-#endif
-
 namespace {
 
 constexpr int kRegThreads = 1024;       // 16 waves, one block per CU
@@ -115,7 +102,7 @@ __global__ __launch_bounds__(kRegThreads, 1) void cwt_reg_r1_kernel(CwtRegDev p)
     const float* __restrict__ prow = p.psiT + p.psiT_off[s] + (long long)b * A;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      if (64 * q < A && !REG_ABL(1)) {                   // wave-uniform: dead spans issue no loads
+      if (64 * q < A) {                   // wave-uniform: dead spans issue no loads
         const int a = t + 64 * q;
         if ((q < 8) == (stage == 0)) xr[q] = xrow[a];
         if (stage == 1) pr[q] = prow[a < A ? a : A - 1];
@@ -148,11 +135,11 @@ __global__ __launch_bounds__(kRegThreads, 1) void cwt_reg_r1_kernel(CwtRegDev p)
       }
       v[q] = {x.x * ps, x.y * ps};
     }
-    if (!REG_ABL(4)) wave1024_front(v, exch, t);
+    wave1024_front(v, exch, t);
     const int nxt = it + 1;
     const bool has_next = nxt < items;
     if (has_next) fetch(nxt, 0);
-    if (!REG_ABL(4)) wave1024_back(v, tw1, tw2, t);
+    wave1024_back(v, tw1, tw2, t);
     if (has_next) fetch(nxt, 1);
     // times W_{2^20}^(b n_a), n_a = t + 64 q:  W^(b t) per lane, W^(64 b q) wave-uniform (lane q computes it)
     cpx<float> base, sq;
@@ -169,7 +156,7 @@ __global__ __launch_bounds__(kRegThreads, 1) void cwt_reg_r1_kernel(CwtRegDev p)
       sw.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sq.x), q));
       sw.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sq.y), q));
       const cpx<float> o = cmul(v[q], cmul(base, sw));
-      if (!REG_ABL(2) || o.x == 12345.678f) yrow[64 * q] = o;
+      yrow[64 * q] = o;
     }
     if (!has_next) break;
     it = nxt;
@@ -197,9 +184,7 @@ __global__ __launch_bounds__(kRegThreads, 1) void cwt_reg_r2_kernel(CwtRegDev p)
   // round-robin over the 8 XCDs, so blocks b and b + 8 share an L2: give THEM the two tiles of a pair (the counters
   // showed every line fetched twice without this, profiles/r02_cwt_traffic_reg.json)
   int bid = blockIdx.x;
-#if SSQ_R2_XCDPAIR
   if (gridDim.x % 16 == 0) bid = 2 * (bid & 7) + 16 * (bid >> 4) + ((bid >> 3) & 1);
-#endif
   int tl = bid;
   if (tl >= tiles) return;
   const int c_ld = tid & 15, r_ld = tid >> 4;            // transposing accesses: column fastest
@@ -212,7 +197,6 @@ __global__ __launch_bounds__(kRegThreads, 1) void cwt_reg_r2_kernel(CwtRegDev p)
     const int j = tile_id & ((1 << tshift) - 1);
     const cpx<float>* __restrict__ src =
         p.ybuf + ((long long)(tr << logD) << 20) + ((d_ld << 20) + (r_ld << 10) + (j * ca + na_ld));
-    if REG_ABL(8) return;
 #pragma unroll
     for (int i = 0; i < 8; ++i) pf[8 * stage + i] = src[(long long)(8 * stage + i) << 16];      // rows r_ld + 64 i
   };
@@ -229,25 +213,17 @@ __global__ __launch_bounds__(kRegThreads, 1) void cwt_reg_r2_kernel(CwtRegDev p)
     for (int i = 0; i < 16; ++i) tile[c_ld * PT + r_ld + 64 * i] = pf[i];
     const int nxt = tl + (int)gridDim.x;
     const bool has_next = nxt < tiles;
-#if SSQ_R2_EARLY
-    if (has_next) {
-      fetch(nxt, 0);
-      fetch(nxt, 1);
-    }
-#endif
     __syncthreads();
     cpx<float> v[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) v[q] = col[t + 64 * q];
     frame_sync<false>();
-    if (!REG_ABL(32)) wave1024_front(v, col, t);
-#if !SSQ_R2_EARLY
+    wave1024_front(v, col, t);
+    // (the next tile's 16 loads at the top of the tile instead: 32 more registers across the FFT, +1.7 % on C4,
+    //  profiles/r02_ab_cwt_r2early.txt)
     if (has_next) fetch(nxt, 0);
-#endif
-    if (!REG_ABL(32)) wave1024_back(v, tw1, tw2, t);
-#if !SSQ_R2_EARLY
+    wave1024_back(v, tw1, tw2, t);
     if (has_next) fetch(nxt, 1);
-#endif
     // D = 2: the k = P/2 term, (-1)^n Y[P/2] with n = d (mod 2), d = this wave's column (mod 2)
     cpx<float> nyq = {0.0f, 0.0f};
     const float sc = p.out_scale[s];
@@ -276,7 +252,6 @@ __global__ __launch_bounds__(kRegThreads, 1) void cwt_reg_r2_kernel(CwtRegDev p)
       for (int i = 0; i < 16; ++i) {
         const cpx<float> val = tile[c_ld * PT + r_ld + 64 * i];
         const int n = n0 + ((65536 * i) << logD) - lo;
-        if (REG_ABL(16) && val.x != 12345.678f) continue;
         if ((unsigned)n < (unsigned)cnt) row[n] = val;
       }
     }

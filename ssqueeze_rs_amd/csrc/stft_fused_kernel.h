@@ -34,20 +34,10 @@
 #include <cstdlib>
 #include <type_traits>
 #include "fft_core.h"
-#include "fft_pk1024.h"
 #include "fft_mixed.h"
 #include "stft_kernels.h"
 
 namespace ssq {
-
-#ifndef SSQ_F64_MAGIC
-#define SSQ_F64_MAGIC 1     // fp64 fixed point by the 1.5 * 2^52 rounding trick (50 fraction bits) instead of f64 -> i64 conversions (62)
-#endif
-
-#ifndef SSQ_F64_W8
-#define SSQ_F64_W8 1        // fp64 n_fft = 1024 with EIGHT waves per block (two per SIMD): exchange rows of T (re, then im), one-deep
-                            // prefetch, weights parked in the row, window table in LDS: 1.95 -> 1.61 ms at batch 64 (r03_ab_f64_w8.txt)
-#endif
 
 // ANY: the any-length modes of the kernel (stft_anylen.hip) keep the plain configuration (their transforms use the
 // exchange row as a row of complex values)
@@ -55,7 +45,9 @@ template <typename T, int LOGN, bool ANY = false>
 struct FusedCfg {
   static constexpr int N = 1 << LOGN;
   static constexpr int L = N / 16;                         // lanes per frame
-  static constexpr bool SPLIT = SSQ_F64_W8 && sizeof(T) == 8 && LOGN == 10 && !ANY;   // exchange the components one after the other
+  // fp64 n_fft = 1024 with EIGHT waves per block (two per SIMD): exchange rows of T (re, then im), one-deep prefetch,
+  // weights parked in the row, window table in LDS: 1.95 -> 1.61 ms at batch 64 (profiles/r03_ab_f64_w8.txt)
+  static constexpr bool SPLIT = sizeof(T) == 8 && LOGN == 10 && !ANY;   // exchange the components one after the other
   static constexpr int W = (sizeof(T) == 4 || SPLIT) ? 8 : 4;   // waves per block
   static constexpr int FPW = (L >= 64) ? 1 : 64 / L;       // frames per wave
   static constexpr int WPF = (L <= 64) ? 1 : L / 64;       // waves per frame
@@ -78,7 +70,7 @@ struct FusedCfg {
   static constexpr int TILE_BYTES = (((2 * PLANE + F) * (int)sizeof(T) + 15) / 16) * 16;   // + col_scale[F]
   using IT = std::conditional_t<sizeof(T) == 4, int, long long>;
   using UT = std::conditional_t<sizeof(T) == 4, unsigned int, unsigned long long>;
-  static constexpr int FRAC = (sizeof(T) == 4) ? 30 : (SSQ_F64_MAGIC ? 50 : 62);      // fixed-point fraction bits (fp64: below 2^51, to_fixed)
+  static constexpr int FRAC = (sizeof(T) == 4) ? 30 : 50;  // fixed-point fraction bits (fp64: below 2^51, to_fixed)
   static constexpr int EMIN = (sizeof(T) == 4) ? -90 : -960;   // keeps 2^(FRAC-e) finite
   static constexpr int LDS_BYTES = TILE_BYTES + EXCH_BYTES + WIN_BYTES + TWL_BYTES;
   static constexpr int NP = num_passes(LOGN);
@@ -104,7 +96,6 @@ __device__ __forceinline__ T from_int(std::conditional_t<sizeof(T) == 4, int, lo
 template <typename T>
 __device__ __forceinline__ std::conditional_t<sizeof(T) == 4, int, long long> to_fixed(T v) {
   if constexpr (sizeof(T) == 4) return cvt_round_i32(v);      // floor(v + 1/2): one instruction
-  else if constexpr (!SSQ_F64_MAGIC) return __double2ll_rn(v);
   else {
     // |v| <= 2^50 (FRAC): adding 1.5 * 2^52 leaves round-to-nearest-even(v) in the low mantissa bits -- one fp64 add and
     // one 64-bit subtract instead of the ~18-instruction f64 -> i64 conversion (there is no native one)
@@ -115,7 +106,7 @@ __device__ __forceinline__ std::conditional_t<sizeof(T) == 4, int, long long> to
 // the way back for |i| < 2^51: exact
 template <typename T>
 __device__ __forceinline__ T fixed_to_real(std::conditional_t<sizeof(T) == 4, int, long long> i) {
-  if constexpr (sizeof(T) == 4 || !SSQ_F64_MAGIC) return (T)i;
+  if constexpr (sizeof(T) == 4) return (T)i;
   else {
     constexpr double kMagic = 6755399441055744.0;
     return __longlong_as_double(i + __double_as_longlong(kMagic)) - kMagic;
@@ -295,39 +286,6 @@ __device__ __forceinline__ void load_samples(const StftDev<T>& p, const TileItem
   }
 }
 
-#ifdef SSQ_STAMPS
-// In-kernel phase stamps (diagnostic build only; never quote its run time, read its SHARES).
-__device__ __forceinline__ unsigned long long ssq_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define SSQ_STAMP(i)                         \
-  do {                                       \
-    const unsigned long long t_ = ssq_stamp(); \
-    st_acc[i] += t_ - st_prev;               \
-    st_prev = t_;                            \
-  } while (0)
-#elif defined(SSQ_MARK)
-// static section markers for instruction counting in the .s (tools/count_sections.py)
-#define SSQ_STAMP(i)                                   \
-  do {                                                 \
-    __builtin_amdgcn_sched_barrier(0);                 \
-    asm volatile("; SSQ_SECTION " #i ::: "memory");     \
-    __builtin_amdgcn_sched_barrier(0);                 \
-  } while (0)
-#else
-#define SSQ_STAMP(i) do { } while (0)
-#endif
-
-#ifdef SSQ_ABLATE_HOOKS
-#define SSQ_ABL(mask) (p.ablate & (mask))       // timing experiments (tools/ablate.sh); results are wrong
-#else
-#define SSQ_ABL(mask) false
-#endif
-
 // TXONLY = true : out_kind == SSQ_OUT_TX (the hot path: branch-free epilogue; at n_fft = 1024 fp32
 //                 a wave runs its two frames of a tile staggered, so one frame's LDS round trips
 //                 hide behind the other frame's arithmetic)
@@ -452,10 +410,6 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
     fr1 = make_frame<T, LOGN, EDGE, MODE != 0>(p, i1.tl, i1.ig, slot, t);
     if constexpr (DEEP) load_samples<T, LOGN, EDGE, MODE>(p, i1.tl, fr1, xb, t);
   }
-#ifdef SSQ_STAMPS
-  unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_prev = ssq_stamp();
-#endif
 
 #pragma unroll 1
   while (true) {
@@ -479,7 +433,6 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
       const cpx<T> wq = C::WIN_LDS ? win_lds[t + L * q] : win_it[t + L * q];
       v[0][q] = {xn[0][q] * wq.x, xn[0][q] * wq.y};
     }
-    SSQ_STAMP(0);
     const bool has_next = i1.ok;
     // rotate the prefetch ring: the next item's samples (loaded one iteration ago) move to xn and the
     // loads of the item after next go out now, a full iteration before they are needed
@@ -496,11 +449,10 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
     if (i2.ok) {
       fr2 = make_frame<T, LOGN, EDGE, MODE != 0>(p, i2.tl, i2.ig, slot, t);
       if constexpr (DEEP) {
-        if (!SSQ_ABL(1)) load_samples<T, LOGN, EDGE, MODE>(p, i2.tl, fr2, xb, t);
+        load_samples<T, LOGN, EDGE, MODE>(p, i2.tl, fr2, xb, t);
       }
     }
 
-    SSQ_STAMP(1);
     if constexpr (MIXR) {
       // the windowed frame goes to its row, is transformed there, and the bins come back below (Z[k] and partner)
 #pragma unroll
@@ -508,7 +460,7 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
         if (t + L * q < p.n_eff) exch[exch_phys(t + L * q)] = v[0][q];
       frame_sync<MULTIWAVE>();
       fft_mixed_row<T, L, MULTIWAVE>(exch, p.n_eff, p.mr_np, p.mr_radix, tw_src, t);
-    } else if (!SSQ_ABL(2)) {
+    } else {
       if constexpr (PAIR) fft_pass_pair<T, LOGN, 0, false, false>(v[0], v[1], exch, twr, tw_src, t);
       else if constexpr (C::SPLIT) fft_pass_split<T, LOGN, 0>(v[0], exch_s, twr, tw_it + N, t);   // compact tables behind W_N
       else fft_pass<T, LOGN, 0, false, TW_REGS, MULTIWAVE>(v[0], exch, twr, tw_src, t);
@@ -531,7 +483,6 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
       }
     }
 
-    SSQ_STAMP(2);
     // ---- partner Z[N-k] for the bins this lane owns: k = t + L*q, q < 8 (+ k = N/2 on t == 0)
     cpx<T> zp[NFW][9];
 #pragma unroll
@@ -588,7 +539,6 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
       }
     }
 
-    SSQ_STAMP(3);
 #pragma unroll
     for (int f = 0; f < NFW; ++f) {
       const int fl = cur[f].fl;
@@ -621,7 +571,6 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
             if (EDGE) m *= lane_on;
             if (q == 8) m *= (t == 0) ? 1.0f : 0.0f;                           // bin N/2 lives on lane 0 only
             if constexpr (ANYLEN) m *= (q < 8 && t + L * q < p.n_freqs) ? 1.0f : 0.0f;   // bins of the n_eff-point transform
-            if (SSQ_ABL(8)) m = lane_on;
             const cpx<T> c = LEB ? cpx<T>{p.leb_unit * m, 0.0f} : cpx<T>{S.x * m, S.y * m};   // weight (:292-296)
             cv[q] = c;
             // kk = ceil(w/dw - 1/2) = -floor(1/2 - w/dw), clamped to the last bin (ssq_stft.rs:280-289)
@@ -681,14 +630,12 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
             }
           }
         }
-        SSQ_STAMP(4);
         // fixed-point scatter: every partial sum of this column is bounded by its L1 mass dw*sum|c|;
         // pick 2^e above it and accumulate round(c * dw * 2^(FRAC-e)) with integer LDS atomics
         const T tot = frame_allreduce<T, L, MULTIWAVE>(l1, lane, reinterpret_cast<T*>(exch), t) * p.dw;
         T scale, inv_scale;
         column_scale<T, C::FRAC, C::EMIN>(tot, p.dw, scale, inv_scale);
         if (t == 0 && cur[f].valid) col_scale[fl] = inv_scale;
-        SSQ_STAMP(5);
         char* pre = reinterpret_cast<char*>(tile_re);
         char* pim = reinterpret_cast<char*>(tile_im);
         if constexpr (WKDBG) {
@@ -747,10 +694,8 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
       }
     }
 
-    SSQ_STAMP(6);
-    if (ig == NG - 1 && !SSQ_ABL(64)) {
+    if (ig == NG - 1) {
       __syncthreads();
-      SSQ_STAMP(7);
       // ---- tile read-out: row segments of F frames, re-zeroing as we go ----
       // thread -> (fixed frame f, rows k0, k0 + RSTEP, ...): LDS offsets and the global row stride are
       // loop constants, so an element costs 2 reads + 2 zero-writes + convert + one 8-byte store
@@ -763,7 +708,7 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
         cpx<T>* __restrict__ og =
             p.out + tl.sig * (long long)p.n_freqs * p.n_frames + tl.frame0 + f + (long long)k0 * p.n_frames;
         const long long gstep = (long long)RSTEP * p.n_frames;
-        const bool fvalid = (tl.frame0 + f < p.n_frames) && !SSQ_ABL(32);
+        const bool fvalid = tl.frame0 + f < p.n_frames;
         const T sc = (TXONLY && !WKDBG) ? col_scale[f] : (T)1;
         IT* tr = tile_re + k0 * PITCH + f;
         IT* ti = tile_im + k0 * PITCH + f;
@@ -787,16 +732,8 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
           if (k0 + NFULL * RSTEP < NF) sweep(NFULL, false);
         }
       }
-      SSQ_STAMP(8);
       __syncthreads();
-      SSQ_STAMP(9);
     }
-#ifdef SSQ_STAMPS
-    if (!has_next) {
-      if (p.stamps && lane == 0)
-        for (int i = 0; i < 12; ++i) p.stamps[((long long)blockIdx.x * C::W + wave) * 12 + i] = st_acc[i];
-    }
-#endif
     if (!has_next) break;
     i0 = i1;
     i1 = i2;

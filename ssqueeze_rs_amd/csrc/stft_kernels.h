@@ -36,9 +36,7 @@ struct StftDev {
   T f_last;                // ssq_freqs[n_freqs-1]
   T inv_alpha;             // dSx = unpacked imaginary channel * inv_alpha (exact: power of two)
   T two_pi_eff;            // 2*pi*alpha when phase_bin is fed alpha*dSx (fused), 2*pi otherwise
-  unsigned long long* stamps;  // diagnostic builds only (-DSSQ_STAMPS): per-wave cycle totals per phase
   float keep_big, keep_bias;   // fp32 TX kernel: keep-mask of |Sx|^2 >= gamma^2 as clamp(den*keep_big + keep_bias)
-  int ablate;              // timing experiments only (env SSQ_ABLATE): bit mask of stages to skip; 0 in production
   T leb_unit;              // 1/n_freqs weight of "lebesgue" (ssq_stft.rs:294), without the dw factor
   // Bluestein mode of the fused kernel (n_fft not a power of two: rustfft plans any length, stft.rs:43-44): the frame
   // of n_eff samples is transformed through two FFTs of the kernel's own length m = 2^LOGN >= 2*n_eff - 1.
@@ -129,9 +127,8 @@ __device__ __forceinline__ bool phase_bin_upstream(const StftDev<T>& p, int i, c
   }
 }
 
-#ifndef SSQ_F64_FASTDIV
-#define SSQ_F64_FASTDIV 1     // fp64: the two quotients of the phase / bin by reciprocal + Newton / residual correction (<= 1 ulp)
-#endif                        // instead of IEEE division sequences: 1 605 -> 1 512 vector instructions per frame, batch 64 1.568 -> 1.510 ms
+// fp64: the two quotients of the phase / bin by reciprocal + Newton / residual correction (<= 1 ulp) instead of IEEE
+// division sequences: 1 605 -> 1 512 vector instructions per frame, batch 64 1.568 -> 1.510 ms
 template <typename T>
 __device__ __forceinline__ bool phase_bin(const StftDev<T>& p, int i, cpx<T> S, cpx<T> dS, T& w_out, int& kk_out) {
   const T den = S.x * S.x + S.y * S.y;
@@ -141,20 +138,14 @@ __device__ __forceinline__ bool phase_bin(const StftDev<T>& p, int i, cpx<T> S, 
   if constexpr (sizeof(T) == 4) {
     pd = num * __builtin_amdgcn_rcpf(den * two_pi);
   } else {
-#if SSQ_F64_FASTDIV
-    {
-      // reciprocal by two Newton steps on v_rcp_f64 and one residual correction: <= 1 ulp, 7 instructions instead of the
-      // 11 of the IEEE division sequence (the quotient feeds a bin decision with its own tie window, not an output)
-      const T d = den * two_pi;
-      T r = __builtin_amdgcn_rcp(d);
-      r = __builtin_fma(__builtin_fma(-d, r, (T)1), r, r);
-      r = __builtin_fma(__builtin_fma(-d, r, (T)1), r, r);
-      const T q0 = num * r;
-      pd = __builtin_fma(__builtin_fma(-d, q0, num), r, q0);
-    }
-#else
-    pd = num / (den * two_pi);
-#endif
+    // reciprocal by two Newton steps on v_rcp_f64 and one residual correction: <= 1 ulp, 7 instructions instead of the
+    // 11 of the IEEE division sequence (the quotient feeds a bin decision with its own tie window, not an output)
+    const T d = den * two_pi;
+    T r = __builtin_amdgcn_rcp(d);
+    r = __builtin_fma(__builtin_fma(-d, r, (T)1), r, r);
+    r = __builtin_fma(__builtin_fma(-d, r, (T)1), r, r);
+    const T q0 = num * r;
+    pd = __builtin_fma(__builtin_fma(-d, q0, num), r, q0);
   }
   const T sfs = (T)i * p.sfs_step;
   T w = fabs(sfs - pd);
@@ -170,13 +161,8 @@ __device__ __forceinline__ bool phase_bin(const StftDev<T>& p, int i, cpx<T> S, 
     kk = (u >= (T)last) ? last : (int)__builtin_ceilf(u);
     if (w != w) kk = 0;          // NaN never wins the scan: k stays 0
   } else {
-#if SSQ_F64_FASTDIV
     const T tq0 = w * p.inv_dw;
     const T tq = __builtin_fma(__builtin_fma(-p.dw, tq0, w), p.inv_dw, tq0);
-#else
-    const T tq = w / p.dw;          // (w * inv_dw would do -- the tie window below re-decides exactly -- but measured 19 %
-                                    //  SLOWER in the fp64 fused kernel: profiles/r03_ab_f64_fixed.txt)
-#endif
     const T u = tq - (T)0.5;
     kk = (u >= (T)last) ? last : (int)ceil(u);
     if (w != w) kk = 0;
