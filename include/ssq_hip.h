@@ -164,6 +164,21 @@ int ssq_cwt_host_v(int dtype, const void* x, int64_t batch, int64_t n_signal, in
 int ssq_ssq_cwt_host_v(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
                        const double* scales, int64_t na, double dt, int nv, const double* ssq_freqs_asc, int freq_dist,
                        int padtype, int squeezing, double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk);
+/* Higher-order upstream GMW(gamma, beta), bandpass norm (_gmw.py:267-295, :366-395; _cwt.py:515-608):
+ *   psih(w) = C(w) exp(-beta ln wc + wc^gamma + beta ln w - w^gamma) for w > 0, C(w) = sum_m coeffs[m] (2 w^gamma)^m,
+ * Nyquist bin halved.  Order k is coeffs = k_consts of _gmw_k_constants (order 0: {2}); an averaged order set is ONE
+ * polynomial, the mean of the orders' k_consts padded with zeros (the transform is linear in the wavelet).
+ * coeffs: [n_groups][n_coeffs], 1 <= n_coeffs <= 17 (orders up to 16), finite; variant must include
+ * SSQ_VARIANT_UPSTREAM.  cwt: Wx, dWx [batch][n_groups][na][cols] -- group g is the transform with polynomial g, all
+ * groups from one forward FFT per signal; na * n_groups <= 32767.  ssq_cwt: n_groups must be 1; ssq_freqs_asc comes
+ * from the caller (upstream: the order-0 wavelet's). */
+int ssq_cwt_host_gmwk(int dtype, const void* x, int64_t batch, int64_t n_signal, double gamma, double beta,
+                      const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
+                      double dt, int l1_norm, int padtype, int rpadded, int variant, void* Wx, void* dWx);
+int ssq_ssq_cwt_host_gmwk(int dtype, const void* x, int64_t batch, int64_t n_signal, double gmw_gamma, double gmw_beta,
+                          const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
+                          double dt, int nv, const double* ssq_freqs_asc, int freq_dist, int padtype, int squeezing,
+                          double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk);
 
 /* ---- plans: device-resident batch pipelines -------------------------------- */
 typedef struct ssq_stft_plan ssq_stft_plan;
@@ -214,6 +229,11 @@ int ssq_cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wa
  * the GMW or (mu, -) of the Morlet wavelet; upstream plans pad by p2up and run on the generic transforms */
 int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wavelet, double p0, double p1,
                           const double* scales, int64_t na, double dt, int padtype, int variant);
+/* the higher-order upstream GMW (coeffs, n_coeffs, n_groups as for ssq_cwt_host_gmwk): the plan has na * n_groups rows,
+ * row g * na + i = scales[i] with polynomial g; exec_ssq needs n_groups == 1 */
+int ssq_cwt_plan_create_gmwk(ssq_cwt_plan** plan, int dtype, int64_t n_signal, double gamma, double beta,
+                             const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
+                             double dt, int padtype, int variant);
 int ssq_cwt_plan_destroy(ssq_cwt_plan* plan);
 int64_t ssq_cwt_plan_workspace_bytes(const ssq_cwt_plan* plan, int64_t batch);
 /* cwt: d_Wx/d_dWx [batch][na][cols]; d_dWx may be NULL */

@@ -78,6 +78,13 @@ _SIGNATURES = {
                                      vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]),
     "ssq_cwt_plan_create_v": (C.c_int, [C.POINTER(vp), C.c_int, i64, C.c_int, C.c_double, C.c_double, vp, i64,
                                         C.c_double, C.c_int, C.c_int]),
+    "ssq_cwt_host_gmwk": (C.c_int, [C.c_int, vp, i64, i64, C.c_double, C.c_double, vp, i64, i64, vp, i64, C.c_double,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ssq_ssq_cwt_host_gmwk": (C.c_int, [C.c_int, vp, i64, i64, C.c_double, C.c_double, vp, i64, i64, vp, i64,
+                                        C.c_double, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp,
+                                        vp, vp]),
+    "ssq_cwt_plan_create_gmwk": (C.c_int, [C.POINTER(vp), C.c_int, i64, C.c_double, C.c_double, vp, i64, i64, vp, i64,
+                                           C.c_double, C.c_int, C.c_int]),
     "ssq_stft_plan_destroy": (C.c_int, [vp]),
     "ssq_stft_plan_is_fused": (C.c_int, [vp]),
     "ssq_stft_plan_workspace_bytes": (i64, [vp, i64, C.c_int]),

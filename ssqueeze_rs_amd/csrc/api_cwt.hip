@@ -28,6 +28,10 @@ struct ssq_cwt_plan {
   // ups_freqs / ups_nv: the ascending frequencies and the voices per octave the next ssq exec bins with.
   int variant = 0, table_code = 0;
   double wp0 = 0.0, wp1 = 0.0;
+  // higher-order upstream GMW (wavelet_table_gmwk_kernel): gmwk_groups polynomials of gmwk_n coefficients; the plan's
+  // rows are the groups one after the other (row r: polynomial r / (na / gmwk_groups), scale scales[r]); empty = codes 2, 3
+  std::vector<double> gmwk;
+  int gmwk_n = 0, gmwk_groups = 1;
   std::vector<double> ups_freqs;
   int ups_nv = 0;
   double dt = 1.0;
@@ -100,16 +104,25 @@ double wavelet_support(int wavelet, int dtype) {
 }
 
 // the same bound for the upstream wavelets (codes 2, 3 of wavelet_table_kernel): scan upward from the peak until the
-// value rounds to zero in T
-double upstream_support(int wavelet, double p0, double p1, int dtype) {
+// value rounds to zero in T.  Higher-order GMWs (wavelet_table_gmwk_kernel, poly = c[0..n)) multiply the envelope by
+// C(w) = sum_m c[m] (2 w^gamma)^m, whose tail is wider: the scan adds ln sum_m |c[m]| (2 w^gamma)^m >= ln |C(w)| (an
+// upper bound without the zeros of C, which would stop the scan early).
+double upstream_support(int wavelet, double p0, double p1, int dtype, const double* poly = nullptr, int n_poly = 0) {
   if (wavelet == SSQ_WAVELET_MORLET) return p0 + (dtype == SSQ_F32 ? 15.0 : 39.5);   // exp(-(w - mu)^2 / 2) underflows
   const double wc = std::exp((1.0 / p0) * (std::log(p1) - std::log(p0)));
   const double c0 = -p1 * std::log(wc) + std::pow(wc, p0);
   const double lim = dtype == SSQ_F32 ? -104.0 : -746.0;                             // ln of the smallest denormal
+  auto ln_c = [&](double w) {
+    if (!poly) return 0.0;
+    const double y = 2.0 * std::pow(w, p0);
+    double a = 0.0;
+    for (int m = n_poly - 1; m >= 0; --m) a = a * y + std::fabs(poly[m]);
+    return std::log(a);
+  };
   double w = wc;
   for (int it = 0; it < 100000; ++it) {
     w += 0.01 * wc;
-    if (c0 + p1 * std::log(w) - std::pow(w, p0) < lim) break;
+    if (c0 + p1 * std::log(w) - std::pow(w, p0) + ln_c(w) < lim) break;
   }
   return w;
 }
@@ -232,7 +245,19 @@ int build_tables(ssq_cwt_plan* pl) {
   SSQ_HIP(hipMalloc(&pl->d_psih, sizeof(T) * (size_t)(total > 0 ? total : 1)));
   SSQ_HIP(hipMalloc((void**)&pl->d_psi_off, sizeof(long long) * off.size()));
   SSQ_HIP(hipMemcpy(pl->d_psi_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
-  if (pl->na > 0) {
+  if (pl->na > 0 && !pl->gmwk.empty()) {
+    const int rows = pl->na / pl->gmwk_groups;
+    for (int g = 0; g < pl->gmwk_groups; ++g) {
+      GmwPoly poly;
+      std::memset(&poly, 0, sizeof(poly));
+      poly.n = pl->gmwk_n;
+      for (int m = 0; m < pl->gmwk_n; ++m) poly.c[m] = pl->gmwk[(size_t)g * pl->gmwk_n + m];
+      const long long r0 = (long long)g * rows;
+      SSQ_HIP(launch_wavelet_table_gmwk<T>((T*)pl->d_psih, pl->d_psi_off + r0, pl->d_band + r0, max_band,
+                                           pl->d_scales + r0, rows, pl->P, pl->wp0, pl->wp1, poly, nullptr));
+    }
+    SSQ_HIP(hipDeviceSynchronize());
+  } else if (pl->na > 0) {
     SSQ_HIP(launch_wavelet_table<T>((T*)pl->d_psih, pl->d_psi_off, pl->d_band, max_band, pl->d_scales, pl->na, pl->P,
                                     pl->variant ? pl->table_code : pl->wavelet, nullptr, pl->wp0, pl->wp1));
     SSQ_HIP(hipDeviceSynchronize());
@@ -791,15 +816,28 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
 
 }  // namespace
 
-extern "C" {
-
-int ssq_cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wavelet, const double* scales,
-                        int64_t na, double dt, int padtype) {
-  return ssq_cwt_plan_create_v(plan, dtype, n_signal, wavelet, 0.0, 0.0, scales, na, dt, padtype, SSQ_VARIANT_RUST);
+// arguments of the higher-order GMW entry points: n_groups polynomials of n_coeffs (1 .. kGmwMaxOrder + 1) finite
+// coefficients each, upstream numerics, at most 32767 rows in all
+static int check_gmwk_args(const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
+                           int variant) {
+  if (!(variant & SSQ_VARIANT_UPSTREAM)) SSQ_FAIL("higher-order GMW: variant must include SSQ_VARIANT_UPSTREAM");
+  if (!coeffs) SSQ_FAIL("higher-order GMW: coeffs is NULL");
+  if (n_coeffs < 1 || n_coeffs > kGmwMaxOrder + 1)
+    SSQ_FAIL("higher-order GMW: n_coeffs must be 1 .. " + std::to_string(kGmwMaxOrder + 1) + " (order <= " +
+             std::to_string(kGmwMaxOrder) + ")");
+  if (n_groups < 1) SSQ_FAIL("higher-order GMW: n_groups must be >= 1");
+  if (na < 1 || !scales) SSQ_FAIL("higher-order GMW: bad scales");
+  if (na * n_groups > 32767) SSQ_FAIL("higher-order GMW: na * n_groups above 32767 rows");
+  for (int64_t i = 0; i < n_coeffs * n_groups; ++i)
+    if (!std::isfinite(coeffs[i])) SSQ_FAIL("higher-order GMW: coefficients must be finite");
+  return 0;
 }
 
-int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wavelet, double p0, double p1,
-                          const double* scales, int64_t na, double dt, int padtype, int variant) {
+// plan creation; gmwk != nullptr: the upstream GMW of higher order (n_groups polynomials of gmwk_n coefficients, the
+// scales repeated once per group), else the table codes 0-3
+static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wavelet, double p0, double p1,
+                           const double* scales, int64_t na, double dt, int padtype, int variant, const double* gmwk,
+                           int gmwk_n, int gmwk_groups) {
   if (!plan) SSQ_FAIL("plan is NULL");
   *plan = nullptr;
   if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
@@ -807,6 +845,11 @@ int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int 
   if (na < 0 || (na > 0 && !scales)) SSQ_FAIL("bad scales");
   if (na > 32767) SSQ_FAIL("too many scales (max 32767)");
   ssq_cwt_plan* pl = new ssq_cwt_plan();
+  if (gmwk) {
+    pl->gmwk.assign(gmwk, gmwk + (size_t)gmwk_n * gmwk_groups);
+    pl->gmwk_n = gmwk_n;
+    pl->gmwk_groups = gmwk_groups;
+  }
   pl->dtype = dtype;
   pl->N = n_signal;
   pl->P = host::next_power_of_2(n_signal + n_signal / 2);        // cwt.rs:87
@@ -882,8 +925,15 @@ int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int 
   const char* os_env = std::getenv("SSQ_CWT_OS");               // tests: 0 switches the time-tile family off
   if ((pl->two_step || pl->big) && !(noprune && noprune[0] == '1')) {
     const double h = 2.0 * M_PI / (double)pl->P;                     // base.rs:20
-    const double wmax = ups ? upstream_support(wavelet, p0, p1, dtype) : wavelet_support(wavelet, dtype);
+    std::vector<double> wmax_g((size_t)pl->gmwk_groups);              // per polynomial group (one without gmwk)
+    for (int g = 0; g < pl->gmwk_groups; ++g)
+      wmax_g[(size_t)g] = !ups ? wavelet_support(wavelet, dtype)
+                               : pl->gmwk.empty() ? upstream_support(wavelet, p0, p1, dtype)
+                                                  : upstream_support(wavelet, p0, p1, dtype,
+                                                                     pl->gmwk.data() + (size_t)g * pl->gmwk_n, pl->gmwk_n);
+    const int64_t rows_g = na / pl->gmwk_groups;
     for (int64_t i = 0; i < na; ++i) {
+      const double wmax = wmax_g[(size_t)(i / rows_g)];
       const double a = scales[i];
       if (!(a > 0.0) || !std::isfinite(a)) continue;
       const double kb = wmax / (a * h) + 2.0;                        // psih_i[k] == 0 for k >= kb
@@ -979,6 +1029,30 @@ int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int 
   return 0;
 }
 
+extern "C" {
+
+int ssq_cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wavelet, const double* scales,
+                        int64_t na, double dt, int padtype) {
+  return ssq_cwt_plan_create_v(plan, dtype, n_signal, wavelet, 0.0, 0.0, scales, na, dt, padtype, SSQ_VARIANT_RUST);
+}
+
+int ssq_cwt_plan_create_v(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wavelet, double p0, double p1,
+                          const double* scales, int64_t na, double dt, int padtype, int variant) {
+  return cwt_plan_create(plan, dtype, n_signal, wavelet, p0, p1, scales, na, dt, padtype, variant, nullptr, 0, 1);
+}
+
+int ssq_cwt_plan_create_gmwk(ssq_cwt_plan** plan, int dtype, int64_t n_signal, double gamma, double beta,
+                             const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
+                             double dt, int padtype, int variant) {
+  if (!plan) SSQ_FAIL("plan is NULL");
+  *plan = nullptr;
+  if (int rc = check_gmwk_args(coeffs, n_coeffs, n_groups, scales, na, variant)) return rc;
+  std::vector<double> rows((size_t)(na * n_groups));
+  for (int64_t g = 0; g < n_groups; ++g) std::copy(scales, scales + na, rows.begin() + g * na);
+  return cwt_plan_create(plan, dtype, n_signal, SSQ_WAVELET_GMW, gamma, beta, rows.data(), na * n_groups, dt, padtype,
+                         variant, coeffs, (int)n_coeffs, (int)n_groups);
+}
+
 int ssq_cwt_plan_destroy(ssq_cwt_plan* pl) {
   if (!pl) return 0;
   hipFree(pl->d_psih);
@@ -1040,6 +1114,7 @@ int ssq_cwt_plan_exec_ssq(ssq_cwt_plan* pl, const void* d_x, int64_t batch, int 
   if (!pl) SSQ_FAIL("plan is NULL");
   if (pl->na == 0) SSQ_FAIL("index out of bounds: scales is empty (ssq_cwt.rs:459)");
   if (batch <= 0) return 0;
+  if (pl->gmwk_groups != 1) SSQ_FAIL("ssq_cwt of a higher-order GMW plan needs one polynomial group");
   if (!d_x || !d_Tx) SSQ_FAIL("device pointer is NULL");
   if (!d_workspace || workspace_bytes < ws_layout(pl).total) SSQ_FAIL("workspace too small");
   if (pl->dtype == SSQ_F32)
@@ -1073,9 +1148,12 @@ struct CwtKey {
   int variant = 0;
   double p0 = 0.0, p1 = 0.0;
   std::string env = plan_env();
+  std::vector<double> gmwk = {};   // higher-order GMW polynomials (empty: table codes 0-3) ...
+  int gmwk_groups = 1;             // ... and their count (the rows are scales x groups)
   bool operator==(const CwtKey& o) const {
     return dtype == o.dtype && wavelet == o.wavelet && padtype == o.padtype && n_signal == o.n_signal && dt == o.dt &&
-           scales == o.scales && variant == o.variant && p0 == o.p0 && p1 == o.p1 && env == o.env;
+           scales == o.scales && variant == o.variant && p0 == o.p0 && p1 == o.p1 && env == o.env && gmwk == o.gmwk &&
+           gmwk_groups == o.gmwk_groups;
   }
 };
 struct CachedCwt {
@@ -1103,9 +1181,16 @@ int cached_cwt_plan(const CwtKey& key, ssq_cwt_plan** out) {
     g_cwt_plans.pop_back();
   }
   ssq_cwt_plan* pl = nullptr;
-  if (int rc = ssq_cwt_plan_create_v(&pl, key.dtype, key.n_signal, key.wavelet, key.p0, key.p1, key.scales.data(),
-                                     (int64_t)key.scales.size(), key.dt, key.padtype, key.variant))
+  if (key.gmwk.empty()) {
+    if (int rc = ssq_cwt_plan_create_v(&pl, key.dtype, key.n_signal, key.wavelet, key.p0, key.p1, key.scales.data(),
+                                       (int64_t)key.scales.size(), key.dt, key.padtype, key.variant))
+      return rc;
+  } else if (int rc = ssq_cwt_plan_create_gmwk(&pl, key.dtype, key.n_signal, key.p0, key.p1, key.gmwk.data(),
+                                                (int64_t)key.gmwk.size() / key.gmwk_groups, key.gmwk_groups,
+                                                key.scales.data(), (int64_t)key.scales.size(), key.dt, key.padtype,
+                                                key.variant)) {
     return rc;
+  }
   g_cwt_plans.insert(g_cwt_plans.begin(), CachedCwt{key, pl, dev});
   *out = pl;
   return 0;
@@ -1135,21 +1220,26 @@ void clear_cwt_plans() {
 }  // namespace ssq
 
 
+// gmwk: n_groups higher-order GMW polynomials of n_coeffs coefficients (nullptr: the wavelet codes); the output has
+// na * n_groups rows per signal
 static int cwt_host_impl(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, const double* scales,
                          int64_t na, double dt, int l1_norm, int padtype, int rpadded, void* Wx, void* dWx, int variant,
-                         double p0, double p1) {
+                         double p0, double p1, const double* gmwk = nullptr, int64_t n_coeffs = 0, int64_t n_groups = 1) {
   if (!x || !Wx) SSQ_FAIL("x or Wx is NULL");
   if (batch <= 0) SSQ_FAIL("batch must be positive");
   if (na == 0) return 0;
   if (!scales) SSQ_FAIL("scales is NULL");
   std::lock_guard<std::mutex> lk(hostpath::mutex());
   ssq_cwt_plan* pl = nullptr;
-  if (int rc = cached_cwt_plan(CwtKey{dtype, wavelet, padtype, n_signal, dt, std::vector<double>(scales, scales + na), variant,
-                                      p0, p1}, &pl))
-    return rc;
+  CwtKey key{dtype, wavelet, padtype, n_signal, dt, std::vector<double>(scales, scales + na), variant, p0, p1};
+  if (gmwk) {
+    key.gmwk.assign(gmwk, gmwk + n_coeffs * n_groups);
+    key.gmwk_groups = (int)n_groups;
+  }
+  if (int rc = cached_cwt_plan(key, &pl)) return rc;
   const long long esz = dtype == SSQ_F32 ? 4 : 8;
   const long long cols = rpadded ? pl->P : n_signal;
-  const long long out1 = na * cols * 2 * esz, in1 = n_signal * esz;
+  const long long out1 = (long long)pl->na * cols * 2 * esz, in1 = n_signal * esz;
   void *dx = nullptr, *dW = nullptr, *ddW = nullptr, *ws = nullptr;
   if (int rc = hostpath::scratch(hostpath::SLOT_X, batch * in1, &dx)) return rc;
   if (int rc = hostpath::scratch(hostpath::SLOT_OUT, 2 * out1, &dW)) return rc;
@@ -1201,22 +1291,30 @@ int ssq_cwt_host_v(int dtype, const void* x, int64_t batch, int64_t n_signal, in
                        p1);
 }
 
+int ssq_cwt_host_gmwk(int dtype, const void* x, int64_t batch, int64_t n_signal, double gamma, double beta,
+                      const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
+                      double dt, int l1_norm, int padtype, int rpadded, int variant, void* Wx, void* dWx) {
+  if (int rc = check_gmwk_args(coeffs, n_coeffs, n_groups, scales, na, variant)) return rc;
+  return cwt_host_impl(dtype, x, batch, n_signal, SSQ_WAVELET_GMW, scales, na, dt, l1_norm, padtype, rpadded, Wx, dWx,
+                       variant, gamma, beta, coeffs, n_coeffs, n_groups);
+}
+
 }  // extern "C"
 
 static int ssq_cwt_host_impl(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet,
                              const double* scales, int64_t na, double dt, int freq_dist, int maprange, int padtype,
                              int squeezing, int flipud, double gamma, void* Tx, double* ssq_freqs, void* dbg_Wx,
                              void* dbg_dWx, void* dbg_wk, int variant, double p0, double p1, const double* ups_freqs,
-                             int ups_nv) {
+                             int ups_nv, const double* gmwk = nullptr, int64_t n_coeffs = 0) {
   if (!x || !Tx) SSQ_FAIL("x or Tx is NULL");
   if (batch <= 0) SSQ_FAIL("batch must be positive");
   if (na <= 0) SSQ_FAIL("index out of bounds: scales is empty (ssq_cwt.rs:459)");
   if (!scales) SSQ_FAIL("scales is NULL");
   std::lock_guard<std::mutex> lk(hostpath::mutex());
   ssq_cwt_plan* pl = nullptr;
-  if (int rc = cached_cwt_plan(CwtKey{dtype, wavelet, padtype, n_signal, dt, std::vector<double>(scales, scales + na), variant,
-                                      p0, p1}, &pl))
-    return rc;
+  CwtKey key{dtype, wavelet, padtype, n_signal, dt, std::vector<double>(scales, scales + na), variant, p0, p1};
+  if (gmwk) key.gmwk.assign(gmwk, gmwk + n_coeffs);
+  if (int rc = cached_cwt_plan(key, &pl)) return rc;
   if (variant & SSQ_VARIANT_UPSTREAM) {
     if (!ups_freqs) SSQ_FAIL("ssq_freqs_asc is NULL");
     pl->ups_freqs.assign(ups_freqs, ups_freqs + na);
@@ -1284,6 +1382,17 @@ int ssq_ssq_cwt_host_v(int dtype, const void* x, int64_t batch, int64_t n_signal
   return ssq_cwt_host_impl(dtype, x, batch, n_signal, wavelet, scales, na, dt, freq_dist, SSQ_MAPRANGE_PEAK, padtype,
                            squeezing, (variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, gamma, Tx, nullptr, Wx, dWx, wk, variant, p0,
                            p1, ssq_freqs_asc, nv);
+}
+
+int ssq_ssq_cwt_host_gmwk(int dtype, const void* x, int64_t batch, int64_t n_signal, double gmw_gamma, double gmw_beta,
+                          const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
+                          double dt, int nv, const double* ssq_freqs_asc, int freq_dist, int padtype, int squeezing,
+                          double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk) {
+  if (int rc = check_gmwk_args(coeffs, n_coeffs, n_groups, scales, na, variant)) return rc;
+  if (n_groups != 1) SSQ_FAIL("higher-order GMW ssq_cwt: n_groups must be 1 (one averaged polynomial)");
+  return ssq_cwt_host_impl(dtype, x, batch, n_signal, SSQ_WAVELET_GMW, scales, na, dt, freq_dist, SSQ_MAPRANGE_PEAK,
+                           padtype, squeezing, (variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, gamma, Tx, nullptr, Wx, dWx, wk,
+                           variant, gmw_gamma, gmw_beta, ssq_freqs_asc, nv, coeffs, n_coeffs);
 }
 
 }  // extern "C"

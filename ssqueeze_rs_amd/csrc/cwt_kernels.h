@@ -66,6 +66,19 @@ template <typename T>
 hipError_t launch_wavelet_table(T* psih, const long long* d_off, const int* d_band, int max_band, const double* d_scales,
                                 int na, long long P, int wavelet, hipStream_t stream, double p0 = 0.0, double p1 = 0.0);
 
+// upstream GMW of order k, bandpass norm (old/ssqueezepy/_gmw.py:267-295, :366-395), or the mean over an order set (the
+// table is linear in the polynomial): psih(w) = C(w) exp(-beta ln wc + wc^gamma + beta ln w - w^gamma) for w > 0, with
+// C(w) = sum_m c[m] (2 w^gamma)^m; Nyquist bin halved like code 2.  Order 0 is c = {2}.
+constexpr int kGmwMaxOrder = 16;
+struct GmwPoly {
+  double c[kGmwMaxOrder + 1];
+  int n;                       // coefficients in use, 1 .. kGmwMaxOrder + 1
+};
+template <typename T>
+hipError_t launch_wavelet_table_gmwk(T* psih, const long long* d_off, const int* d_band, int max_band,
+                                     const double* d_scales, int na, long long P, double gamma, double beta,
+                                     const GmwPoly& poly, hipStream_t stream);
+
 // P > 2^24 (beyond the two-step tile transforms): the same pipeline through the batched any-length device FFT
 // (fft_generic.h, Stockham passes through global memory) -- functional for any length the memory holds, not tuned.
 template <typename T>

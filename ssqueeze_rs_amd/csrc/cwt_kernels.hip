@@ -424,6 +424,44 @@ hipError_t launch_wavelet_table(T* psih, const long long* d_off, const int* d_ba
   return hipGetLastError();
 }
 
+// upstream GMW times a polynomial in y = 2 w^gamma (higher orders, order sets averaged into one polynomial): the
+// envelope, guard and Nyquist halving of code 2 above, C(w) by Horner in fp64, rounded once to T.  A kernel of its own so
+// that the code of wavelet_table_kernel stays as it is.
+template <typename T>
+__global__ void wavelet_table_gmwk_kernel(T* __restrict__ psih, const long long* __restrict__ off,
+                                          const int* __restrict__ band, const double* __restrict__ scales, int na,
+                                          long long P, double gamma, double beta, GmwPoly poly) {
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int s = blockIdx.y;
+  if (s >= na || k >= band[s]) return;
+  const double h = 1.0 * (2.0 * 3.14159265358979323846) / (double)P;
+  const double w = scales[s] * ((double)k * h);
+  double v = 0.0;
+  if (w > 0.0) {
+    const double wc = exp((1.0 / gamma) * (log(beta) - log(gamma)));    // morsefreq, _gmw.py:611-657
+    const double wg = pow(w, gamma);
+    const double y = 2.0 * wg;
+    double c = 0.0;
+#pragma unroll
+    for (int m = kGmwMaxOrder; m >= 0; --m)                              // (fixed trip count: constant kernarg offsets)
+      if (m < poly.n) c = c * y + poly.c[m];
+    v = c * exp(-beta * log(wc) + pow(wc, gamma) + beta * log(w) - wg);
+  }
+  if (2 * k == P) v *= 0.5;
+  psih[off[s] + k] = (T)v;
+}
+
+template <typename T>
+hipError_t launch_wavelet_table_gmwk(T* psih, const long long* d_off, const int* d_band, int max_band,
+                                     const double* d_scales, int na, long long P, double gamma, double beta,
+                                     const GmwPoly& poly, hipStream_t stream) {
+  if (poly.n < 1 || poly.n > kGmwMaxOrder + 1) return hipErrorInvalidValue;
+  dim3 grid((unsigned)((max_band + 255) / 256), (unsigned)na, 1);
+  hipLaunchKernelGGL(wavelet_table_gmwk_kernel<T>, grid, dim3(256), 0, stream, psih, d_off, d_band, d_scales, na, P,
+                     gamma, beta, poly);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------ tiny-P direct sums ----
 template <typename T>
 __global__ void cwt_naive_fwd_kernel(CwtDev<T> p) {
@@ -691,6 +729,8 @@ int cwt_tile_rows(int logm) {
   template hipError_t launch_cwt_tile<T>(int, const CwtDev<T>&, hipStream_t);                         \
   template hipError_t launch_wavelet_table<T>(T*, const long long*, const int*, int, const double*, int, long long, int, \
                                               hipStream_t, double, double);                          \
+  template hipError_t launch_wavelet_table_gmwk<T>(T*, const long long*, const int*, int, const double*, int,       \
+                                                   long long, double, double, const GmwPoly&, hipStream_t);        \
   template hipError_t launch_cwt_naive_fwd<T>(const CwtDev<T>&, hipStream_t);                         \
   template hipError_t launch_cwt_big_fwd<T>(const CwtDev<T>&, cpx<T>*, hipStream_t);                  \
   template hipError_t launch_cwt_big_inv<T>(const CwtDev<T>&, cpx<T>*, hipStream_t);                  \

@@ -11,6 +11,11 @@ Supported subset (anything else raises ValueError naming the option):
   * `window`: ndarray (upstream's default DPSS / named windows come from scipy.signal, which callers can pass in);
   * `scales`: explicit exponentially spaced ndarray ('log' scaletype; the automatic 'log-piecewise' bounds are not built);
   * wavelets 'gmw' (gamma, beta; bandpass norm, order 0) and 'morlet' (mu) -- names, or (name, {params});
+  * higher-order GMWs through `cwt_higher_order` (_cwt.py:515-608), `ssq_cwt(order=)` and `cwt(order=<tuple / list /
+    range>, average=)`: orders 0 .. 16, bandpass norm (`l1_norm=True`); an averaged order set is one transform with the
+    averaged wavelet (the transform is linear in it), `average=False` runs every order from one forward FFT per signal.
+    `cwt` keeps rejecting a bare int `order` other than 0 (the suite pins that ValueError); `order=(k,)` or
+    `cwt_higher_order(x, order=k)` is the same transform;
   * difftype 'trig'; squeezing 'sum' / 'lebesgue'; padtype 'reflect' / 'zero'; full inverses (no component curves);
   * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
     serial backward trace (`parallel` is accepted and ignored).
@@ -25,6 +30,8 @@ old/tests/ridge_extraction_test.py:17-26 (`test_basic`).
 from __future__ import annotations
 
 import ctypes as C
+import math
+import warnings
 
 import numpy as np
 
@@ -34,6 +41,7 @@ from ._rs import _call, _cdtype, _ptr
 
 VARIANT_UPSTREAM, VARIANT_MODULATED, VARIANT_FLIPUD = 1, 2, 4
 EPS32, EPS64 = float(np.finfo(np.float32).eps), float(np.finfo(np.float64).eps)
+GMW_MAX_ORDER = 16                      # the highest GMW order the library builds (csrc/cwt_kernels.h: kGmwMaxOrder)
 
 
 # ------------------------------------------------------------------------------------------------------- helpers ----
@@ -79,6 +87,64 @@ def _wavelet(wavelet):
     if name == "morlet":
         return WAVELET["morlet"], float(kw.get("mu", 13.4)), 0.0
     raise ValueError(f"wavelet {name!r}: the MI355X engine builds 'gmw' and 'morlet'")
+
+
+def gmw_k_constants(gamma, beta, k):
+    """_gmw.py:366-395 (`_gmw_k_constants`, bandpass norm) in fp64: the coefficients of the order-k GMW's polynomial in
+    y = 2 w^gamma, psih_k(w) = sum_m k_consts[m] y^m * exp(-beta ln wc + wc^gamma + beta ln w - w^gamma)."""
+    gamma, beta, k = float(gamma), float(beta), int(k)
+    r = (2 * beta + 1) / gamma
+    c = r - 1
+    coeff = math.sqrt(math.exp(math.lgamma(r) + math.lgamma(k + 1) - math.lgamma(k + r)))
+    out = np.zeros(k + 1, dtype=np.float64)
+    for m in range(k + 1):
+        fact = math.exp(math.lgamma(k + c + 1) - math.lgamma(c + m + 1) - math.lgamma(k - m + 1))
+        out[m] = (-1) ** m * fact / math.gamma(m + 1)
+    return out * coeff * 2
+
+
+def gmw_order_coefficients(gamma, beta, orders, average=True):
+    """The polynomials the library evaluates for the GMW orders `orders`: [len(orders), n] float64, each order's
+    `gmw_k_constants` padded with zeros to n = max(orders) + 1; with `average`, [1, n]: their mean over the orders (the
+    averaged wavelet, whose transform is the mean of the orders' transforms)."""
+    orders = [int(k) for k in orders]
+    n = max(orders) + 1
+    polys = np.zeros((len(orders), n), dtype=np.float64)
+    for i, k in enumerate(orders):
+        polys[i, :k + 1] = gmw_k_constants(gamma, beta, k)
+    return polys.mean(axis=0, keepdims=True) if average else polys
+
+
+def _wavelet_name(wavelet):
+    return wavelet if isinstance(wavelet, str) else wavelet[0]
+
+
+def _order_args(order, average, wavelet, l1_norm=True, higher=False):
+    """_cwt.py:236-241 and cwt_higher_order's _process_args (:566-590) -> None for the plain transform, else
+    (orders, average) with upstream's rules: an int order is one transform; a tuple / list / range averages unless
+    `average` is False; a single order with `average=True` warns and does not average.  `higher`: cwt_higher_order's
+    own entry, which takes every order (0 included) through the GMW check."""
+    is_set = isinstance(order, (tuple, list, range))
+    orders = tuple(order) if is_set else (order,)
+    for k in orders:
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"`order` must be an int or a tuple / list / range of ints (got {order!r})")
+        if k < 0:
+            raise ValueError(f"`order` must be >= 0 (got {order!r})")
+        if k > GMW_MAX_ORDER:
+            raise ValueError(f"`order` above {GMW_MAX_ORDER} is not built (got {order!r})")
+    if not orders:
+        raise ValueError("`order` is empty")
+    if not (is_set or higher) and orders[0] == 0:
+        return None                                        # _cwt.py:236: `order > 0` only
+    if _wavelet_name(wavelet) != "gmw":
+        raise ValueError("`order`: the wavelet must be GMW for higher-order transforms (got %r)" % (wavelet,))
+    if not l1_norm and any(k != 0 for k in orders):
+        raise ValueError("`order` with `l1_norm=False`: upstream's energy-normalised GMW is not built")
+    if len(orders) == 1 and average:
+        warnings.warn("`average` ignored with single `order`")
+        average = False
+    return tuple(int(k) for k in orders), bool(average or (average is None and is_set))
 
 
 def _scales(scales):
@@ -239,9 +305,32 @@ def cwt(x, wavelet="gmw", scales="log-piecewise", fs=None, t=None, nv=32, l1_nor
         nan_checks=None, patience=0):
     """ssqueezepy.cwt (old/ssqueezepy/_cwt.py:12-318) -> (Wx, scales[, dWx]).  `scales` must be an explicit array (the
     default string asks for upstream's automatic bounds, which are not built); `vectorized`, `astensor`, `cache_wavelet`,
-    `nan_checks`, `patience` select code paths with identical numbers upstream and are accepted and unused."""
-    if order != 0 or average is not None:
-        raise ValueError("higher-order GMWs (`order`, `average`) are not built")
+    `nan_checks`, `patience` select code paths with identical numbers upstream and are accepted and unused.
+    `order` / `average`: an order set (tuple / list / range) gives higher-order GMWs as `cwt_higher_order` -- the mean
+    over the orders, or a list of arrays (one per order) with `average=False`.  A bare int `order` other than 0 raises
+    ValueError, as it always has here: `order=(k,)` or `cwt_higher_order(x, order=k)` computes order k."""
+    if isinstance(order, (int, np.integer)) and not isinstance(order, (bool, np.bool_)) and order > 0:
+        raise ValueError("`cwt`: a bare int `order` other than 0 is not accepted; pass `order=(k,)` or call "
+                         "`cwt_higher_order(x, order=k)`")
+    return _cwt(x, wavelet, scales, fs, t, nv, l1_norm, derivative, padtype, rpadded,
+                _order_args(order, average, wavelet, l1_norm))
+
+
+def cwt_higher_order(x, wavelet="gmw", order=1, average=None, astensor=True, **kw):
+    """ssqueezepy.cwt_higher_order (old/ssqueezepy/_cwt.py:515-608) -> (Wx, scales[, dWx]); `kw` are `cwt`'s.
+    Wx (and dWx) is the mean over the orders, or a list with one array per order (`average=False`)."""
+    kw = dict(kw)
+    for k in ("vectorized", "cache_wavelet", "nan_checks", "patience"):
+        kw.pop(k, None)
+    args = _order_args(order, average, wavelet, kw.get("l1_norm", True), higher=True)
+    a = [kw.pop(k, d) for k, d in (("scales", "log-piecewise"), ("fs", None), ("t", None), ("nv", 32), ("l1_norm", True),
+                                   ("derivative", False), ("padtype", "reflect"), ("rpadded", False))]
+    if kw:
+        raise TypeError(f"cwt_higher_order: unexpected keyword arguments {sorted(kw)}")
+    return _cwt(x, wavelet, *a, args)
+
+
+def _cwt(x, wavelet, scales, fs, t, nv, l1_norm, derivative, padtype, rpadded, order_args):
     if isinstance(scales, np.ndarray):
         nv = None                                            # _cwt.py:226-227
     lib = _lib.load()
@@ -252,16 +341,32 @@ def cwt(x, wavelet="gmw", scales="log-piecewise", fs=None, t=None, nv=32, l1_nor
     s, _nv = _scales(scales)
     if nv is not None and nv != _nv:
         raise Exception("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))   # cwt_utils.py:229-231
+    orders, average = order_args if order_args else ((0,), True)
+    if all(k == 0 for k in orders) and (average or len(orders) == 1):
+        order_args = None                                  # the order-0 wavelet itself: the plain table (code 2)
+    polys = gmw_order_coefficients(p0, p1, orders, average) if order_args else None
+    groups = 1 if polys is None else polys.shape[0]
     _lib.require_gpu()
     cols = p2up(N)[0] if rpadded else N
-    shape = (batch, len(s), cols)
+    shape = (batch, groups * len(s), cols)
     Wx = _lib.pinned_empty(shape, _cdtype(code))
     dWx = _lib.pinned_empty(shape, _cdtype(code)) if derivative else None
-    _call(lib.ssq_cwt_host_v(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, int(bool(l1_norm)),
-                             _pad_code(padtype), int(bool(rpadded)), VARIANT_UPSTREAM, _ptr(Wx), _ptr(dWx)))
+    if polys is None:
+        _call(lib.ssq_cwt_host_v(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, int(bool(l1_norm)),
+                                 _pad_code(padtype), int(bool(rpadded)), VARIANT_UPSTREAM, _ptr(Wx), _ptr(dWx)))
+    else:
+        polys = np.ascontiguousarray(polys)
+        _call(lib.ssq_cwt_host_gmwk(code, _ptr(xa), batch, N, p0, p1, _ptr(polys), polys.shape[1], groups, _ptr(s),
+                                    len(s), dt, int(bool(l1_norm)), _pad_code(padtype), int(bool(rpadded)),
+                                    VARIANT_UPSTREAM, _ptr(Wx), _ptr(dWx)))
     sc = s.astype(np.float32 if code == SSQ_F32 else np.float64)
-    if not batched:
-        Wx, dWx = Wx[0], (dWx[0] if derivative else None)
+
+    def split(A):                                          # [batch, groups * na, cols] -> per order, batch axis dropped
+        A = A.reshape(batch, groups, len(s), cols)
+        parts = [A[:, g] if batched else A[0, g] for g in range(groups)]
+        return parts if groups > 1 else parts[0]
+    Wx = split(Wx)
+    dWx = split(dWx) if derivative else None
     return (Wx, sc, dWx) if derivative else (Wx, sc)
 
 
@@ -293,10 +398,15 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
             cache_wavelet=None, get_w=False, get_dWx=False):
     """ssqueezepy.ssq_cwt (old/ssqueezepy/_ssq_cwt.py:12-311) -> (Tx, Wx, ssq_freqs, scales[, w][, dWx])."""
     lib = _lib.load()
-    if difftype != "trig" or order != 0:
-        raise ValueError("only difftype='trig', order=0 are built")
+    if difftype != "trig":
+        raise ValueError("only difftype='trig' is built")
     if squeezing not in SQUEEZE:
         raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
+    # _ssq_cwt.py:228-241: Wx of the order (set) averaged, dWx by `trigdiff` of the padded Wx -- the derivative transform of
+    # the averaged wavelet up to rounding; ssq_freqs below stay the order-0 wavelet's (ssqueeze gets `wavelet` itself)
+    order_args = _order_args(order, isinstance(order, (tuple, list, range)), wavelet)
+    if order_args and all(k == 0 for k in order_args[0]):
+        order_args = None
     xa, batched, code = _signal(x)
     batch, N = xa.shape
     dt = _dt(fs, t, N)
@@ -315,10 +425,17 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
     dWx = _lib.pinned_empty(shape, cdt) if get_dWx else None
     wk = _lib.pinned_empty(shape, cdt) if get_w else None
     variant = VARIANT_UPSTREAM | (VARIANT_FLIPUD if flipud else 0)
-    _call(lib.ssq_ssq_cwt_host_v(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, _nv, _ptr(f_asc),
-                                 0 if scaletype == "log" else 1, _pad_code(padtype), SQUEEZE[squeezing],
-                                 -1.0 if gamma is None else float(gamma), variant, _ptr(Tx), _ptr(Wx), _ptr(dWx),
-                                 _ptr(wk)))
+    if order_args is None:
+        _call(lib.ssq_ssq_cwt_host_v(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, _nv, _ptr(f_asc),
+                                     0 if scaletype == "log" else 1, _pad_code(padtype), SQUEEZE[squeezing],
+                                     -1.0 if gamma is None else float(gamma), variant, _ptr(Tx), _ptr(Wx), _ptr(dWx),
+                                     _ptr(wk)))
+    else:
+        poly = np.ascontiguousarray(gmw_order_coefficients(p0, p1, *order_args))
+        _call(lib.ssq_ssq_cwt_host_gmwk(code, _ptr(xa), batch, N, p0, p1, _ptr(poly), poly.shape[1], 1, _ptr(s), len(s),
+                                        dt, _nv, _ptr(f_asc), 0 if scaletype == "log" else 1, _pad_code(padtype),
+                                        SQUEEZE[squeezing], -1.0 if gamma is None else float(gamma), variant, _ptr(Tx),
+                                        _ptr(Wx), _ptr(dWx), _ptr(wk)))
     rdt = np.float32 if code == SSQ_F32 else np.float64
     out = [Tx if batched else Tx[0], Wx if batched else Wx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]   # ssqueezing.py:199-205
     if get_w:
