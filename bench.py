@@ -2,6 +2,7 @@
 """bench.py -- headline benchmark: TF-bins/s of ssq_stft (n_fft=1024, hop=256, fp32) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --total-batch B] [--gather] [--dump-outputs DIR]
+                    [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 One "step" = one pass of the fused ssq_stft hot path over one batch of synthetic signals of 2^20 samples resident
@@ -15,8 +16,13 @@ The number of GPUs is the WORLD SIZE, never the flag: under torch.distributed.ru
 processes itself (fresh children through torch.distributed.run, before this process touches any GPU) and
 relays their JSON line and exit code.
 
-Outside the timed region the bench checks what it timed: three signals of the batch are copied back and compared
-bitwise with the single-signal path of the same library, and signal 0 with the committed BASELINE-config-2
+A plain run does only what the headline figure needs: it sets up, runs in, warms up, times the K steps, writes its
+outputs if asked and prints the line.  `--full` adds everything else the bench measures or checks: the validation
+below, the secondary legs (one C2 signal, fp64, the C4 / C5 ssq_cwt legs) and the CPU baselines, each of them still
+skipped by its own `--no-*` option.
+
+With `--full` the bench checks what it times, outside the timed region: three signals of the batch are copied back and
+compared bitwise with the single-signal path of the same library, and signal 0 with the committed BASELINE-config-2
 checksums (tests/golden/c2_summary.npz) -> "validated".
 
 `--dump-outputs DIR` writes what the last timed step left in Tx (rank 0's signals) as .npy files, float32 with a
@@ -61,13 +67,16 @@ def parse_args(argv=None):
     ap.add_argument("--hop", type=int, default=256)
     ap.add_argument("--distinct", type=int, default=0,
                     help="distinct synthetic signals per rank (0 = all of them distinct); fewer are tiled to the batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the fp64 and one-signal (C2) secondary legs")
-    ap.add_argument("--no-validate", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also validate what is timed and run the secondary legs and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary legs")
+    ap.add_argument("--no-validate", action="store_true", help="with --full: skip the validation")
     ap.add_argument("--settle-ms", type=float, default=80.0,
                     help="untimed run-in of the same step before the W warm-up steps (reported as settle_ms): the first "
                          "~30 ms of this kernel after any gap run 5-8 %% slower than its steady state (clock ramp)")
-    ap.add_argument("--no-c5", action="store_true", help="skip the fp64 BASELINE-config-5 secondary legs (17 - 170 GB)")
+    ap.add_argument("--no-c5", action="store_true",
+                    help="with --full: skip the fp64 BASELINE-config-5 secondary legs (17 - 170 GB)")
     ap.add_argument("--gather", action="store_true", help="also time the optional RCCL all_gather of the Tx shards")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write rank 0's Tx of the last step (whole signals + a seeded sample) "
@@ -150,9 +159,22 @@ def measured_traffic(B, log2n, n_fft, hop, file=None):
         return None
 
 
+SYNTH_THREADS = 16                 # host threads that generate the inputs (NumPy releases the GIL in its loops)
+
+
 def synth_rows(first, count, N, dtype):
+    """Signals first .. first + count - 1 as [count, N] rows, generated on up to SYNTH_THREADS host threads: each row
+    is synth_signal's own result, so the rows do not depend on the number of threads."""
+    from concurrent.futures import ThreadPoolExecutor
     from ssqueeze_rs_amd.synth import synth_signal   # synthetic workload generator (SURVEY §8d)
-    return np.stack([synth_signal(N, first + b, dtype) for b in range(count)])
+    out = np.empty((count, N), dtype=dtype)
+
+    def fill(b):
+        out[b] = synth_signal(N, first + b, dtype)
+
+    with ThreadPoolExecutor(max_workers=max(1, min(count, SYNTH_THREADS, len(os.sched_getaffinity(0))))) as ex:
+        list(ex.map(fill, range(count)))
+    return out
 
 
 def cpu_baseline(N, n_fft, hop, budget_s=20.0):
@@ -551,10 +573,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Check what is about to be timed (outside the timed region, and before it: the check's own launches and copies
-    # also bring the device out of its idle clocks before the W warm-up steps).
+    # --full: check what is about to be timed (outside the timed region, and before it: the check's own launches and
+    # copies also bring the device out of its idle clocks before the W warm-up steps).
     validation = None
-    if not args.no_validate:
+    if args.full and not args.no_validate:
         validation = leg.validate(first)
         if use_dist:
             okt = torch.tensor([1 if validation["ok"] else 0], device="cuda", dtype=torch.int32)
@@ -572,10 +594,11 @@ def main():
     if args.dump_outputs and rank == 0:
         dumped = dump_outputs(args.dump_outputs, out_t, leg)
 
-    # Secondary legs (N = 1 only) run AFTER the headline's timed region (round 2 ran them before it, which lengthened the
-    # undisclosed warm-up): the only load in front of the K timed steps is the disclosed run-in (settle_ms) + W steps.
+    # Secondary legs (--full, N = 1 only) run AFTER the headline's timed region (round 2 ran them before it, which
+    # lengthened the undisclosed warm-up): the only load in front of the K timed steps is the disclosed run-in
+    # (settle_ms) + W steps.
     sec = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         sec = {}
         # (1) BASELINE config 2: ONE signal (latency-bound: one launch of the edge-capable kernel)
         one = Leg(lib, _lib, np.float32, N, n_fft, hop, 1, stream)
@@ -717,7 +740,7 @@ def main():
     ok = validation is None or validation.get("ok_all_ranks", validation["ok"])
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(N, n_fft, hop)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(line) + "\n").encode())

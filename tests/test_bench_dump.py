@@ -58,7 +58,7 @@ def test_bench_dump_matches_the_batch_front_end(tmp_path):
     B, log2n, steps = 4, 16, 3
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
                         "--warmup", "1", "--batch", str(B), "--log2n", str(log2n), "--settle-ms", "0",
-                        "--no-secondary", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                        "--full", "--no-secondary", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
