@@ -34,6 +34,9 @@ enum { SSQ_PAD_REFLECT = 0, SSQ_PAD_ZERO = 1 };          /* stft_utils.rs:19-65,
 enum { SSQ_SQUEEZE_SUM = 0, SSQ_SQUEEZE_LEBESGUE = 1 };  /* ssq_stft.rs:292-296, ssq_cwt.rs:199-206 */
 enum { SSQ_WAVELET_GMW = 0, SSQ_WAVELET_MORLET = 1 };    /* cwt.rs:496-543 */
 enum { SSQ_FREQS_LOG = 0, SSQ_FREQS_LINEAR = 1 };        /* ssq_cwt.rs:56-112 */
+/* upstream only (ssq_ssq_cwt_host_rows, _gmwk_rows): frequencies exponential on two segments (ssqueezing.py:247-283),
+ * binned by algos.py:860-877 */
+enum { SSQ_FREQS_LOG_PIECEWISE = 2 };
 enum { SSQ_MAPRANGE_PEAK = 0, SSQ_MAPRANGE_MAXIMAL = 1 };/* ssq_cwt.rs:450-461 */
 /* numerics variant of a plan / host call (bit flags).  0 = the Rust reference (rust/src/spectral/ *.rs).
  * SSQ_VARIANT_UPSTREAM = the vendored upstream ssqueezepy the Rust crate was derived from (SURVEY 8(f)-4,
@@ -152,6 +155,9 @@ int ssq_upstream_adm(int wavelet, double p0, double p1, int which_cwt, double* o
 int ssq_upstream_center_frequency(int wavelet, double p0, double p1, double scale, int64_t n_padded, double* wc);
 /* utils/common.py:32-51: padded length 2^(1 + round(log2 n)), left pad n1 >= right pad n2 */
 int ssq_upstream_p2up(int64_t n_signal, int64_t* n_up, int64_t* n1, int64_t* n2);
+/* wavelet.fn of the upstream wavelet at scale 1 (wavelets.py:409-523; GMW bandpass order 0: p0 = gamma, p1 = beta;
+ * Morlet: p0 = mu), fp64, for the scale search of utils/cwt_utils.py: out[i] = psih(w[i]), i < n.  Host only. */
+int ssq_upstream_psih(int wavelet, double p0, double p1, const double* w, int64_t n, double* out);
 /* ssqueezepy.cwt       old/ssqueezepy/_cwt.py:12-318 with explicit scales.  Wx, dWx: [batch][na][cols],
  * cols = rpadded ? n_up : N; dWx may be NULL. */
 int ssq_cwt_host_v(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
@@ -179,6 +185,24 @@ int ssq_ssq_cwt_host_gmwk(int dtype, const void* x, int64_t batch, int64_t n_sig
                           const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
                           double dt, int nv, const double* ssq_freqs_asc, int freq_dist, int padtype, int squeezing,
                           double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk);
+/* ssq_ssq_cwt_host_v / _gmwk on any upstream scale grid (ssqueezing.py:122-133, algos.py:860-897); the two above are
+ * these with row_const[i] = ln2/nv.  variant must include SSQ_VARIANT_UPSTREAM.
+ *   row_const: [na] finite, the weight of row i, out[k, j] += Wx[i, j] * row_const[i] (squeezing 'lebesgue':
+ *              row_const[i] / na): ln2 / nv[i] for 'log' / 'log-piecewise' scales (nv per row: nv_from_scales),
+ *              (s[1] - s[0]) / s[i] for 'linear' scales;
+ *   freq_kind: SSQ_FREQS_LOG, SSQ_FREQS_LINEAR or SSQ_FREQS_LOG_PIECEWISE -- the bin rule of ssq_freqs_asc;
+ *   freq_transition: SSQ_FREQS_LOG_PIECEWISE only (ignored otherwise): the index idx, 2 <= idx <= na-1, splitting
+ *              ssq_freqs_asc into [:idx] and [idx:] (logscale_transition_idx, cwt_utils.py:375-395, found by the caller
+ *              on the frequencies in their own dtype); the second segment's bins start at row idx-1 (algos.py:364-370). */
+int ssq_ssq_cwt_host_rows(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                          const double* scales, int64_t na, double dt, const double* row_const,
+                          const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition, int padtype,
+                          int squeezing, double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk);
+int ssq_ssq_cwt_host_gmwk_rows(int dtype, const void* x, int64_t batch, int64_t n_signal, double gmw_gamma,
+                               double gmw_beta, const double* coeffs, int64_t n_coeffs, int64_t n_groups,
+                               const double* scales, int64_t na, double dt, const double* row_const,
+                               const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition, int padtype,
+                               int squeezing, double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk);
 
 /* ---- plans: device-resident batch pipelines -------------------------------- */
 typedef struct ssq_stft_plan ssq_stft_plan;

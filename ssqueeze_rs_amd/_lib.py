@@ -72,6 +72,7 @@ _SIGNATURES = {
     "ssq_upstream_adm": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "ssq_upstream_center_frequency": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, i64, C.POINTER(C.c_double)]),
     "ssq_upstream_p2up": (C.c_int, [i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+    "ssq_upstream_psih": (C.c_int, [C.c_int, C.c_double, C.c_double, vp, i64, vp]),
     "ssq_cwt_host_v": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, C.c_double, C.c_int,
                                  C.c_int, C.c_int, C.c_int, vp, vp]),
     "ssq_ssq_cwt_host_v": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, C.c_double, C.c_int,
@@ -83,6 +84,11 @@ _SIGNATURES = {
     "ssq_ssq_cwt_host_gmwk": (C.c_int, [C.c_int, vp, i64, i64, C.c_double, C.c_double, vp, i64, i64, vp, i64,
                                         C.c_double, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp,
                                         vp, vp]),
+    "ssq_ssq_cwt_host_rows": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, C.c_double,
+                                        vp, vp, C.c_int, i64, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]),
+    "ssq_ssq_cwt_host_gmwk_rows": (C.c_int, [C.c_int, vp, i64, i64, C.c_double, C.c_double, vp, i64, i64, vp, i64,
+                                             C.c_double, vp, vp, C.c_int, i64, C.c_int, C.c_int, C.c_double, C.c_int,
+                                             vp, vp, vp, vp]),
     "ssq_cwt_plan_create_gmwk": (C.c_int, [C.POINTER(vp), C.c_int, i64, C.c_double, C.c_double, vp, i64, i64, vp, i64,
                                            C.c_double, C.c_int, C.c_int]),
     "ssq_stft_plan_destroy": (C.c_int, [vp]),

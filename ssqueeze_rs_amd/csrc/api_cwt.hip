@@ -1,6 +1,7 @@
 // api_cwt.hip -- CWT-family plans and host entry points of the C-ABI (include/ssq_hip.h).
 // Replaces the PyO3 functions `cwt` / `cwt_simd` (rust/src/spectral/cwt.rs:46-144,
 // cwt_simd.rs:52-150) and `ssq_cwt` (rust/src/spectral/ssq_cwt.rs:244-493).
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -25,7 +26,9 @@ struct ssq_cwt_plan {
   int wavelet = 0, padtype = 0, na = 0;
   // upstream-parity mode (SSQ_VARIANT_UPSTREAM; old/ssqueezepy): p2up padding, normalised wavelets (wavelet table codes
   // 2 = GMW(gamma = wp0, beta = wp1), 3 = Morlet(mu = wp0)) with a halved Nyquist bin, the generic transforms only.
-  // ups_freqs / ups_nv: the ascending frequencies and the voices per octave the next ssq exec bins with.
+  // ups_freqs / ups_const: the ascending frequencies and the row weights (ssqueezing.py:122-133) the next ssq exec bins
+  // with; ups_rows: the weights differ between rows or the bins are log-piecewise (cwt_reassign_rows_kernel, weights in
+  // d_ups_const); ups_idx: the transition of log-piecewise frequencies (ups_freqs[:idx], ups_freqs[idx:])
   int variant = 0, table_code = 0;
   double wp0 = 0.0, wp1 = 0.0;
   // higher-order upstream GMW (wavelet_table_gmwk_kernel): gmwk_groups polynomials of gmwk_n coefficients; the plan's
@@ -33,7 +36,10 @@ struct ssq_cwt_plan {
   std::vector<double> gmwk;
   int gmwk_n = 0, gmwk_groups = 1;
   std::vector<double> ups_freqs;
-  int ups_nv = 0;
+  std::vector<double> ups_const;
+  bool ups_rows = false;
+  int ups_idx = 0;
+  void* d_ups_const = nullptr; // [na] T
   double dt = 1.0;
   std::vector<double> scales;
   void* d_psih = nullptr;      // wavelet table: scale s at psi_off[s], band[s] entries of T (zero beyond: not stored)
@@ -639,7 +645,8 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
   std::vector<double> f((size_t)pl->na);
   const bool ups = pl->variant != 0;
   if (ups) {
-    if ((int)pl->ups_freqs.size() != pl->na || pl->ups_nv < 1) SSQ_FAIL("upstream ssq exec: frequencies / nv not set");
+    if ((int)pl->ups_freqs.size() != pl->na || (int)pl->ups_const.size() != pl->na)
+      SSQ_FAIL("upstream ssq exec: frequencies / row weights not set");
     f = pl->ups_freqs;
   } else if (int rc = ssq_cwt_ssq_freqs(pl->scales.data(), pl->na, pl->N, pl->dt, maprange, freq_dist, f.data())) {
     return rc;
@@ -647,20 +654,33 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
   const int n = pl->na;
   CwtSsqDev<T> q;
   std::memset(&q, 0, sizeof(q));
+  CwtRowsDev<T> rows{};
   q.N = pl->N;
   q.na = n;
   q.is_log = (n > 1 && (f[1] / f[0] > 1.1)) ? 1 : 0;                      // ssq_cwt.rs:135-139
   if (ups) {
     // old/ssqueezepy/algos.py:356-363 (log: vlmin = log2 v[0], dvl = log2 v[1] - log2 v[0]) and :87-90 (linear)
     if (n < 2) SSQ_FAIL("upstream ssq_cwt needs at least 2 scales");
-    q.is_log = freq_dist == SSQ_FREQS_LOG ? 1 : 0;
+    if (freq_dist != SSQ_FREQS_LOG && freq_dist != SSQ_FREQS_LINEAR && freq_dist != SSQ_FREQS_LOG_PIECEWISE)
+      SSQ_FAIL("upstream ssq_cwt: freq_kind must be SSQ_FREQS_LOG, _LINEAR or _LOG_PIECEWISE");
+    q.is_log = freq_dist != SSQ_FREQS_LINEAR ? 1 : 0;
     const double vmin = q.is_log ? std::log2(f[0]) : f[0];
-    const double dv = q.is_log ? std::log2(f[1]) - std::log2(f[0]) : f[1] - f[0];
+    double dv = q.is_log ? std::log2(f[1]) - std::log2(f[0]) : f[1] - f[0];
+    if (freq_dist == SSQ_FREQS_LOG_PIECEWISE) {                           // algos.py:364-370
+      const int idx = pl->ups_idx;                                        // found by the caller in the input's dtype
+      if (idx < 2 || idx > n - 1) SSQ_FAIL("upstream ssq_cwt: freq_transition must be 2 .. na-1 for log-piecewise");
+      rows.piecewise = 1;
+      rows.idx1 = idx - 1;
+      rows.vlmin1 = (T)std::log2(f[(size_t)idx - 1]);
+      rows.dvl1 = (T)std::max(std::log2(f[(size_t)idx]) - std::log2(f[(size_t)idx - 1]), 2.220446049250313e-16);
+      dv = std::max(dv, 2.220446049250313e-16);                             // _ensure_nonzero_nonnegative (:340-347)
+    }
     q.bin_min = (T)vmin;
     q.bin_step = (T)dv;
     q.inv_bin_step = (T)(1.0 / dv);
     q.variant = 1;
-    q.tx_const = (T)(std::log(2.0) / (double)pl->ups_nv);                // ssqueezing.py:122-124
+    q.tx_const = (T)pl->ups_const[0];                                     // ssqueezing.py:122-133
+    rows.row_const = (const T*)pl->d_ups_const;
   } else if (q.is_log) {                                                  // :142-149
     const double lmin = std::log2(f[0]);
     const double lstep = n > 1 ? (std::log2(f[n - 1]) - lmin) / (double)(n - 1) : 1.0;
@@ -791,7 +811,7 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
           while (s1 < n && !pl->os_mask[(size_t)s1]) ++s1;
           q.s_begin = s0;
           q.s_end = s1;
-          SSQ_HIP(launch_cwt_reassign<T>(q, st, false));
+          SSQ_HIP(launch_cwt_reassign<T>(q, st, false, ups && pl->ups_rows ? &rows : nullptr));
           s0 = s1;
         }
       }
@@ -802,7 +822,7 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
       q.s_begin = 0;
       q.s_end = n;
       if (sweep) SSQ_HIP(launch_cwt_reassign_sweep<T>(q, st, self_zero));
-      else SSQ_HIP(launch_cwt_reassign<T>(q, st, !side_clear));
+      else SSQ_HIP(launch_cwt_reassign<T>(q, st, !side_clear, ups && pl->ups_rows ? &rows : nullptr));
     }
     if (d_dbg_Wx)
       SSQ_HIP(hipMemcpyAsync((cpx<T>*)d_dbg_Wx + b * plane, W, (size_t)plane * sizeof(cpx<T>),
@@ -1082,6 +1102,7 @@ int ssq_cwt_plan_destroy(ssq_cwt_plan* pl) {
   hipFree(pl->d_xa_off);
   hipFree(pl->d_xa_int);
   hipFree(pl->d_xa_scale);
+  hipFree(pl->d_ups_const);
   if (pl->ev_fork) (void)hipEventDestroy(pl->ev_fork);
   if (pl->ev_join) (void)hipEventDestroy(pl->ev_join);
   if (pl->side) (void)hipStreamDestroy(pl->side);
@@ -1305,7 +1326,8 @@ static int ssq_cwt_host_impl(int dtype, const void* x, int64_t batch, int64_t n_
                              const double* scales, int64_t na, double dt, int freq_dist, int maprange, int padtype,
                              int squeezing, int flipud, double gamma, void* Tx, double* ssq_freqs, void* dbg_Wx,
                              void* dbg_dWx, void* dbg_wk, int variant, double p0, double p1, const double* ups_freqs,
-                             int ups_nv, const double* gmwk = nullptr, int64_t n_coeffs = 0) {
+                             const double* ups_const, int64_t ups_idx, const double* gmwk = nullptr,
+                             int64_t n_coeffs = 0) {
   if (!x || !Tx) SSQ_FAIL("x or Tx is NULL");
   if (batch <= 0) SSQ_FAIL("batch must be positive");
   if (na <= 0) SSQ_FAIL("index out of bounds: scales is empty (ssq_cwt.rs:459)");
@@ -1317,8 +1339,26 @@ static int ssq_cwt_host_impl(int dtype, const void* x, int64_t batch, int64_t n_
   if (int rc = cached_cwt_plan(key, &pl)) return rc;
   if (variant & SSQ_VARIANT_UPSTREAM) {
     if (!ups_freqs) SSQ_FAIL("ssq_freqs_asc is NULL");
+    if (!ups_const) SSQ_FAIL("row_const is NULL");
+    for (int64_t i = 0; i < na; ++i)
+      if (!std::isfinite(ups_const[i])) SSQ_FAIL("row_const must be finite");
     pl->ups_freqs.assign(ups_freqs, ups_freqs + na);
-    pl->ups_nv = ups_nv;
+    pl->ups_const.assign(ups_const, ups_const + na);
+    if (freq_dist == SSQ_FREQS_LOG_PIECEWISE && (ups_idx < 2 || ups_idx > na - 1))
+      SSQ_FAIL("freq_transition must be 2 .. na-1 for SSQ_FREQS_LOG_PIECEWISE");
+    pl->ups_idx = (int)ups_idx;
+    // one weight for every row on a log / linear frequency grid: the scalar-constant kernel (the exponential scales)
+    pl->ups_rows = freq_dist == SSQ_FREQS_LOG_PIECEWISE ||
+                   std::any_of(ups_const, ups_const + na, [&](double c) { return c != ups_const[0]; });
+    if (pl->ups_rows) {
+      if (!pl->d_ups_const) SSQ_HIP(hipMalloc(&pl->d_ups_const, (size_t)na * sizeof(double)));
+      if (dtype == SSQ_F32) {
+        const std::vector<float> c32(ups_const, ups_const + na);
+        SSQ_HIP(hipMemcpy(pl->d_ups_const, c32.data(), (size_t)na * sizeof(float), hipMemcpyHostToDevice));
+      } else {
+        SSQ_HIP(hipMemcpy(pl->d_ups_const, ups_const, (size_t)na * sizeof(double), hipMemcpyHostToDevice));
+      }
+    }
   }
   const long long esz = dtype == SSQ_F32 ? 4 : 8;
   const long long out1 = na * n_signal * 2 * esz, in1 = n_signal * esz;
@@ -1373,15 +1413,47 @@ int ssq_ssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, 
                      int squeezing, int flipud, double gamma, void* Tx, double* ssq_freqs, void* dbg_Wx,
                      void* dbg_dWx, void* dbg_wk) {
   return ssq_cwt_host_impl(dtype, x, batch, n_signal, wavelet, scales, na, dt, freq_dist, maprange, padtype, squeezing,
-                           flipud, gamma, Tx, ssq_freqs, dbg_Wx, dbg_dWx, dbg_wk, SSQ_VARIANT_RUST, 0.0, 0.0, nullptr, 0);
+                           flipud, gamma, Tx, ssq_freqs, dbg_Wx, dbg_dWx, dbg_wk, SSQ_VARIANT_RUST, 0.0, 0.0, nullptr,
+                           nullptr, 0);
+}
+
+int ssq_ssq_cwt_host_rows(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                          const double* scales, int64_t na, double dt, const double* row_const,
+                          const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition, int padtype,
+                          int squeezing, double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk) {
+  if (!(variant & SSQ_VARIANT_UPSTREAM)) SSQ_FAIL("ssq_ssq_cwt_host_rows: variant must include SSQ_VARIANT_UPSTREAM");
+  return ssq_cwt_host_impl(dtype, x, batch, n_signal, wavelet, scales, na, dt, freq_kind, SSQ_MAPRANGE_PEAK, padtype,
+                           squeezing, (variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, gamma, Tx, nullptr, Wx, dWx, wk, variant, p0,
+                           p1, ssq_freqs_asc, row_const, freq_transition);
+}
+
+int ssq_ssq_cwt_host_gmwk_rows(int dtype, const void* x, int64_t batch, int64_t n_signal, double gmw_gamma,
+                               double gmw_beta, const double* coeffs, int64_t n_coeffs, int64_t n_groups,
+                               const double* scales, int64_t na, double dt, const double* row_const,
+                               const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition, int padtype,
+                               int squeezing, double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk) {
+  if (int rc = check_gmwk_args(coeffs, n_coeffs, n_groups, scales, na, variant)) return rc;
+  if (n_groups != 1) SSQ_FAIL("higher-order GMW ssq_cwt: n_groups must be 1 (one averaged polynomial)");
+  return ssq_cwt_host_impl(dtype, x, batch, n_signal, SSQ_WAVELET_GMW, scales, na, dt, freq_kind, SSQ_MAPRANGE_PEAK,
+                           padtype, squeezing, (variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, gamma, Tx, nullptr, Wx, dWx, wk,
+                           variant, gmw_gamma, gmw_beta, ssq_freqs_asc, row_const, freq_transition, coeffs, n_coeffs);
+}
+
+// the exponential-scale entry points: ln 2 / nv for every row (ssqueezing.py:122-124)
+static std::vector<double> log_row_const(int nv, int64_t na) {
+  return std::vector<double>((size_t)(na > 0 ? na : 0), std::log(2.0) / (double)nv);
 }
 
 int ssq_ssq_cwt_host_v(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
                        const double* scales, int64_t na, double dt, int nv, const double* ssq_freqs_asc, int freq_dist,
                        int padtype, int squeezing, double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk) {
+  const bool ups = (variant & SSQ_VARIANT_UPSTREAM) != 0;
+  if (ups && nv < 1) SSQ_FAIL("upstream ssq exec: frequencies / nv not set");
+  if (ups && freq_dist != SSQ_FREQS_LOG) freq_dist = SSQ_FREQS_LINEAR;   // (every kind but log bins linearly here)
+  const std::vector<double> c = log_row_const(nv, na);
   return ssq_cwt_host_impl(dtype, x, batch, n_signal, wavelet, scales, na, dt, freq_dist, SSQ_MAPRANGE_PEAK, padtype,
                            squeezing, (variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, gamma, Tx, nullptr, Wx, dWx, wk, variant, p0,
-                           p1, ssq_freqs_asc, nv);
+                           p1, ssq_freqs_asc, c.data(), 0);
 }
 
 int ssq_ssq_cwt_host_gmwk(int dtype, const void* x, int64_t batch, int64_t n_signal, double gmw_gamma, double gmw_beta,
@@ -1389,10 +1461,12 @@ int ssq_ssq_cwt_host_gmwk(int dtype, const void* x, int64_t batch, int64_t n_sig
                           double dt, int nv, const double* ssq_freqs_asc, int freq_dist, int padtype, int squeezing,
                           double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk) {
   if (int rc = check_gmwk_args(coeffs, n_coeffs, n_groups, scales, na, variant)) return rc;
-  if (n_groups != 1) SSQ_FAIL("higher-order GMW ssq_cwt: n_groups must be 1 (one averaged polynomial)");
-  return ssq_cwt_host_impl(dtype, x, batch, n_signal, SSQ_WAVELET_GMW, scales, na, dt, freq_dist, SSQ_MAPRANGE_PEAK,
-                           padtype, squeezing, (variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, gamma, Tx, nullptr, Wx, dWx, wk,
-                           variant, gmw_gamma, gmw_beta, ssq_freqs_asc, nv, coeffs, n_coeffs);
+  if (nv < 1) SSQ_FAIL("upstream ssq exec: frequencies / nv not set");
+  if (freq_dist != SSQ_FREQS_LOG) freq_dist = SSQ_FREQS_LINEAR;
+  const std::vector<double> c = log_row_const(nv, na);
+  return ssq_ssq_cwt_host_gmwk_rows(dtype, x, batch, n_signal, gmw_gamma, gmw_beta, coeffs, n_coeffs, n_groups, scales,
+                                    na, dt, c.data(), ssq_freqs_asc, freq_dist, 0, padtype, squeezing, gamma, variant,
+                                    Tx, Wx, dWx, wk);
 }
 
 }  // extern "C"

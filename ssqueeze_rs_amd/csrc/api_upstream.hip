@@ -269,6 +269,13 @@ int ssq_upstream_center_frequency(int wavelet, double p0, double p1, double scal
   return 0;
 }
 
+int ssq_upstream_psih(int wavelet, double p0, double p1, const double* w, int64_t n, double* out) {
+  if (!w || !out || n < 0) SSQ_FAIL("bad arguments");
+  if (wavelet != SSQ_WAVELET_GMW && wavelet != SSQ_WAVELET_MORLET) SSQ_FAIL("unknown wavelet");
+  for (int64_t i = 0; i < n; ++i) out[i] = psih_up(wavelet, p0, p1, w[i]);
+  return 0;
+}
+
 int ssq_upstream_p2up(int64_t n_signal, int64_t* n_up, int64_t* n1, int64_t* n2) {
   if (n_signal < 1 || !n_up || !n1 || !n2) SSQ_FAIL("bad arguments");
   host::p2up(n_signal, n_up, n1, n2);

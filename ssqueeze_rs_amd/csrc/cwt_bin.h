@@ -10,7 +10,8 @@ namespace ssq {
 // ssq_cwt.rs:15-47 (phase_cwt) and :116-222 (ssqueeze).
 // Phase transform and bin of one (scale, time) element: returns the Tx row (after flipud) or -1.
 // The upstream variant's rule (old/ssqueezepy/algos.py:899-940), plain arithmetic in T: the normalised wavelets cannot
-// overflow fp32.  Called by the column-ordered reassignment only (cwt_reassign_kernel), never by the tile kernels.
+// overflow fp32.  Called by the column-ordered reassignment only (cwt_reassign_kernel, cwt_reassign_rows_kernel), never
+// by the tile kernels.
 template <typename T>
 __device__ __forceinline__ int reassign_bin_upstream(const CwtSsqDev<T>& p, cpx<T> Wv, cpx<T> dW, T& w) {
     const T A = dW.x, B = dW.y, C = Wv.x, D = Wv.y;
@@ -24,6 +25,25 @@ __device__ __forceinline__ int reassign_bin_upstream(const CwtSsqDev<T>& p, cpx<
     if (!(v == v)) bin = 0;
     return p.flipud ? (p.na - 1 - bin) : bin;
   }
+
+// The same for a log-piecewise frequency grid (algos.py:860-877, :356-370): the second segment above vlmin1, the first
+// below it; round half to even.  NaN (after the |Wx| > gamma test) lands in row 0 and +inf in row na-1, as above.
+template <typename T>
+__device__ __forceinline__ int reassign_bin_upstream_pw(const CwtSsqDev<T>& p, const CwtRowsDev<T>& r, cpx<T> Wv,
+                                                        cpx<T> dW, T& w) {
+  const T A = dW.x, B = dW.y, C = Wv.x, D = Wv.y;
+  if (!(hypot(C, D) > p.gamma)) {
+    w = (T)INFINITY;
+    return -1;
+  }
+  w = fabs((B * C - A * D) / ((C * C + D * D) * (T)6.283185307179586));
+  const T wl = log2(w);
+  T v;
+  if (wl > r.vlmin1) v = rint((wl - r.vlmin1) / r.dvl1) + (T)r.idx1;
+  else v = fmax(rint((wl - p.bin_min) / p.bin_step), (T)0);    // NaN -> 0, -inf -> 0
+  const int bin = (v >= (T)(p.na - 1)) ? p.na - 1 : (v == v ? (int)v : 0);
+  return p.flipud ? (p.na - 1 - bin) : bin;
+}
 
 template <typename T>
 __device__ __forceinline__ int reassign_bin(const CwtSsqDev<T>& p, cpx<T> Wv, cpx<T> dW, T& w) {

@@ -114,8 +114,21 @@ struct CwtSsqDev {
   int variant;
   T tx_const;
 };
+// upstream ssq_cwt on scale grids other than the exponential one (ssqueezing.py:122-133, algos.py:860-877):
+// cwt_reassign_rows_kernel weights row i by row_const[i] instead of tx_const and, with `piecewise`, bins log2 w by the
+// two-segment map of _get_params_find_closest_log (:356-370): log2 w > vlmin1 -> k = min(rint((log2 w - vlmin1) / dvl1)
+// + idx1, na - 1), else k = max(rint((log2 w - bin_min) / bin_step), 0) (the first segment: CwtSsqDev's bin_min, bin_step)
 template <typename T>
-hipError_t launch_cwt_reassign(const CwtSsqDev<T>& p, hipStream_t stream, bool clear);   // clear: zero Tx first
+struct CwtRowsDev {
+  const T* row_const;    // [na]
+  int piecewise;
+  int idx1;
+  T vlmin1;
+  T dvl1;
+};
+template <typename T>
+hipError_t launch_cwt_reassign(const CwtSsqDev<T>& p, hipStream_t stream, bool clear,
+                               const CwtRowsDev<T>* rows = nullptr);   // clear: zero Tx first; rows: upstream per-row rule
 // the same with a per-lane bitmap of written rows: the first run in a row stores without reading.  zero_fill: the rows
 // never touched are stored as zeros at the end, so Tx needs no clear at all; otherwise Tx must be zero on entry
 template <typename T>

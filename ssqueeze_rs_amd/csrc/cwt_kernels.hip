@@ -608,6 +608,63 @@ __global__ void cwt_reassign_kernel(CwtSsqDev<T> p) {
   }
 }
 
+// The upstream rule on scale grids other than the exponential one: the same column walk with row i weighted by
+// r.row_const[i] and, for log-piecewise frequencies, the two-segment bins (CwtRowsDev).  A kernel of its own so that
+// cwt_reassign_kernel's code stays as it is for the exponential grid and the reference variant: a force-inlined walk
+// shared by both changed that kernel's machine code (tools/compare_isa.py), so keep the two walks in step by hand.
+template <typename T, int UN>
+__global__ void cwt_reassign_rows_kernel(CwtSsqDev<T> p, CwtRowsDev<T> r) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= p.N) return;
+  const cpx<T>* __restrict__ Wxp = p.Wx + j;
+  const cpx<T>* __restrict__ dWxp = p.dWx + j;
+  int k_cur = -1;
+  cpx<T> acc = {(T)0, (T)0};
+  auto flush = [&]() {
+    if (k_cur >= 0) {
+      const long long d = (long long)k_cur * p.N + j;
+      cpx<T> t = p.Tx[d];
+      t.x += acc.x;
+      t.y += acc.y;
+      p.Tx[d] = t;
+    }
+  };
+  for (int i0 = p.s_begin; i0 < p.s_end; i0 += UN) {
+    cpx<T> Wb[UN], dWb[UN];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int ii = (i0 + u < p.s_end) ? i0 + u : p.s_end - 1;
+      Wb[u] = Wxp[(long long)ii * p.N];
+      dWb[u] = dWxp[(long long)ii * p.N];
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int i = i0 + u;
+      if (i >= p.s_end) break;
+      const cpx<T> Wv = Wb[u];
+      T w;
+      const int kk = r.piecewise ? reassign_bin_upstream_pw(p, r, Wv, dWb[u], w)
+                                 : reassign_bin_upstream(p, Wv, dWb[u], w);
+      if (p.wk) p.wk[(long long)i * p.N + j] = {w, (T)kk};
+      if (kk != k_cur) {
+        flush();
+        k_cur = kk;
+        acc = {(T)0, (T)0};
+      }
+      if (kk >= 0) {                         // out[k, j] += Wx[i, j] * const[i]  (algos.py:190-192, :876-877)
+        const T c = r.row_const[i];
+        if (p.squeezing == 1) {
+          acc.x += p.leb_val * c;
+        } else {
+          acc.x += Wv.x * c;
+          acc.y += Wv.y * c;
+        }
+      }
+    }
+  }
+  flush();
+}
+
 // The whole call in one launch WITHOUT a cleared Tx: every lane keeps a bitmap of the rows of its column it has written
 // (in LDS, [word][lane]); the first run that lands in a row stores, a later one read-modify-writes, and at the end the
 // rows never touched are stored as zeros -- every Tx cell is written once and (revisits aside) never read: 2.15 GB of
@@ -696,15 +753,23 @@ hipError_t launch_cwt_reassign_sweep(const CwtSsqDev<T>& p, hipStream_t stream, 
 }
 
 template <typename T>
-hipError_t launch_cwt_reassign(const CwtSsqDev<T>& p, hipStream_t stream, bool clear) {
+hipError_t launch_cwt_reassign(const CwtSsqDev<T>& p, hipStream_t stream, bool clear, const CwtRowsDev<T>* rows) {
   if (clear) {
     const hipError_t e = hipMemsetAsync(p.Tx, 0, (size_t)p.na * (size_t)p.N * sizeof(cpx<T>), stream);
     if (e != hipSuccess) return e;
   }
   if (p.s_end <= p.s_begin) return hipSuccess;
   const dim3 grid((unsigned)((p.N + 63) / 64));
-  if (p.s_end - p.s_begin <= 4) hipLaunchKernelGGL((cwt_reassign_kernel<T, 4>), grid, dim3(64), 0, stream, p);
-  else hipLaunchKernelGGL((cwt_reassign_kernel<T, 8>), grid, dim3(64), 0, stream, p);
+  if (rows) {
+    if (p.s_end - p.s_begin <= 4)
+      hipLaunchKernelGGL((cwt_reassign_rows_kernel<T, 4>), grid, dim3(64), 0, stream, p, *rows);
+    else
+      hipLaunchKernelGGL((cwt_reassign_rows_kernel<T, 8>), grid, dim3(64), 0, stream, p, *rows);
+  } else if (p.s_end - p.s_begin <= 4) {
+    hipLaunchKernelGGL((cwt_reassign_kernel<T, 4>), grid, dim3(64), 0, stream, p);
+  } else {
+    hipLaunchKernelGGL((cwt_reassign_kernel<T, 8>), grid, dim3(64), 0, stream, p);
+  }
   return hipGetLastError();
 }
 
@@ -735,7 +800,7 @@ int cwt_tile_rows(int logm) {
   template hipError_t launch_cwt_big_fwd<T>(const CwtDev<T>&, cpx<T>*, hipStream_t);                  \
   template hipError_t launch_cwt_big_inv<T>(const CwtDev<T>&, cpx<T>*, hipStream_t);                  \
   template hipError_t launch_cwt_naive_inv<T>(const CwtDev<T>&, int, hipStream_t);                    \
-  template hipError_t launch_cwt_reassign<T>(const CwtSsqDev<T>&, hipStream_t, bool);                 \
+  template hipError_t launch_cwt_reassign<T>(const CwtSsqDev<T>&, hipStream_t, bool, const CwtRowsDev<T>*); \
   template hipError_t launch_cwt_reassign_sweep<T>(const CwtSsqDev<T>&, hipStream_t, bool);            \
   template bool cwt_reassign_can_sweep<T>(int);
 SSQ_INST(float)

@@ -9,7 +9,13 @@ everything per sample runs in HIP kernels.  There is no CPU fallback.
 
 Supported subset (anything else raises ValueError naming the option):
   * `window`: ndarray (upstream's default DPSS / named windows come from scipy.signal, which callers can pass in);
-  * `scales`: explicit exponentially spaced ndarray ('log' scaletype; the automatic 'log-piecewise' bounds are not built);
+  * `scales`: an explicit ndarray of any grid upstream accepts -- 'log', 'log-piecewise' or 'linear', classified by
+    `infer_scaletype` (utils/cwt_utils.py:264-298).  Upstream's own grids come from `process_scales('log-piecewise', N,
+    wavelet)` and the other scale utilities of utils/cwt_utils.py (`make_scales`, `cwt_scalebounds`, ...; module
+    `upstream_scales`, re-exported here); the string forms of `scales` themselves are not accepted;
+  * `ssq_cwt(ssq_freqs=)`: None (the scale type of `scales`), 'log', 'linear', 'log-piecewise' or an array (its type
+    inferred, ssqueezing.py:193-194); log-piecewise frequencies are binned by the two-segment rule (algos.py:860-877)
+    and every row is weighted as ssqueezing.py:122-133 weighs it;
   * wavelets 'gmw' (gamma, beta; bandpass norm, order 0) and 'morlet' (mu) -- names, or (name, {params});
   * higher-order GMWs through `cwt_higher_order` (_cwt.py:515-608), `ssq_cwt(order=)` and `cwt(order=<tuple / list /
     range>, average=)`: orders 0 .. 16, bandpass norm (`l1_norm=True`); an averaged order set is one transform with the
@@ -38,8 +44,12 @@ import numpy as np
 from . import _lib
 from ._lib import PAD, SQUEEZE, SSQ_F32, SSQ_F64, WAVELET
 from ._rs import _call, _cdtype, _ptr
+from .upstream_scales import (cwt_scalebounds, find_downsampling_scale, find_first_occurrence,  # noqa: F401
+                              find_max_scale, find_max_scale_alt, find_maximum, find_min_scale, infer_scaletype,
+                              logscale_transition_idx, make_scales, nv_from_scales, process_scales)
 
 VARIANT_UPSTREAM, VARIANT_MODULATED, VARIANT_FLIPUD = 1, 2, 4
+FREQS = {"log": 0, "linear": 1, "log-piecewise": 2}     # include/ssq_hip.h: SSQ_FREQS_LOG, _LINEAR, _LOG_PIECEWISE
 EPS32, EPS64 = float(np.finfo(np.float32).eps), float(np.finfo(np.float64).eps)
 GMW_MAX_ORDER = 16                      # the highest GMW order the library builds (csrc/cwt_kernels.h: kGmwMaxOrder)
 
@@ -147,14 +157,37 @@ def _order_args(order, average, wavelet, l1_norm=True, higher=False):
     return tuple(int(k) for k in orders), bool(average or (average is None and is_set))
 
 
+def _own_dtype(a):
+    """1-D view of an array in its own float dtype (float32 / float64; anything else as float64): upstream's scale-type
+    and transition tests (cwt_utils.py:264-298, :375-395) take their thresholds from it."""
+    a = np.asarray(a)
+    return (a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)).reshape(-1)
+
+
 def _scales(scales):
+    """-> (s float64 [na], scaletype, nv, s_own) by utils/cwt_utils.py:264-298; s_own: the array in its own dtype, on
+    which the transition of a log-piecewise grid is found (float32 grids have float32 thresholds, as upstream).  An
+    array within 4e-12 of exponential spacing is 'log' with int nv (this mirror's check of float64 grids since it was
+    built); any other goes through `infer_scaletype` ('linear': nv None; 'log-piecewise': nv per row) and raises
+    ValueError where upstream does, or where upstream's transforms fail later (a log-piecewise segment of one scale)."""
     if not isinstance(scales, np.ndarray):
-        raise ValueError("`scales` must be an explicit ndarray (the automatic scale bounds of 'log-piecewise' / 'log' are "
-                         "not built)")
+        raise ValueError("`scales` must be an explicit ndarray (the string forms are not accepted; "
+                         "`process_scales(scales, N, wavelet)` builds upstream's grids)")
     s = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
-    if len(s) < 2 or np.mean(np.abs(np.diff(np.log(s), 2))) >= 4e-15 * 1e3:     # utils/cwt_utils.py:264-298
-        raise ValueError("`scales` must be exponentially spaced (scaletype 'log')")
-    return s, int(np.round(1 / np.diff(np.log2(s))[0]))
+    s_own = _own_dtype(scales)
+    if len(s) < 2:
+        raise ValueError("`scales` must hold at least 2 scales")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d2 = np.mean(np.abs(np.diff(np.log(s), 2)))
+    if not d2 >= 4e-15 * 1e3:
+        return s, "log", int(np.round(1 / np.diff(np.log2(s))[0])), s_own
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scaletype, nv = infer_scaletype(s_own)
+    if scaletype == "log-piecewise":
+        idx = logscale_transition_idx(s_own)
+        if idx is None or idx < 2 or len(s) - idx < 2:     # upstream's _exp_fm / icwt fail on a one-scale segment
+            raise ValueError("log-piecewise `scales` need at least 2 scales on either side of the transition")
+    return s, scaletype, nv, s_own
 
 
 def _dt(fs, t, N):
@@ -303,8 +336,9 @@ def _issq(Tx, scale, row_scale=None):
 def cwt(x, wavelet="gmw", scales="log-piecewise", fs=None, t=None, nv=32, l1_norm=True, derivative=False,
         padtype="reflect", rpadded=False, vectorized=True, astensor=True, cache_wavelet=None, order=0, average=None,
         nan_checks=None, patience=0):
-    """ssqueezepy.cwt (old/ssqueezepy/_cwt.py:12-318) -> (Wx, scales[, dWx]).  `scales` must be an explicit array (the
-    default string asks for upstream's automatic bounds, which are not built); `vectorized`, `astensor`, `cache_wavelet`,
+    """ssqueezepy.cwt (old/ssqueezepy/_cwt.py:12-318) -> (Wx, scales[, dWx]).  `scales` must be an explicit array of any
+    upstream grid ('log', 'log-piecewise', 'linear'; `process_scales(<string>, N, wavelet)` builds upstream's default
+    grids, the strings themselves are not accepted); `vectorized`, `astensor`, `cache_wavelet`,
     `nan_checks`, `patience` select code paths with identical numbers upstream and are accepted and unused.
     `order` / `average`: an order set (tuple / list / range) gives higher-order GMWs as `cwt_higher_order` -- the mean
     over the orders, or a list of arrays (one per order) with `average=False`.  A bare int `order` other than 0 raises
@@ -338,8 +372,8 @@ def _cwt(x, wavelet, scales, fs, t, nv, l1_norm, derivative, padtype, rpadded, o
     batch, N = xa.shape
     dt = _dt(fs, t, N)
     wcode, p0, p1 = _wavelet(wavelet)
-    s, _nv = _scales(scales)
-    if nv is not None and nv != _nv:
+    s, scaletype, _nv, _ = _scales(scales)
+    if scaletype == "log" and nv is not None and nv != _nv:
         raise Exception("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))   # cwt_utils.py:229-231
     orders, average = order_args if order_args else ((0,), True)
     if all(k == 0 for k in orders) and (average or len(orders) == 1):
@@ -370,26 +404,58 @@ def _cwt(x, wavelet, scales, fs, t, nv, l1_norm, derivative, padtype, rpadded, o
     return (Wx, sc, dWx) if derivative else (Wx, sc)
 
 
-def _ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype):
-    """ssqueezing.py:218-290 (ascending)."""
+def _ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype, s_own=None):
+    """ssqueezing.py:218-290 (ascending); s_own: the scales in the caller's dtype (the transition of 'log-piecewise' is
+    found on them, as upstream finds it on its `scales`)."""
     na = len(s)
+
+    def peak_freq(scale):                                  # ssqueezing.py:301-310 (maprange 'peak')
+        wc = C.c_double(0)
+        _call(_lib.load().ssq_upstream_center_frequency(wcode, p0, p1, float(scale), p2up(N)[0], C.byref(wc)))
+        return wc.value / (2 * np.pi) / dt
     if maprange == "maximal":
         fm, fM = 1 / (dt * N), 1 / (2 * dt)
     elif maprange == "peak":
-        lib = _lib.load()
-        Np = p2up(N)[0]
-        wc = C.c_double(0)
-        _call(lib.ssq_upstream_center_frequency(wcode, p0, p1, float(s[-1]), Np, C.byref(wc)))
-        fm = wc.value / (2 * np.pi) / dt
-        _call(lib.ssq_upstream_center_frequency(wcode, p0, p1, float(s[0]), Np, C.byref(wc)))
-        fM = wc.value / (2 * np.pi) / dt
+        fm, fM = peak_freq(s[-1]), peak_freq(s[0])
     else:
         raise ValueError(f"maprange {maprange!r}: 'peak' and 'maximal' are built")
+    if scaletype == "log-piecewise":
+        idx = logscale_transition_idx(s if s_own is None else s_own)
+        if idx is None:
+            scaletype = "log"
+        else:                                              # :253-279: exponential from fm to f1, then from f1 to fM
+            f1 = peak_freq(s[idx])
+            t1 = np.arange(0, na - idx - 1) / (na - 1)
+            t2 = np.arange(na - idx - 1, na) / (na - 1)
+            t1 = np.hstack([t1, t2[0]])
+
+            def exp_fm(t, fmin, fmax):                     # :294-298 (_exp_fm)
+                tmin, tmax = t.min(), t.max()
+                a = (fmin ** tmax / fmax ** tmin) ** (1 / (tmax - tmin))
+                b = fmax ** (1 / tmax) * (1 / a) ** (1 / tmax)
+                return a * b ** t
+            f = np.hstack([exp_fm(t1, fm, f1)[:-1], exp_fm(t2, f1, fM)])
+            ssq_idx = logscale_transition_idx(f)
+            if ssq_idx is None:
+                raise Exception("couldn't find logscale transition index of generated `ssq_freqs`; something went "
+                                "wrong")
+            assert (na - ssq_idx) == idx, "{} != {}".format(na - ssq_idx, idx)
+            return f
     if scaletype == "log":
         return fm * np.power(fM / fm, np.arange(na) / (na - 1))
     if scaletype == "linear":
         return np.linspace(fm, fM, na)
-    raise ValueError(f"ssq_freqs {scaletype!r}: 'log' and 'linear' are built")
+    raise ValueError(f"ssq_freqs {scaletype!r}: 'log', 'log-piecewise' and 'linear' are built")
+
+
+def _row_const(s, scaletype, nv):
+    """ssqueezing.py:122-133: the weight of every row, ln2 / nv (nv per row for 'log-piecewise', re-inferred from the
+    array as :168-169 does) or (s[1] - s[0]) / s for 'linear'."""
+    if scaletype == "log":
+        return np.full(len(s), np.log(2) / nv)
+    if scaletype == "log-piecewise":
+        return np.ascontiguousarray(np.log(2) / np.asarray(nv, dtype=np.float64).reshape(-1))
+    return np.ascontiguousarray((s[1] - s[0]) / s)
 
 
 def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, ssq_freqs=None, padtype="reflect",
@@ -411,13 +477,32 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
     batch, N = xa.shape
     dt = _dt(fs, t, N)
     wcode, p0, p1 = _wavelet(wavelet)
-    s, _nv = _scales(scales)
-    if nv is not None and nv != _nv:
+    s, cwt_scaletype, _nv, s_own = _scales(scales)
+    if cwt_scaletype == "log" and nv is not None and nv != _nv:
         raise Exception("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))
-    scaletype = ssq_freqs if isinstance(ssq_freqs, str) else "log"
-    if ssq_freqs is not None and not isinstance(ssq_freqs, str):
-        raise ValueError("`ssq_freqs` arrays are not built: None, 'log' or 'linear'")
-    f_asc = np.ascontiguousarray(_ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype), dtype=np.float64)
+    row_const = _row_const(s, cwt_scaletype, _nv)
+    # ssqueezing.py:172-194: a string names the frequencies' type, None takes the scales' (this mirror has always binned
+    # exponential scales on 'log' frequencies), an array has its type inferred
+    if isinstance(ssq_freqs, np.ndarray):
+        f_asc = np.ascontiguousarray(ssq_freqs, dtype=np.float64).reshape(-1)
+        if len(f_asc) != len(s):
+            raise ValueError("`ssq_freqs` must have one frequency per scale (%s != %s)" % (len(f_asc), len(s)))
+        f_own = _own_dtype(ssq_freqs)
+        scaletype, _ = infer_scaletype(f_own)
+    elif ssq_freqs is None or isinstance(ssq_freqs, str):
+        scaletype = ssq_freqs if isinstance(ssq_freqs, str) else cwt_scaletype
+        if scaletype == "log-piecewise" and maprange == "maximal":
+            raise ValueError("can't have `ssq_scaletype = log-piecewise` or tuple with `maprange = 'maximal'` "
+                             "(got %s)" % str(maprange))                                          # :181-184
+        f_asc = np.ascontiguousarray(_ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype, s_own),
+                                     dtype=np.float64)
+        f_own = f_asc                                      # (computed in float64, as upstream's)
+    else:
+        raise ValueError("`ssq_freqs` must be None, 'log', 'log-piecewise', 'linear' or an array")
+    # algos.py:356-370: the two-segment rule at the frequencies' transition, found in their own dtype; none: one segment
+    f_idx = logscale_transition_idx(f_own) if scaletype == "log-piecewise" else None
+    if scaletype == "log-piecewise" and f_idx is None:
+        scaletype = "log"
     _lib.require_gpu()
     shape = (batch, len(s), N)
     cdt = _cdtype(code)
@@ -425,17 +510,17 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
     dWx = _lib.pinned_empty(shape, cdt) if get_dWx else None
     wk = _lib.pinned_empty(shape, cdt) if get_w else None
     variant = VARIANT_UPSTREAM | (VARIANT_FLIPUD if flipud else 0)
+    g = -1.0 if gamma is None else float(gamma)
     if order_args is None:
-        _call(lib.ssq_ssq_cwt_host_v(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, _nv, _ptr(f_asc),
-                                     0 if scaletype == "log" else 1, _pad_code(padtype), SQUEEZE[squeezing],
-                                     -1.0 if gamma is None else float(gamma), variant, _ptr(Tx), _ptr(Wx), _ptr(dWx),
-                                     _ptr(wk)))
+        _call(lib.ssq_ssq_cwt_host_rows(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, _ptr(row_const),
+                                        _ptr(f_asc), FREQS[scaletype], f_idx or 0, _pad_code(padtype),
+                                        SQUEEZE[squeezing], g, variant, _ptr(Tx), _ptr(Wx), _ptr(dWx), _ptr(wk)))
     else:
         poly = np.ascontiguousarray(gmw_order_coefficients(p0, p1, *order_args))
-        _call(lib.ssq_ssq_cwt_host_gmwk(code, _ptr(xa), batch, N, p0, p1, _ptr(poly), poly.shape[1], 1, _ptr(s), len(s),
-                                        dt, _nv, _ptr(f_asc), 0 if scaletype == "log" else 1, _pad_code(padtype),
-                                        SQUEEZE[squeezing], -1.0 if gamma is None else float(gamma), variant, _ptr(Tx),
-                                        _ptr(Wx), _ptr(dWx), _ptr(wk)))
+        _call(lib.ssq_ssq_cwt_host_gmwk_rows(code, _ptr(xa), batch, N, p0, p1, _ptr(poly), poly.shape[1], 1, _ptr(s),
+                                             len(s), dt, _ptr(row_const), _ptr(f_asc), FREQS[scaletype], f_idx or 0,
+                                             _pad_code(padtype), SQUEEZE[squeezing], g, variant, _ptr(Tx), _ptr(Wx),
+                                             _ptr(dWx), _ptr(wk)))
     rdt = np.float32 if code == SSQ_F32 else np.float64
     out = [Tx if batched else Tx[0], Wx if batched else Wx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]   # ssqueezing.py:199-205
     if get_w:
@@ -455,14 +540,25 @@ def issq_cwt(Tx, wavelet="gmw", cc=None, cw=None):
 
 def icwt(Wx, wavelet="gmw", scales="log-piecewise", nv=None, one_int=True, x_len=None, x_mean=0, padtype="reflect",
          rpadded=False, l1_norm=True):
-    """ssqueezepy.icwt (old/ssqueezepy/_cwt.py:321-452), one-integral form on exponential scales:
-    (2 / Cpsi) ln(2^(1/nv)) sum_a Re Wx[a] / (1 or sqrt(a))  + x_mean."""
+    """ssqueezepy.icwt (old/ssqueezepy/_cwt.py:321-452), one-integral form:
+    'log' scales:    (2 / Cpsi) ln(2^(1/nv)) sum_a Re Wx[a] / (1 or sqrt(a)) + x_mean;
+    'linear':        (2 / Cpsi) (pi / 4) sum_a Re Wx[a] / (a or a^1.5) + x_mean (:438-448, :477-492);
+    'log-piecewise': the 'log' inverses of the two segments either side of the transition, summed (:418-427; each
+                     adds x_mean, as upstream's do)."""
     if not one_int:
         raise ValueError("only the one-integral inverse (one_int=True) is built")
-    s, _nv = _scales(scales)
+    s, scaletype, _nv, s_own = _scales(scales)
     if Wx.shape[0] != len(s):
         raise AssertionError("%s != %s" % (len(s), Wx.shape[0]))
-    x = _issq(Wx, (2.0 / adm_ssq(wavelet)) * np.log(2 ** (1 / _nv)), None if l1_norm else 1.0 / np.sqrt(s))
+    if scaletype == "log-piecewise":                        # the segments in the caller's dtype, as upstream splits them
+        idx = logscale_transition_idx(s_own)
+        kw = dict(wavelet=wavelet, one_int=one_int, x_len=x_len, x_mean=x_mean, padtype=padtype, rpadded=rpadded,
+                  l1_norm=l1_norm)
+        return icwt(Wx[:idx], scales=s_own[:idx], **kw) + icwt(Wx[idx:], scales=s_own[idx:], **kw)
+    if scaletype == "linear":
+        x = _issq(Wx, (2.0 / adm_ssq(wavelet)) * np.pi / 4, 1.0 / (s if l1_norm else s ** 1.5))
+    else:
+        x = _issq(Wx, (2.0 / adm_ssq(wavelet)) * np.log(2 ** (1 / _nv)), None if l1_norm else 1.0 / np.sqrt(s))
     return x + x_mean
 
 
