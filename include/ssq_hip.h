@@ -296,6 +296,22 @@ int ssq_extract_ridges_host(int dtype, int param_dtype, int is_complex, const vo
 int ssq_ridge_track_host(int dtype, int param_dtype, const void* cost, int64_t batch, int64_t n_freqs, int64_t n_time,
                          const void* metric, double penalty, int64_t* ridge_idxs, void* pen_out);
 
+/* ---- component inversion: ssqueezepy.issq_cwt / issq_stft with cc, cw (old/ssqueezepy/_ssq_cwt.py:381-417) -----
+ * Tx: [batch][rows][cols] complex of `dtype` (interleaved); cc, cw: [batch][cols][n_comp] int64, the layout of
+ * ssq_ridges_exec's ridge_idxs, each value read as upstream's astype('int32') reads it (its low 32 bits); cw NULL:
+ * cw_const everywhere.  For component k of column j the band is the rows clip(cc - cw, 0, rows) ..
+ * clip(cc + cw, 0, rows) (int32 arithmetic) cut at rows - 1, empty where cc == -1.  x: [batch][n_comp + 1][cols]
+ * float64, x[k] = scale * the sum of Re Tx over band k (bands may overlap: a row counts in every band holding it),
+ * x[n_comp] = scale * the sum over the rows of no band; fp64 sums for both dtypes, in an order fixed by rows alone.
+ * scale: 2 / adm_ssq(wavelet) (issq_cwt), 2 / window[n_fft / 2] (issq_stft).  1 <= n_comp <= 524280.
+ * Device pointers, async on `stream`. */
+int ssq_issq_components_exec(int dtype, const void* d_Tx, int64_t batch, int64_t rows, int64_t cols,
+                             const int64_t* d_cc, const int64_t* d_cw, int64_t cw_const, int64_t n_comp, double scale,
+                             double* d_x, void* stream);
+/* the same on host arrays (synchronous); rejects a cc, cw or cw_const outside the int32 range */
+int ssq_issq_components_host(int dtype, const void* Tx, int64_t batch, int64_t rows, int64_t cols, const int64_t* cc,
+                             const int64_t* cw, int64_t cw_const, int64_t n_comp, double scale, double* x_out);
+
 /* ---- multi-GPU: the optional final gather of the batch-sharded results over xGMI ------------------------------
  * Signals are independent (the reference's batch is a Python loop over channels, tests/stft_ssq_test.py:230), so the
  * data path has no collective; a consumer that wants every rank to hold all shards calls ssq_gather_shards after its

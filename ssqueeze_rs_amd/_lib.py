@@ -110,6 +110,8 @@ _SIGNATURES = {
     "ssq_extract_ridges_host": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, i64, i64, i64, vp, vp, C.c_double, i64,
                                           C.c_double, vp, vp, vp, vp]),
     "ssq_ridge_track_host": (C.c_int, [C.c_int, C.c_int, vp, i64, i64, i64, vp, C.c_double, vp, vp]),
+    "ssq_issq_components_exec": (C.c_int, [C.c_int, vp, i64, i64, i64, vp, vp, i64, i64, C.c_double, vp, vp]),
+    "ssq_issq_components_host": (C.c_int, [C.c_int, vp, i64, i64, i64, vp, vp, i64, i64, C.c_double, vp]),
     "ssq_rccl_available": (C.c_int, []),
     "ssq_rccl_unique_id": (C.c_int, [vp]),
     "ssq_rccl_comm_init": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.c_int]),

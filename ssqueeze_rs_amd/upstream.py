@@ -22,7 +22,10 @@ Supported subset (anything else raises ValueError naming the option):
     averaged wavelet (the transform is linear in it), `average=False` runs every order from one forward FFT per signal.
     `cwt` keeps rejecting a bare int `order` other than 0 (the suite pins that ValueError); `order=(k,)` or
     `cwt_higher_order(x, order=k)` is the same transform;
-  * difftype 'trig'; squeezing 'sum' / 'lebesgue'; padtype 'reflect' / 'zero'; full inverses (no component curves);
+  * difftype 'trig'; squeezing 'sum' / 'lebesgue'; padtype 'reflect' / 'zero';
+  * `issq_cwt` / `issq_stft`: the full inverse, and the component inversion by curves `cc`, `cw`
+    (_ssq_cwt.py:381-417): float64 [K + 1, N], or [B, K + 1, N] for a batched `Tx` [B, F, N] with the curves of a
+    batched `extract_ridges`; the full inverse takes 2-D `Tx` only;
   * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
     serial backward trace (`parallel` is accepted and ignored).
 dtype: float64 in -> complex128 (upstream's 'float64'); float32 in -> complex64 (upstream's default 'float32').
@@ -306,13 +309,19 @@ def ssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=Non
 
 
 def issq_stft(Tx, window=None, cc=None, cw=None, n_fft=None, win_len=None, hop_len=1, modulated=True):
-    """ssqueezepy.issq_stft (old/ssqueezepy/_ssq_stft.py:139-198), full inverse."""
+    """ssqueezepy.issq_stft (old/ssqueezepy/_ssq_stft.py:139-198).  `cc`, `cw` None: the full inverse [N] in Tx's real
+    dtype.  Otherwise the component inversion of `issq_cwt`, scaled by 2 / window[len(window) // 2]: float64
+    [K + 1, N], or [B, K + 1, N] for a batched `Tx` [B, F, N]."""
     if not modulated:
         raise ValueError("inversion with `modulated == False` is unsupported.")
     if hop_len != 1:
         raise ValueError("inversion with `hop_len != 1` is unsupported.")
-    if cc is not None or cw is not None:
-        raise ValueError("component inversion (cc, cw) is not built: full inverse only")
+    comp = _component_args(Tx, cc, cw)
+    if comp is not None:
+        n_fft = n_fft or (Tx.shape[-2] - 1) * 2
+        win_len = win_len or n_fft
+        win = get_window(window, win_len, n_fft)
+        return _issq_components(*comp, 2.0 / float(win[len(win) // 2]))
     n_fft = n_fft or (Tx.shape[0] - 1) * 2
     win_len = win_len or n_fft
     win = get_window(window, win_len, n_fft)
@@ -330,6 +339,63 @@ def _issq(Tx, scale, row_scale=None):
     rs = None if row_scale is None else np.ascontiguousarray(row_scale, dtype=np.float64)
     _call(lib.ssq_issq_host(code, _ptr(Tc), Tc.shape[0], Tc.shape[1], float(scale), _ptr(rs), _ptr(x)))
     return x
+
+
+def _component_args(Tx, cc, cw):
+    """_ssq_cwt.py:406-417 (`_process_component_inversion_args`) and the shapes `_invert_components` (:381-403) works
+    with -> None for the full inverse, else (Tx, cc, cw, batched): Tx [B, F, N], cc and cw [B, N, K] int32 values.
+    A 1-D cc / cw (a [B, N] one for a batched Tx) is one component; both are cast with astype('int32') (floats
+    truncate toward zero); cc must have one row per column of Tx; cw at least K columns, of which the first K are
+    read, broadcast against cc as upstream's `cc[:, n] + cw[:, n]` broadcasts.  Raises before any GPU work."""
+    if cc is None and cw is None:
+        return None
+    if cc is None or cw is None:
+        raise ValueError("`cc` and `cw` must be passed together (both None: the full inverse)")
+    if not isinstance(Tx, np.ndarray) or Tx.ndim not in (2, 3) or Tx.dtype not in (np.complex64, np.complex128):
+        raise TypeError("`Tx` must be a 2D [F, N] (or batched 3D [B, F, N]) complex64 / complex128 array")
+    batched = Tx.ndim == 3
+    Tb = Tx if batched else Tx[None]
+    B, F, N = Tb.shape
+    lead = 1 if batched else 0
+
+    def as_curves(a, name):
+        a = np.asarray(a)
+        if a.ndim == lead + 1:
+            a = a[..., None]
+        if a.ndim != lead + 2:
+            raise ValueError(f"`{name}` must be {'2D [B, N] or 3D [B, N, K]' if batched else '1D [N] or 2D [N, K]'}"
+                             f" (got shape {a.shape})")
+        return a.astype("int32")
+    cc, cw = as_curves(cc, "cc"), as_curves(cw, "cw")
+    if cc.shape[:-1] != ((B, N) if batched else (N,)):
+        raise ValueError(f"`cc` must have one row per column of `Tx` ({N}){' per signal' if batched else ''} "
+                         f"(got shape {cc.shape})")
+    K = cc.shape[-1]
+    if K < 1:
+        raise ValueError("`cc` must hold at least one component")
+    if cw.shape[-1] < K:
+        raise ValueError(f"`cw` must have at least as many columns as `cc` ({cw.shape[-1]} < {K})")
+    try:
+        cw = np.broadcast_to(cw[..., :K], cc.shape)
+    except ValueError:
+        raise ValueError(f"`cw` of shape {cw.shape} does not broadcast against `cc` of shape {cc.shape}") from None
+    return Tb, cc, cw, batched
+
+
+def _issq_components(Tb, cc, cw, batched, scale):
+    """_ssq_cwt.py:381-403 (`_invert_components`) times `scale` on the GPU (issq_components.hip) -> float64
+    [K + 1, N] (or [B, K + 1, N]): the band sums of Re Tx, then the remainder over the rows of no band."""
+    lib = _lib.load()
+    B, F, N = Tb.shape
+    K = cc.shape[-1]
+    code = SSQ_F32 if Tb.dtype == np.complex64 else SSQ_F64
+    _lib.require_gpu()
+    Tc = np.ascontiguousarray(Tb)
+    cc64 = np.ascontiguousarray(cc, dtype=np.int64).reshape(B, N, K)
+    cw64 = np.ascontiguousarray(cw, dtype=np.int64).reshape(B, N, K)
+    x = np.empty((B, K + 1, N), dtype=np.float64)
+    _call(lib.ssq_issq_components_host(code, _ptr(Tc), B, F, N, _ptr(cc64), _ptr(cw64), 0, K, float(scale), _ptr(x)))
+    return x if batched else x[0]
 
 
 # ---------------------------------------------------------------------------------------------------- CWT family ----
@@ -532,9 +598,15 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
 
 
 def issq_cwt(Tx, wavelet="gmw", cc=None, cw=None):
-    """ssqueezepy.issq_cwt (old/ssqueezepy/_ssq_cwt.py:313-378), full inverse: (2 / Css) sum_rows Re Tx."""
-    if cc is not None or cw is not None:
-        raise ValueError("component inversion (cc, cw) is not built: full inverse only")
+    """ssqueezepy.issq_cwt (old/ssqueezepy/_ssq_cwt.py:313-417).  `cc`, `cw` None: the full inverse
+    (2 / Css) sum_rows Re Tx, [N] in Tx's real dtype.  Otherwise curve centres and half-widths (rows of Tx, one per
+    column; 1-D: one curve, 2-D [N, K]: K curves, as `extract_ridges` returns them) -> float64 [K + 1, N]: row k < K the
+    sum of Re Tx over the rows clip(cc - cw, 0, F) .. clip(cc + cw, 0, F) of each column (none where cc == -1), row K
+    the sum over the rows no curve covers, all times 2 / Css.  Extension: a batched Tx [B, F, N] with cc, cw [B, N] or
+    [B, N, K] (batched `extract_ridges` output) -> [B, K + 1, N]."""
+    comp = _component_args(Tx, cc, cw)
+    if comp is not None:
+        return _issq_components(*comp, 2.0 / adm_ssq(wavelet))
     return _issq(Tx, 2.0 / adm_ssq(wavelet))
 
 
