@@ -312,6 +312,43 @@ int ssq_issq_components_exec(int dtype, const void* d_Tx, int64_t batch, int64_t
 int ssq_issq_components_host(int dtype, const void* Tx, int64_t batch, int64_t rows, int64_t cols, const int64_t* cc,
                              const int64_t* cw, int64_t cw_const, int64_t n_comp, double scale, double* x_out);
 
+/* ---- synchrosqueezing of a given transform: ssqueezepy.phase_cwt / phase_stft / ssqueeze -------------------------
+ * (old/ssqueezepy/algos.py:706-857, :126-252; ssqueezing.py:13-245).  Wx, dWx: [batch][rows][cols] complex of `dtype`
+ * (interleaved); w: [batch][rows][cols] real of `dtype`; 1 <= rows <= 32767, 1 <= cols < 2^31.
+ * Phase transform: w = |(B C - A D) / ((C^2 + D^2) 2 pi)| for Wx = C + iD, dWx = A + iB (STFT: Sfs given, [rows] real
+ * of `dtype`: |Sfs[row] - ...|), +inf where |Wx| < gamma (a value is kept when |Wx| >= gamma, algos.py:724). */
+int ssq_phase_exec(int dtype, const void* d_Wx, const void* d_dWx, const void* d_Sfs, int64_t batch, int64_t rows,
+                   int64_t cols, double gamma, void* d_w, void* stream);
+int ssq_phase_host(int dtype, const void* Wx, const void* dWx, const void* Sfs, int64_t batch, int64_t rows,
+                   int64_t cols, double gamma, void* w);
+/* ssqueeze only: squeezing 'abs' sums |Wx| into a real Tx (ssqueezing.py:185-186) */
+enum { SSQ_SQUEEZE_ABS = 2 };
+/* Squeeze from w (algos.py:153-252, `indexed_sum_onfly`): Tx[k, j] += Wx[i, j] * row_const[i] for every w[i, j] not
+ * infinite, k by the bin rule of ssq_freqs_asc as for ssq_ssq_cwt_host_rows (freq_kind, freq_transition; clamped,
+ * round half to even, k -> rows-1-k with flipud).  squeezing: SSQ_SQUEEZE_SUM (Tx complex), _LEBESGUE (Wx not read, may
+ * be NULL: every row contributes 1/rows, Tx complex), _ABS (|Wx|, Tx real [batch][rows][cols]).  Tx is overwritten.
+ * exec: d_row_const [rows] real of `dtype` on the device; ssq_freqs_asc [rows] fp64 on the host, read during the call
+ * only.  host: row_const [rows] fp64, finite. */
+int ssq_ssqueeze_w_exec(int dtype, const void* d_Wx, const void* d_w, int64_t batch, int64_t rows, int64_t cols,
+                        const void* d_row_const, const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition,
+                        int squeezing, int flipud, void* d_Tx, void* stream);
+int ssq_ssqueeze_w_host(int dtype, const void* Wx, const void* w, int64_t batch, int64_t rows, int64_t cols,
+                        const double* row_const, const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition,
+                        int squeezing, int flipud, void* Tx);
+/* Squeeze from dWx (algos.py:126-150, `ssqueeze_fast`): the phase transform, kept where |Wx| > gamma (algos.py:864),
+ * binned and summed as above; squeezing SSQ_SQUEEZE_SUM or _LEBESGUE.  CWT (Sfs NULL): the fused ssq_cwt's
+ * reassignment kernel, with the parameters of ssq_ssq_cwt_host_rows.  STFT (Sfs given): the fused upstream ssq_stft's,
+ * freq_kind SSQ_FREQS_LINEAR, weight and bin width ssq_freqs_asc[1] - ssq_freqs_asc[0] (ssqueezing.py:129-130), the
+ * first bin at Sfs[0], which must equal ssq_freqs_asc[0] (the host call checks it); row_const is not read, batch <= 65535.
+ * Tx: [batch][rows][cols] complex, overwritten. */
+int ssq_ssqueeze_dwx_exec(int dtype, const void* d_Wx, const void* d_dWx, const void* d_Sfs, int64_t batch,
+                          int64_t rows, int64_t cols, const void* d_row_const, const double* ssq_freqs_asc,
+                          int freq_kind, int64_t freq_transition, int squeezing, int flipud, double gamma, void* d_Tx,
+                          void* stream);
+int ssq_ssqueeze_dwx_host(int dtype, const void* Wx, const void* dWx, const void* Sfs, int64_t batch, int64_t rows,
+                          int64_t cols, const double* row_const, const double* ssq_freqs_asc, int freq_kind,
+                          int64_t freq_transition, int squeezing, int flipud, double gamma, void* Tx);
+
 /* ---- multi-GPU: the optional final gather of the batch-sharded results over xGMI ------------------------------
  * Signals are independent (the reference's batch is a Python loop over channels, tests/stft_ssq_test.py:230), so the
  * data path has no collective; a consumer that wants every rank to hold all shards calls ssq_gather_shards after its

@@ -112,6 +112,15 @@ _SIGNATURES = {
     "ssq_ridge_track_host": (C.c_int, [C.c_int, C.c_int, vp, i64, i64, i64, vp, C.c_double, vp, vp]),
     "ssq_issq_components_exec": (C.c_int, [C.c_int, vp, i64, i64, i64, vp, vp, i64, i64, C.c_double, vp, vp]),
     "ssq_issq_components_host": (C.c_int, [C.c_int, vp, i64, i64, i64, vp, vp, i64, i64, C.c_double, vp]),
+    "ssq_phase_exec": (C.c_int, [C.c_int, vp, vp, vp, i64, i64, i64, C.c_double, vp, vp]),
+    "ssq_phase_host": (C.c_int, [C.c_int, vp, vp, vp, i64, i64, i64, C.c_double, vp]),
+    "ssq_ssqueeze_w_exec": (C.c_int, [C.c_int, vp, vp, i64, i64, i64, vp, vp, C.c_int, i64, C.c_int, C.c_int, vp,
+                                      vp]),
+    "ssq_ssqueeze_w_host": (C.c_int, [C.c_int, vp, vp, i64, i64, i64, vp, vp, C.c_int, i64, C.c_int, C.c_int, vp]),
+    "ssq_ssqueeze_dwx_exec": (C.c_int, [C.c_int, vp, vp, vp, i64, i64, i64, vp, vp, C.c_int, i64, C.c_int, C.c_int,
+                                        C.c_double, vp, vp]),
+    "ssq_ssqueeze_dwx_host": (C.c_int, [C.c_int, vp, vp, vp, i64, i64, i64, vp, vp, C.c_int, i64, C.c_int, C.c_int,
+                                        C.c_double, vp]),
     "ssq_rccl_available": (C.c_int, []),
     "ssq_rccl_unique_id": (C.c_int, [vp]),
     "ssq_rccl_comm_init": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.c_int]),

@@ -26,6 +26,10 @@ Supported subset (anything else raises ValueError naming the option):
   * `issq_cwt` / `issq_stft`: the full inverse, and the component inversion by curves `cc`, `cw`
     (_ssq_cwt.py:381-417): float64 [K + 1, N], or [B, K + 1, N] for a batched `Tx` [B, F, N] with the curves of a
     batched `extract_ridges`; the full inverse takes 2-D `Tx` only;
+  * `ssqueeze` (ssqueezing.py:13-245) on a transform the caller holds, from `w` or `dWx`, CWT or STFT, 2-D or batched
+    3-D: `ssq_freqs` None / 'log' / 'linear' / 'log-piecewise' / an array, maprange 'peak' / 'maximal', squeezing
+    'sum' / 'lebesgue' / 'abs' / a function (from `dWx`: 'sum' only), `was_padded`, `flipud`; STFT needs an array
+    `ssq_freqs` (and `Sfs` with ssq_freqs[0] == Sfs[0] from `dSx`); `phase_cwt` (difftype 'trig') and `phase_stft`;
   * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
     serial backward trace (`parallel` is accepted and ignored).
 dtype: float64 in -> complex128 (upstream's 'float64'); float32 in -> complex64 (upstream's default 'float32').
@@ -470,14 +474,16 @@ def _cwt(x, wavelet, scales, fs, t, nv, l1_norm, derivative, padtype, rpadded, o
     return (Wx, sc, dWx) if derivative else (Wx, sc)
 
 
-def _ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype, s_own=None):
+def _ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype, s_own=None, was_padded=True):
     """ssqueezing.py:218-290 (ascending); s_own: the scales in the caller's dtype (the transition of 'log-piecewise' is
-    found on them, as upstream finds it on its `scales`)."""
+    found on them, as upstream finds it on its `scales`); was_padded: centre frequencies on the p2up(N) grid, else on
+    the N-point one (:301-304)."""
     na = len(s)
+    n_grid = p2up(N)[0] if was_padded else N
 
     def peak_freq(scale):                                  # ssqueezing.py:301-310 (maprange 'peak')
         wc = C.c_double(0)
-        _call(_lib.load().ssq_upstream_center_frequency(wcode, p0, p1, float(scale), p2up(N)[0], C.byref(wc)))
+        _call(_lib.load().ssq_upstream_center_frequency(wcode, p0, p1, float(scale), n_grid, C.byref(wc)))
         return wc.value / (2 * np.pi) / dt
     if maprange == "maximal":
         fm, fM = 1 / (dt * N), 1 / (2 * dt)
@@ -632,6 +638,186 @@ def icwt(Wx, wavelet="gmw", scales="log-piecewise", nv=None, one_int=True, x_len
     else:
         x = _issq(Wx, (2.0 / adm_ssq(wavelet)) * np.log(2 ** (1 / _nv)), None if l1_norm else 1.0 / np.sqrt(s))
     return x + x_mean
+
+
+# --------------------------------------------------------------------------------- synchrosqueezing a transform ----
+SSQUEEZE_MODES = {"sum": 0, "lebesgue": 1, "abs": 2}   # include/ssq_hip.h: SSQ_SQUEEZE_SUM, _LEBESGUE, _ABS
+
+
+def _cmap(A, name):
+    """A 2-D [F, N] or batched 3-D [B, F, N] complex64 / complex128 map -> (A [B, F, N] contiguous, batched, code)."""
+    if not isinstance(A, np.ndarray) or A.ndim not in (2, 3) or A.dtype not in (np.complex64, np.complex128):
+        raise TypeError(f"`{name}` must be a 2D [F, N] (or batched 3D [B, F, N]) complex64 / complex128 ndarray")
+    batched = A.ndim == 3
+    return np.ascontiguousarray(A if batched else A[None]), batched, (SSQ_F32 if A.dtype == np.complex64 else SSQ_F64)
+
+
+def _like(B, A, name):
+    """`B` as a complex array of `A`'s shape and dtype ([B, F, N] contiguous)."""
+    if not isinstance(B, np.ndarray) or B.shape != A.shape or B.dtype.kind != "c":
+        raise ValueError(f"`{name}` must be a complex ndarray of the shape of `Wx` {A.shape}")
+    return np.ascontiguousarray(B if B.ndim == 3 else B[None], dtype=A.dtype)
+
+
+def _rdtype(code):
+    return np.float32 if code == SSQ_F32 else np.float64
+
+
+def _phase(Wx, dWx, Sfs, gamma):
+    Wb, batched, code = _cmap(Wx, "Wx")
+    dWb = _like(dWx, Wx, "dWx")
+    B, F, N = Wb.shape
+    rdt = _rdtype(code)
+    sfs = None
+    if Sfs is not None:
+        sfs = np.ascontiguousarray(np.asarray(Sfs).reshape(-1), dtype=rdt)
+        if len(sfs) != F:
+            raise ValueError(f"`Sfs` must have one frequency per row of `Sx` ({len(sfs)} != {F})")
+    lib = _lib.load()
+    _lib.require_gpu()
+    w = np.empty((B, F, N), dtype=rdt)
+    _call(lib.ssq_phase_host(code, _ptr(Wb), _ptr(dWb), _ptr(sfs), B, F, N, float(gamma), _ptr(w)))
+    return w if batched else w[0]
+
+
+def phase_cwt(Wx, dWx, difftype="trig", gamma=None, parallel=None):
+    """ssqueezepy.phase_cwt (old/ssqueezepy/_ssq_cwt.py:420-509, algos.py:706-741): w = |Im(dWx / Wx)| / (2 pi), real in
+    Wx's real dtype, +inf where |Wx| < gamma.  `gamma=None` is upstream's default here, sqrt(eps) of the dtype (:488-489;
+    ssq_cwt passes 10 eps).  `parallel` is accepted and unused."""
+    if difftype != "trig":
+        raise ValueError(f"difftype {difftype!r}: only 'trig' is built")
+    _, _, code = _cmap(Wx, "Wx")
+    if gamma is None:
+        gamma = math.sqrt(EPS32 if code == SSQ_F32 else EPS64)
+    return _phase(Wx, dWx, None, gamma)
+
+
+def phase_stft(Sx, dSx, Sfs, gamma=None, parallel=None):
+    """ssqueezepy.phase_stft (old/ssqueezepy/_ssq_stft.py:200-246, algos.py:784-816): w = |Sfs[row] - Im(dSx / Sx) /
+    (2 pi)|, +inf where |Sx| < gamma; `gamma=None` is 10 eps of the dtype.  `parallel` is accepted and unused."""
+    _, _, code = _cmap(Sx, "Sx")
+    if gamma is None:
+        gamma = 10 * (EPS32 if code == SSQ_F32 else EPS64)
+    if Sfs is None:
+        raise ValueError("`Sfs` must be given")
+    return _phase(Sx, dSx, Sfs, gamma)
+
+
+def ssqueeze(Wx, w=None, ssq_freqs=None, scales=None, Sfs=None, fs=None, t=None, squeezing="sum", maprange="maximal",
+             wavelet=None, gamma=None, was_padded=True, flipud=False, dWx=None, transform="cwt"):
+    """ssqueezepy.ssqueeze (old/ssqueezepy/ssqueezing.py:13-245) -> (Tx, ssq_freqs) on a transform the caller holds:
+    `Wx` [F, N] (or a batch [B, F, N], one launch) complex64 / complex128 with `w` (its phase transform) or `dWx`.
+    From `w`, a value counts where w is finite (algos.py:173-252); from `dWx`, where |Wx| > gamma (:860-968), with the
+    kernels of ssq_cwt / ssq_stft.  `gamma=None` (upstream requires it with `dWx`) is 10 eps of the dtype, what ssq_cwt
+    and ssq_stft pass.  squeezing 'sum', 'lebesgue' (1 / F per row: a batch squeezes as its signals one by one),
+    'abs' (real Tx) or a function applied to `Wx` here (its complex result is cast to Wx's dtype; a real one gives a
+    real Tx); with `dWx` only 'sum' (upstream would take the phase from the replaced `Wx` too).  Not built, raising
+    ValueError: maprange 'energy' or a tuple; transform 'stft' without an array `ssq_freqs` or, from `dWx`, without
+    `Sfs` or with ssq_freqs[0] != Sfs[0] (pass `w = phase_stft(...)` instead)."""
+    # ---- every refusal before any GPU work
+    if transform not in ("cwt", "stft"):
+        raise ValueError("`transform` must be one of: cwt, stft (got %s)" % transform)
+    Wb, batched, code = _cmap(Wx, "Wx")
+    B, F, N = Wb.shape
+    rdt = _rdtype(code)
+    if w is None and dWx is None:
+        raise ValueError("if `w` is None, `dWx` must not be")
+    if w is not None:
+        w = np.asarray(w)
+        if w.shape != Wx.shape or w.dtype.kind not in "fiu":
+            raise ValueError(f"`w` must be a real ndarray of the shape of `Wx` {Wx.shape}")
+        if w.min() < 0:
+            raise ValueError("found negatives in `w`")
+    if callable(squeezing) and not isinstance(squeezing, str):
+        mode = None
+    elif isinstance(squeezing, str) and squeezing in SSQUEEZE_MODES:
+        mode = squeezing
+    else:
+        raise ValueError(f"squeezing {squeezing!r}: 'sum', 'lebesgue', 'abs' or a function")
+    if w is None and squeezing != "sum":
+        raise ValueError(f"squeezing {squeezing!r} with `w=None`: only 'sum' is built from `dWx` (upstream takes the "
+                         "phase from the replaced `Wx` too); compute `w = phase_cwt(Wx, dWx)` / `phase_stft` first")
+    if isinstance(maprange, (tuple, list)) or maprange == "energy":
+        raise ValueError(f"maprange {maprange!r}: 'peak' and 'maximal' are built")
+    if maprange not in ("peak", "maximal"):
+        raise ValueError(f"maprange {maprange!r}: must be one of 'maximal', 'peak'")
+    dt = _dt(fs, t, N)
+    f_idx = None
+    if transform == "cwt":
+        if scales is None:
+            raise ValueError("`scales` can't be None if `transform == 'cwt'`")
+        s, cwt_scaletype, _nv, s_own = _scales(scales)
+        if len(s) != F:
+            raise ValueError("`scales` must have one scale per row of `Wx` (%s != %s)" % (len(s), F))
+        row_const = _row_const(s, cwt_scaletype, _nv)                                   # ssqueezing.py:122-127
+        if isinstance(ssq_freqs, np.ndarray):
+            f_own = _own_dtype(ssq_freqs)
+            scaletype, _ = infer_scaletype(f_own)                                        # :193-194
+        elif ssq_freqs is None or isinstance(ssq_freqs, str):
+            scaletype = ssq_freqs if isinstance(ssq_freqs, str) else cwt_scaletype      # :172-176
+            if scaletype == "log-piecewise" and maprange == "maximal":
+                raise ValueError("can't have `ssq_scaletype = log-piecewise` or tuple with `maprange = 'maximal'` "
+                                 "(got %s)" % str(maprange))                             # :178-182
+            if maprange == "peak" and wavelet is None:
+                raise ValueError("`wavelet` must be given with maprange 'peak'")
+            wcode, p0, p1 = _wavelet(wavelet) if wavelet is not None else (0, 0.0, 0.0)
+            f_own = np.asarray(_ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype, s_own, was_padded),
+                               dtype=np.float64)
+            ssq_freqs = f_own
+        else:
+            raise ValueError("`ssq_freqs` must be None, 'log', 'log-piecewise', 'linear' or an array")
+        f_idx = logscale_transition_idx(f_own) if scaletype == "log-piecewise" else None
+        if scaletype == "log-piecewise" and f_idx is None:
+            scaletype = "log"
+        Sfs_t = None
+    else:
+        if not isinstance(ssq_freqs, np.ndarray):
+            raise ValueError("transform 'stft': `ssq_freqs` must be an array (ssq_stft passes Sfs)")
+        f_own = _own_dtype(ssq_freqs)
+        scaletype = "linear"                                                             # :189-191
+        row_const = np.full(F, float(f_own[1] - f_own[0]))                               # :129-130
+        Sfs_t = None
+        if w is None:
+            if Sfs is None:
+                raise ValueError("transform 'stft' with `w=None`: `Sfs` must be given")
+            Sfs_t = np.ascontiguousarray(np.asarray(Sfs).reshape(-1), dtype=rdt)
+            if len(Sfs_t) != F:
+                raise ValueError(f"`Sfs` must have one frequency per row of `Sx` ({len(Sfs_t)} != {F})")
+            if Sfs_t[0] != rdt(f_own[0]):
+                raise ValueError("transform 'stft' with `w=None` bins from Sfs[0]: ssq_freqs[0] != Sfs[0] is not "
+                                 "built; pass `w = phase_stft(Sx, dSx, Sfs)` instead")
+    f_asc = np.ascontiguousarray(f_own, dtype=np.float64)
+    if len(f_asc) != F:
+        raise ValueError("`ssq_freqs` must have one frequency per row of `Wx` (%s != %s)" % (len(f_asc), F))
+    kind, trans = FREQS[scaletype], f_idx or 0
+    # ---- `Wx` replaced as ssqueezing.py:183-188 does
+    real_out = mode == "abs"
+    if mode is None:
+        Wv = np.asarray(squeezing(Wx))
+        if Wv.shape != Wx.shape:
+            raise ValueError(f"`squeezing` must return an array of the shape of `Wx` {Wx.shape} (got {Wv.shape})")
+        real_out = Wv.dtype.kind != "c"
+        Wb = np.ascontiguousarray(Wv if batched else Wv[None], dtype=Wb.dtype)
+        mode = "sum"
+    lib = _lib.load()
+    _lib.require_gpu()
+    if w is not None:
+        wb = np.ascontiguousarray(w if batched else w[None], dtype=rdt)
+        Tx = np.empty((B, F, N), dtype=rdt if mode == "abs" else Wb.dtype)
+        _call(lib.ssq_ssqueeze_w_host(code, None if mode == "lebesgue" else _ptr(Wb), _ptr(wb), B, F, N,
+                                      _ptr(row_const), _ptr(f_asc), kind, trans, SSQUEEZE_MODES[mode], int(bool(flipud)),
+                                      _ptr(Tx)))
+    else:
+        dWb = _like(dWx, Wx, "dWx")
+        g = 10 * (EPS32 if code == SSQ_F32 else EPS64) if gamma is None else float(gamma)
+        Tx = np.empty((B, F, N), dtype=Wb.dtype)
+        _call(lib.ssq_ssqueeze_dwx_host(code, _ptr(Wb), _ptr(dWb), _ptr(Sfs_t), B, F, N, _ptr(row_const), _ptr(f_asc),
+                                        kind, trans, SSQUEEZE_MODES[mode], int(bool(flipud)), g, _ptr(Tx)))
+    if real_out and Tx.dtype.kind == "c":
+        Tx = np.ascontiguousarray(Tx.real)
+    if transform == "cwt" or flipud:                                                     # :199-205
+        ssq_freqs = ssq_freqs[::-1]
+    return (Tx if batched else Tx[0]), ssq_freqs
 
 
 # ---------------------------------------------------------------------------------------------- ridge extraction ----
