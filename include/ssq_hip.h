@@ -141,12 +141,36 @@ int ssq_ssq_stft_host_v(int dtype, const void* x, int64_t batch, int64_t n_signa
  * Sx: [n_fft/2+1][n_frames] complex of `dtype`; window: [n_fft]; x_out: [N] real of `dtype`. */
 int ssq_istft_host(int dtype, const void* Sx, int64_t n_frames, const double* window, int64_t n_fft, int64_t hop,
                    int64_t n_signal, int modulated, int win_exp, void* x_out);
+/* The same for `batch` spectra Sx [batch][n_fft/2+1][n_frames] -> x_out [batch][N], one window and shape for all.
+ * Power-of-two n_fft in 16 .. 4096 with hop <= n_fft and at least 256 tiles per signal (a tile: 16 frames, or twice the
+ * (n_fft - 1) / hop frames that overlap a sample if that is more) run the streaming kernel of csrc/istft_fused.hip (one
+ * pass over Sx, one write of x, no workspace beside them: tiles recompute the few frames they share); every other shape
+ * runs the three-kernel path of ssq_istft_host one signal at a time.  The batch goes through the device in slices sized
+ * from its free memory.  Signal b's result does not depend on `batch`.  SSQ_ISTFT_FUSED in the environment: 0 selects the
+ * three-kernel path, 1 the streaming kernel wherever it takes the (n_fft, hop). */
+int ssq_istft_batch_host(int dtype, const void* Sx, int64_t batch, int64_t n_frames, const double* window, int64_t n_fft,
+                         int64_t hop, int64_t n_signal, int modulated, int win_exp, void* x_out);
+/* The same on device buffers: d_Sx [batch][n_fft/2+1][n_frames], d_x [batch][N]; `window` on the host.  path -1: the
+ * path ssq_istft_batch_host takes, 0: the three kernels per signal, 1: the fused kernel (an error where it does not take
+ * the shape).  Synchronous.  kernel_ms (may be NULL): the time of the kernels alone, from HIP events around the launches
+ * with tables and workspace set up before them. */
+int ssq_istft_batch_exec(int dtype, const void* d_Sx, int64_t batch, int64_t n_frames, const double* window, int64_t n_fft,
+                         int64_t hop, int64_t n_signal, int modulated, int win_exp, int path, void* d_x, float* kernel_ms);
+/* Device bytes ssq_istft_batch_host needs beside one slice of Sx itself (x and the tables; for the three-kernel
+ * path its per-signal [n_frames][n_fft] workspace), computed on the host; *fused (may be NULL) says which path the shape
+ * takes.  -1 on a bad shape. */
+int64_t ssq_istft_batch_workspace_bytes(int dtype, int64_t batch, int64_t n_frames, int64_t n_fft, int64_t hop,
+                                        int64_t n_signal, int* fused);
 /* ssqueezepy.issq_stft / issq_cwt, full inverse (_ssq_stft.py:139-198, _ssq_cwt.py:313-378):
  * x_out[j] = scale * sum_rows row_scale[row] * Re Tx[row][j]   (scale = 2 / window[n_fft/2]  resp.  2 / adm_ssq;
  * row_scale NULL = 1; the one-integral icwt of _cwt.py:477-492 is the same sum with 1/sqrt(a) rows for the L2 norm).
  * Tx: [rows][cols] complex of `dtype`; x_out: [cols] real of `dtype`. */
 int ssq_issq_host(int dtype, const void* Tx, int64_t rows, int64_t cols, double scale, const double* row_scale,
                   void* x_out);
+/* The same for Tx [batch][rows][cols] -> x_out [batch][cols]; entry b equals ssq_issq_host on Tx[b] bit for bit.
+ * row_scale [rows] (shared by the batch) may be NULL. */
+int ssq_issq_batch_host(int dtype, const void* Tx, int64_t batch, int64_t rows, int64_t cols, double scale,
+                        const double* row_scale, void* x_out);
 /* upstream wavelets: SSQ_WAVELET_GMW with (p0, p1) = (gamma, beta), L1 / bandpass norm (_gmw.py:187-210);
  * SSQ_WAVELET_MORLET with p0 = mu (wavelets.py:497-523).
  * adm_ssq = int_0^inf conj(psih(w)) / w dw, adm_cwt = int |psih|^2 / w (utils/cwt_utils.py:28-63, trapezoid on the

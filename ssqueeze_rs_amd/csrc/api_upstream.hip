@@ -6,12 +6,14 @@
 // The forward transforms of the mode live beside the Rust-variant ones (api_stft.hip, api_cwt.hip: *_v entry points).
 #include <cmath>
 #include <complex>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../../include/ssq_hip.h"
 #include "fft_generic.h"
 #include "host_math.h"
+#include "istft_fused.h"
 #include "ssq_common.h"
 
 using namespace ssq;
@@ -72,6 +74,48 @@ __global__ void issq_colsum_kernel(const cpx<T>* __restrict__ Tx, long long rows
   x[j] = (T)(acc * scale);
 }
 
+// the same sum for a slice of signals, one per blockIdx.y: per thread exactly the arithmetic of issq_colsum_kernel
+template <typename T>
+__global__ void issq_colsum_batch_kernel(const cpx<T>* __restrict__ Tx_all, long long rows, long long cols, double scale,
+                                         const double* __restrict__ row_scale, T* __restrict__ x_all) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= cols) return;
+  const cpx<T>* __restrict__ Tx = Tx_all + (long long)blockIdx.y * rows * cols;
+  T* __restrict__ x = x_all + (long long)blockIdx.y * cols;
+  double acc = 0.0;
+  if (row_scale) {
+    for (long long r = 0; r < rows; ++r) acc += (double)Tx[r * cols + j].x * row_scale[r];
+  } else {
+    for (long long r = 0; r < rows; ++r) acc += (double)Tx[r * cols + j].x;
+  }
+  x[j] = (T)(acc * scale);
+}
+
+// signals of `per_signal` device bytes each that fit beside `fixed` bytes: most of the free memory, at most `cap`
+long long slice_signals(long long batch, double per_signal, double fixed, long long cap) {
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)1 << 30;
+  double room = 0.8 * (double)free_b - fixed;
+  long long s = room > per_signal ? (long long)(room / per_signal) : 1;      // one signal is always tried: hipMalloc reports the rest
+  if (s > cap) s = cap;
+  if (s > batch) s = batch;
+  return s < 1 ? 1 : s;
+}
+
+// the three kernels of one signal on device buffers: d_Z [n_frames][n], d_work fft_work_elems(n, n_frames) elements
+template <typename T>
+hipError_t istft_three_dev(const cpx<T>* d_S, int64_t n_frames, const double* d_wp, const double* d_wn, int64_t n, int64_t hop,
+                           int64_t N, int modulated, cpx<T>* d_Z, cpx<T>* d_work, T* d_x) {
+  hipLaunchKernelGGL(istft_expand_kernel<T>, dim3((unsigned)((n_frames + 255) / 256), (unsigned)(n < 65535 ? n : 65535)), dim3(256), 0,
+                     nullptr,
+                     d_S, (int)n, (int)n_frames, d_Z);
+  hipError_t e = fft_any_batched<T>(d_Z, d_work, n, n_frames, +1, nullptr);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(istft_ola_kernel<T>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, d_Z, (int)n,
+                     (int)n_frames, (int)hop, (long long)N, modulated, d_wp, d_wn, d_x);
+  return hipGetLastError();
+}
+
 template <typename T>
 int istft_typed(const void* Sx, int64_t n_frames, const std::vector<double>& wpow, const std::vector<double>& wnorm,
                 int64_t n, int64_t hop, int64_t N, int modulated, void* x_out) {
@@ -98,13 +142,7 @@ int istft_typed(const void* Sx, int64_t n_frames, const std::vector<double>& wpo
     if (fail(hipMemcpy(d_S, Sx, sizeof(cpx<T>) * nf * n_frames, hipMemcpyHostToDevice), "hipMemcpy")) break;
     if (fail(hipMemcpy(d_wp, wpow.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
     if (fail(hipMemcpy(d_wn, wnorm.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    hipLaunchKernelGGL(istft_expand_kernel<T>, dim3((unsigned)((n_frames + 255) / 256), (unsigned)(n < 65535 ? n : 65535)), dim3(256), 0,
-                       nullptr,
-                       d_S, (int)n, (int)n_frames, d_Z);
-    if (fail(fft_any_batched<T>(d_Z, d_work, n, n_frames, +1, nullptr), "fft_any_batched")) break;
-    hipLaunchKernelGGL(istft_ola_kernel<T>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, d_Z, (int)n,
-                       (int)n_frames, (int)hop, (long long)N, modulated, d_wp, d_wn, d_x);
-    if (fail(hipGetLastError(), "istft kernels")) break;
+    if (fail(istft_three_dev<T>(d_S, n_frames, d_wp, d_wn, n, hop, N, modulated, d_Z, d_work, d_x), "istft kernels")) break;
     if (fail(hipMemcpy(x_out, d_x, sizeof(T) * N, hipMemcpyDeviceToHost), "hipMemcpy")) break;
   } while (false);
   hipFree(d_S);
@@ -137,6 +175,180 @@ int issq_typed(const void* Tx, int64_t rows, int64_t cols, double scale, const d
   hipFree(d_r);
   SSQ_HIP(e);
   return 0;
+}
+
+// Device bytes of the fused path for `slice` signals: Sx in, x out and the three tables
+template <typename T>
+double istft_fused_bytes(const IstftPlan& pl, long long slice, long long N, bool with_sx) {
+  const double nf = (double)(pl.n / 2 + 1);
+  double per = (double)sizeof(T) * (double)N;
+  if (with_sx) per += (double)sizeof(cpx<T>) * nf * (double)pl.n_frames;
+  return per * (double)slice + (double)pl.n * (16.0 + (double)sizeof(cpx<T>));
+}
+
+template <typename T>
+int istft_batch_fused(const IstftPlan& pl, const void* Sx, int64_t batch, const std::vector<double>& wpow,
+                      const std::vector<double>& wnorm, int64_t N, int modulated, void* x_out) {
+  const int64_t n = pl.n, nf = n / 2 + 1, n_frames = pl.n_frames;
+  const long long slice = slice_signals(batch, istft_fused_bytes<T>(pl, 1, N, true) - istft_fused_bytes<T>(pl, 0, N, true),
+                                        istft_fused_bytes<T>(pl, 0, N, true), 65535);
+  std::vector<cpx<T>> tw((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)i / (long double)n;
+    tw[i] = {(T)cosl(ang), (T)(-sinl(ang))};
+  }
+  cpx<T>*d_S = nullptr, *d_tw = nullptr;
+  double *d_wp = nullptr, *d_wn = nullptr;
+  T* d_x = nullptr;
+  int rc = 0;
+  auto fail = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == 0) {
+      set_error(std::string(what) + ": " + hipGetErrorString(e));
+      rc = 2;
+    }
+    return e != hipSuccess;
+  };
+  const size_t sx_sig = sizeof(cpx<T>) * (size_t)nf * (size_t)n_frames;
+  do {
+    if (fail(hipMalloc((void**)&d_S, sx_sig * slice), "hipMalloc")) break;
+    if (fail(hipMalloc((void**)&d_x, sizeof(T) * (size_t)N * slice), "hipMalloc")) break;
+    if (fail(hipMalloc((void**)&d_tw, sizeof(cpx<T>) * n), "hipMalloc")) break;
+    if (fail(hipMalloc((void**)&d_wp, sizeof(double) * n), "hipMalloc")) break;
+    if (fail(hipMalloc((void**)&d_wn, sizeof(double) * n), "hipMalloc")) break;
+    if (fail(hipMemcpy(d_tw, tw.data(), sizeof(cpx<T>) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
+    if (fail(hipMemcpy(d_wp, wpow.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
+    if (fail(hipMemcpy(d_wn, wnorm.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
+    for (int64_t b0 = 0; b0 < batch && rc == 0; b0 += slice) {
+      const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
+      if (fail(hipMemcpy(d_S, (const char*)Sx + sx_sig * b0, sx_sig * nb, hipMemcpyHostToDevice), "hipMemcpy")) break;
+      if (fail(launch_istft_fused<T>(pl, d_S, nb, N, modulated, d_tw, d_wp, d_wn, d_x, nullptr), "istft_fused_kernel")) break;
+      if (fail(hipMemcpy((char*)x_out + sizeof(T) * (size_t)N * b0, d_x, sizeof(T) * (size_t)N * nb, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+    }
+  } while (false);
+  hipFree(d_S);
+  hipFree(d_x);
+  hipFree(d_tw);
+  hipFree(d_wp);
+  hipFree(d_wn);
+  return rc;
+}
+
+template <typename T>
+int issq_batch_typed(const void* Tx, int64_t batch, int64_t rows, int64_t cols, double scale, const double* row_scale,
+                     void* x_out) {
+  const size_t map_b = sizeof(cpx<T>) * (size_t)rows * (size_t)cols;
+  const long long slice = slice_signals(batch, (double)map_b + (double)sizeof(T) * (double)cols, 8.0 * (double)rows, 65535);
+  cpx<T>* d_T = nullptr;
+  T* d_x = nullptr;
+  double* d_r = nullptr;
+  int rc = 0;
+  auto fail = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == 0) {
+      set_error(std::string(what) + ": " + hipGetErrorString(e));
+      rc = 2;
+    }
+    return e != hipSuccess;
+  };
+  do {
+    if (fail(hipMalloc((void**)&d_T, map_b * slice), "hipMalloc")) break;
+    if (fail(hipMalloc((void**)&d_x, sizeof(T) * (size_t)cols * slice), "hipMalloc")) break;
+    if (row_scale) {
+      if (fail(hipMalloc((void**)&d_r, sizeof(double) * rows), "hipMalloc")) break;
+      if (fail(hipMemcpy(d_r, row_scale, sizeof(double) * rows, hipMemcpyHostToDevice), "hipMemcpy")) break;
+    }
+    for (int64_t b0 = 0; b0 < batch && rc == 0; b0 += slice) {
+      const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
+      if (fail(hipMemcpy(d_T, (const char*)Tx + map_b * b0, map_b * nb, hipMemcpyHostToDevice), "hipMemcpy")) break;
+      hipLaunchKernelGGL(issq_colsum_batch_kernel<T>, dim3((unsigned)((cols + 255) / 256), (unsigned)nb), dim3(256), 0, nullptr, d_T,
+                         (long long)rows, (long long)cols, scale, d_r, d_x);
+      if (fail(hipGetLastError(), "issq_colsum_batch_kernel")) break;
+      if (fail(hipMemcpy((char*)x_out + sizeof(T) * (size_t)cols * b0, d_x, sizeof(T) * (size_t)cols * nb, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+    }
+  } while (false);
+  hipFree(d_T);
+  hipFree(d_x);
+  hipFree(d_r);
+  return rc;
+}
+
+// The inverse of a batch that already lives on the device (d_Sx, d_x), by the path asked for; the kernels' own time
+// (HIP events around the launches, tables and workspace set up before) goes to *kernel_ms when it is not NULL.
+template <typename T>
+int istft_batch_exec_typed(const void* d_Sx, int64_t batch, int64_t n_frames, const std::vector<double>& wpow,
+                           const std::vector<double>& wnorm, int64_t n, int64_t hop, int64_t N, int modulated, bool fused,
+                           const IstftPlan& pl, void* d_x_out, float* kernel_ms) {
+  const int64_t nf = n / 2 + 1;
+  cpx<T>*d_tw = nullptr, *d_Z = nullptr, *d_work = nullptr;
+  double *d_wp = nullptr, *d_wn = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  const cpx<T>* d_S = (const cpx<T>*)d_Sx;
+  T* d_x = (T*)d_x_out;
+  int rc = 0;
+  auto fail = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == 0) {
+      set_error(std::string(what) + ": " + hipGetErrorString(e));
+      rc = 2;
+    }
+    return e != hipSuccess;
+  };
+  do {
+    if (fail(hipMalloc((void**)&d_wp, sizeof(double) * n), "hipMalloc")) break;
+    if (fail(hipMalloc((void**)&d_wn, sizeof(double) * n), "hipMalloc")) break;
+    if (fail(hipMemcpy(d_wp, wpow.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
+    if (fail(hipMemcpy(d_wn, wnorm.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
+    if (fused) {
+      std::vector<cpx<T>> tw((size_t)n);
+      for (int64_t i = 0; i < n; ++i) {
+        const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)i / (long double)n;
+        tw[i] = {(T)cosl(ang), (T)(-sinl(ang))};
+      }
+      if (fail(hipMalloc((void**)&d_tw, sizeof(cpx<T>) * n), "hipMalloc")) break;
+      if (fail(hipMemcpy(d_tw, tw.data(), sizeof(cpx<T>) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
+    } else {
+      const long long we = fft_work_elems(n, n_frames);
+      if (fail(hipMalloc((void**)&d_Z, sizeof(cpx<T>) * n * n_frames), "hipMalloc")) break;
+      if (fail(hipMalloc((void**)&d_work, sizeof(cpx<T>) * (we > 0 ? we : 1)), "hipMalloc")) break;
+    }
+    if (kernel_ms) {
+      if (fail(hipEventCreate(&ev0), "hipEventCreate") || fail(hipEventCreate(&ev1), "hipEventCreate")) break;
+      if (fail(hipEventRecord(ev0, nullptr), "hipEventRecord")) break;
+    }
+    if (fused) {
+      for (int64_t b0 = 0; b0 < batch && rc == 0; b0 += 65535) {
+        const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
+        fail(launch_istft_fused<T>(pl, d_S + b0 * nf * n_frames, nb, N, modulated, d_tw, d_wp, d_wn, d_x + b0 * N, nullptr),
+             "istft_fused_kernel");
+      }
+    } else {
+      for (int64_t b = 0; b < batch && rc == 0; ++b)
+        fail(istft_three_dev<T>(d_S + b * nf * n_frames, n_frames, d_wp, d_wn, n, hop, N, modulated, d_Z, d_work, d_x + b * N),
+             "istft kernels");
+    }
+    if (rc) break;
+    if (kernel_ms) {
+      if (fail(hipEventRecord(ev1, nullptr), "hipEventRecord")) break;
+      if (fail(hipEventSynchronize(ev1), "hipEventSynchronize")) break;
+      if (fail(hipEventElapsedTime(kernel_ms, ev0, ev1), "hipEventElapsedTime")) break;
+    } else if (fail(hipDeviceSynchronize(), "hipDeviceSynchronize")) {
+      break;
+    }
+  } while (false);
+  if (ev0) hipEventDestroy(ev0);
+  if (ev1) hipEventDestroy(ev1);
+  hipFree(d_tw);
+  hipFree(d_Z);
+  hipFree(d_work);
+  hipFree(d_wp);
+  hipFree(d_wn);
+  return rc;
+}
+
+// Which path a shape takes: the fused kernel where it takes the shape and the signal has enough tiles to fill the device.
+// SSQ_ISTFT_FUSED in the environment (A/B): 0 never, 1 wherever the kernel takes the shape.
+bool istft_use_fused(int64_t n, int64_t hop, int64_t n_frames, IstftPlan* pl) {
+  if (!istft_fused_plan(n, hop, n_frames, pl)) return false;
+  if (const char* e = std::getenv("SSQ_ISTFT_FUSED")) return std::atoi(e) != 0;
+  return pl->preferred;
 }
 
 // ---- upstream wavelets in fp64 (host) ----
@@ -223,6 +435,95 @@ int ssq_istft_host(int dtype, const void* Sx, int64_t n_frames, const double* wi
   }
   return dtype == SSQ_F32 ? istft_typed<float>(Sx, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, x_out)
                           : istft_typed<double>(Sx, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, x_out);
+}
+
+int ssq_istft_batch_host(int dtype, const void* Sx, int64_t batch, int64_t n_frames, const double* window, int64_t n_fft,
+                         int64_t hop, int64_t n_signal, int modulated, int win_exp, void* x_out) {
+  if (!Sx || !window || !x_out) SSQ_FAIL("NULL argument");
+  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
+  if (batch < 1) SSQ_FAIL("batch must be >= 1");
+  if (n_fft < 1 || hop < 1 || n_frames < 1 || n_signal < 1 || win_exp < 0) SSQ_FAIL("bad istft shape");
+  if (n_fft > (1 << 24)) SSQ_FAIL("n_fft too large");
+  if ((n_signal - 1) / hop + 1 != n_frames) SSQ_FAIL("Sx has the wrong number of frames for (N, hop_len)");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
+  std::vector<double> wpow((size_t)n_fft), wnorm((size_t)n_fft);
+  for (int64_t i = 0; i < n_fft; ++i) {
+    wpow[i] = win_exp == 0 ? 1.0 : std::pow(window[i], (double)win_exp);       // utils/stft_utils.py:159-162
+    wnorm[i] = std::pow(window[i], (double)(win_exp + 1));                      // :186
+  }
+  IstftPlan pl;
+  if (istft_use_fused(n_fft, hop, n_frames, &pl))
+    return dtype == SSQ_F32 ? istft_batch_fused<float>(pl, Sx, batch, wpow, wnorm, n_signal, modulated, x_out)
+                            : istft_batch_fused<double>(pl, Sx, batch, wpow, wnorm, n_signal, modulated, x_out);
+  // every other length: the three-kernel path, one signal at a time (its [n_frames][n_fft] workspace is per signal)
+  const size_t esz = dtype == SSQ_F32 ? 4 : 8;
+  const size_t sx_sig = 2 * esz * (size_t)(n_fft / 2 + 1) * (size_t)n_frames;
+  for (int64_t b = 0; b < batch; ++b) {
+    const void* S = (const char*)Sx + sx_sig * b;
+    void* xo = (char*)x_out + esz * (size_t)n_signal * b;
+    const int rc = dtype == SSQ_F32 ? istft_typed<float>(S, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, xo)
+                                    : istft_typed<double>(S, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, xo);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int ssq_istft_batch_exec(int dtype, const void* d_Sx, int64_t batch, int64_t n_frames, const double* window, int64_t n_fft,
+                         int64_t hop, int64_t n_signal, int modulated, int win_exp, int path, void* d_x, float* kernel_ms) {
+  if (!d_Sx || !window || !d_x) SSQ_FAIL("NULL argument");
+  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
+  if (batch < 1) SSQ_FAIL("batch must be >= 1");
+  if (n_fft < 1 || hop < 1 || n_frames < 1 || n_signal < 1 || win_exp < 0) SSQ_FAIL("bad istft shape");
+  if (n_fft > (1 << 24)) SSQ_FAIL("n_fft too large");
+  if ((n_signal - 1) / hop + 1 != n_frames) SSQ_FAIL("Sx has the wrong number of frames for (N, hop_len)");
+  if (path < -1 || path > 1) SSQ_FAIL("path must be -1 (as ssq_istft_batch_host chooses), 0 (three kernels) or 1 (fused)");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
+  IstftPlan pl;
+  const bool can = istft_fused_plan(n_fft, hop, n_frames, &pl);
+  if (path == 1 && !can) SSQ_FAIL("the fused istft kernel does not take this (n_fft, hop_len)");
+  const bool fused = path == 1 || (path == -1 && istft_use_fused(n_fft, hop, n_frames, &pl));
+  std::vector<double> wpow((size_t)n_fft), wnorm((size_t)n_fft);
+  for (int64_t i = 0; i < n_fft; ++i) {
+    wpow[i] = win_exp == 0 ? 1.0 : std::pow(window[i], (double)win_exp);
+    wnorm[i] = std::pow(window[i], (double)(win_exp + 1));
+  }
+  return dtype == SSQ_F32
+             ? istft_batch_exec_typed<float>(d_Sx, batch, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, fused, pl, d_x, kernel_ms)
+             : istft_batch_exec_typed<double>(d_Sx, batch, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, fused, pl, d_x, kernel_ms);
+}
+
+int64_t ssq_istft_batch_workspace_bytes(int dtype, int64_t batch, int64_t n_frames, int64_t n_fft, int64_t hop,
+                                        int64_t n_signal, int* fused) {
+  if (fused) *fused = 0;
+  if ((dtype != SSQ_F32 && dtype != SSQ_F64) || batch < 1 || n_fft < 1 || n_fft > (1 << 24) || hop < 1 || n_frames < 1 ||
+      n_signal < 1) {
+    set_error("bad istft shape");
+    return -1;
+  }
+  const double csz = dtype == SSQ_F32 ? 8.0 : 16.0;
+  IstftPlan pl;
+  if (istft_use_fused(n_fft, hop, n_frames, &pl)) {
+    if (fused) *fused = 1;
+    return (int64_t)(dtype == SSQ_F32 ? istft_fused_bytes<float>(pl, batch, n_signal, false)
+                                      : istft_fused_bytes<double>(pl, batch, n_signal, false));
+  }
+  const long long we = fft_work_elems(n_fft, n_frames);
+  return (int64_t)(csz * ((double)n_fft * (double)n_frames + (double)(we > 0 ? we : 1)) + 16.0 * (double)n_fft +
+                   0.5 * csz * (double)n_signal);
+}
+
+int ssq_issq_batch_host(int dtype, const void* Tx, int64_t batch, int64_t rows, int64_t cols, double scale,
+                        const double* row_scale, void* x_out) {
+  if (!Tx || !x_out) SSQ_FAIL("NULL argument");
+  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
+  if (batch < 1) SSQ_FAIL("batch must be >= 1");
+  if (rows < 1 || cols < 1) SSQ_FAIL("empty Tx");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
+  return dtype == SSQ_F32 ? issq_batch_typed<float>(Tx, batch, rows, cols, scale, row_scale, x_out)
+                          : issq_batch_typed<double>(Tx, batch, rows, cols, scale, row_scale, x_out);
 }
 
 int ssq_issq_host(int dtype, const void* Tx, int64_t rows, int64_t cols, double scale, const double* row_scale,

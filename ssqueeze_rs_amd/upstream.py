@@ -25,7 +25,11 @@ Supported subset (anything else raises ValueError naming the option):
   * difftype 'trig'; squeezing 'sum' / 'lebesgue'; padtype 'reflect' / 'zero';
   * `issq_cwt` / `issq_stft`: the full inverse, and the component inversion by curves `cc`, `cw`
     (_ssq_cwt.py:381-417): float64 [K + 1, N], or [B, K + 1, N] for a batched `Tx` [B, F, N] with the curves of a
-    batched `extract_ridges`; the full inverse takes 2-D `Tx` only;
+    batched `extract_ridges`; the full inverses `istft`, `issq_stft`, `issq_cwt` and `icwt` take a 2-D map or a batch
+    [B, F, N] -> [B, N] from one call (one window / wavelet / scale grid for the batch; `icwt(x_mean=)` a scalar or
+    one mean per signal); power-of-two `n_fft` 16 .. 4096 with `hop_len <= n_fft` of a batched `istft` run the
+    streaming kernel of csrc/istft_fused.hip when a signal has at least 256 tiles of frames, every other
+    shape the three-kernel path of the 2-D call per signal;
   * `ssqueeze` (ssqueezing.py:13-245) on a transform the caller holds, from `w` or `dWx`, CWT or STFT, 2-D or batched
     3-D: `ssq_freqs` None / 'log' / 'linear' / 'log-piecewise' / an array, maprange 'peak' / 'maximal', squeezing
     'sum' / 'lebesgue' / 'abs' / a function (from `dWx`: 'sum' only), `was_padded`, `flipud`; STFT needs an array
@@ -254,19 +258,28 @@ def stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, p
 
 
 def istft(Sx, window=None, n_fft=None, win_len=None, hop_len=1, N=None, modulated=True, win_exp=1):
-    """ssqueezepy.istft (old/ssqueezepy/_stft.py:196-254)."""
+    """ssqueezepy.istft (old/ssqueezepy/_stft.py:196-254).  `Sx` [n_fft//2 + 1, n_frames] -> [N]; extension: a batch
+    [B, n_fft//2 + 1, n_frames] -> [B, N] from one call (one window, n_fft, hop_len, N for all of it; signal b's result
+    does not depend on B)."""
     lib = _lib.load()
-    if not isinstance(Sx, np.ndarray) or Sx.ndim != 2 or Sx.dtype not in (np.complex64, np.complex128):
-        raise TypeError("`Sx` must be a 2D complex64 / complex128 array")
-    n_fft = n_fft or (Sx.shape[0] - 1) * 2
+    if not isinstance(Sx, np.ndarray) or Sx.ndim not in (2, 3) or Sx.dtype not in (np.complex64, np.complex128):
+        raise TypeError("`Sx` must be a 2D (or batched 3D [B, n_fft//2 + 1, n_frames]) complex64 / complex128 array")
+    n_fft = n_fft or (Sx.shape[-2] - 1) * 2
     win_len = win_len or n_fft
-    N = N or hop_len * Sx.shape[1]
-    if Sx.shape[0] != n_fft // 2 + 1:
-        raise ValueError("`Sx` has %d rows, n_fft=%d needs %d" % (Sx.shape[0], n_fft, n_fft // 2 + 1))
+    N = N or hop_len * Sx.shape[-1]
+    if Sx.shape[-2] != n_fft // 2 + 1:
+        raise ValueError("`Sx` has %d rows, n_fft=%d needs %d" % (Sx.shape[-2], n_fft, n_fft // 2 + 1))
+    if Sx.ndim == 3 and Sx.shape[0] < 1:
+        raise ValueError("`Sx` holds no signal (B == 0)")
     win = get_window(window, win_len, n_fft)
     code = SSQ_F32 if Sx.dtype == np.complex64 else SSQ_F64
     _lib.require_gpu()
     Sc = np.ascontiguousarray(Sx)
+    if Sx.ndim == 3:
+        x = np.empty((Sc.shape[0], N), dtype=_rdtype(code))
+        _call(lib.ssq_istft_batch_host(code, _ptr(Sc), Sc.shape[0], Sc.shape[2], _ptr(win), n_fft, hop_len, N,
+                                       int(bool(modulated)), int(win_exp), _ptr(x)))
+        return x
     x = np.empty(N, dtype=np.float32 if code == SSQ_F32 else np.float64)
     _call(lib.ssq_istft_host(code, _ptr(Sc), Sc.shape[1], _ptr(win), n_fft, hop_len, N, int(bool(modulated)),
                              int(win_exp), _ptr(x)))
@@ -314,7 +327,7 @@ def ssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=Non
 
 def issq_stft(Tx, window=None, cc=None, cw=None, n_fft=None, win_len=None, hop_len=1, modulated=True):
     """ssqueezepy.issq_stft (old/ssqueezepy/_ssq_stft.py:139-198).  `cc`, `cw` None: the full inverse [N] in Tx's real
-    dtype.  Otherwise the component inversion of `issq_cwt`, scaled by 2 / window[len(window) // 2]: float64
+    dtype ([B, N] for a batched `Tx` [B, F, N]).  Otherwise the component inversion of `issq_cwt`, scaled by 2 / window[len(window) // 2]: float64
     [K + 1, N], or [B, K + 1, N] for a batched `Tx` [B, F, N]."""
     if not modulated:
         raise ValueError("inversion with `modulated == False` is unsupported.")
@@ -326,21 +339,39 @@ def issq_stft(Tx, window=None, cc=None, cw=None, n_fft=None, win_len=None, hop_l
         win_len = win_len or n_fft
         win = get_window(window, win_len, n_fft)
         return _issq_components(*comp, 2.0 / float(win[len(win) // 2]))
-    n_fft = n_fft or (Tx.shape[0] - 1) * 2
+    _full_map(Tx, "Tx")
+    n_fft = n_fft or (Tx.shape[-2] - 1) * 2
     win_len = win_len or n_fft
     win = get_window(window, win_len, n_fft)
     return _issq(Tx, 2.0 / float(win[len(win) // 2]))
 
 
+class _RowCountError(AssertionError, ValueError):
+    """`icwt`'s row-count refusal: upstream's AssertionError (_cwt.py:398), and a ValueError like every other refusal."""
+
+
+def _full_map(Tx, name):
+    """The refusals of a full inverse's map, 2-D [F, N] or batched 3-D [B, F, N], before any GPU work."""
+    if not isinstance(Tx, np.ndarray) or Tx.ndim not in (2, 3) or Tx.dtype not in (np.complex64, np.complex128):
+        raise TypeError(f"`{name}` must be a 2D (or batched 3D [B, F, N]) complex64 / complex128 array")
+    if Tx.ndim == 3 and Tx.shape[0] < 1:
+        raise ValueError(f"`{name}` holds no signal (B == 0)")
+
+
 def _issq(Tx, scale, row_scale=None):
+    """scale * sum_rows row_scale[row] * Re Tx[row] -> [N], or [B, N] for a batched Tx (entry b bitwise the 2-D call)."""
     lib = _lib.load()
-    if not isinstance(Tx, np.ndarray) or Tx.ndim != 2 or Tx.dtype not in (np.complex64, np.complex128):
-        raise TypeError("`Tx` must be a 2D complex64 / complex128 array")
+    _full_map(Tx, "Tx")
     code = SSQ_F32 if Tx.dtype == np.complex64 else SSQ_F64
     _lib.require_gpu()
     Tc = np.ascontiguousarray(Tx)
-    x = np.empty(Tc.shape[1], dtype=np.float32 if code == SSQ_F32 else np.float64)
     rs = None if row_scale is None else np.ascontiguousarray(row_scale, dtype=np.float64)
+    if Tx.ndim == 3:
+        x = np.empty((Tc.shape[0], Tc.shape[2]), dtype=_rdtype(code))
+        _call(lib.ssq_issq_batch_host(code, _ptr(Tc), Tc.shape[0], Tc.shape[1], Tc.shape[2], float(scale), _ptr(rs),
+                                      _ptr(x)))
+        return x
+    x = np.empty(Tc.shape[1], dtype=np.float32 if code == SSQ_F32 else np.float64)
     _call(lib.ssq_issq_host(code, _ptr(Tc), Tc.shape[0], Tc.shape[1], float(scale), _ptr(rs), _ptr(x)))
     return x
 
@@ -605,7 +636,7 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
 
 def issq_cwt(Tx, wavelet="gmw", cc=None, cw=None):
     """ssqueezepy.issq_cwt (old/ssqueezepy/_ssq_cwt.py:313-417).  `cc`, `cw` None: the full inverse
-    (2 / Css) sum_rows Re Tx, [N] in Tx's real dtype.  Otherwise curve centres and half-widths (rows of Tx, one per
+    (2 / Css) sum_rows Re Tx, [N] in Tx's real dtype ([B, N] for a batched `Tx` [B, F, N]).  Otherwise curve centres and half-widths (rows of Tx, one per
     column; 1-D: one curve, 2-D [N, K]: K curves, as `extract_ridges` returns them) -> float64 [K + 1, N]: row k < K the
     sum of Re Tx over the rows clip(cc - cw, 0, F) .. clip(cc + cw, 0, F) of each column (none where cc == -1), row K
     the sum over the rows no curve covers, all times 2 / Css.  Extension: a batched Tx [B, F, N] with cc, cw [B, N] or
@@ -622,21 +653,29 @@ def icwt(Wx, wavelet="gmw", scales="log-piecewise", nv=None, one_int=True, x_len
     'log' scales:    (2 / Cpsi) ln(2^(1/nv)) sum_a Re Wx[a] / (1 or sqrt(a)) + x_mean;
     'linear':        (2 / Cpsi) (pi / 4) sum_a Re Wx[a] / (a or a^1.5) + x_mean (:438-448, :477-492);
     'log-piecewise': the 'log' inverses of the two segments either side of the transition, summed (:418-427; each
-                     adds x_mean, as upstream's do)."""
+                     adds x_mean, as upstream's do).
+    Extension: a batch `Wx` [B, na, N] -> [B, N]; `x_mean` a scalar or one value per signal."""
     if not one_int:
         raise ValueError("only the one-integral inverse (one_int=True) is built")
     s, scaletype, _nv, s_own = _scales(scales)
-    if Wx.shape[0] != len(s):
-        raise AssertionError("%s != %s" % (len(s), Wx.shape[0]))
+    _full_map(Wx, "Wx")
+    if Wx.shape[-2] != len(s):
+        raise _RowCountError("%s != %s" % (len(s), Wx.shape[-2]))
+    if Wx.ndim == 3:                                        # one mean per signal, or one for all
+        xm = np.asarray(x_mean)
+        if xm.ndim > 1 or (xm.ndim == 1 and xm.shape[0] != Wx.shape[0]):
+            raise ValueError(f"`x_mean` must be a scalar or one value per signal ({Wx.shape[0]}); got shape {xm.shape}")
     if scaletype == "log-piecewise":                        # the segments in the caller's dtype, as upstream splits them
         idx = logscale_transition_idx(s_own)
         kw = dict(wavelet=wavelet, one_int=one_int, x_len=x_len, x_mean=x_mean, padtype=padtype, rpadded=rpadded,
                   l1_norm=l1_norm)
-        return icwt(Wx[:idx], scales=s_own[:idx], **kw) + icwt(Wx[idx:], scales=s_own[idx:], **kw)
+        return icwt(Wx[..., :idx, :], scales=s_own[:idx], **kw) + icwt(Wx[..., idx:, :], scales=s_own[idx:], **kw)
     if scaletype == "linear":
         x = _issq(Wx, (2.0 / adm_ssq(wavelet)) * np.pi / 4, 1.0 / (s if l1_norm else s ** 1.5))
     else:
         x = _issq(Wx, (2.0 / adm_ssq(wavelet)) * np.log(2 ** (1 / _nv)), None if l1_norm else 1.0 / np.sqrt(s))
+    if Wx.ndim == 3 and np.ndim(x_mean) == 1:               # a column in x's dtype: what a Python float per 2-D call adds
+        return x + np.asarray(x_mean).reshape(-1, 1).astype(x.dtype)
     return x + x_mean
 
 
