@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ssq_hip.h"
+#include "dev_buffers.h"
 #include "fft_generic.h"
 #include "host_math.h"
 
@@ -81,15 +82,6 @@ __global__ void icwt_finish_kernel(const cpx<double>* __restrict__ acc, long lon
   if (j >= n) return;
   x[j] = (acc[j].x * inv_n) * final_norm + x_mean;
 }
-
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { hipFree(p); }
-  int alloc(long long bytes) {
-    SSQ_HIP(hipMalloc(&p, (size_t)(bytes > 0 ? bytes : 16)));
-    return 0;
-  }
-};
 
 // ------------------------------------------------------------------------------ wavelet helpers (host) ----
 using cd = std::complex<double>;
@@ -210,60 +202,57 @@ int ssq_icwt_host(int dtype, const void* Wx, int64_t na, int64_t n_times, int wa
   const double adm = (wavelet == SSQ_WAVELET_MORLET) ? 0.776 : 1.0;                   // cwt.rs:578-582
   const double dj = (na > 1 && scales[1] > scales[0]) ? std::log(scales[1] / scales[0]) : 0.1;   // :593-597
   const double final_norm = (2.0 / adm) * dj;
-  const long long esz = dtype == SSQ_F32 ? 8 : 16;
+  const size_t esz = dtype == SSQ_F32 ? 8 : 16;
   std::vector<double> fac((size_t)(na > 0 ? na : 1));
   for (int64_t i = 0; i < na; ++i) {
     if (one_int) fac[i] = l1_norm ? 1.0 : 1.0 / std::sqrt(scales[i]);                 // :605-609
     else fac[i] = l1_norm ? 1.0 / scales[i] : 1.0 / (std::sqrt(scales[i]) * std::sqrt(scales[i]));   // :679-683
   }
-  DevBuf dW, dfac, dx, dsc;
-  if (int rc = dW.alloc(na * n_times * esz)) return rc;
-  if (int rc = dfac.alloc(na * 8)) return rc;
-  if (int rc = dsc.alloc(na * 8)) return rc;
-  if (int rc = dx.alloc(x_len * 8)) return rc;
-  if (na > 0) {
-    SSQ_HIP(hipMemcpy(dW.p, Wx, (size_t)(na * n_times * esz), hipMemcpyHostToDevice));
-    SSQ_HIP(hipMemcpy(dfac.p, fac.data(), (size_t)(na * 8), hipMemcpyHostToDevice));
-    SSQ_HIP(hipMemcpy(dsc.p, scales, (size_t)(na * 8), hipMemcpyHostToDevice));
-  }
+  const size_t nsc = (size_t)(na > 0 ? na : 0), nx = (size_t)x_len;          // no scales: the holder's minimum size
+  HostCallBufs d;
+  void *dW, *dfac, *dsc, *dx;
+  SSQ_HIP(d.upload(&dW, Wx, nsc * (size_t)n_times * esz));
+  SSQ_HIP(d.upload(&dfac, fac.data(), nsc * 8));
+  SSQ_HIP(d.upload(&dsc, scales, nsc * 8));
+  SSQ_HIP(d.alloc(&dx, nx * 8));
   const dim3 blk(256), grd((unsigned)((x_len + 255) / 256));
   if (one_int) {
     if (dtype == SSQ_F32)
-      hipLaunchKernelGGL(icwt_one_int_kernel<float>, grd, blk, 0, nullptr, (const cpx<float>*)dW.p, (long long)n_times, (int)na,
-                         (const double*)dfac.p, final_norm, x_mean, (long long)x_len, (double*)dx.p);
+      hipLaunchKernelGGL(icwt_one_int_kernel<float>, grd, blk, 0, nullptr, (const cpx<float>*)dW, (long long)n_times, (int)na,
+                         (const double*)dfac, final_norm, x_mean, (long long)x_len, (double*)dx);
     else
-      hipLaunchKernelGGL(icwt_one_int_kernel<double>, grd, blk, 0, nullptr, (const cpx<double>*)dW.p, (long long)n_times,
-                         (int)na, (const double*)dfac.p, final_norm, x_mean, (long long)x_len, (double*)dx.p);
+      hipLaunchKernelGGL(icwt_one_int_kernel<double>, grd, blk, 0, nullptr, (const cpx<double>*)dW, (long long)n_times,
+                         (int)na, (const double*)dfac, final_norm, x_mean, (long long)x_len, (double*)dx);
     SSQ_HIP(hipGetLastError());
   } else {
     // FFT of every row (any length: rustfft plans any x_len), filter bank sum, one inverse FFT
-    DevBuf rows, work, acc;
+    void *rows, *work, *acc;
     const long long nrow = na > 0 ? na : 1;
     long long we = fft_work_elems(x_len, nrow);
     const long long we1 = fft_work_elems(x_len, 1);
     if (we1 > we) we = we1;
-    if (int rc = rows.alloc(nrow * x_len * 16)) return rc;
-    if (int rc = work.alloc(we * 16)) return rc;
-    if (int rc = acc.alloc(x_len * 16)) return rc;
+    SSQ_HIP(d.alloc(&rows, (size_t)nrow * nx * 16));
+    SSQ_HIP(d.alloc(&work, (size_t)(we > 0 ? we : 0) * 16));
+    SSQ_HIP(d.alloc(&acc, nx * 16));
     if (na > 0) {
       const dim3 g2((unsigned)((x_len * na + 255) / 256));
       if (dtype == SSQ_F32)
-        hipLaunchKernelGGL(icwt_gather_kernel<float>, g2, blk, 0, nullptr, (const cpx<float>*)dW.p, (long long)n_times,
-                           (long long)x_len, (int)na, (cpx<double>*)rows.p);
+        hipLaunchKernelGGL(icwt_gather_kernel<float>, g2, blk, 0, nullptr, (const cpx<float>*)dW, (long long)n_times,
+                           (long long)x_len, (int)na, (cpx<double>*)rows);
       else
-        hipLaunchKernelGGL(icwt_gather_kernel<double>, g2, blk, 0, nullptr, (const cpx<double>*)dW.p, (long long)n_times,
-                           (long long)x_len, (int)na, (cpx<double>*)rows.p);
-      SSQ_HIP(fft_any_batched<double>((cpx<double>*)rows.p, (cpx<double>*)work.p, x_len, na, -1, nullptr));
+        hipLaunchKernelGGL(icwt_gather_kernel<double>, g2, blk, 0, nullptr, (const cpx<double>*)dW, (long long)n_times,
+                           (long long)x_len, (int)na, (cpx<double>*)rows);
+      SSQ_HIP(fft_any_batched<double>((cpx<double>*)rows, (cpx<double>*)work, x_len, na, -1, nullptr));
     }
-    hipLaunchKernelGGL(icwt_filter_sum_kernel, grd, blk, 0, nullptr, (const cpx<double>*)rows.p, (long long)x_len, (int)na,
-                       (const double*)dsc.p, (const double*)dfac.p, wavelet, (cpx<double>*)acc.p);
-    SSQ_HIP(fft_any_batched<double>((cpx<double>*)acc.p, (cpx<double>*)work.p, x_len, 1, +1, nullptr));
-    hipLaunchKernelGGL(icwt_finish_kernel, grd, blk, 0, nullptr, (const cpx<double>*)acc.p, (long long)x_len,
-                       1.0 / (double)x_len, final_norm, x_mean, (double*)dx.p);
+    hipLaunchKernelGGL(icwt_filter_sum_kernel, grd, blk, 0, nullptr, (const cpx<double>*)rows, (long long)x_len, (int)na,
+                       (const double*)dsc, (const double*)dfac, wavelet, (cpx<double>*)acc);
+    SSQ_HIP(fft_any_batched<double>((cpx<double>*)acc, (cpx<double>*)work, x_len, 1, +1, nullptr));
+    hipLaunchKernelGGL(icwt_finish_kernel, grd, blk, 0, nullptr, (const cpx<double>*)acc, (long long)x_len,
+                       1.0 / (double)x_len, final_norm, x_mean, (double*)dx);
     SSQ_HIP(hipGetLastError());
   }
   SSQ_HIP(hipDeviceSynchronize());
-  SSQ_HIP(hipMemcpy(x_out, dx.p, (size_t)(x_len * 8), hipMemcpyDeviceToHost));
+  SSQ_HIP(hipMemcpy(x_out, dx, nx * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -11,10 +11,10 @@
 #include <vector>
 
 #include "../../include/ssq_hip.h"
+#include "dev_buffers.h"
 #include "fft_generic.h"
 #include "host_math.h"
 #include "istft_fused.h"
-#include "ssq_common.h"
 
 using namespace ssq;
 
@@ -60,21 +60,8 @@ __global__ void istft_ola_kernel(const cpx<T>* __restrict__ Y, int n, int n_fram
   x[i] = (T)(wn > tiny ? acc / wn : acc);
 }
 
-template <typename T>
-__global__ void issq_colsum_kernel(const cpx<T>* __restrict__ Tx, long long rows, long long cols, double scale,
-                                   const double* __restrict__ row_scale, T* __restrict__ x) {
-  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= cols) return;
-  double acc = 0.0;
-  if (row_scale) {
-    for (long long r = 0; r < rows; ++r) acc += (double)Tx[r * cols + j].x * row_scale[r];
-  } else {
-    for (long long r = 0; r < rows; ++r) acc += (double)Tx[r * cols + j].x;
-  }
-  x[j] = (T)(acc * scale);
-}
-
-// the same sum for a slice of signals, one per blockIdx.y: per thread exactly the arithmetic of issq_colsum_kernel
+// x[b][j] = scale * sum_r Re Tx[b][r][j] * row_scale[r] (row_scale NULL: 1), one signal per blockIdx.y, accumulated in
+// fp64 with the rows in order
 template <typename T>
 __global__ void issq_colsum_batch_kernel(const cpx<T>* __restrict__ Tx_all, long long rows, long long cols, double scale,
                                          const double* __restrict__ row_scale, T* __restrict__ x_all) {
@@ -120,61 +107,30 @@ template <typename T>
 int istft_typed(const void* Sx, int64_t n_frames, const std::vector<double>& wpow, const std::vector<double>& wnorm,
                 int64_t n, int64_t hop, int64_t N, int modulated, void* x_out) {
   const int64_t nf = n / 2 + 1;
-  cpx<T>*d_S = nullptr, *d_Z = nullptr, *d_work = nullptr;
-  double *d_wp = nullptr, *d_wn = nullptr;
-  T* d_x = nullptr;
-  int rc = 0;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == 0) {
-      set_error(std::string(what) + ": " + hipGetErrorString(e));
-      rc = 2;
-    }
-    return e != hipSuccess;
-  };
-  do {
-    if (fail(hipMalloc((void**)&d_S, sizeof(cpx<T>) * nf * n_frames), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_Z, sizeof(cpx<T>) * n * n_frames), "hipMalloc")) break;
-    const long long we = fft_work_elems(n, n_frames);
-    if (fail(hipMalloc((void**)&d_work, sizeof(cpx<T>) * (we > 0 ? we : 1)), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_wp, sizeof(double) * n), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_wn, sizeof(double) * n), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_x, sizeof(T) * N), "hipMalloc")) break;
-    if (fail(hipMemcpy(d_S, Sx, sizeof(cpx<T>) * nf * n_frames, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    if (fail(hipMemcpy(d_wp, wpow.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    if (fail(hipMemcpy(d_wn, wnorm.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    if (fail(istft_three_dev<T>(d_S, n_frames, d_wp, d_wn, n, hop, N, modulated, d_Z, d_work, d_x), "istft kernels")) break;
-    if (fail(hipMemcpy(x_out, d_x, sizeof(T) * N, hipMemcpyDeviceToHost), "hipMemcpy")) break;
-  } while (false);
-  hipFree(d_S);
-  hipFree(d_Z);
-  hipFree(d_work);
-  hipFree(d_wp);
-  hipFree(d_wn);
-  hipFree(d_x);
-  return rc;
+  const long long we = fft_work_elems(n, n_frames);
+  HostCallBufs d;
+  void *d_S, *d_Z, *d_work, *d_wp, *d_wn, *d_x;
+  SSQ_HIP(d.upload(&d_S, Sx, sizeof(cpx<T>) * nf * n_frames));
+  SSQ_HIP(d.alloc(&d_Z, sizeof(cpx<T>) * n * n_frames));
+  SSQ_HIP(d.alloc(&d_work, sizeof(cpx<T>) * (we > 0 ? we : 1)));
+  SSQ_HIP(d.upload(&d_wp, wpow.data(), sizeof(double) * n));
+  SSQ_HIP(d.upload(&d_wn, wnorm.data(), sizeof(double) * n));
+  SSQ_HIP(d.alloc(&d_x, sizeof(T) * N));
+  SSQ_HIP(istft_three_dev<T>((const cpx<T>*)d_S, n_frames, (const double*)d_wp, (const double*)d_wn, n, hop, N, modulated,
+                             (cpx<T>*)d_Z, (cpx<T>*)d_work, (T*)d_x));
+  SSQ_HIP(hipMemcpy(x_out, d_x, sizeof(T) * N, hipMemcpyDeviceToHost));
+  return 0;
 }
 
+// exp(-2 pi i k / n), k < n: the twiddle table of the fused inverse
 template <typename T>
-int issq_typed(const void* Tx, int64_t rows, int64_t cols, double scale, const double* row_scale, void* x_out) {
-  cpx<T>* d_T = nullptr;
-  T* d_x = nullptr;
-  double* d_r = nullptr;
-  SSQ_HIP(hipMalloc((void**)&d_T, sizeof(cpx<T>) * rows * cols));
-  hipError_t e = hipMalloc((void**)&d_x, sizeof(T) * cols);
-  if (e == hipSuccess && row_scale) e = hipMalloc((void**)&d_r, sizeof(double) * rows);
-  if (e == hipSuccess && row_scale) e = hipMemcpy(d_r, row_scale, sizeof(double) * rows, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_T, Tx, sizeof(cpx<T>) * rows * cols, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(issq_colsum_kernel<T>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, nullptr, d_T,
-                       (long long)rows, (long long)cols, scale, d_r, d_x);
-    e = hipGetLastError();
+std::vector<cpx<T>> istft_twiddles(int64_t n) {
+  std::vector<cpx<T>> tw((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)i / (long double)n;
+    tw[i] = {(T)cosl(ang), (T)(-sinl(ang))};
   }
-  if (e == hipSuccess) e = hipMemcpy(x_out, d_x, sizeof(T) * cols, hipMemcpyDeviceToHost);
-  hipFree(d_T);
-  hipFree(d_x);
-  hipFree(d_r);
-  SSQ_HIP(e);
-  return 0;
+  return tw;
 }
 
 // Device bytes of the fused path for `slice` signals: Sx in, x out and the three tables
@@ -192,45 +148,23 @@ int istft_batch_fused(const IstftPlan& pl, const void* Sx, int64_t batch, const 
   const int64_t n = pl.n, nf = n / 2 + 1, n_frames = pl.n_frames;
   const long long slice = slice_signals(batch, istft_fused_bytes<T>(pl, 1, N, true) - istft_fused_bytes<T>(pl, 0, N, true),
                                         istft_fused_bytes<T>(pl, 0, N, true), 65535);
-  std::vector<cpx<T>> tw((size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)i / (long double)n;
-    tw[i] = {(T)cosl(ang), (T)(-sinl(ang))};
-  }
-  cpx<T>*d_S = nullptr, *d_tw = nullptr;
-  double *d_wp = nullptr, *d_wn = nullptr;
-  T* d_x = nullptr;
-  int rc = 0;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == 0) {
-      set_error(std::string(what) + ": " + hipGetErrorString(e));
-      rc = 2;
-    }
-    return e != hipSuccess;
-  };
+  const std::vector<cpx<T>> tw = istft_twiddles<T>(n);
   const size_t sx_sig = sizeof(cpx<T>) * (size_t)nf * (size_t)n_frames;
-  do {
-    if (fail(hipMalloc((void**)&d_S, sx_sig * slice), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_x, sizeof(T) * (size_t)N * slice), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_tw, sizeof(cpx<T>) * n), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_wp, sizeof(double) * n), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_wn, sizeof(double) * n), "hipMalloc")) break;
-    if (fail(hipMemcpy(d_tw, tw.data(), sizeof(cpx<T>) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    if (fail(hipMemcpy(d_wp, wpow.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    if (fail(hipMemcpy(d_wn, wnorm.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    for (int64_t b0 = 0; b0 < batch && rc == 0; b0 += slice) {
-      const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
-      if (fail(hipMemcpy(d_S, (const char*)Sx + sx_sig * b0, sx_sig * nb, hipMemcpyHostToDevice), "hipMemcpy")) break;
-      if (fail(launch_istft_fused<T>(pl, d_S, nb, N, modulated, d_tw, d_wp, d_wn, d_x, nullptr), "istft_fused_kernel")) break;
-      if (fail(hipMemcpy((char*)x_out + sizeof(T) * (size_t)N * b0, d_x, sizeof(T) * (size_t)N * nb, hipMemcpyDeviceToHost), "hipMemcpy")) break;
-    }
-  } while (false);
-  hipFree(d_S);
-  hipFree(d_x);
-  hipFree(d_tw);
-  hipFree(d_wp);
-  hipFree(d_wn);
-  return rc;
+  HostCallBufs d;
+  void *d_S, *d_x, *d_tw, *d_wp, *d_wn;
+  SSQ_HIP(d.alloc(&d_S, sx_sig * slice));
+  SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)N * slice));
+  SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(cpx<T>) * n));
+  SSQ_HIP(d.upload(&d_wp, wpow.data(), sizeof(double) * n));
+  SSQ_HIP(d.upload(&d_wn, wnorm.data(), sizeof(double) * n));
+  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
+    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
+    SSQ_HIP(hipMemcpy(d_S, (const char*)Sx + sx_sig * b0, sx_sig * nb, hipMemcpyHostToDevice));
+    SSQ_HIP(launch_istft_fused<T>(pl, (const cpx<T>*)d_S, nb, N, modulated, (const cpx<T>*)d_tw, (const double*)d_wp,
+                                  (const double*)d_wn, (T*)d_x, nullptr));
+    SSQ_HIP(hipMemcpy((char*)x_out + sizeof(T) * (size_t)N * b0, d_x, sizeof(T) * (size_t)N * nb, hipMemcpyDeviceToHost));
+  }
+  return 0;
 }
 
 template <typename T>
@@ -238,38 +172,30 @@ int issq_batch_typed(const void* Tx, int64_t batch, int64_t rows, int64_t cols, 
                      void* x_out) {
   const size_t map_b = sizeof(cpx<T>) * (size_t)rows * (size_t)cols;
   const long long slice = slice_signals(batch, (double)map_b + (double)sizeof(T) * (double)cols, 8.0 * (double)rows, 65535);
-  cpx<T>* d_T = nullptr;
-  T* d_x = nullptr;
-  double* d_r = nullptr;
-  int rc = 0;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == 0) {
-      set_error(std::string(what) + ": " + hipGetErrorString(e));
-      rc = 2;
-    }
-    return e != hipSuccess;
-  };
-  do {
-    if (fail(hipMalloc((void**)&d_T, map_b * slice), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_x, sizeof(T) * (size_t)cols * slice), "hipMalloc")) break;
-    if (row_scale) {
-      if (fail(hipMalloc((void**)&d_r, sizeof(double) * rows), "hipMalloc")) break;
-      if (fail(hipMemcpy(d_r, row_scale, sizeof(double) * rows, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    }
-    for (int64_t b0 = 0; b0 < batch && rc == 0; b0 += slice) {
-      const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
-      if (fail(hipMemcpy(d_T, (const char*)Tx + map_b * b0, map_b * nb, hipMemcpyHostToDevice), "hipMemcpy")) break;
-      hipLaunchKernelGGL(issq_colsum_batch_kernel<T>, dim3((unsigned)((cols + 255) / 256), (unsigned)nb), dim3(256), 0, nullptr, d_T,
-                         (long long)rows, (long long)cols, scale, d_r, d_x);
-      if (fail(hipGetLastError(), "issq_colsum_batch_kernel")) break;
-      if (fail(hipMemcpy((char*)x_out + sizeof(T) * (size_t)cols * b0, d_x, sizeof(T) * (size_t)cols * nb, hipMemcpyDeviceToHost), "hipMemcpy")) break;
-    }
-  } while (false);
-  hipFree(d_T);
-  hipFree(d_x);
-  hipFree(d_r);
-  return rc;
+  HostCallBufs d;
+  void *d_T, *d_x, *d_r = nullptr;
+  SSQ_HIP(d.alloc(&d_T, map_b * slice));
+  SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)cols * slice));
+  if (row_scale) SSQ_HIP(d.upload(&d_r, row_scale, sizeof(double) * rows));
+  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
+    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
+    SSQ_HIP(hipMemcpy(d_T, (const char*)Tx + map_b * b0, map_b * nb, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(issq_colsum_batch_kernel<T>, dim3((unsigned)((cols + 255) / 256), (unsigned)nb), dim3(256), 0, nullptr,
+                       (const cpx<T>*)d_T, (long long)rows, (long long)cols, scale, (const double*)d_r, (T*)d_x);
+    SSQ_HIP(hipGetLastError());
+    SSQ_HIP(hipMemcpy((char*)x_out + sizeof(T) * (size_t)cols * b0, d_x, sizeof(T) * (size_t)cols * nb, hipMemcpyDeviceToHost));
+  }
+  return 0;
 }
+
+// the two timing events of ssq_istft_batch_exec, released on every path
+struct TimingEvents {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~TimingEvents() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
+};
 
 // The inverse of a batch that already lives on the device (d_Sx, d_x), by the path asked for; the kernels' own time
 // (HIP events around the launches, tables and workspace set up before) goes to *kernel_ms when it is not NULL.
@@ -278,69 +204,68 @@ int istft_batch_exec_typed(const void* d_Sx, int64_t batch, int64_t n_frames, co
                            const std::vector<double>& wnorm, int64_t n, int64_t hop, int64_t N, int modulated, bool fused,
                            const IstftPlan& pl, void* d_x_out, float* kernel_ms) {
   const int64_t nf = n / 2 + 1;
-  cpx<T>*d_tw = nullptr, *d_Z = nullptr, *d_work = nullptr;
-  double *d_wp = nullptr, *d_wn = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   const cpx<T>* d_S = (const cpx<T>*)d_Sx;
   T* d_x = (T*)d_x_out;
-  int rc = 0;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == 0) {
-      set_error(std::string(what) + ": " + hipGetErrorString(e));
-      rc = 2;
+  HostCallBufs d;
+  TimingEvents t;
+  void *d_wp, *d_wn, *d_tw = nullptr, *d_Z = nullptr, *d_work = nullptr;
+  SSQ_HIP(d.upload(&d_wp, wpow.data(), sizeof(double) * n));
+  SSQ_HIP(d.upload(&d_wn, wnorm.data(), sizeof(double) * n));
+  if (fused) {
+    const std::vector<cpx<T>> tw = istft_twiddles<T>(n);
+    SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(cpx<T>) * n));
+  } else {
+    const long long we = fft_work_elems(n, n_frames);
+    SSQ_HIP(d.alloc(&d_Z, sizeof(cpx<T>) * n * n_frames));
+    SSQ_HIP(d.alloc(&d_work, sizeof(cpx<T>) * (we > 0 ? we : 1)));
+  }
+  if (kernel_ms) {
+    SSQ_HIP(hipEventCreate(&t.ev0));
+    SSQ_HIP(hipEventCreate(&t.ev1));
+    SSQ_HIP(hipEventRecord(t.ev0, nullptr));
+  }
+  if (fused) {
+    for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+      const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
+      SSQ_HIP(launch_istft_fused<T>(pl, d_S + b0 * nf * n_frames, nb, N, modulated, (const cpx<T>*)d_tw, (const double*)d_wp,
+                                    (const double*)d_wn, d_x + b0 * N, nullptr));
     }
-    return e != hipSuccess;
-  };
-  do {
-    if (fail(hipMalloc((void**)&d_wp, sizeof(double) * n), "hipMalloc")) break;
-    if (fail(hipMalloc((void**)&d_wn, sizeof(double) * n), "hipMalloc")) break;
-    if (fail(hipMemcpy(d_wp, wpow.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    if (fail(hipMemcpy(d_wn, wnorm.data(), sizeof(double) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    if (fused) {
-      std::vector<cpx<T>> tw((size_t)n);
-      for (int64_t i = 0; i < n; ++i) {
-        const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)i / (long double)n;
-        tw[i] = {(T)cosl(ang), (T)(-sinl(ang))};
-      }
-      if (fail(hipMalloc((void**)&d_tw, sizeof(cpx<T>) * n), "hipMalloc")) break;
-      if (fail(hipMemcpy(d_tw, tw.data(), sizeof(cpx<T>) * n, hipMemcpyHostToDevice), "hipMemcpy")) break;
-    } else {
-      const long long we = fft_work_elems(n, n_frames);
-      if (fail(hipMalloc((void**)&d_Z, sizeof(cpx<T>) * n * n_frames), "hipMalloc")) break;
-      if (fail(hipMalloc((void**)&d_work, sizeof(cpx<T>) * (we > 0 ? we : 1)), "hipMalloc")) break;
-    }
-    if (kernel_ms) {
-      if (fail(hipEventCreate(&ev0), "hipEventCreate") || fail(hipEventCreate(&ev1), "hipEventCreate")) break;
-      if (fail(hipEventRecord(ev0, nullptr), "hipEventRecord")) break;
-    }
-    if (fused) {
-      for (int64_t b0 = 0; b0 < batch && rc == 0; b0 += 65535) {
-        const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
-        fail(launch_istft_fused<T>(pl, d_S + b0 * nf * n_frames, nb, N, modulated, d_tw, d_wp, d_wn, d_x + b0 * N, nullptr),
-             "istft_fused_kernel");
-      }
-    } else {
-      for (int64_t b = 0; b < batch && rc == 0; ++b)
-        fail(istft_three_dev<T>(d_S + b * nf * n_frames, n_frames, d_wp, d_wn, n, hop, N, modulated, d_Z, d_work, d_x + b * N),
-             "istft kernels");
-    }
-    if (rc) break;
-    if (kernel_ms) {
-      if (fail(hipEventRecord(ev1, nullptr), "hipEventRecord")) break;
-      if (fail(hipEventSynchronize(ev1), "hipEventSynchronize")) break;
-      if (fail(hipEventElapsedTime(kernel_ms, ev0, ev1), "hipEventElapsedTime")) break;
-    } else if (fail(hipDeviceSynchronize(), "hipDeviceSynchronize")) {
-      break;
-    }
-  } while (false);
-  if (ev0) hipEventDestroy(ev0);
-  if (ev1) hipEventDestroy(ev1);
-  hipFree(d_tw);
-  hipFree(d_Z);
-  hipFree(d_work);
-  hipFree(d_wp);
-  hipFree(d_wn);
-  return rc;
+  } else {
+    for (int64_t b = 0; b < batch; ++b)
+      SSQ_HIP(istft_three_dev<T>(d_S + b * nf * n_frames, n_frames, (const double*)d_wp, (const double*)d_wn, n, hop, N,
+                                 modulated, (cpx<T>*)d_Z, (cpx<T>*)d_work, d_x + b * N));
+  }
+  if (kernel_ms) {
+    SSQ_HIP(hipEventRecord(t.ev1, nullptr));
+    SSQ_HIP(hipEventSynchronize(t.ev1));
+    SSQ_HIP(hipEventElapsedTime(kernel_ms, t.ev0, t.ev1));
+  } else {
+    SSQ_HIP(hipDeviceSynchronize());
+  }
+  return 0;
+}
+
+// The argument checks the three ssq_istft_* entry points share, in their order (batch: 1 for the single-signal form)
+int istft_args(int dtype, const void* Sx, int64_t batch, int64_t n_frames, const double* window, int64_t n_fft, int64_t hop,
+               int64_t n_signal, int win_exp, const void* x_out) {
+  if (!Sx || !window || !x_out) SSQ_FAIL("NULL argument");
+  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
+  if (batch < 1) SSQ_FAIL("batch must be >= 1");
+  if (n_fft < 1 || hop < 1 || n_frames < 1 || n_signal < 1 || win_exp < 0) SSQ_FAIL("bad istft shape");
+  if (n_fft > (1 << 24)) SSQ_FAIL("n_fft too large");
+  if ((n_signal - 1) / hop + 1 != n_frames) SSQ_FAIL("Sx has the wrong number of frames for (N, hop_len)");
+  return 0;
+}
+
+// The window's two tables, built once every check has passed: wpow = window^win_exp (utils/stft_utils.py:159-162),
+// wnorm = window^(win_exp+1) (:186)
+void istft_window_tables(const double* window, int64_t n_fft, int win_exp, std::vector<double>& wpow, std::vector<double>& wnorm) {
+  wpow.resize((size_t)n_fft);
+  wnorm.resize((size_t)n_fft);
+  for (int64_t i = 0; i < n_fft; ++i) {
+    wpow[i] = win_exp == 0 ? 1.0 : std::pow(window[i], (double)win_exp);
+    wnorm[i] = std::pow(window[i], (double)(win_exp + 1));
+  }
 }
 
 // Which path a shape takes: the fused kernel where it takes the shape and the signal has enough tiles to fill the device.
@@ -421,37 +346,20 @@ extern "C" {
 
 int ssq_istft_host(int dtype, const void* Sx, int64_t n_frames, const double* window, int64_t n_fft, int64_t hop,
                    int64_t n_signal, int modulated, int win_exp, void* x_out) {
-  if (!Sx || !window || !x_out) SSQ_FAIL("NULL argument");
-  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
-  if (n_fft < 1 || hop < 1 || n_frames < 1 || n_signal < 1 || win_exp < 0) SSQ_FAIL("bad istft shape");
-  if (n_fft > (1 << 24)) SSQ_FAIL("n_fft too large");
-  if ((n_signal - 1) / hop + 1 != n_frames) SSQ_FAIL("Sx has the wrong number of frames for (N, hop_len)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
-  std::vector<double> wpow((size_t)n_fft), wnorm((size_t)n_fft);
-  for (int64_t i = 0; i < n_fft; ++i) {
-    wpow[i] = win_exp == 0 ? 1.0 : std::pow(window[i], (double)win_exp);       // utils/stft_utils.py:159-162
-    wnorm[i] = std::pow(window[i], (double)(win_exp + 1));                      // :186
-  }
+  if (int rc = istft_args(dtype, Sx, 1, n_frames, window, n_fft, hop, n_signal, win_exp, x_out)) return rc;
+  if (int rc = require_device()) return rc;
+  std::vector<double> wpow, wnorm;
+  istft_window_tables(window, n_fft, win_exp, wpow, wnorm);
   return dtype == SSQ_F32 ? istft_typed<float>(Sx, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, x_out)
                           : istft_typed<double>(Sx, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, x_out);
 }
 
 int ssq_istft_batch_host(int dtype, const void* Sx, int64_t batch, int64_t n_frames, const double* window, int64_t n_fft,
                          int64_t hop, int64_t n_signal, int modulated, int win_exp, void* x_out) {
-  if (!Sx || !window || !x_out) SSQ_FAIL("NULL argument");
-  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
-  if (batch < 1) SSQ_FAIL("batch must be >= 1");
-  if (n_fft < 1 || hop < 1 || n_frames < 1 || n_signal < 1 || win_exp < 0) SSQ_FAIL("bad istft shape");
-  if (n_fft > (1 << 24)) SSQ_FAIL("n_fft too large");
-  if ((n_signal - 1) / hop + 1 != n_frames) SSQ_FAIL("Sx has the wrong number of frames for (N, hop_len)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
-  std::vector<double> wpow((size_t)n_fft), wnorm((size_t)n_fft);
-  for (int64_t i = 0; i < n_fft; ++i) {
-    wpow[i] = win_exp == 0 ? 1.0 : std::pow(window[i], (double)win_exp);       // utils/stft_utils.py:159-162
-    wnorm[i] = std::pow(window[i], (double)(win_exp + 1));                      // :186
-  }
+  if (int rc = istft_args(dtype, Sx, batch, n_frames, window, n_fft, hop, n_signal, win_exp, x_out)) return rc;
+  if (int rc = require_device()) return rc;
+  std::vector<double> wpow, wnorm;
+  istft_window_tables(window, n_fft, win_exp, wpow, wnorm);
   IstftPlan pl;
   if (istft_use_fused(n_fft, hop, n_frames, &pl))
     return dtype == SSQ_F32 ? istft_batch_fused<float>(pl, Sx, batch, wpow, wnorm, n_signal, modulated, x_out)
@@ -471,24 +379,15 @@ int ssq_istft_batch_host(int dtype, const void* Sx, int64_t batch, int64_t n_fra
 
 int ssq_istft_batch_exec(int dtype, const void* d_Sx, int64_t batch, int64_t n_frames, const double* window, int64_t n_fft,
                          int64_t hop, int64_t n_signal, int modulated, int win_exp, int path, void* d_x, float* kernel_ms) {
-  if (!d_Sx || !window || !d_x) SSQ_FAIL("NULL argument");
-  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
-  if (batch < 1) SSQ_FAIL("batch must be >= 1");
-  if (n_fft < 1 || hop < 1 || n_frames < 1 || n_signal < 1 || win_exp < 0) SSQ_FAIL("bad istft shape");
-  if (n_fft > (1 << 24)) SSQ_FAIL("n_fft too large");
-  if ((n_signal - 1) / hop + 1 != n_frames) SSQ_FAIL("Sx has the wrong number of frames for (N, hop_len)");
+  if (int rc = istft_args(dtype, d_Sx, batch, n_frames, window, n_fft, hop, n_signal, win_exp, d_x)) return rc;
   if (path < -1 || path > 1) SSQ_FAIL("path must be -1 (as ssq_istft_batch_host chooses), 0 (three kernels) or 1 (fused)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
+  if (int rc = require_device()) return rc;
   IstftPlan pl;
   const bool can = istft_fused_plan(n_fft, hop, n_frames, &pl);
   if (path == 1 && !can) SSQ_FAIL("the fused istft kernel does not take this (n_fft, hop_len)");
+  std::vector<double> wpow, wnorm;
+  istft_window_tables(window, n_fft, win_exp, wpow, wnorm);
   const bool fused = path == 1 || (path == -1 && istft_use_fused(n_fft, hop, n_frames, &pl));
-  std::vector<double> wpow((size_t)n_fft), wnorm((size_t)n_fft);
-  for (int64_t i = 0; i < n_fft; ++i) {
-    wpow[i] = win_exp == 0 ? 1.0 : std::pow(window[i], (double)win_exp);
-    wnorm[i] = std::pow(window[i], (double)(win_exp + 1));
-  }
   return dtype == SSQ_F32
              ? istft_batch_exec_typed<float>(d_Sx, batch, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, fused, pl, d_x, kernel_ms)
              : istft_batch_exec_typed<double>(d_Sx, batch, n_frames, wpow, wnorm, n_fft, hop, n_signal, modulated, fused, pl, d_x, kernel_ms);
@@ -520,8 +419,7 @@ int ssq_issq_batch_host(int dtype, const void* Tx, int64_t batch, int64_t rows, 
   if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
   if (batch < 1) SSQ_FAIL("batch must be >= 1");
   if (rows < 1 || cols < 1) SSQ_FAIL("empty Tx");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
+  if (int rc = require_device()) return rc;
   return dtype == SSQ_F32 ? issq_batch_typed<float>(Tx, batch, rows, cols, scale, row_scale, x_out)
                           : issq_batch_typed<double>(Tx, batch, rows, cols, scale, row_scale, x_out);
 }
@@ -531,10 +429,9 @@ int ssq_issq_host(int dtype, const void* Tx, int64_t rows, int64_t cols, double 
   if (!Tx || !x_out) SSQ_FAIL("NULL argument");
   if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
   if (rows < 1 || cols < 1) SSQ_FAIL("empty Tx");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
-  return dtype == SSQ_F32 ? issq_typed<float>(Tx, rows, cols, scale, row_scale, x_out)
-                          : issq_typed<double>(Tx, rows, cols, scale, row_scale, x_out);
+  if (int rc = require_device()) return rc;
+  return dtype == SSQ_F32 ? issq_batch_typed<float>(Tx, 1, rows, cols, scale, row_scale, x_out)   // one signal: a batch of one
+                          : issq_batch_typed<double>(Tx, 1, rows, cols, scale, row_scale, x_out);
 }
 
 int ssq_upstream_adm(int wavelet, double p0, double p1, int which_cwt, double* out) {

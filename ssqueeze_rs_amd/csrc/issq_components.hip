@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "../../include/ssq_hip.h"
-#include "ssq_common.h"
+#include "dev_buffers.h"
 
 using namespace ssq;
 
@@ -223,12 +223,6 @@ int check_args(int dtype, int64_t batch, int64_t rows, int64_t cols, int64_t n_c
 
 bool fits_int32(int64_t v) { return v >= INT32_MIN && v <= INT32_MAX; }
 
-int require_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -280,27 +274,17 @@ int ssq_issq_components_host(int dtype, const void* Tx, int64_t batch, int64_t r
   if (int rc = require_device()) return rc;
   const size_t tx_bytes = (size_t)(batch * rows * cols) * (dtype == SSQ_F64 ? 16 : 8);
   const size_t x_bytes = (size_t)(batch * (n_comp + 1) * cols) * sizeof(double);
-  void *dT = nullptr, *dcc = nullptr, *dcw = nullptr, *dx = nullptr;
-  hipError_t e = hipMalloc(&dT, tx_bytes);
-  if (e == hipSuccess) e = hipMalloc(&dcc, nb * sizeof(int64_t));
-  if (e == hipSuccess && cw) e = hipMalloc(&dcw, nb * sizeof(int64_t));
-  if (e == hipSuccess) e = hipMalloc(&dx, x_bytes);
-  if (e == hipSuccess) e = hipMemcpy(dT, Tx, tx_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dcc, cc, nb * sizeof(int64_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess && cw) e = hipMemcpy(dcw, cw, nb * sizeof(int64_t), hipMemcpyHostToDevice);
-  int rc = 0;
-  if (e == hipSuccess) {
-    rc = ssq_issq_components_exec(dtype, dT, batch, rows, cols, static_cast<const int64_t*>(dcc),
-                                  static_cast<const int64_t*>(dcw), cw_const, n_comp, scale, static_cast<double*>(dx),
-                                  nullptr);
-    if (rc == 0) e = hipMemcpy(x_out, dx, x_bytes, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(dT);
-  (void)hipFree(dcc);
-  (void)hipFree(dcw);
-  (void)hipFree(dx);
-  if (rc) return rc;
-  SSQ_HIP(e);
+  HostCallBufs d;
+  void *dT, *dcc, *dcw = nullptr, *dx;
+  SSQ_HIP(d.upload(&dT, Tx, tx_bytes));
+  SSQ_HIP(d.upload(&dcc, cc, nb * sizeof(int64_t)));
+  if (cw) SSQ_HIP(d.upload(&dcw, cw, nb * sizeof(int64_t)));
+  SSQ_HIP(d.alloc(&dx, x_bytes));
+  if (int rc = ssq_issq_components_exec(dtype, dT, batch, rows, cols, static_cast<const int64_t*>(dcc),
+                                        static_cast<const int64_t*>(dcw), cw_const, n_comp, scale, static_cast<double*>(dx),
+                                        nullptr))
+    return rc;
+  SSQ_HIP(hipMemcpy(x_out, dx, x_bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "../../include/ssq_hip.h"
-#include "ssq_common.h"
+#include "dev_buffers.h"
 
 using namespace ssq;
 
@@ -432,27 +432,6 @@ int exec_typed(int is_complex, const void* Tf, int64_t batch, int F, int64_t N, 
   return 0;
 }
 
-// RAII list of device allocations for the host entry points
-struct DevAllocs {
-  std::vector<void*> ptrs;
-  ~DevAllocs() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  hipError_t alloc(void** p, size_t bytes) {
-    *p = nullptr;
-    if (bytes == 0) return hipSuccess;
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) ptrs.push_back(*p);
-    return e;
-  }
-};
-
-int require_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -495,20 +474,17 @@ int ssq_extract_ridges_host(int dtype, int param_dtype, int is_complex, const vo
   if (int rc = require_device()) return rc;
   const size_t es = dtype == SSQ_F64 ? 8 : 4, ps = param_dtype == SSQ_F64 ? 8 : 4;
   const size_t n = (size_t)(batch * n_freqs * n_time), outs = (size_t)(batch * n_time * n_ridges);
-  DevAllocs d;
+  HostCallBufs d;
   void *dT, *dm, *ds = nullptr, *di, *df = nullptr, *de = nullptr, *dc = nullptr, *dw;
   const int64_t wsb = (int64_t)ws_bytes(dtype, batch, n_freqs, n_time);
-  SSQ_HIP(d.alloc(&dT, n * es * (is_complex ? 2 : 1)));
-  SSQ_HIP(d.alloc(&dm, (size_t)n_freqs * ps));
-  if (scales) SSQ_HIP(d.alloc(&ds, (size_t)n_freqs * ps));
+  SSQ_HIP(d.upload(&dT, Tf, n * es * (is_complex ? 2 : 1)));
+  SSQ_HIP(d.upload(&dm, metric, (size_t)n_freqs * ps));
+  if (scales) SSQ_HIP(d.upload(&ds, scales, (size_t)n_freqs * ps));
   SSQ_HIP(d.alloc(&di, outs * sizeof(int64_t)));
   if (ridge_f) SSQ_HIP(d.alloc(&df, outs * ps));
   if (ridge_e) SSQ_HIP(d.alloc(&de, outs * ps));
   if (cost_out) SSQ_HIP(d.alloc(&dc, n * (size_t)n_ridges * es));
   SSQ_HIP(d.alloc(&dw, (size_t)wsb));
-  SSQ_HIP(hipMemcpy(dT, Tf, n * es * (is_complex ? 2 : 1), hipMemcpyHostToDevice));
-  SSQ_HIP(hipMemcpy(dm, metric, (size_t)n_freqs * ps, hipMemcpyHostToDevice));
-  if (ds) SSQ_HIP(hipMemcpy(ds, scales, (size_t)n_freqs * ps, hipMemcpyHostToDevice));
   if (int rc = ssq_ridges_exec(dtype, param_dtype, is_complex, dT, batch, n_freqs, n_time, dm, ds, penalty, n_ridges, bw,
                                static_cast<int64_t*>(di), df, de, dc, dw, wsb, nullptr))
     return rc;
@@ -527,15 +503,13 @@ int ssq_ridge_track_host(int dtype, int param_dtype, const void* cost, int64_t b
   const size_t es = dtype == SSQ_F64 ? 8 : 4, ps = param_dtype == SSQ_F64 ? 8 : 4;
   const int64_t F = n_freqs, N = n_time;
   const size_t n = (size_t)(batch * F * N);
-  DevAllocs d;
+  HostCallBufs d;
   void *dsrc, *dct, *dpen, *dm, *dr;
-  SSQ_HIP(d.alloc(&dsrc, n * es));
+  SSQ_HIP(d.upload(&dsrc, cost, n * es));
   SSQ_HIP(d.alloc(&dct, n * es));
   SSQ_HIP(d.alloc(&dpen, n * es));
-  SSQ_HIP(d.alloc(&dm, (size_t)F * ps));
+  SSQ_HIP(d.upload(&dm, metric, (size_t)F * ps));
   SSQ_HIP(d.alloc(&dr, (size_t)(batch * N) * sizeof(int)));
-  SSQ_HIP(hipMemcpy(dsrc, cost, n * es, hipMemcpyHostToDevice));
-  SSQ_HIP(hipMemcpy(dm, metric, (size_t)F * ps, hipMemcpyHostToDevice));
   const dim3 cgrid((unsigned)((N + 63) / 64), (unsigned)batch);
   int rc = 0;
   if (dtype == SSQ_F32) {

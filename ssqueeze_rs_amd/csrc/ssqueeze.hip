@@ -18,7 +18,7 @@
 
 #include "../../include/ssq_hip.h"
 #include "cwt_kernels.h"
-#include "ssq_common.h"
+#include "dev_buffers.h"
 #include "stft_kernels.h"
 
 using namespace ssq;
@@ -284,32 +284,7 @@ int squeeze_dwx_typed(const void* Wx, const void* dWx, const void* Sfs, int64_t 
   return 0;
 }
 
-int require_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) SSQ_FAIL("no HIP device visible (there is no CPU fallback)");
-  return 0;
-}
-
-// device buffers of one synchronous host call, freed on every path
-struct DevBufs {
-  std::vector<void*> p;
-  ~DevBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  hipError_t alloc(void** out, size_t bytes) {
-    *out = nullptr;
-    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-    if (e == hipSuccess) p.push_back(*out);
-    return e;
-  }
-  hipError_t upload(void** out, const void* src, size_t bytes) {
-    hipError_t e = alloc(out, bytes);
-    if (e == hipSuccess && src) e = hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice);
-    return e;
-  }
-};
-
-int upload_row_const(DevBufs& d, int dtype, const double* row_const, int64_t rows, void** out) {
+int upload_row_const(HostCallBufs& d, int dtype, const double* row_const, int64_t rows, void** out) {
   if (!row_const) SSQ_FAIL("row_const is NULL");
   for (int64_t i = 0; i < rows; ++i)
     if (!std::isfinite(row_const[i])) SSQ_FAIL("row_const must be finite");
@@ -341,7 +316,7 @@ int ssq_phase_host(int dtype, const void* Wx, const void* dWx, const void* Sfs, 
   if (!Wx || !dWx || !w) SSQ_FAIL("NULL argument");
   if (int rc = require_device()) return rc;
   const size_t esz = dtype == SSQ_F64 ? 8 : 4, n = (size_t)(batch * rows * cols);
-  DevBufs d;
+  HostCallBufs d;
   void *dW = nullptr, *ddW = nullptr, *dS = nullptr, *dw = nullptr;
   SSQ_HIP(d.upload(&dW, Wx, n * 2 * esz));
   SSQ_HIP(d.upload(&ddW, dWx, n * 2 * esz));
@@ -375,7 +350,7 @@ int ssq_ssqueeze_w_host(int dtype, const void* Wx, const void* w, int64_t batch,
   if (int rc = require_device()) return rc;
   const size_t esz = dtype == SSQ_F64 ? 8 : 4, n = (size_t)(batch * rows * cols);
   const size_t tx_bytes = n * (squeezing == SSQ_SQUEEZE_ABS ? esz : 2 * esz);
-  DevBufs d;
+  HostCallBufs d;
   void *dW = nullptr, *dw = nullptr, *dc = nullptr, *dT = nullptr;
   if (squeezing != SSQ_SQUEEZE_LEBESGUE) SSQ_HIP(d.upload(&dW, Wx, n * 2 * esz));
   SSQ_HIP(d.upload(&dw, w, n * esz));
@@ -416,7 +391,7 @@ int ssq_ssqueeze_dwx_host(int dtype, const void* Wx, const void* dWx, const void
     if (s0 != f0) SSQ_FAIL("STFT from dSx: ssq_freqs_asc[0] must equal Sfs[0]");
   }
   if (int rc = require_device()) return rc;
-  DevBufs d;
+  HostCallBufs d;
   void *dW = nullptr, *ddW = nullptr, *dS = nullptr, *dc = nullptr, *dT = nullptr;
   SSQ_HIP(d.upload(&dW, Wx, n * 2 * esz));
   SSQ_HIP(d.upload(&ddW, dWx, n * 2 * esz));
