@@ -244,6 +244,18 @@ int ssq_stft_plan_destroy(ssq_stft_plan* plan);
 int ssq_stft_plan_is_fused(const ssq_stft_plan* plan);
 /* bytes of device scratch exec needs for `batch` signals with output kind `out_kind` */
 int64_t ssq_stft_plan_workspace_bytes(const ssq_stft_plan* plan, int64_t batch, int out_kind);
+/* Read-only: what ssq_stft_plan_exec would launch for `out_kind` and `batch` signals on the fused kernels --
+ * frames per output tile, tiles over the whole batch and the grid (persistent blocks: each walks
+ * ceil(total_tiles / max_blocks) tiles at most).  Where a pass is an interior launch plus an edge launch, total_tiles
+ * is their sum and max_blocks the larger grid.  Plans on the unfused kernels report tile_frames = 0 (and 0 tiles).
+ * Out-pointers may be NULL.  Launches nothing. */
+int ssq_stft_plan_launch_info(const ssq_stft_plan* plan, int out_kind, int64_t batch, int* tile_frames,
+                              int64_t* total_tiles, int64_t* max_blocks);
+/* The same per launch, in launch order: n_launch is 0 (unfused plan), 1 or 2; for launch i, edge[i] is 1 for the
+ * edge-capable kernel (padding by index mirroring) and 0 for the interior kernel (direct loads), tiles[i] its tiles
+ * over the batch, blocks[i] its grid.  The arrays hold at least 2 entries; any pointer may be NULL. */
+int ssq_stft_plan_launch_list(const ssq_stft_plan* plan, int out_kind, int64_t batch, int* n_launch, int* edge,
+                              int64_t* tiles, int64_t* blocks);
 /* d_x: [batch][N]; d_out: [batch][n_freqs][n_frames] complex; async on `stream` (hipStream_t). */
 int ssq_stft_plan_exec(ssq_stft_plan* plan, int out_kind, const void* d_x, int64_t batch,
                        void* d_out, void* d_workspace, int64_t workspace_bytes, void* stream);

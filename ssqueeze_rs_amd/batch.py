@@ -75,6 +75,21 @@ class SsqStftBatch:
         _lib.check(self.lib.ssq_device_sync())
         return out
 
+    def launch_info(self, batch: int, out_kind: int = _lib.OUT_TX) -> Tuple[int, int, int]:
+        """(tile_frames, total_tiles, max_blocks) of what `run` launches for `batch` signals
+        (ssq_stft_plan_launch_info): persistent blocks walk more than one tile once total_tiles > max_blocks."""
+        tf, tiles, blocks = C.c_int(), C.c_int64(), C.c_int64()
+        _lib.check(self.lib.ssq_stft_plan_launch_info(self.plan, out_kind, int(batch), C.byref(tf), C.byref(tiles),
+                                                      C.byref(blocks)))
+        return tf.value, tiles.value, blocks.value
+
+    def launch_list(self, batch: int, out_kind: int = _lib.OUT_TX):
+        """[(edge, tiles, blocks)] per launch of what `run` launches for `batch` signals (ssq_stft_plan_launch_list):
+        one edge-capable launch over all tiles, or the interior launch followed by the edge launch."""
+        n, edge, tiles, blocks = C.c_int(), (C.c_int * 2)(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
+        _lib.check(self.lib.ssq_stft_plan_launch_list(self.plan, out_kind, int(batch), C.byref(n), edge, tiles, blocks))
+        return [(edge[i], tiles[i], blocks[i]) for i in range(n.value)]
+
     def close(self):
         if getattr(self, "plan", None):
             self.lib.ssq_dev_free(self.d_x)

@@ -410,6 +410,55 @@ int ssq_stft_plan_destroy(ssq_stft_plan* pl) {
 
 int ssq_stft_plan_is_fused(const ssq_stft_plan* pl) { return pl && pl->fused ? 1 : 0; }
 
+// the launch shape of a fused pass, from the launchers' own helper on the very parameter block exec builds
+static int plan_launch_shape(const ssq_stft_plan* pl, int out_kind, int64_t batch, FusedLaunchShape& shape) {
+  if (!pl) SSQ_FAIL("plan is NULL");
+  if (out_kind < SSQ_OUT_TX || out_kind > SSQ_OUT_WK) SSQ_FAIL("bad out_kind");
+  if (batch < 0 || batch > 0x7fffffff) SSQ_FAIL("bad batch");
+  shape = FusedLaunchShape{};
+  if (!pl->fused || batch == 0) return 0;
+  if (pl->dtype == SSQ_F32) {
+    const StftDev<float> p = make_dev<float>(pl, out_kind, nullptr, nullptr, batch, SigLayout{});
+    SSQ_HIP(fused_launch_shape<float>(p, pl->fft_len, pl->cu_count, batch, shape));
+  } else {
+    const StftDev<double> p = make_dev<double>(pl, out_kind, nullptr, nullptr, batch, SigLayout{});
+    SSQ_HIP(fused_launch_shape<double>(p, pl->fft_len, pl->cu_count, batch, shape));
+  }
+  return 0;
+}
+
+int ssq_stft_plan_launch_info(const ssq_stft_plan* pl, int out_kind, int64_t batch, int* tile_frames,
+                              int64_t* total_tiles, int64_t* max_blocks) {
+  if (tile_frames) *tile_frames = 0;
+  if (total_tiles) *total_tiles = 0;
+  if (max_blocks) *max_blocks = 0;
+  FusedLaunchShape shape;
+  if (int rc = plan_launch_shape(pl, out_kind, batch, shape)) return rc;
+  long long tiles = 0, blocks = 0;
+  for (int i = 0; i < shape.n_launch; ++i) {
+    tiles += shape.launch[i].total_tiles;
+    blocks = std::max(blocks, shape.launch[i].blocks);
+  }
+  if (tile_frames) *tile_frames = shape.tile_frames;
+  if (total_tiles) *total_tiles = tiles;
+  if (max_blocks) *max_blocks = blocks;
+  return 0;
+}
+
+int ssq_stft_plan_launch_list(const ssq_stft_plan* pl, int out_kind, int64_t batch, int* n_launch, int* edge,
+                              int64_t* tiles, int64_t* blocks) {
+  if (n_launch) *n_launch = 0;
+  FusedLaunchShape shape;
+  if (int rc = plan_launch_shape(pl, out_kind, batch, shape)) return rc;
+  if (n_launch) *n_launch = shape.n_launch;
+  for (int i = 0; i < shape.n_launch; ++i) {
+    if (edge) edge[i] = shape.launch[i].edge;
+    if (tiles) tiles[i] = shape.launch[i].total_tiles;
+    if (blocks) blocks[i] = shape.launch[i].blocks;
+  }
+  return 0;
+}
+
 int64_t ssq_stft_plan_workspace_bytes(const ssq_stft_plan* pl, int64_t batch, int out_kind) {
   if (!pl || pl->fused) return 0;
   const int64_t elem = (pl->dtype == SSQ_F32 ? 8 : 16);

@@ -282,12 +282,14 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
         const float d = (sfs0 + (float)q * sfs_q) - pd;
         const float w = fabsf(d);
         float m = fma_clamp01(den, p.keep_big, p.keep_bias) * fma_clamp01(d, 0.0f, 1.0f);
+        if constexpr (LEB) m = leb_keep_f32(m, den, w, p.gamma2);
         if (EDGE) m *= lane_on;
         if (q == 8) m *= (t == 0) ? 1.0f : 0.0f;
         const cpx<T> c = LEB ? cpx<T>{p.leb_unit * m, 0.0f} : cpx<T>{S.x * m, S.y * m};
         cv[q] = c;
         int kneg = cvt_floor_i32(__builtin_fmaf(-w, p.inv_dw, 0.5f));
         kneg = kneg < neg_last ? neg_last : kneg;
+        if constexpr (LEB) kneg = (w != w) ? 0 : kneg;          // a kept NaN bin: the scan leaves k = 0 (leb_keep_f32)
         dstb[q] = __mul24(kneg, -(PITCH * CELL)) + fl * CELL;
         l1 += fabsf(c.x) + fabsf(c.y);
         if constexpr (WKDBG) {
@@ -342,9 +344,12 @@ bool fused_supported(int n_fft) {
   return n_fft >= 64 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0;
 }
 
+// The launches of one pass of the power-of-two kernels: the ONLY place that decides tile size, launch split and grid.
+// launch_one launches what this returns; ssq_stft_plan_launch_info reports it.
 template <typename T, int LOGN>
-static hipError_t launch_one(const StftDev<T>& p0, int cu_count, long long batch, hipStream_t stream) {
+static FusedLaunchShape shape_one(const StftDev<T>& p0, int cu_count, long long batch) {
   using C = FusedCfg<T, LOGN>;
+  FusedLaunchShape s;
   int per_cu = (160 * 1024) / C::LDS_BYTES;
   if (per_cu < 1) per_cu = 1;
   if (per_cu * C::W > 32) per_cu = 32 / C::W;
@@ -353,7 +358,9 @@ static hipError_t launch_one(const StftDev<T>& p0, int cu_count, long long batch
   // profiles/r01_ab_two_8wave_blocks.txt)
   bool tx1024 = false;
   if constexpr (sizeof(T) == 4 && LOGN == 10) tx1024 = (p0.out_kind == 0 || p0.out_kind == 3) && p0.n_eff == C::N;
+  s.tx1024 = tx1024;
   const int TF = tx1024 ? Hi1024::F : C::F;   // frames per tile of the kernel that will run
+  s.tile_frames = TF;
   // interior tiles [lo, hi): every frame of the tile reads only inside the signal
   const long long span = (long long)TF * p0.hop;
   const int tps_all = (p0.n_frames + TF - 1) / TF;
@@ -370,33 +377,51 @@ static hipError_t launch_one(const StftDev<T>& p0, int cu_count, long long batch
   bool single_launch = (long long)tps_all * batch <= 4 * blocks_one_wave;   // measured break-even: a few waves
   if (const char* e = std::getenv("SSQ_SINGLE_LAUNCH")) single_launch = std::atoi(e) != 0;   // tests: force either path
   for (int edge = single_launch ? 1 : 0; edge < 2; ++edge) {
-    StftDev<T> p = p0;
+    FusedLaunchShape::Launch l;
+    l.edge = edge;
     if (single_launch) {
-      p.ta0 = 0;
-      p.ta_n = tps_all;
-      p.tb0 = 0;
-      p.tiles_per_signal = tps_all;
+      l.ta0 = 0;
+      l.ta_n = tps_all;
+      l.tb0 = 0;
+      l.tiles_per_signal = tps_all;
     } else if (!edge) {
-      p.ta0 = (int)lo;
-      p.ta_n = (int)(hi - lo);
-      p.tb0 = 0;
-      p.tiles_per_signal = p.ta_n;
+      l.ta0 = (int)lo;
+      l.ta_n = (int)(hi - lo);
+      l.tb0 = 0;
+      l.tiles_per_signal = l.ta_n;
     } else {
-      p.ta0 = 0;
-      p.ta_n = (int)lo;
-      p.tb0 = (int)hi;
-      p.tiles_per_signal = (int)lo + (tps_all - (int)hi);
+      l.ta0 = 0;
+      l.ta_n = (int)lo;
+      l.tb0 = (int)hi;
+      l.tiles_per_signal = (int)lo + (tps_all - (int)hi);
     }
-    p.total_tiles = (long long)p.tiles_per_signal * batch;
-    if (p.total_tiles <= 0) continue;
-    long long blocks = (long long)cu_count * per_cu;
-    if (blocks > p.total_tiles) blocks = p.total_tiles;
-    const dim3 g((unsigned)blocks), b(C::W * 64);
+    l.total_tiles = (long long)l.tiles_per_signal * batch;
+    if (l.total_tiles <= 0) continue;
+    l.blocks = tx1024 ? (long long)cu_count : (long long)cu_count * per_cu;   // tx1024: one block per CU
+    if (l.blocks > l.total_tiles) l.blocks = l.total_tiles;
+    s.launch[s.n_launch++] = l;
+  }
+  return s;
+}
+
+template <typename T, int LOGN>
+static hipError_t launch_one(const StftDev<T>& p0, int cu_count, long long batch, hipStream_t stream) {
+  using C = FusedCfg<T, LOGN>;
+  const FusedLaunchShape s = shape_one<T, LOGN>(p0, cu_count, batch);
+  const bool tx1024 = s.tx1024;
+  for (int i = 0; i < s.n_launch; ++i) {
+    const FusedLaunchShape::Launch& l = s.launch[i];
+    const int edge = l.edge;
+    StftDev<T> p = p0;
+    p.ta0 = l.ta0;
+    p.ta_n = l.ta_n;
+    p.tb0 = l.tb0;
+    p.tiles_per_signal = l.tiles_per_signal;
+    p.total_tiles = l.total_tiles;
+    const dim3 g((unsigned)l.blocks), b(C::W * 64);
     if constexpr (sizeof(T) == 4 && LOGN == 10) {
       if (tx1024) {
-        long long nb = cu_count;                      // one block per CU
-        if (nb > p.total_tiles) nb = p.total_tiles;
-        const dim3 gh((unsigned)nb), bh(Hi1024::THREADS);
+        const dim3 gh((unsigned)l.blocks), bh(Hi1024::THREADS);
         if (p.out_kind == 3) {
           if (edge) hipLaunchKernelGGL((stft_tx1024_kernel<true, false, true>), gh, bh, 0, stream, p);
           else hipLaunchKernelGGL((stft_tx1024_kernel<false, false, true>), gh, bh, 0, stream, p);
@@ -434,31 +459,23 @@ static hipError_t launch_one(const StftDev<T>& p0, int cu_count, long long batch
 
 template <typename T>
 int fused_tile_frames(int n_fft) {
-  switch (n_fft) {
-    case 64: return FusedCfg<T, 6>::F;
-    case 128: return FusedCfg<T, 7>::F;
-    case 256: return FusedCfg<T, 8>::F;
-    case 512: return FusedCfg<T, 9>::F;
-    case 1024: return FusedCfg<T, 10>::F;
-    case 2048: return FusedCfg<T, 11>::F;
-    case 4096: return FusedCfg<T, 12>::F;
-  }
-  return 0;
+  return for_fused_len(n_fft, 0, [](auto L) { return (int)FusedCfg<T, decltype(L)::value>::F; });
 }
 
 template <typename T>
 hipError_t launch_stft_fused(const StftDev<T>& p, int n_fft, int cu_count, long long batch, hipStream_t stream) {
   if (p.n_eff != n_fft) return launch_stft_anylen<T>(p, n_fft, cu_count, batch, stream);   // stft_anylen.hip
-  switch (n_fft) {
-    case 64: return launch_one<T, 6>(p, cu_count, batch, stream);
-    case 128: return launch_one<T, 7>(p, cu_count, batch, stream);
-    case 256: return launch_one<T, 8>(p, cu_count, batch, stream);
-    case 512: return launch_one<T, 9>(p, cu_count, batch, stream);
-    case 1024: return launch_one<T, 10>(p, cu_count, batch, stream);
-    case 2048: return launch_one<T, 11>(p, cu_count, batch, stream);
-    case 4096: return launch_one<T, 12>(p, cu_count, batch, stream);
-  }
-  return hipErrorInvalidValue;
+  return for_fused_len(n_fft, hipErrorInvalidValue,
+                       [&](auto L) { return launch_one<T, decltype(L)::value>(p, cu_count, batch, stream); });
+}
+
+template <typename T>
+hipError_t fused_launch_shape(const StftDev<T>& p, int n_fft, int cu_count, long long batch, FusedLaunchShape& shape) {
+  if (p.n_eff != n_fft) return anylen_launch_shape<T>(p, n_fft, cu_count, batch, shape);   // stft_anylen.hip
+  return for_fused_len(n_fft, hipErrorInvalidValue, [&](auto L) {
+    shape = shape_one<T, decltype(L)::value>(p, cu_count, batch);
+    return hipSuccess;
+  });
 }
 
 template bool fused_supported<float>(int);
@@ -467,5 +484,7 @@ template int fused_tile_frames<float>(int);
 template int fused_tile_frames<double>(int);
 template hipError_t launch_stft_fused<float>(const StftDev<float>&, int, int, long long, hipStream_t);
 template hipError_t launch_stft_fused<double>(const StftDev<double>&, int, int, long long, hipStream_t);
+template hipError_t fused_launch_shape<float>(const StftDev<float>&, int, int, long long, FusedLaunchShape&);
+template hipError_t fused_launch_shape<double>(const StftDev<double>&, int, int, long long, FusedLaunchShape&);
 
 }  // namespace ssq

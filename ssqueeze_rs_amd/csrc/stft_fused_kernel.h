@@ -80,6 +80,22 @@ struct FusedCfg {
   static_assert(LDS_BYTES <= LDS_MAX, "LDS budget");
 };
 
+// The ONE table of transform lengths the fused kernel is instantiated for: fn(std::integral_constant<int, LOGN>{}) for
+// n = 2^LOGN, `none` for any other length.  Launchers, launch-shape helpers and the tile-size lookup all go through it.
+template <typename R, typename Fn>
+static inline R for_fused_len(int n, R none, Fn&& fn) {
+  switch (n) {
+    case 64: return fn(std::integral_constant<int, 6>{});
+    case 128: return fn(std::integral_constant<int, 7>{});
+    case 256: return fn(std::integral_constant<int, 8>{});
+    case 512: return fn(std::integral_constant<int, 9>{});
+    case 1024: return fn(std::integral_constant<int, 10>{});
+    case 2048: return fn(std::integral_constant<int, 11>{});
+    case 4096: return fn(std::integral_constant<int, 12>{});
+  }
+  return none;
+}
+
 __device__ __forceinline__ int cvt_round_i32(float x);
 
 // bit casts between T and its integer twin (debug outputs travel through the integer tile)
@@ -169,6 +185,15 @@ __device__ __forceinline__ int cvt_round_i32(float x) {                     // f
   int r;
   asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
   return r;
+}
+
+// fp32 Lebesgue weight mask.  The clamped-fma mask above is 0 for a NaN bin, which is harmless in sum mode (the weight
+// Sx * 0 is NaN all the same and the column comes out NaN) but would DROP the bin's constant weight 1/n_freqs here.  The
+// reference skips a bin only for |Sx| < gamma or infinite w (ssq_stft.rs:23, :278): a NaN bin is kept and its scan leaves
+// k = 0 (set next to the bin index).  Same rule as phase_bin, which the fp64 kernels use.
+__device__ __forceinline__ float leb_keep_f32(float m, float den, float w, float gamma2) {
+  const bool skip = (den < gamma2) || (fabsf(w) == INFINITY);      // both false for NaN
+  return (den != den || w != w) ? (skip ? 0.0f : 1.0f) : m;
 }
 
 // Power-of-two fixed-point scale of a column: 2^e > tot, scale = dw * 2^(FRAC-e), inv = 2^(e-FRAC).
@@ -568,6 +593,7 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
             const float w = fabsf((sfs0 + (float)q * sfs_q) - pd);            // ssq_stft.rs:33
             // keep = (|Sx|^2 >= gamma^2) and (w finite)   (ssq_stft.rs:23, :278) as a 0/1 float
             float m = fma_clamp01(den, p.keep_big, p.keep_bias) * fma_clamp01(w, 0.0f, 1.0f);
+            if constexpr (LEB) m = leb_keep_f32(m, den, w, p.gamma2);
             if (EDGE) m *= lane_on;
             if (q == 8) m *= (t == 0) ? 1.0f : 0.0f;                           // bin N/2 lives on lane 0 only
             if constexpr (ANYLEN) m *= (q < 8 && t + L * q < p.n_freqs) ? 1.0f : 0.0f;   // bins of the n_eff-point transform
@@ -576,6 +602,7 @@ __global__ __launch_bounds__((FusedCfg<T, LOGN, MODE != 0>::W * 64)) void stft_f
             // kk = ceil(w/dw - 1/2) = -floor(1/2 - w/dw), clamped to the last bin (ssq_stft.rs:280-289)
             int kneg = cvt_floor_i32(__builtin_fmaf(-w, p.inv_dw, 0.5f));
             kneg = kneg < neg_last ? neg_last : kneg;
+            if constexpr (LEB) kneg = (w != w) ? 0 : kneg;      // a kept NaN bin: the scan leaves k = 0 (leb_keep_f32)
             dstb[q] = __mul24(kneg, -(PITCH * (int)sizeof(T))) + fl4;
             l1 += fabsf(c.x) + fabsf(c.y);
             if constexpr (WKDBG) {

@@ -71,12 +71,30 @@ template <typename T>
 bool fused_supported(int n_fft);
 template <typename T>
 int fused_tile_frames(int n_fft);          // frames per output tile (F)
+// What one fused pass launches: the tile size of the kernel that runs, and per launch the tiles of one signal it covers
+// (StftDev::ta0/ta_n/tb0), its tile count over the batch and its grid.  The launchers build this once and launch exactly
+// what it says; the read-only query (ssq_stft_plan_launch_info) reports the same object.
+struct FusedLaunchShape {
+  int tile_frames = 0;
+  int n_launch = 0;
+  bool tx1024 = false;           // fp32 n_fft = 1024 Tx / (w, k): the 16-wave kernel
+  struct Launch {
+    int edge = 0;                // the edge-capable instantiation (padding by index mirroring)
+    int ta0 = 0, ta_n = 0, tb0 = 0, tiles_per_signal = 0;
+    long long total_tiles = 0, blocks = 0;
+  } launch[2];
+};
 // launches the interior-tile kernel (direct loads) and the edge-tile kernel (mirrored/zero padding)
 template <typename T>
 hipError_t launch_stft_fused(const StftDev<T>& p, int n_fft, int cu_count, long long batch, hipStream_t stream);
 // the any-length modes of the same kernel (stft_anylen.hip): p.n_eff != fft_len
 template <typename T>
 hipError_t launch_stft_anylen(const StftDev<T>& p, int fft_len, int cu_count, long long batch, hipStream_t stream);
+// the shape launch_stft_fused / launch_stft_anylen would launch for the same arguments (nothing is launched)
+template <typename T>
+hipError_t fused_launch_shape(const StftDev<T>& p, int n_fft, int cu_count, long long batch, FusedLaunchShape& shape);
+template <typename T>
+hipError_t anylen_launch_shape(const StftDev<T>& p, int fft_len, int cu_count, long long batch, FusedLaunchShape& shape);
 
 // generic any-n_fft kernels (stft_generic.hip); tables are always double
 struct GenericTabs {

@@ -19,6 +19,31 @@ def test_library_exports_every_declared_symbol():
     assert lib.ssq_hello_from_bin() == b"Hello from ssqueeze!"          # lib.rs:16-19
 
 
+def test_launch_info_is_declared_bound_and_rejects_bad_arguments():
+    """ssq_stft_plan_launch_info: in the header, in the ctypes table with the header's argument list, and a NULL
+    plan is an error with a message (the query itself needs a plan, hence a GPU: tests/test_gpu_stft_walk.py)."""
+    lib = _lib.load()
+    assert "ssq_stft_plan_launch_info" in _lib.header_symbols()
+    res, args = _lib._SIGNATURES["ssq_stft_plan_launch_info"]
+    assert res is C.c_int
+    assert args == [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    with open(_lib.HEADER_PATH) as f:
+        decl = f.read().split("int ssq_stft_plan_launch_info(", 1)[1].split(");", 1)[0]
+    assert [a.strip().rsplit(" ", 1)[0] for a in decl.replace("\n", " ").split(",")] == [
+        "const ssq_stft_plan*", "int", "int64_t", "int*", "int64_t*", "int64_t*"]
+    tf, tiles, blocks = C.c_int(7), C.c_int64(7), C.c_int64(7)
+    assert lib.ssq_stft_plan_launch_info(None, _lib.OUT_TX, 1, C.byref(tf), C.byref(tiles), C.byref(blocks)) != 0
+    assert b"plan is NULL" in lib.ssq_last_error()
+    # the per-launch form of the same query
+    res, args = _lib._SIGNATURES["ssq_stft_plan_launch_list"]
+    assert res is C.c_int
+    assert args == [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                    C.POINTER(C.c_int64)]
+    n = C.c_int(7)
+    assert lib.ssq_stft_plan_launch_list(None, _lib.OUT_TX, 1, C.byref(n), None, None, None) != 0 and n.value == 0
+    assert b"plan is NULL" in lib.ssq_last_error()
+
+
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
