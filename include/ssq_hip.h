@@ -31,6 +31,9 @@ extern "C" {
 
 enum { SSQ_F32 = 0, SSQ_F64 = 1 };
 enum { SSQ_PAD_REFLECT = 0, SSQ_PAD_ZERO = 1 };          /* stft_utils.rs:19-65, utils/array.rs:52-98 */
+/* upstream-variant plans and the *_host_v entry points only (utils/common.py:54-158): np.pad 'symmetric', 'edge', 'wrap'.
+ * The reference-variant entry points keep their rule: 0 reflects, every other code pads with zeros. */
+enum { SSQ_PAD_SYMMETRIC = 2, SSQ_PAD_REPLICATE = 3, SSQ_PAD_WRAP = 4 };
 enum { SSQ_SQUEEZE_SUM = 0, SSQ_SQUEEZE_LEBESGUE = 1 };  /* ssq_stft.rs:292-296, ssq_cwt.rs:199-206 */
 enum { SSQ_WAVELET_GMW = 0, SSQ_WAVELET_MORLET = 1 };    /* cwt.rs:496-543 */
 enum { SSQ_FREQS_LOG = 0, SSQ_FREQS_LINEAR = 1 };        /* ssq_cwt.rs:56-112 */
@@ -71,6 +74,10 @@ int ssq_log_scales(int64_t n_signal, int64_t nv, int simd_variant, int64_t* na, 
 int ssq_size_window(const double* window, int64_t win_n, int64_t n_fft, double* out);
 /* ssq_stft.rs:131-179: spectral derivative of the window (Nyquist term kept) */
 int ssq_diff_window(const double* window, int64_t n_fft, double* out);
+/* The index map every forward kernel fetches padded samples through: padded position m (m < 0 left of the signal,
+ * m >= n right of it) -> *idx = source sample in [0, n), or -1 where the pad is zero.  Host code, no GPU needed.
+ * Non-zero return for a pad type outside SSQ_PAD_* or n < 1. */
+int ssq_pad_index(int padtype, int64_t m, int64_t n, int64_t* idx);
 /* ssq_cwt.rs:450-469: the `ssq_freqs` vector ssq_cwt returns */
 int ssq_cwt_ssq_freqs(const double* scales, int64_t na, int64_t n_signal, double dt,
                       int maprange, int freq_dist, double* ssq_freqs);
@@ -296,6 +303,9 @@ int ssq_cwt_plan_create_gmwk(ssq_cwt_plan** plan, int dtype, int64_t n_signal, d
                              double dt, int padtype, int variant);
 int ssq_cwt_plan_destroy(ssq_cwt_plan* plan);
 int64_t ssq_cwt_plan_workspace_bytes(const ssq_cwt_plan* plan, int64_t batch);
+/* How many scales of an ssq exec the cwt_os families serve (time tiles, decimated, analytic-input and full-circle
+ * tiles).  0: the naive / tile / two-step / big kernels alone, which is what every upstream-variant plan gets. */
+int ssq_cwt_plan_tiled_rows(const ssq_cwt_plan* plan);
 /* cwt: d_Wx/d_dWx [batch][na][cols]; d_dWx may be NULL */
 int ssq_cwt_plan_exec_cwt(ssq_cwt_plan* plan, const void* d_x, int64_t batch, int l1_norm,
                           int rpadded, void* d_Wx, void* d_dWx,

@@ -41,6 +41,7 @@ _SIGNATURES = {
     "ssq_device_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(i64), C.c_char_p, C.c_int]),
     "ssq_stft_shape": (C.c_int, [i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]),
     "ssq_cwt_pad_len": (C.c_int, [i64, C.POINTER(i64), C.POINTER(i64)]),
+    "ssq_pad_index": (C.c_int, [C.c_int, i64, i64, C.POINTER(i64)]),
     "ssq_log_scales": (C.c_int, [i64, i64, C.c_int, C.POINTER(i64), vp]),
     "ssq_size_window": (C.c_int, [vp, i64, i64, vp]),
     "ssq_diff_window": (C.c_int, [vp, i64, vp]),
@@ -109,6 +110,7 @@ _SIGNATURES = {
     "ssq_cwt_plan_create": (C.c_int, [C.POINTER(vp), C.c_int, i64, C.c_int, vp, i64, C.c_double, C.c_int]),
     "ssq_cwt_plan_destroy": (C.c_int, [vp]),
     "ssq_cwt_plan_workspace_bytes": (i64, [vp, i64]),
+    "ssq_cwt_plan_tiled_rows": (C.c_int, [vp]),
     "ssq_cwt_plan_exec_cwt": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, i64, vp]),
     "ssq_cwt_plan_exec_ssq": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                         vp, vp, vp, vp, vp, i64, vp]),

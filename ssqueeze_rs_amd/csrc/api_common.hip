@@ -7,6 +7,7 @@
 
 #include "../../include/ssq_hip.h"
 #include "host_math.h"
+#include "pad_index.h"
 #include "ssq_common.h"
 
 namespace ssq {
@@ -109,6 +110,16 @@ int ssq_cwt_ssq_freqs(const double* scales, int64_t na, int64_t n_signal, double
   }
   std::vector<double> f = host::cwt_ssq_freqs(na, fmin, fmax, freq_dist == SSQ_FREQS_LINEAR);
   std::memcpy(ssq_freqs, f.data(), f.size() * sizeof(double));
+  return 0;
+}
+
+// the loaders' own index map (pad_index.h), evaluated on the host
+int ssq_pad_index(int padtype, int64_t m, int64_t n, int64_t* idx) {
+  if (!idx) SSQ_FAIL("idx is NULL");
+  *idx = -1;
+  if (padtype < SSQ_PAD_REFLECT || padtype > SSQ_PAD_WRAP) SSQ_FAIL("unknown pad type (0 reflect, 1 zero, 2 symmetric, 3 replicate, 4 wrap)");
+  if (n < 1) SSQ_FAIL("empty input signal");
+  *idx = (int64_t)pad_index(padtype, (long long)m, (long long)n);
   return 0;
 }
 

@@ -894,7 +894,10 @@ static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int
     }
   }
   pl->wavelet = wavelet;
-  pl->padtype = padtype;
+  // reference variant: reflect, and every other code pads with zeros; upstream plans hand the code to the loaders as it
+  // is (pad_index.h: 0-4).  The time-tile, register-core and full-circle families below are reference-variant only, so
+  // they meet codes 0 and 1 alone
+  pl->padtype = ups ? padtype : (padtype != SSQ_PAD_REFLECT ? SSQ_PAD_ZERO : SSQ_PAD_REFLECT);
   pl->na = (int)na;
   pl->dt = dt;
   pl->scales.assign(scales, scales + na);
@@ -1108,6 +1111,13 @@ int ssq_cwt_plan_destroy(ssq_cwt_plan* pl) {
   if (pl->side) (void)hipStreamDestroy(pl->side);
   delete pl;
   return 0;
+}
+
+int ssq_cwt_plan_tiled_rows(const ssq_cwt_plan* pl) {
+  if (!pl) return 0;
+  int rows = 0;
+  for (const auto m : pl->os_mask) rows += m ? 1 : 0;
+  return rows;
 }
 
 int64_t ssq_cwt_plan_workspace_bytes(const ssq_cwt_plan* pl, int64_t batch) {

@@ -1,6 +1,7 @@
 // api_stft.hip -- STFT-family plans and host entry points of the C-ABI (include/ssq_hip.h).
 // Replaces the PyO3 functions `stft` (rust/src/spectral/stft.rs:12-95) and `ssq_stft`
 // (rust/src/spectral/ssq_stft.rs:72-313).
+#include <cassert>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -310,11 +311,13 @@ int ssq_stft_plan_create_v(ssq_stft_plan** plan, int dtype, int64_t n_signal, co
   pl->n_freqs = (int)nf;
   pl->n_frames = (int)nfr;
   pl->pad_left = (int)((n_fft - 1) / 2);                     // stft_utils.rs:21-22
-  pl->padtype = padtype;
+  const bool ups = (variant & SSQ_VARIANT_UPSTREAM) != 0;
+  // reference variant: reflect, and every other code pads with zeros (stft_utils.rs:19-65); upstream plans hand the code
+  // to the loaders as it is (pad_index.h: 0-4, an unknown code pads with zeros there as well)
+  pl->padtype = ups ? padtype : (padtype != SSQ_PAD_REFLECT ? SSQ_PAD_ZERO : SSQ_PAD_REFLECT);
   pl->squeezing = squeezing;
   pl->fs = fs;
   pl->gamma = gamma < 0 ? 10.0 * 2.2204460492503131e-16 : gamma;   // ssq_stft.rs:258-261
-  const bool ups = (variant & SSQ_VARIANT_UPSTREAM) != 0;
   pl->variant = variant;
   if (ups) {
     // old/ssqueezepy: padlength N + n_fft - 1 with the LARGER half on the left (utils/common.py:111-116), frames
@@ -380,6 +383,9 @@ int ssq_stft_plan_create_v(ssq_stft_plan** plan, int dtype, int64_t n_signal, co
     pl->blue = true;
     pl->fused = true;
   }
+  // The fused kernels compile pad codes 0 and 1 alone (pad_index.h).  No plan can hand them another: a reference plan's
+  // code was folded to 0 / 1 above, and an upstream plan set force_generic, so it is never fused.
+  assert(!pl->fused || pl->padtype == SSQ_PAD_REFLECT || pl->padtype == SSQ_PAD_ZERO);
   pl->tile_frames = pl->fused ? (f32 ? fused_tile_frames<float>(pl->fft_len) : fused_tile_frames<double>(pl->fft_len)) : 1;
   // everything else that is long enough to matter: the batched any-length device FFT (force_generic keeps the direct
   // sums as the independent second implementation of the parity tests)

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
         for (int q = 0; q < 16; ++q) xv[q] = xs[pos0 + L * q];
       } else {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) xv[q] = load_padded_flat(xs, pos0 + L * q, p.n_signal, p.padtype, valid);
+        for (int q = 0; q < 16; ++q) xv[q] = load_padded_flat<false>(xs, pos0 + L * q, p.n_signal, p.padtype, valid);
       }
     }
   };

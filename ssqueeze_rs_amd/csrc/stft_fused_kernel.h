@@ -279,7 +279,7 @@ __device__ __forceinline__ void load_samples(const StftDev<T>& p, const TileItem
     } else {
 #pragma unroll
       for (int q = 0; q < 16; ++q)
-        xv[q] = load_padded_flat(w.xs, w.pos0 + L * q, p.n_signal, p.padtype, w.valid && t + L * q < p.n_eff);
+        xv[q] = load_padded_flat<false>(w.xs, w.pos0 + L * q, p.n_signal, p.padtype, w.valid && t + L * q < p.n_eff);
     }
   } else if constexpr (BLUE) {
     // only the n_eff samples of the frame are read (the table's zero padding must not meet a NaN beyond it); they all
@@ -292,7 +292,7 @@ __device__ __forceinline__ void load_samples(const StftDev<T>& p, const TileItem
     } else {
 #pragma unroll
       for (int q = 0; q < 8; ++q)
-        xv[q] = load_padded_flat(w.xs, w.pos0 + L * q, p.n_signal, p.padtype, w.valid && t + L * q < p.n_eff);
+        xv[q] = load_padded_flat<false>(w.xs, w.pos0 + L * q, p.n_signal, p.padtype, w.valid && t + L * q < p.n_eff);
     }
 #pragma unroll
     for (int q = 8; q < 16; ++q) xv[q] = (T)0;
@@ -306,7 +306,7 @@ __device__ __forceinline__ void load_samples(const StftDev<T>& p, const TileItem
       for (int q = 0; q < 16; ++q) xv[q] = w.xs[w.pos0 + L * q];
     } else {
 #pragma unroll
-      for (int q = 0; q < 16; ++q) xv[q] = load_padded_flat(w.xs, w.pos0 + L * q, p.n_signal, p.padtype, w.valid != 0);
+      for (int q = 0; q < 16; ++q) xv[q] = load_padded_flat<false>(w.xs, w.pos0 + L * q, p.n_signal, p.padtype, w.valid != 0);
     }
   }
 }

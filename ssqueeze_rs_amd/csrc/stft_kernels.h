@@ -1,5 +1,6 @@
 // stft_kernels.h -- device parameter block + launch entry points of the STFT family.
 #pragma once
+#include "pad_index.h"
 #include "ssq_common.h"
 
 namespace ssq {
@@ -218,24 +219,21 @@ __device__ __forceinline__ bool phase_bin(const StftDev<T>& p, int i, cpx<T> S, 
   return !skip;
 }
 
-// padded sample fetch: stft_utils.rs:19-65 by index mirroring (no padded copy)
+// padded sample fetch by index mapping (no padded copy): pad_index.h holds the map of all pad types
 template <typename T>
 __device__ __forceinline__ T load_padded(const T* __restrict__ xs, long long m, long long n, int padtype) {
   if (m >= 0 && m < n) return xs[m];
-  if (padtype != 0) return (T)0;
-  long long mm = (m < 0) ? -m : (2 * n - 2 - m);
-  if (mm >= 0 && mm < n) return xs[mm];
-  return (T)0;
+  const long long idx = pad_index(padtype, m, n);
+  return idx >= 0 ? xs[idx] : (T)0;
 }
 
-// The same fetch without branches (index selects, one unconditional load): a loader that takes it for many samples in
-// a row keeps all its loads in flight (the branchy form waits for each load at the join).  `live` = false returns 0.
-template <typename T>
+// The same fetch without a branch around the load (index selects, one unconditional load): a loader that takes it for
+// many samples in a row keeps all its loads in flight (the branchy form waits for each load at the join).  `live` =
+// false returns 0.  NEW_MODES = false: pad codes 0 and 1 alone (pad_index.h; the fused STFT kernels).
+template <bool NEW_MODES = true, typename T>
 __device__ __forceinline__ T load_padded_flat(const T* __restrict__ xs, long long m, long long n, int padtype, bool live) {
-  const bool in = m >= 0 && m < n;
-  const long long mm = (m < 0) ? -m : (2 * n - 2 - m);
-  const bool ok = live && (in || (padtype == 0 && mm >= 0 && mm < n));
-  const long long idx = in ? m : mm;
+  const long long idx = pad_index<NEW_MODES>(padtype, m, n);
+  const bool ok = live && idx >= 0;
   const T v = xs[ok ? idx : 0];
   return ok ? v : (T)0;
 }

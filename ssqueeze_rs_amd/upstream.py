@@ -22,7 +22,8 @@ Supported subset (anything else raises ValueError naming the option):
     averaged wavelet (the transform is linear in it), `average=False` runs every order from one forward FFT per signal.
     `cwt` keeps rejecting a bare int `order` other than 0 (the suite pins that ValueError); `order=(k,)` or
     `cwt_higher_order(x, order=k)` is the same transform;
-  * difftype 'trig'; squeezing 'sum' / 'lebesgue'; padtype 'reflect' / 'zero';
+  * difftype 'trig'; squeezing 'sum' / 'lebesgue'; padtype 'reflect' / 'zero' / 'symmetric' / 'replicate' /
+    'wrap' (all of utils/common.py:54-158, fetched by index mapping on the device: csrc/pad_index.h);
   * `issq_cwt` / `issq_stft`: the full inverse, and the component inversion by curves `cc`, `cw`
     (_ssq_cwt.py:381-417): float64 [K + 1, N], or [B, K + 1, N] for a batched `Tx` [B, F, N] with the curves of a
     batched `extract_ridges`; the full inverses `istft`, `issq_stft`, `issq_cwt` and `icwt` take a 2-D map or a batch
@@ -53,7 +54,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from ._lib import PAD, SQUEEZE, SSQ_F32, SSQ_F64, WAVELET
+from ._lib import SQUEEZE, SSQ_F32, SSQ_F64, WAVELET
 from ._rs import _call, _cdtype, _ptr
 from .upstream_scales import (cwt_scalebounds, find_downsampling_scale, find_first_occurrence,  # noqa: F401
                               find_max_scale, find_max_scale_alt, find_maximum, find_min_scale, infer_scaletype,
@@ -62,6 +63,8 @@ from .upstream_scales import (cwt_scalebounds, find_downsampling_scale, find_fir
 VARIANT_UPSTREAM, VARIANT_MODULATED, VARIANT_FLIPUD = 1, 2, 4
 FREQS = {"log": 0, "linear": 1, "log-piecewise": 2}     # include/ssq_hip.h: SSQ_FREQS_LOG, _LINEAR, _LOG_PIECEWISE
 EPS32, EPS64 = float(np.finfo(np.float32).eps), float(np.finfo(np.float64).eps)
+# utils/common.py:54-158; include/ssq_hip.h: SSQ_PAD_*.  (`_lib.PAD` is the reference drop-in's table: two names.)
+PAD_MODES = {"reflect": 0, "zero": 1, "symmetric": 2, "replicate": 3, "wrap": 4}
 GMW_MAX_ORDER = 16                      # the highest GMW order the library builds (csrc/cwt_kernels.h: kGmwMaxOrder)
 
 
@@ -77,9 +80,14 @@ def _signal(x):
 
 
 def _pad_code(padtype):
-    if padtype not in PAD:
-        raise ValueError(f"padtype {padtype!r}: the MI355X engine builds 'reflect' and 'zero'")
-    return PAD[padtype]
+    """Pad code of upstream's `padtype` (`padsignal`, utils/common.py:54-158).  The kernels fetch padded samples through
+    one index map (csrc/pad_index.h), no padded copy: 'reflect' is one mirror about the end sample and 'zero' zeros,
+    as before; 'symmetric', 'replicate' and 'wrap' are np.pad's 'symmetric', 'edge' and 'wrap' in closed form, for any
+    pad width.  Upstream slices 'symmetric' out of ONE reversed copy (common.py:144-149), which agrees with np.pad
+    while a pad is no wider than the signal and comes up short beyond that; np.pad is followed there."""
+    if not isinstance(padtype, str) or padtype not in PAD_MODES:
+        raise ValueError(f"padtype {padtype!r}: must be one of 'reflect', 'zero', 'symmetric', 'replicate', 'wrap'")
+    return PAD_MODES[padtype]
 
 
 def get_window(window, win_len, n_fft=None):
