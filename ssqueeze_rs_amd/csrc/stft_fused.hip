@@ -119,7 +119,10 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
                                                              (long long)k0 * p.n_frames);
         const long long gstep4 = (long long)RS2 * p.n_frames / 2;     // in float4 units
         // (round 3: a wave-uniform base + 32-bit per-thread offset does not make the compiler take the SGPR-base store form --
-        //  loop strength reduction rebuilds the 64-bit vector address chain either way)
+        //  loop strength reduction rebuilds the 64-bit vector address chain either way.  A raw buffer store through a
+        //  per-signal descriptor does take it -- 10 vector instructions per sweep, no address arithmetic -- and so does a
+        //  64-bit LDS exchange in place of the read + CELL0 store (one ds_wrxchg_rtn_b64 per cell); on top of the short
+        //  Nyquist pass neither pays: +0.4 ... +0.7 % and +-0, profiles/readout_ab_parts.txt)
         const T sc0 = col_scale[2 * fp], sc1 = col_scale[2 * fp + 1];
         long long* tc = reinterpret_cast<long long*>(tile_re) + k0 * PITCH + 2 * fp;
         auto sweep2 = [&](int j) {
@@ -269,8 +272,12 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
       const float lane_on = valid ? 1.0f : 0.0f;
       const float sfs0 = (float)t * p.sfs_step, sfs_q = (float)L * p.sfs_step;
       const int neg_last = -(p.n_freqs - 1);
+      // sum mode: the wave-wide loop serves bins t + 64 q, q < 8, and k = 512 follows it in a shorter form.  The Lebesgue
+      // instantiation keeps the ninth pass: with the split it spills 10 dwords instead of none.
+      constexpr bool NYQ = !LEB;
+      constexpr int NQ = NYQ ? 8 : 9;
 #pragma unroll
-      for (int q = 0; q < 9; ++q) {
+      for (int q = 0; q < NQ; ++q) {
         const cpx<T> zk = v[q], zn = zp[q];
         const cpx<T> S = {zk.x + zn.x, zk.y - zn.y};
         const cpx<T> dS = {zk.y + zn.y, zn.x - zk.x};
@@ -297,6 +304,39 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
           kdbg[q] = (m != 0.0f) ? -kneg : -1;
         }
       }
+      if constexpr (NYQ) {
+        // ---- k = 512 (Nyquist), owned by lane 0: the loop body at q = 8 with zn = zk (zp[8] IS v[8], on every lane),
+        //      every step below equal to the general one in value, NaN cases included (-1.5 %, same bits:
+        //      profiles/readout_ab_parts.txt):
+        //   S.x = zk.x + zk.x;  S.y = zk.y - zk.y = +0, or NaN for a non-finite zk.y;  dS.x = zk.y + zk.y;
+        //   dS.y = zk.x - zk.x = +0, or NaN exactly when S.x is not finite either;
+        //   den = S.x^2 + S.y^2 = round(S.x^2) (+ 0), NaN with S.y: fma(S.x, S.x, S.y) under either contraction;
+        //   num = dS.y S.x - dS.x S.y is +-0, or NaN exactly when S.x or dS.x is not finite (a NaN S.y comes with a
+        //         non-finite dS.x): 0 S.x + 0 dS.x has the same NaN cases and is +-0 otherwise -- the sign of a zero pd is
+        //         lost in Sfs - pd, Sfs(512) > 0;  pd = num * rcp(..) still turns NaN for den = 0 (0 * inf);
+        //   so d is Sfs(512) or NaN, and the masks, w and the bin index are taken from that true d as before;
+        //   c.y = S.y m is +-0 or (m is finite) the NaN of S.y: |c.y| = |S.y| for the column's L1, and its fixed-point
+        //         value rounds to 0 both ways (the conversion takes NaN to 0), so the 64-bit add is hi = ia >> 31, lo = ia.
+        const cpx<T> zk = v[8];
+        const float sx = zk.x + zk.x, sy = zk.y - zk.y, dsx = zk.y + zk.y;
+        const float den = __builtin_fmaf(sx, sx, sy);
+        const float num = __builtin_fmaf(0.0f, sx, 0.0f * dsx);
+        const float pd = num * __builtin_amdgcn_rcpf(den * p.two_pi_eff);
+        const float d = (sfs0 + 8.0f * sfs_q) - pd;
+        const float w = fabsf(d);
+        float m = fma_clamp01(den, p.keep_big, p.keep_bias) * fma_clamp01(d, 0.0f, 1.0f);
+        if (EDGE) m *= lane_on;
+        m *= (t == 0) ? 1.0f : 0.0f;
+        cv[8] = cpx<T>{sx * m, 0.0f};
+        int kneg = cvt_floor_i32(__builtin_fmaf(-w, p.inv_dw, 0.5f));
+        kneg = kneg < neg_last ? neg_last : kneg;
+        dstb[8] = __mul24(kneg, -(PITCH * CELL)) + fl * CELL;
+        l1 += fabsf(cv[8].x) + fabsf(sy);
+        if constexpr (WKDBG) {
+          wdbg[8] = w;
+          kdbg[8] = (m != 0.0f) ? -kneg : -1;
+        }
+      }
       const T tot = frame_allreduce<T, L, false>(l1, t, nullptr, t) * p.dw;
       T scale, inv_scale;
       column_scale<T, H::FRAC, H::EMIN>(tot, p.dw, scale, inv_scale);
@@ -316,7 +356,7 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
           const int ia = cvt_round_i32(cv[q].x * scale);
-          const int ib = LEB ? 0 : cvt_round_i32(cv[q].y * scale);
+          const int ib = (LEB || q == 8) ? 0 : cvt_round_i32(cv[q].y * scale);
           if (q < 8 || t == 0) {
             if (LEB) {
               atomicAdd(reinterpret_cast<unsigned*>(ptile + dstb[q]), (unsigned)ia);             // RE >= 0: no borrow
