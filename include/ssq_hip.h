@@ -168,6 +168,36 @@ int ssq_istft_batch_exec(int dtype, const void* d_Sx, int64_t batch, int64_t n_f
  * takes.  -1 on a bad shape. */
 int64_t ssq_istft_batch_workspace_bytes(int dtype, int64_t batch, int64_t n_frames, int64_t n_fft, int64_t hop,
                                         int64_t n_signal, int* fused);
+/* Second-order ("vertical") synchrosqueezed STFT, `upstream.ssq_stft2` (csrc/stft_sst2.hip; upstream has no
+ * such transform).  Conventions of ssq_ssq_stft_host_v: window [n_fft] already sized, padtype SSQ_PAD_*, squeezing
+ * SSQ_SQUEEZE_*, gamma < 0: 10 eps of the dtype, variant: the SSQ_VARIANT_MODULATED and SSQ_VARIANT_FLIPUD bits (the
+ * others are ignored).  n_fft must be a power of two from 16 to 4096.  Per-sample, with g1 = g', g2 = g'' (spectral
+ * derivatives, Nyquist term zeroed), tg = u g, tg1 = u g1, u = j - n_fft/2, and V, V1, V2, Vt, Vt1 the STFTs with them:
+ *   w1 = k/n_fft - (V1/V)/(2 pi i),  D = Vt V1 - Vt1 V,  q = (V2 V - V1^2)/(2 pi i D),  w2 = w1 - q Vt/V;
+ *   the bin's frequency is fs |Re w2| where |D| > gamma^2 and Re w2 is finite, else fs |Re w1|; bins with |V| > gamma
+ *   are reassigned by the upstream rule (clamped round-half-even on np.linspace(0, fs/2, n_freqs)), rows ascending.
+ * Tx, Sx: [batch][n_freqs][n_frames] complex of `dtype`; ssq_freqs: [n_freqs] (reversed with FLIPUD; may be NULL);
+ * w2 (may be NULL): [batch][n_freqs][n_frames] REAL of `dtype`, +inf where a bin is not kept.  Synchronous; the batch
+ * goes through the device in slices sized from its free memory, and signal b's result does not depend on `batch`. */
+int ssq_ssq_stft2_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                       int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, void* Tx,
+                       double* ssq_freqs, void* Sx, void* w2);
+/* The fp64 window tables the transform is defined on, as the library builds them for `window` [n_fft] (host only, no
+ * GPU): g1 = g', g2 = g'' (spectral derivatives, Nyquist term zeroed), tg = u g, tg1 = u g1, u = j - n_fft/2; each
+ * [n_fft].  g2 is a second derivative by FFT: its rounding noise (1e-11 of its size at n_fft = 1024) differs between any
+ * two FFTs that build it and moves the operator on ill-conditioned bins, so a reference takes the tables from here. */
+int ssq_ssq_stft2_window_tables(const double* window, int64_t n_fft, double* g1, double* g2, double* tg, double* tg1);
+/* Device bytes of the workspace ssq_ssq_stft2_exec needs (the packed map (w2, bin) of every bin and, for SSQ_F32, the
+ * signals widened to fp64: the transforms and the operator run in fp64 for either dtype), computed on the host;
+ * -1 on a shape ssq_ssq_stft2_host refuses. */
+int64_t ssq_ssq_stft2_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop);
+/* The same transform on device buffers: d_x [batch][N], d_Tx, d_Sx, d_w2 (may be NULL) as above, d_workspace of at least
+ * ssq_ssq_stft2_workspace_bytes bytes; `window` on the host.  Synchronous.  kernel_ms (may be NULL): the time of the
+ * kernels alone (clearing Tx, the operator kernel, the scatter), from HIP events around the launches with the tables set
+ * up before them. */
+int ssq_ssq_stft2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                       int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, void* d_Tx, void* d_Sx,
+                       void* d_w2, void* d_workspace, int64_t workspace_bytes, float* kernel_ms);
 /* ssqueezepy.issq_stft / issq_cwt, full inverse (_ssq_stft.py:139-198, _ssq_cwt.py:313-378):
  * x_out[j] = scale * sum_rows row_scale[row] * Re Tx[row][j]   (scale = 2 / window[n_fft/2]  resp.  2 / adm_ssq;
  * row_scale NULL = 1; the one-integral icwt of _cwt.py:477-492 is the same sum with 1/sqrt(a) rows for the L2 norm).

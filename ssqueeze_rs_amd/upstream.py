@@ -35,6 +35,10 @@ Supported subset (anything else raises ValueError naming the option):
     3-D: `ssq_freqs` None / 'log' / 'linear' / 'log-piecewise' / an array, maprange 'peak' / 'maximal', squeezing
     'sum' / 'lebesgue' / 'abs' / a function (from `dWx`: 'sum' only), `was_padded`, `flipud`; STFT needs an array
     `ssq_freqs` (and `Sfs` with ssq_freqs[0] == Sfs[0] from `dSx`); `phase_cwt` (difftype 'trig') and `phase_stft`;
+  * `ssq_stft2`: the second-order ("vertical") synchrosqueezed STFT, which upstream does not have (the definition is this
+    project's: DESIGN 4.11, csrc/stft_sst2.hip): the conventions of `ssq_stft` (ndarray window, the five padtypes,
+    'sum' / 'lebesgue', `flipud`, `modulated`, batches) with a power-of-two `n_fft` from 16 to 4096; its `Tx` inverts
+    through `issq_stft` like a first-order one;
   * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
     serial backward trace (`parallel` is accepted and ignored).
 dtype: float64 in -> complex128 (upstream's 'float64'); float32 in -> complex64 (upstream's default 'float32').
@@ -330,6 +334,64 @@ def ssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=Non
         out.append(w if batched else w[0])
     if get_dWx:
         out.append(dSx if batched else dSx[0])
+    return tuple(out)
+
+
+SST2_MIN_N_FFT, SST2_MAX_N_FFT = 16, 4096     # csrc/stft_sst2.hip: one frame is held by n_fft / 16 lanes of a workgroup
+
+
+def ssq_stft2(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
+              squeezing="sum", gamma=None, flipud=False, get_w=False):
+    """Second-order ("vertical") synchrosqueezed STFT -> (Tx, Sx, ssq_freqs, Sfs[, w2]); not in upstream (Oberlin,
+    Meignen and Perrier 2015; Behera, Meignen and Oberlin 2018), conventions of `ssq_stft`.
+
+    With g the sized window, g1 and g2 its first and second spectral derivatives (Nyquist term zeroed), tg = u g,
+    tg1 = u g1 (u = sample index - n_fft // 2) and V, V1, V2, Vt, Vt1 the STFTs of `x` with them, per sample:
+        w1 = k / n_fft - (V1 / V) / (2 pi i)       D = Vt V1 - Vt1 V       q = (V2 V - V1^2) / (2 pi i D)
+        w2 = w1 - q Vt / V
+    A bin's frequency is fs |Re w2| where |D| > gamma^2 and Re w2 is finite, else fs |Re w1| (`ssq_stft`'s w); bins with
+    |V| > gamma (default 10 eps of the dtype) are reassigned by `ssq_stft`'s rule, every column's rows in ascending
+    order (no atomics: the result does not depend on the batch).  For a linear chirp under a Gaussian window Re w2 is
+    the instantaneous frequency, where the first-order w is biased by the chirp rate.  `Sx` equals `stft(x, ...)`;
+    `w2` (get_w=True) is +inf where a bin is not kept.  `Tx` sums to the same rows as a first-order one, so
+    `issq_stft`, `extract_ridges` and the component inversion take it unchanged.
+
+    float32 in gives complex64 / float32 out, but the transforms and the operator run in fp64 for either dtype (the
+    operator is a quotient of two differences of products: fp32 transforms of 1024 points and more put over one
+    strong bin in a thousand into another bin than fp64 ones); the bin is taken from the `w2` the call reports.
+
+    `n_fft` must be a power of two from 16 to 4096 (ValueError otherwise, before any GPU work).  Every (dtype, n_fft)
+    in that range is built without register spills or scratch (profiles/sst2_resources.txt), so none is refused on
+    those grounds."""
+    lib = _lib.load()
+    if squeezing not in SQUEEZE:
+        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
+    xa, batched, code = _signal(x)
+    batch, N = xa.shape
+    fs = 1.0 / _dt(fs, t, N)
+    n_fft = n_fft or min(N // hop_len, 512)
+    if (not isinstance(n_fft, (int, np.integer)) or isinstance(n_fft, (bool, np.bool_))
+            or not SST2_MIN_N_FFT <= n_fft <= SST2_MAX_N_FFT or n_fft & (n_fft - 1)):
+        raise ValueError(f"n_fft {n_fft!r}: ssq_stft2 takes a power of two from {SST2_MIN_N_FFT} to {SST2_MAX_N_FFT}")
+    n_fft = int(n_fft)
+    if win_len is None:
+        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
+    win = get_window(window, win_len, n_fft)
+    pad = _pad_code(padtype)
+    _lib.require_gpu()
+    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0) | (VARIANT_FLIPUD if flipud else 0)
+    n_freqs, n_frames = n_fft // 2 + 1, (N - 1) // hop_len + 1
+    shape = (batch, n_freqs, n_frames)
+    cdt, rdt = _cdtype(code), _rdtype(code)
+    Tx, Sx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
+    w2 = _lib.pinned_empty(shape, rdt) if get_w else None
+    f = np.empty(n_freqs, dtype=np.float64)
+    _call(lib.ssq_ssq_stft2_host(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, pad, SQUEEZE[squeezing],
+                                 -1.0 if gamma is None else float(gamma), variant, _ptr(Tx), _ptr(f), _ptr(Sx), _ptr(w2)))
+    Sfs = np.linspace(0, .5 * fs, n_freqs, dtype=rdt)
+    out = [Tx if batched else Tx[0], Sx if batched else Sx[0], f.astype(rdt), Sfs]
+    if get_w:
+        out.append(w2 if batched else w2[0])
     return tuple(out)
 
 
