@@ -264,6 +264,37 @@ int ssq_ssq_cwt_host_gmwk_rows(int dtype, const void* x, int64_t batch, int64_t 
                                const double* scales, int64_t na, double dt, const double* row_const,
                                const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition, int padtype,
                                int squeezing, double gamma, int variant, void* Tx, void* Wx, void* dWx, void* wk);
+/* Second-order ("vertical") synchrosqueezed CWT, `upstream.ssq_cwt2` (csrc/cwt_sst2.hip; upstream has no
+ * such transform).  Arguments as ssq_ssq_cwt_host_rows (wavelet SSQ_WAVELET_GMW with (gamma, beta) or _MORLET with mu;
+ * variant: the SSQ_VARIANT_FLIPUD bit, the others are ignored; gamma < 0: 10 eps of the dtype).  Per-sample, with
+ * P = p2up(n_signal), xh the DFT of the padded signal, xi_k = 2 pi k / P for k <= P/2 (zero tables above), and for
+ * scale a the fp64 tables T0 = psih(a xi), T1 = a psih'(a xi) (both halved at 2k == P):
+ *   W = F^-1[xh T0], W1 = F^-1[xh i xi T0], W2 = F^-1[xh (-xi^2) T0], Wt = F^-1[xh (-i) T1], Wt1 = F^-1[xh xi T1];
+ *   D = W^2 + Wt1 W - Wt W1,  c = (W2 W - W1^2) / D,  om1 = W1 / W,  om2 = om1 - c Wt / W;
+ *   w2 = |Im om2| / (2 pi dt) where |D| > gamma^2 and Im om2 is finite, else |Im om1| / (2 pi dt); +inf where |W| < gamma.
+ * Wx = W (upstream's L1-normalised cwt); Tx = the scatter of Wx under w2 by ssq_ssqueeze_w_exec's rule.  Transforms and
+ * operator run in fp64 for either dtype; Wx and w2 are rounded once on store and the scatter runs on the rounded values.
+ * Tx, Wx: [batch][na][n_signal] complex of `dtype`; w2: the same shape, REAL of `dtype` (host: may be NULL).
+ * The batch x na rows go through the workspace in chunks of R rows: 16 P (batch + 10 R) bytes; a row's result does not
+ * depend on R or on the batch.  work_limit_bytes: 0 for the preferred size, else at least min_bytes. */
+int ssq_ssq_cwt2_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                      const double* scales, int64_t na, double dt, const double* row_const, const double* ssq_freqs_asc,
+                      int freq_kind, int64_t freq_transition, int padtype, int squeezing, double gamma, int variant,
+                      int64_t work_limit_bytes, void* Tx, void* Wx, void* w2);
+/* Device bytes of the workspace: returns the preferred size (every row in one chunk, capped at 2 GiB) and stores the
+ * least one (one row per chunk) in *min_bytes (may be NULL); computed on the host; -1 on a bad shape. */
+int64_t ssq_ssq_cwt2_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int64_t* min_bytes);
+/* The same transform on device buffers: d_x [batch][n_signal], d_Tx, d_Wx, d_w2 (required) as above, d_workspace of
+ * workspace_bytes >= min_bytes (its size sets R); scales, row_const, ssq_freqs_asc on the host.  Synchronous on
+ * `stream`.  kernel_ms (may be NULL): the time of the kernels alone, from HIP events around the launches. */
+int ssq_ssq_cwt2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                      const double* scales, int64_t na, double dt, const double* row_const, const double* ssq_freqs_asc,
+                      int freq_kind, int64_t freq_transition, int padtype, int squeezing, double gamma, int variant,
+                      void* d_Tx, void* d_Wx, void* d_w2, void* d_workspace, int64_t workspace_bytes, void* stream,
+                      float* kernel_ms);
+/* The two fp64 tables of one scale on the host (no GPU), by the functions the kernel evaluates them with
+ * (csrc/cwt_sst2_wavelets.h): T0, T1 [P], zero above P/2.  P a power of two. */
+int ssq_ssq_cwt2_tables(int wavelet, double p0, double p1, double scale, int64_t P, double* T0, double* T1);
 
 /* ---- plans: device-resident batch pipelines -------------------------------- */
 typedef struct ssq_stft_plan ssq_stft_plan;

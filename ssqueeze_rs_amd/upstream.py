@@ -39,6 +39,10 @@ Supported subset (anything else raises ValueError naming the option):
     project's: DESIGN 4.11, csrc/stft_sst2.hip): the conventions of `ssq_stft` (ndarray window, the five padtypes,
     'sum' / 'lebesgue', `flipud`, `modulated`, batches) with a power-of-two `n_fft` from 16 to 4096; its `Tx` inverts
     through `issq_stft` like a first-order one;
+  * `ssq_cwt2`: the second-order synchrosqueezed CWT, which upstream does not have either (the definition is this
+    project's: DESIGN 4.12, csrc/cwt_sst2.hip): the conventions of `ssq_cwt` (ndarray scales of the three grids,
+    `ssq_freqs` None / a string / an array, maprange 'peak' / 'maximal', 'sum' / 'lebesgue', the five padtypes, `flipud`,
+    batches) for the order-0 'gmw' and 'morlet' wavelets; its `Tx` inverts through `issq_cwt` like a first-order one;
   * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
     serial backward trace (`parallel` is accepted and ignored).
 dtype: float64 in -> complex128 (upstream's 'float64'); float32 in -> complex64 (upstream's default 'float32').
@@ -631,25 +635,9 @@ def _row_const(s, scaletype, nv):
     return np.ascontiguousarray((s[1] - s[0]) / s)
 
 
-def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, ssq_freqs=None, padtype="reflect",
-            squeezing="sum", maprange="peak", difftype="trig", difforder=None, gamma=None, vectorized=True,
-            preserve_transform=None, astensor=True, order=0, nan_checks=None, patience=0, flipud=True,
-            cache_wavelet=None, get_w=False, get_dWx=False):
-    """ssqueezepy.ssq_cwt (old/ssqueezepy/_ssq_cwt.py:12-311) -> (Tx, Wx, ssq_freqs, scales[, w][, dWx])."""
-    lib = _lib.load()
-    if difftype != "trig":
-        raise ValueError("only difftype='trig' is built")
-    if squeezing not in SQUEEZE:
-        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
-    # _ssq_cwt.py:228-241: Wx of the order (set) averaged, dWx by `trigdiff` of the padded Wx -- the derivative transform of
-    # the averaged wavelet up to rounding; ssq_freqs below stay the order-0 wavelet's (ssqueeze gets `wavelet` itself)
-    order_args = _order_args(order, isinstance(order, (tuple, list, range)), wavelet)
-    if order_args and all(k == 0 for k in order_args[0]):
-        order_args = None
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    dt = _dt(fs, t, N)
-    wcode, p0, p1 = _wavelet(wavelet)
+def _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt):
+    """The scale and frequency grids of `ssq_cwt` / `ssq_cwt2` -> (s float64 [na], row_const, f_asc float64 ascending,
+    scaletype of the frequencies, f_idx: their 'log-piecewise' transition or None).  Every refusal of the two grids."""
     s, cwt_scaletype, _nv, s_own = _scales(scales)
     if cwt_scaletype == "log" and nv is not None and nv != _nv:
         raise Exception("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))
@@ -676,6 +664,29 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
     f_idx = logscale_transition_idx(f_own) if scaletype == "log-piecewise" else None
     if scaletype == "log-piecewise" and f_idx is None:
         scaletype = "log"
+    return s, row_const, f_asc, scaletype, f_idx
+
+
+def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, ssq_freqs=None, padtype="reflect",
+            squeezing="sum", maprange="peak", difftype="trig", difforder=None, gamma=None, vectorized=True,
+            preserve_transform=None, astensor=True, order=0, nan_checks=None, patience=0, flipud=True,
+            cache_wavelet=None, get_w=False, get_dWx=False):
+    """ssqueezepy.ssq_cwt (old/ssqueezepy/_ssq_cwt.py:12-311) -> (Tx, Wx, ssq_freqs, scales[, w][, dWx])."""
+    lib = _lib.load()
+    if difftype != "trig":
+        raise ValueError("only difftype='trig' is built")
+    if squeezing not in SQUEEZE:
+        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
+    # _ssq_cwt.py:228-241: Wx of the order (set) averaged, dWx by `trigdiff` of the padded Wx -- the derivative transform of
+    # the averaged wavelet up to rounding; ssq_freqs below stay the order-0 wavelet's (ssqueeze gets `wavelet` itself)
+    order_args = _order_args(order, isinstance(order, (tuple, list, range)), wavelet)
+    if order_args and all(k == 0 for k in order_args[0]):
+        order_args = None
+    xa, batched, code = _signal(x)
+    batch, N = xa.shape
+    dt = _dt(fs, t, N)
+    wcode, p0, p1 = _wavelet(wavelet)
+    s, row_const, f_asc, scaletype, f_idx = _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt)
     _lib.require_gpu()
     shape = (batch, len(s), N)
     cdt = _cdtype(code)
@@ -701,6 +712,66 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
         out.append(w if batched else w[0])
     if get_dWx:
         out.append(dWx if batched else dWx[0])
+    return tuple(out)
+
+
+def ssq_cwt2(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, ssq_freqs=None, padtype="reflect",
+             squeezing="sum", maprange="peak", gamma=None, flipud=True, get_w=False):
+    """Second-order ("vertical") synchrosqueezed CWT -> (Tx, Wx, ssq_freqs, scales[, w2]); not in upstream (Oberlin and
+    Meignen 2017), conventions of `ssq_cwt`.
+
+    Per sample, with P, n1, n2 = p2up(N), xh the DFT of the padded signal, xi_k = 2 pi k / P for k <= P/2 (analytic
+    tables: zero above) and, for scale a, T0 = psih(a xi), T1 = a psih'(a xi) in fp64 (both halved at 2k == P):
+        W = F^-1[xh T0]   W1 = F^-1[xh i xi T0]   W2 = F^-1[xh (-xi^2) T0]   Wt = F^-1[xh (-i) T1]   Wt1 = F^-1[xh xi T1]
+        D = W^2 + Wt1 W - Wt W1      c = (W2 W - W1^2) / D      om1 = W1 / W      om2 = om1 - c Wt / W
+    A bin's frequency is |Im om2| / (2 pi dt) where |D| > gamma^2 and Im om2 is finite, else |Im om1| / (2 pi dt)
+    (`ssq_cwt`'s w), and +inf where |W| < gamma (default 10 eps of the dtype).  For a signal whose logarithm is
+    quadratic in time (a Gaussian-modulated linear chirp) Im om2 is the instantaneous frequency for any wavelet, where
+    the first-order w is biased by the chirp rate times the wavelet's time spread.  `Wx` is W, upstream's L1-normalised
+    `cwt`; `Tx` is `ssqueeze(Wx, w2, ...)`: every column's rows in ascending order, no atomics (the result does not
+    depend on the batch), upstream's row weights, so `issq_cwt`, `extract_ridges` and the component inversion take it
+    unchanged.  `w2` (get_w=True) is real, +inf where a bin is not kept.
+
+    float32 in gives complex64 / float32 out, but the transforms and the operator run in fp64 for either dtype (the
+    operator is a quotient of two differences of products); `Wx` and `w2` are rounded once and the scatter runs in the
+    call's dtype on the rounded values.
+
+    Built: wavelets 'gmw' (order 0, bandpass norm) and 'morlet'; an ndarray `scales` of any of the three grids;
+    `ssq_freqs` None, a string or an array; maprange 'peak' / 'maximal'; 'sum' / 'lebesgue'; the five padtypes; 1-D or
+    batched 2-D `x`.  Anything else raises ValueError before any GPU work."""
+    lib = _lib.load()
+    if squeezing not in SQUEEZE:
+        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
+    xa, batched, code = _signal(x)
+    batch, N = xa.shape
+    if N < 2:
+        raise ValueError("`x` must hold at least 2 samples")
+    dt = _dt(fs, t, N)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError("`fs` / `t` must give a positive sampling period")
+    wcode, p0, p1 = _wavelet(wavelet)
+    if not p0 > 0 or (wcode == WAVELET["gmw"] and not p1 > 0):
+        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
+    if isinstance(scales, np.ndarray) and scales.dtype.kind in "fiu" and not (np.isfinite(scales).all() and (scales > 0).all()):
+        raise ValueError("`scales` must be positive and finite")
+    s, row_const, f_asc, scaletype, f_idx = _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt)
+    if not np.isfinite(f_asc).all():
+        raise ValueError("`ssq_freqs` must be finite")
+    if gamma is not None and math.isnan(float(gamma)):
+        raise ValueError("`gamma` is NaN")
+    pad = _pad_code(padtype)
+    _lib.require_gpu()
+    shape = (batch, len(s), N)
+    cdt, rdt = _cdtype(code), _rdtype(code)
+    Tx, Wx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
+    w2 = _lib.pinned_empty(shape, rdt) if get_w else None
+    _call(lib.ssq_ssq_cwt2_host(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, _ptr(row_const), _ptr(f_asc),
+                                FREQS[scaletype], f_idx or 0, pad, SQUEEZE[squeezing],
+                                -1.0 if gamma is None else float(gamma), VARIANT_FLIPUD if flipud else 0, 0, _ptr(Tx),
+                                _ptr(Wx), _ptr(w2)))
+    out = [Tx if batched else Tx[0], Wx if batched else Wx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]
+    if get_w:
+        out.append(w2 if batched else w2[0])
     return tuple(out)
 
 
