@@ -198,6 +198,32 @@ int64_t ssq_ssq_stft2_workspace_bytes(int dtype, int64_t batch, int64_t n_signal
 int ssq_ssq_stft2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
                        int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, void* d_Tx, void* d_Sx,
                        void* d_w2, void* d_workspace, int64_t workspace_bytes, float* kernel_ms);
+/* Time-reassigned synchrosqueezed STFT, `upstream.tssq_stft` (csrc/stft_tsst.hip; He, Tu, Bao, Hu and Zhang
+ * 2019; upstream has no such transform): every coefficient moves along TIME to its estimated group delay.  window [n_fft]
+ * already sized, padtype SSQ_PAD_*, order 1 or 2, gamma < 0: 10 eps of the dtype (NaN is refused), variant: the
+ * SSQ_VARIANT_MODULATED bit (the others are ignored).  n_fft must be a power of two from 16 to 4096.  Per-sample, with
+ * the window tables and the STFTs V, V1, V2, Vt, Vt1 of ssq_ssq_stft2_host, frame m centred on sample m hop:
+ *   d1 = Re(Vt/V),  D = Vt V1 - Vt1 V,  num = V2 V - V1^2,  d2 = Re(Vt/V + V1 D / (V num));
+ *   offset = d2 where order = 2, |num| > gamma^2, d2 is finite and |d2| <= n_fft/2, else d1; clamped to +- n_fft/2;
+ *   tau = offset / fs in `dtype`, +inf where |V| <= gamma;  r = rint(tau / (hop/fs)) in `dtype` (0 where not finite);
+ *   m' = clip(m + r, 0, n_frames - 1);  Tx[k][m'] += Sx[k][m] exp(-2 pi i ((k (m - m') hop) mod n_fft) / n_fft), every
+ *   cell in ascending source frame (no atomics: signal b's result does not depend on `batch` or on the tiling).
+ * Tx, Sx: [batch][n_freqs][n_frames] complex of `dtype`; tau (may be NULL): [batch][n_freqs][n_frames] REAL of `dtype`,
+ * seconds relative to the frame's own time.  Synchronous; the batch goes through the device in slices sized from its
+ * free memory. */
+int ssq_tssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                       int64_t hop, double fs, int padtype, int order, double gamma, int variant, void* Tx, void* Sx,
+                       void* tau);
+/* Device bytes of the workspace ssq_tssq_stft_exec needs (for SSQ_F32 the signals widened to fp64, then one int16
+ * relative target per bin), computed on the host; -1 on a shape ssq_tssq_stft_host refuses. */
+int64_t ssq_tssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop);
+/* The same transform on device buffers: d_x [batch][N], d_Tx, d_Sx, d_tau (may be NULL) as above, d_workspace of at least
+ * ssq_tssq_stft_workspace_bytes bytes; `window` on the host.  Synchronous.  kernel_ms (may be NULL): TWO floats, the
+ * time of the operator kernel (with the widening of a float32 call) and of the time scatter, from HIP events around
+ * the launches with the tables set up before them. */
+int ssq_tssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                       int64_t hop, double fs, int padtype, int order, double gamma, int variant, void* d_Tx, void* d_Sx,
+                       void* d_tau, void* d_workspace, int64_t workspace_bytes, float* kernel_ms);
 /* ssqueezepy.issq_stft / issq_cwt, full inverse (_ssq_stft.py:139-198, _ssq_cwt.py:313-378):
  * x_out[j] = scale * sum_rows row_scale[row] * Re Tx[row][j]   (scale = 2 / window[n_fft/2]  resp.  2 / adm_ssq;
  * row_scale NULL = 1; the one-integral icwt of _cwt.py:477-492 is the same sum with 1/sqrt(a) rows for the L2 norm).

@@ -1,0 +1,690 @@
+// stft_tsst.hip -- time-reassigned synchrosqueezed STFT, `upstream.tssq_stft`, orders 1 and 2 (He, Tu, Bao,
+// Hu and Zhang 2019).  Upstream has no such transform: the definition is the project's own, restated in numpy by
+// tests/helpers/tsst_ref.py.  It is the dual of stft_sst2.hip: every coefficient moves along TIME to its estimated group
+// delay.  Per-sample units, fs enters at the end.  With n = n_fft, u[j] = j - n/2, the five windows g, g1, g2, tg, tg1
+// of stft_sst2.hip and V, V1, V2, Vt, Vt1 the STFTs of x with them (frame m centred on sample m hop):
+//   d1 = Re(Vt/V)       D = Vt V1 - Vt1 V       num = V2 V - V1^2       d2 = Re(Vt/V + V1 D / (V num))
+//   offset = d2 where order = 2, |num| > gamma^2, d2 is finite and |d2| <= n/2, else d1; clamped to [-n/2, n/2]
+//   tau = offset / fs (fp64, rounded once to the call's dtype), +inf where |V| <= gamma
+//   r = rint(tau / (hop/fs)) in the call's dtype (0 where not finite)      m' = clip(m + r, 0, n_frames - 1)
+//   Tx[k, m'] += Sx[k, m] exp(-2 pi i ((k (m - m') hop) mod n) / n)         in ascending source frame m
+//
+//   tsst_operator_kernel : stft_sst2.hip's frame ownership and transforms (a COPY, so that ssq_stft2's machine code
+//                          stays what it is): 256 lanes own a tile of consecutive frames, n/16 lanes a frame, three
+//                          packed fp64 transforms for order 2, ONE (x (g + i tg)) for order 1; the time operator per
+//                          bin; Sx, tau and the relative target r (int16, kTsstNone where the bin is not kept) out
+//                          through the LDS transpose, so that global stores run along frames.
+//   tsst_scatter_kernel  : a workgroup owns a tile of target frames of one row and stages the int16 targets of the
+//                          sources within H = ceil(n / (2 hop)) frames of it in LDS.  A wave owns 64 consecutive target
+//                          cells, one per lane, walks the sources 64 at a time in ascending order, and hands the hits
+//                          of each step to the lanes that own their cells: all at once where no two hits of the step
+//                          share a cell (the usual case), else one by one in ascending lane order (ballot, readlane).
+//                          The owner adds them with a compensated (Neumaier) fp64 sum.  Every cell is therefore the sum of
+//                          its contributions in ascending source frame whatever the tiling or the batch, no atomics,
+//                          and every cell of Tx is written exactly once (no clear of Tx).
+#include <cmath>
+#include <vector>
+
+#include "../../include/ssq_hip.h"
+#include "dev_buffers.h"
+#include "fft_core.h"
+#include "host_math.h"
+#include "stft_kernels.h"
+
+namespace ssq {
+
+constexpr int kTsstThreads = 256;
+constexpr int kTsstRoundsPerTile = 4;      // store tiles one workgroup of the operator kernel walks
+constexpr int kTsstNone = -32768;          // the relative target of a bin that is not kept
+constexpr int kTsstMaxReach = 2048;        // H at n_fft = 4096, hop 1
+constexpr int kTsstMaxTile = 4096;         // target frames of one scatter workgroup
+constexpr int kTsstStage = kTsstMaxTile + 2 * kTsstMaxReach;
+
+// O: the dtype of the call (float or double: x in, Sx / tau / Tx out).  The transforms and the operator always run in
+// fp64, on the widened signal, as in stft_sst2.hip.
+// What the operator kernel needs only when it stores a tile.  It lives in device memory and is read there, behind an
+// opaque offset: as kernel arguments these would sit in scalar registers across the transforms, which are at the limit.
+template <typename O>
+struct TsstOut {
+  cpx<O>* Sx;              // [batch][F][n_frames]
+  O* tau;                  // [batch][F][n_frames], or nullptr
+  short* rel;              // [batch][F][n_frames]  m' - m, or kTsstNone
+  double fs;
+  O step;                  // hop / fs in the call's dtype: the target rule runs on the tau the call reports
+};
+
+template <typename O>
+struct TsstDev {
+  const double* x;         // [batch][n_signal], widened by tsst_widen_kernel for a float32 call
+  const cpx<double>* tw;   // the passes' twiddle tables, passes 1, 2, .. back to back
+  const cpx<double>* wa;   // order 2: (g, g1 a1); order 1: (g, tg at)      a*: powers of two that level the channels
+  const double* wb;        // order 2: tg at
+  const cpx<double>* wc;   // order 2: (tg1 at1, g2 a2)
+  const TsstOut<O>* out;
+  long long n_signal, n_frames;
+  int hop, padtype, rot, tile_frames, b0;   // b0: the signal of blockIdx.y = 0
+  double gamma, gamma_sq;
+  double h1, it, ht1, h2;  // 0.5 / a1, 1 / at (order 1: 0.5 / at), 0.5 / at1, 0.5 / a2
+};
+
+template <int LOGN>
+struct TsstCfg {
+  static constexpr int N = 1 << LOGN, L = N / 16, FPR = kTsstThreads / L, ROW = N + N / 16, F = N / 2 + 1;
+  static constexpr bool MULTI = L > 64;
+  static constexpr int TFS = FPR, SP = TFS >= 8 ? TFS + 1 : TFS;
+};
+
+__device__ __forceinline__ int tsst_opaque_zero() {
+  int z;
+  asm volatile("s_mov_b32 %0, 0" : "=s"(z));
+  return z;
+}
+
+// The 16 samples of a lane (stft_sst2.hip's loader: an edge frame goes through the pad index map in a rolled loop)
+template <typename O, int LOGN>
+__device__ __forceinline__ void tsst_samples(const TsstDev<O>& p, const double* __restrict__ xs, long long pos0, int t,
+                                             bool valid, bool interior, double* row, double (&xv)[16]) {
+  constexpr int N = 1 << LOGN, L = N / 16;
+  if (interior) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) xv[q] = xs[pos0 + ((t + L * q + p.rot) & (N - 1))];
+  } else {
+#pragma unroll 1
+    for (int q = 0; q < 16; ++q)
+      row[t + L * q] = load_padded_flat(xs, pos0 + ((t + L * q + p.rot) & (N - 1)), p.n_signal, p.padtype, valid);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) xv[q] = row[t + L * q];
+  }
+}
+
+// Z = A + i B of two real-input spectra -> A[k] h_a, B[k] h_b for the lane's bins t + L q, q <= 8
+template <typename T, int LOGN, bool MULTI>
+__device__ __forceinline__ void tsst_split(const cpx<T> (&v)[16], cpx<T>* exch, int t, T h_a, T h_b, cpx<T> (&A)[9],
+                                           cpx<T> (&B)[9]) {
+  constexpr int N = 1 << LOGN, L = N / 16;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) exch[exch_phys(t + L * q)] = v[q];
+  frame_sync<MULTI>();
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    const int idx = t + L * q;
+    const cpx<T> zp = exch[exch_phys((N - idx) & (N - 1))];
+    A[q] = {(v[q].x + zp.x) * h_a, (v[q].y - zp.y) * h_a};
+    B[q] = {(v[q].y + zp.y) * h_b, (zp.x - v[q].x) * h_b};
+  }
+  frame_sync<MULTI>();
+}
+
+__device__ __forceinline__ double tsst_clamp(double d, double h) { return d < -h ? -h : (d > h ? h : d); }   // keeps a NaN
+
+// first order: the group-delay offset Re(Vt / V) in samples, or +inf where the bin is not kept
+template <typename O>
+__device__ __forceinline__ double tsst_operator1(const TsstDev<O>& p, double half, cpx<double> V, cpx<double> Vt) {
+  const double den = V.x * V.x + V.y * V.y;
+  const double d1 = (Vt.x * V.x + Vt.y * V.y) / den;
+  return hypot(V.x, V.y) > p.gamma ? tsst_clamp(d1, half) : (double)INFINITY;
+}
+
+// second order: Re(Vt/V + V1 D / (V num)) where the chirp fit is usable, else the first-order offset
+template <typename O>
+__device__ __forceinline__ double tsst_operator2(const TsstDev<O>& p, double half, cpx<double> V, cpx<double> V1,
+                                                 cpx<double> V2, cpx<double> Vt, cpx<double> Vt1) {
+  using T = double;
+  const T den = V.x * V.x + V.y * V.y;
+  const T d1 = (Vt.x * V.x + Vt.y * V.y) / den;
+  const cpx<T> D = cmul(Vt, V1) - cmul(Vt1, V);
+  const cpx<T> num = cmul(V2, V) - cmul(V1, V1);
+  const cpx<T> a = cmul(V1, D), b = cmul(V, num);
+  const T d2 = d1 + (a.x * b.x + a.y * b.y) / (b.x * b.x + b.y * b.y);     // Re(a / b)
+  const bool second = hypot(num.x, num.y) > p.gamma_sq && isfinite(d2) && fabs(d2) <= half;
+  return hypot(V.x, V.y) > p.gamma ? tsst_clamp(second ? d2 : d1, half) : (T)INFINITY;
+}
+
+template <typename O, int LOGN, int ORDER>
+__global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstDev<O> p) {
+  using T = double;
+  using C = TsstCfg<LOGN>;
+  constexpr int N = C::N, L = C::L, FPR = C::FPR, ROW = C::ROW, F = C::F, TFS = C::TFS, SP = C::SP;
+  constexpr bool MULTI = C::MULTI;
+  __shared__ __attribute__((aligned(16))) cpx<T> exch_all[FPR * ROW];
+  __shared__ __attribute__((aligned(16))) cpx<T> st_s[F * SP];
+  __shared__ __attribute__((aligned(16))) cpx<T> st_m[F * SP];      // order 2: V1, then (offset or inf, -)
+
+  const int tid = threadIdx.x;
+  int g = tid / L;                                         // frame slot of the round
+  const int t = tid % L;                                   // lane inside the frame
+  if constexpr (L >= 64) g = __builtin_amdgcn_readfirstlane(g);        // one frame (or part of one) per wave: scalar
+  cpx<T>* exch = exch_all + g * ROW;
+
+  const long long nfr = p.n_frames;
+  const long long b = (long long)blockIdx.y + p.b0;
+  const int f_tile = (int)blockIdx.x * p.tile_frames;                   // frames fit an int: n_frames <= 2^30
+  const int f_end = (long long)f_tile + p.tile_frames < nfr ? f_tile + p.tile_frames : (int)nfr;
+
+  for (int fr0 = f_tile; fr0 < f_end; fr0 += TFS) {                     // a round = a store tile: FPR frames side by side
+    {
+      const int f = fr0 + g;
+      const bool valid = f < f_end;                                      // (a frame past the end transforms zeros)
+      const long long pos0 = (long long)f * p.hop - N / 2;              // the larger half of the n - 1 pad samples on the left
+      const T* __restrict__ xs = p.x + (b + tsst_opaque_zero()) * p.n_signal;   // (formed per round, not held)
+      const bool interior = valid && pos0 >= 0 && pos0 + N <= p.n_signal;
+      T xv[16];
+      tsst_samples<O, LOGN>(p, xs, pos0, t + tsst_opaque_zero(), valid, interior, reinterpret_cast<T*>(exch), xv);
+      frame_sync<MULTI>();      // (an edge frame's samples went through the row: all read before the first exchange writes it)
+      const int slot = g;
+      cpx<T> v[16];
+      if constexpr (ORDER == 1) {
+        // one packed transform x (g + i tg): V and Vt are all the first-order offset needs
+        cpx<T> V[9], Vt[9];
+        const int z = tsst_opaque_zero(), tz = t + z;
+        const cpx<T>* __restrict__ wa = p.wa + z;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const cpx<T> w = wa[(tz + L * q + p.rot) & (N - 1)];
+          v[q] = {xv[q] * w.x, xv[q] * w.y};
+        }
+        fft_pass_compact<T, LOGN, 0, MULTI>(v, exch, p.tw + z, tz);
+        tsst_split<T, LOGN, MULTI>(v, exch, tz, (T)0.5, p.it, V, Vt);
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+          const int k = tz + L * q;
+          if (k <= N / 2) {
+            st_s[k * SP + slot] = V[q];
+            st_m[k * SP + slot] = {tsst_operator1<O>(p, (T)(N / 2), V[q], Vt[q]), (T)0};
+          }
+        }
+      } else {
+        // The three transforms of stft_sst2.hip, in its order and with its opaque offsets and scheduling barriers (what
+        // keeps the kernel inside 256 registers): (g, g1) first, V into the store tile and V1 parked in the
+        // lane's own map slots; tg alone; (tg1, g2) last.
+        cpx<T> Vt[9], Vt1[9], V2[9];
+        {
+          cpx<T> V[9], V1[9];
+          const int z = tsst_opaque_zero(), tz = t + z;
+          const cpx<T>* __restrict__ wa = p.wa + z;
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            const cpx<T> w = wa[(tz + L * q + p.rot) & (N - 1)];
+            v[q] = {xv[q] * w.x, xv[q] * w.y};
+          }
+          fft_pass_compact<T, LOGN, 0, MULTI>(v, exch, p.tw + z, tz);
+          tsst_split<T, LOGN, MULTI>(v, exch, tz, (T)0.5, p.h1, V, V1);
+#pragma unroll
+          for (int q = 0; q < 9; ++q) {
+            const int k = tz + L * q;
+            if (k <= N / 2) {
+              st_s[k * SP + slot] = V[q];
+              st_m[k * SP + slot] = V1[q];
+            }
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+          const int z = tsst_opaque_zero(), tz = t + z;
+          const T* __restrict__ wb = p.wb + z;                           // real input: its spectrum is the transform itself
+#pragma unroll
+          for (int q = 0; q < 16; ++q) v[q] = {xv[q] * wb[(tz + L * q + p.rot) & (N - 1)], (T)0};
+          fft_pass_compact<T, LOGN, 0, MULTI>(v, exch, p.tw + z, tz);
+#pragma unroll
+          for (int q = 0; q < 9; ++q) Vt[q] = cscale(v[q], p.it);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+          const int z = tsst_opaque_zero(), tz = t + z;
+          const cpx<T>* __restrict__ wc = p.wc + z;
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            const cpx<T> w = wc[(tz + L * q + p.rot) & (N - 1)];
+            v[q] = {xv[q] * w.x, xv[q] * w.y};
+          }
+          fft_pass_compact<T, LOGN, 0, MULTI>(v, exch, p.tw + z, tz);
+          tsst_split<T, LOGN, MULTI>(v, exch, tz, p.ht1, p.h2, Vt1, V2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const int te = t + tsst_opaque_zero();
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+          const int k = te + L * q;
+          if (k <= N / 2) {
+            const cpx<T> V = st_s[k * SP + slot], V1 = st_m[k * SP + slot];
+            st_m[k * SP + slot] = {tsst_operator2<O>(p, (T)(N / 2), V, V1, V2[q], Vt[q], Vt1[q]), (T)0};
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // the outputs' addresses are fetched and formed here, so that no pointer is held across the transforms
+    const TsstOut<O> po = p.out[tsst_opaque_zero()];
+    const long long ob = b * (long long)F * nfr;
+    cpx<O>* __restrict__ Sx = po.Sx + ob;
+    O* __restrict__ tau_out = po.tau ? po.tau + ob : nullptr;
+    short* __restrict__ rel_out = po.rel + ob;
+    const int nft = f_end - fr0 < TFS ? f_end - fr0 : TFS;
+    for (int e = tid; e < F * TFS; e += kTsstThreads) {                  // neighbouring lanes: neighbouring frames of a bin
+      const int k = e / TFS, fl = e % TFS;
+      if (fl < nft) {
+        const long long m = (long long)fr0 + fl, o = (long long)k * nfr + m;
+        const cpx<T> S = st_s[k * SP + fl];
+        Sx[o] = {(O)S.x, (O)S.y};
+        const T off = st_m[k * SP + fl].x;
+        O tau = (O)INFINITY;
+        int rel = kTsstNone;
+        if (off != (T)INFINITY) {
+          tau = (O)(off / po.fs);
+          const O v = tau / po.step;
+          // |r| <= ceil(n / (2 hop)), the offset being clamped; the bound below only keeps a quotient of denormals
+          // (an fs next to the dtype's smallest number) inside an int16
+          const O rv = isfinite(v) ? rint(v) : (O)0;
+          const long long r = (long long)(rv < (O)-4096 ? (O)-4096 : (rv > (O)4096 ? (O)4096 : rv));
+          long long mt = m + r;
+          mt = mt < 0 ? 0 : (mt > nfr - 1 ? nfr - 1 : mt);
+          rel = (int)(mt - m);
+        }
+        if (tau_out) tau_out[o] = tau;
+        rel_out[o] = (short)rel;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void tsst_widen_kernel(const float* __restrict__ in, double* __restrict__ out, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (double)in[i];
+}
+
+template <typename O>
+struct TsstScat {
+  const cpx<O>* Sx;        // [batch][F][n_frames]
+  const short* rel;        // [batch][F][n_frames]
+  const cpx<double>* rot;  // [n]  exp(-2 pi i j / n)
+  cpx<O>* Tx;              // [batch][F][n_frames]
+  long long n_frames;
+  int n_freqs, n, hop, reach, tile;    // reach = H <= kTsstMaxReach; tile <= kTsstMaxTile, a multiple of 256
+};
+
+__device__ __forceinline__ void tsst_neumaier(double& s, double& c, double x) {
+  const double t = s + x;
+  c += fabs(s) >= fabs(x) ? (s - t) + x : (x - t) + s;
+  s = t;
+}
+
+// lane j's value of v, j the same in every lane
+__device__ __forceinline__ double tsst_readlane(double v, int j) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
+}
+
+template <typename O>
+__global__ __launch_bounds__(kTsstThreads) void tsst_scatter_kernel(const TsstScat<O> p) {
+  __shared__ short rel_s[kTsstStage];
+  __shared__ int slot_s[kTsstThreads];
+  const long long nfr = p.n_frames;
+  const int k = blockIdx.y;
+  const long long base = ((long long)blockIdx.z * p.n_freqs + k) * nfr;
+  const long long t0 = (long long)blockIdx.x * p.tile;                    // the targets [t0, t1) are this workgroup's
+  const long long t1 = t0 + p.tile < nfr ? t0 + p.tile : nfr;
+  const long long s0 = t0 - p.reach > 0 ? t0 - p.reach : 0;              // the sources [s0, s1) can reach them
+  const long long s1 = t1 + p.reach < nfr ? t1 + p.reach : nfr;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < (int)(s1 - s0); i += kTsstThreads) rel_s[i] = p.rel[base + s0 + i];
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  volatile int* slot = slot_s + 64 * wave;                                // the wave's own 64 slots: no workgroup barrier
+  for (long long g0 = t0 + 64 * wave; g0 < t1; g0 += kTsstThreads) {     // the wave's 64 cells, one per lane
+    double sr = 0, si = 0, cr = 0, ci = 0;
+    for (long long c0 = g0 - p.reach; c0 <= g0 + 63 + p.reach; c0 += 64) {   // 64 sources a step, ascending
+      const long long m = c0 + lane;
+      int r = kTsstNone;
+      if (m >= s0 && m < s1) r = rel_s[m - s0];
+      const long long tl = m + r - g0;
+      const bool hit = r != kTsstNone && tl >= 0 && tl < 64;
+      double zr = 0, zi = 0;
+      if (hit) {
+        const cpx<O> S = p.Sx[base + m];
+        // (k (m - m') hop) mod n = (-k r hop) mod n: the factors reduced first, so that the product stays in an int
+        const int rh = (int)(((long long)r * p.hop) & (p.n - 1));
+        const cpx<double> w = p.rot[(p.n - ((k * rh) & (p.n - 1))) & (p.n - 1)];
+        zr = (double)S.x * w.x - (double)S.y * w.y;
+        zi = (double)S.x * w.y + (double)S.y * w.x;
+      }
+      unsigned long long mask = __ballot(hit);
+      if (mask) {
+        // Which cells does this step feed?  Every hit writes its lane into its cell's slot; a hit that does not read its
+        // own lane back shares the cell with another hit of the step.
+        slot[lane] = -1;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        if (hit) slot[(int)tl] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        const int from = slot[lane];
+        const bool clash = hit && slot[(int)tl] != lane;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");             // (all read before the next step writes)
+        if (__ballot(clash) == 0) {
+          // at most one value a cell: the order inside the step does not enter, all cells take theirs at once
+          const int src = from < 0 ? lane : from;
+          const double ar = __shfl(zr, src), ai = __shfl(zi, src);
+          if (from >= 0) {
+            tsst_neumaier(sr, cr, ar);
+            tsst_neumaier(si, ci, ai);
+          }
+        } else {
+          while (mask) {                                                   // the step's hits in ascending source frame
+            const int j = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const int tj = __builtin_amdgcn_readlane((int)tl, j);
+            const double ar = tsst_readlane(zr, j), ai = tsst_readlane(zi, j);
+            if (lane == tj) {
+              tsst_neumaier(sr, cr, ar);
+              tsst_neumaier(si, ci, ai);
+            }
+          }
+        }
+      }
+    }
+    if (g0 + lane < t1) p.Tx[base + g0 + lane] = {(O)(sr + cr), (O)(si + ci)};
+  }
+}
+
+template <typename T, int LOGN>
+static hipError_t tsst_launch_one(TsstDev<T> p, int order, long long batch, hipStream_t stream) {
+  p.tile_frames = TsstCfg<LOGN>::TFS * kTsstRoundsPerTile;
+  const long long tiles = (p.n_frames + p.tile_frames - 1) / p.tile_frames;
+  if (tiles > 0x7fffffffLL || batch > 65535) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)tiles, (unsigned)batch), block(kTsstThreads);
+  if (order == 1)
+    hipLaunchKernelGGL((tsst_operator_kernel<T, LOGN, 1>), grid, block, 0, stream, p);
+  else
+    hipLaunchKernelGGL((tsst_operator_kernel<T, LOGN, 2>), grid, block, 0, stream, p);
+  return hipGetLastError();
+}
+
+template <typename T>
+static hipError_t tsst_launch(const TsstDev<T>& p, int logn, int order, long long batch, hipStream_t stream) {
+  switch (logn) {
+    case 4: return tsst_launch_one<T, 4>(p, order, batch, stream);
+    case 5: return tsst_launch_one<T, 5>(p, order, batch, stream);
+    case 6: return tsst_launch_one<T, 6>(p, order, batch, stream);
+    case 7: return tsst_launch_one<T, 7>(p, order, batch, stream);
+    case 8: return tsst_launch_one<T, 8>(p, order, batch, stream);
+    case 9: return tsst_launch_one<T, 9>(p, order, batch, stream);
+    case 10: return tsst_launch_one<T, 10>(p, order, batch, stream);
+    case 11: return tsst_launch_one<T, 11>(p, order, batch, stream);
+    case 12: return tsst_launch_one<T, 12>(p, order, batch, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
+}  // namespace ssq
+
+using namespace ssq;
+
+namespace {
+
+// a power of two a with a * max|tab| within a factor two of `level` (exact to apply and to undo)
+double tsst_level_scale(const std::vector<double>& tab, double level) {
+  double m = 0;
+  for (double v : tab) m = std::fmax(m, std::fabs(v));
+  if (!(m > 0) || !(level > 0) || !std::isfinite(level / m)) return 1.0;
+  int e = 0;
+  std::frexp(level / m, &e);
+  return std::ldexp(1.0, e - 1);
+}
+
+struct TsstShape {
+  int logn = 0, order = 2, reach = 1, tile = 1024;
+  int64_t n_freqs = 0, n_frames = 0;
+  double fs = 1.0, gamma = 0.0;
+};
+
+// The argument checks of the three entry points, and the shape they work on (sets the error and returns non-zero)
+int tsst_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop, double fs, int padtype, int order,
+               double gamma, TsstShape* s) {
+  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
+  if (batch < 1) SSQ_FAIL("batch must be >= 1");
+  if (n_fft < 16 || n_fft > 4096 || (n_fft & (n_fft - 1)) != 0)
+    SSQ_FAIL("tssq_stft: n_fft must be a power of two from 16 to 4096");
+  if (n_signal < 1 || hop < 1) SSQ_FAIL("tssq_stft: n_signal and hop must be >= 1");
+  if (hop > 0x7fffffffLL) SSQ_FAIL("tssq_stft: hop does not fit an int");
+  if (padtype < SSQ_PAD_REFLECT || padtype > 4) SSQ_FAIL("tssq_stft: unknown padtype");
+  if (order != 1 && order != 2) SSQ_FAIL("tssq_stft: order must be 1 or 2");
+  if (gamma != gamma) SSQ_FAIL("tssq_stft: gamma is NaN");
+  if (!(fs > 0) || !std::isfinite(fs)) SSQ_FAIL("tssq_stft: fs must be positive");
+  s->logn = 0;
+  while ((1LL << s->logn) < n_fft) ++s->logn;
+  s->order = order;
+  s->n_freqs = n_fft / 2 + 1;
+  s->n_frames = (n_signal - 1) / hop + 1;
+  if (s->n_frames > (1LL << 30)) SSQ_FAIL("tssq_stft: too many frames");
+  s->reach = (int)((n_fft / 2 + hop - 1) / hop);              // H = ceil(n / (2 hop)) <= kTsstMaxReach
+  s->tile = 2 * s->reach < 1024 ? 1024 : (2 * s->reach + 255) / 256 * 256;   // halo re-read (tile + 2 H) / tile <= 2
+  s->fs = fs;
+  s->gamma = gamma < 0 ? 10.0 * (dtype == SSQ_F64 ? 2.2204460492503131e-16 : 1.1920928955078125e-07) : gamma;
+  return 0;
+}
+
+// the call's tables on the device (held by `d`) and the two parameter blocks without their signal / output pointers
+template <typename T>
+int tsst_tables(HostCallBufs& d, const TsstShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
+                int padtype, int variant, TsstDev<T>* p, TsstScat<T>* sc) {
+  const std::vector<double> g(window, window + n);
+  std::vector<double> g1 = host::diff_window(window, n, true);
+  std::vector<double> g2 = host::diff_window(g1.data(), n, true);
+  std::vector<double> tg((size_t)n), tg1((size_t)n);
+  for (int64_t j = 0; j < n; ++j) {
+    const double u = (double)(j - n / 2);
+    tg[j] = u * window[j];
+    tg1[j] = u * g1[j];
+  }
+  double mg = 0;
+  for (double v : g) mg = std::fmax(mg, std::fabs(v));
+  const double a1 = tsst_level_scale(g1, mg), a2 = tsst_level_scale(g2, mg), at = tsst_level_scale(tg, mg),
+               at1 = tsst_level_scale(tg1, mg);
+  std::vector<cpx<double>> wa((size_t)n), wc((size_t)n), tw, rot((size_t)n);
+  std::vector<double> wb((size_t)n);
+  for (int64_t j = 0; j < n; ++j) {
+    wa[j] = s.order == 1 ? cpx<double>{g[j], tg[j] * at} : cpx<double>{g[j], g1[j] * a1};
+    wb[j] = tg[j] * at;
+    wc[j] = {tg1[j] * at1, g2[j] * a2};
+    const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)j / (long double)n;
+    rot[j] = {(double)cosl(ang), (double)(-sinl(ang))};
+  }
+  for (int P = 1; P < num_passes(s.logn); ++P) {             // read coalesced by fft_pass_compact
+    const int R = pass_radix(s.logn, P), NS = pass_ns(s.logn, P);
+    for (int m = 0; m < R; ++m)
+      for (int k = 0; k < NS; ++k) {
+        const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)((long long)k * m) /
+                                (long double)((long long)NS * R);
+        tw.push_back({(double)cosl(ang), (double)(-sinl(ang))});
+      }
+  }
+  void *d_tw, *d_wa, *d_wb, *d_wc, *d_rot;
+  SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(cpx<double>) * tw.size()));
+  SSQ_HIP(d.upload(&d_wa, wa.data(), sizeof(cpx<double>) * n));
+  SSQ_HIP(d.upload(&d_wb, wb.data(), sizeof(double) * n));
+  SSQ_HIP(d.upload(&d_wc, wc.data(), sizeof(cpx<double>) * n));
+  SSQ_HIP(d.upload(&d_rot, rot.data(), sizeof(cpx<double>) * n));
+  *p = TsstDev<T>{};
+  p->tw = (const cpx<double>*)d_tw;
+  p->wa = (const cpx<double>*)d_wa;
+  p->wb = (const double*)d_wb;
+  p->wc = (const cpx<double>*)d_wc;
+  p->n_signal = n_signal;
+  p->n_frames = s.n_frames;
+  p->hop = (int)hop;
+  p->padtype = padtype;
+  p->rot = (variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
+  p->gamma = s.gamma;
+  p->gamma_sq = s.gamma * s.gamma;
+  p->h1 = 0.5 / a1;
+  p->it = s.order == 1 ? 0.5 / at : 1.0 / at;
+  p->ht1 = 0.5 / at1;
+  p->h2 = 0.5 / a2;
+  *sc = TsstScat<T>{};
+  sc->rot = (const cpx<double>*)d_rot;
+  sc->n_frames = s.n_frames;
+  sc->n_freqs = (int)s.n_freqs;
+  sc->n = (int)n;
+  sc->hop = (int)hop;
+  sc->reach = s.reach;
+  sc->tile = s.tile;
+  return 0;
+}
+
+// the operator kernel's output block (TsstOut) on the device, held by `d`
+template <typename T>
+int tsst_out_block(HostCallBufs& d, const TsstShape& s, int64_t hop, void* d_Sx, void* d_tau, void* d_rel, TsstDev<T>* p) {
+  TsstOut<T> o{};
+  o.Sx = (cpx<T>*)d_Sx;
+  o.tau = (T*)d_tau;
+  o.rel = (short*)d_rel;
+  o.fs = s.fs;
+  o.step = (T)((double)hop / s.fs);
+  void* d_o;
+  SSQ_HIP(d.upload(&d_o, &o, sizeof(o)));
+  p->out = (const TsstOut<T>*)d_o;
+  return 0;
+}
+
+// both kernels of `nb` signals on device buffers; ev (may be nullptr): an event recorded between the two
+template <typename T>
+hipError_t tsst_run(TsstDev<T> p, TsstScat<T> sc, const TsstShape& s, const T* d_x, int64_t nb, cpx<T>* d_Tx, cpx<T>* d_Sx,
+                    short* d_rel, double* d_xd /* float32 calls: [nb][n_signal] */, hipEvent_t ev) {
+  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
+  hipError_t e;
+  const double* xd;
+  if constexpr (sizeof(T) == 4) {
+    const long long n = (long long)nb * p.n_signal;
+    hipLaunchKernelGGL(tsst_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const float*)d_x, d_xd, n);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    xd = d_xd;
+  } else {
+    xd = (const double*)d_x;
+  }
+  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
+    const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
+    p.x = xd;
+    p.b0 = (int)b0;
+    if ((e = tsst_launch<T>(p, s.logn, s.order, n1, nullptr)) != hipSuccess) return e;
+  }
+  if (ev && (e = hipEventRecord(ev, nullptr)) != hipSuccess) return e;
+  const long long tiles = (s.n_frames + s.tile - 1) / s.tile;
+  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
+    const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
+    sc.Sx = d_Sx + map_sig * b0;
+    sc.rel = d_rel + map_sig * b0;
+    sc.Tx = d_Tx + map_sig * b0;
+    hipLaunchKernelGGL(tsst_scatter_kernel<T>, dim3((unsigned)tiles, (unsigned)s.n_freqs, (unsigned)n1), dim3(kTsstThreads), 0,
+                       nullptr, sc);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+template <typename T>
+int tsst_host_typed(const TsstShape& s, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
+                    int64_t hop, int padtype, int variant, void* Tx, void* Sx, void* tau) {
+  HostCallBufs d;
+  TsstDev<T> p;
+  TsstScat<T> sc;
+  if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
+  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
+  // signals per slice: most of the free memory (a signal's result does not depend on the slice it is in)
+  const double per = (double)(sizeof(T) == 4 ? 12 : 8) * (double)n_signal +
+                     (double)map_sig * (2.0 * sizeof(cpx<T>) + sizeof(short) + (tau ? sizeof(T) : 0));
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)1 << 30;
+  int64_t slice = (int64_t)(0.8 * (double)free_b / per);
+  if (slice > batch) slice = batch;
+  if (slice < 1) slice = 1;                                  // one signal is always tried: hipMalloc reports the rest
+  void *d_x, *d_Tx, *d_Sx, *d_rel, *d_tau = nullptr, *d_xd = nullptr;
+  SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)n_signal * slice));
+  if (sizeof(T) == 4) SSQ_HIP(d.alloc(&d_xd, sizeof(double) * (size_t)n_signal * slice));
+  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * map_sig * slice));
+  SSQ_HIP(d.alloc(&d_Sx, sizeof(cpx<T>) * map_sig * slice));
+  SSQ_HIP(d.alloc(&d_rel, sizeof(short) * map_sig * slice));
+  if (tau) SSQ_HIP(d.alloc(&d_tau, sizeof(T) * map_sig * slice));
+  if (int rc = tsst_out_block<T>(d, s, hop, d_Sx, d_tau, d_rel, &p)) return rc;
+  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
+    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
+    SSQ_HIP(hipMemcpy(d_x, (const T*)x + (size_t)n_signal * b0, sizeof(T) * (size_t)n_signal * nb, hipMemcpyHostToDevice));
+    SSQ_HIP(tsst_run<T>(p, sc, s, (const T*)d_x, nb, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, (short*)d_rel, (double*)d_xd, nullptr));
+    SSQ_HIP(hipMemcpy((cpx<T>*)Tx + map_sig * b0, d_Tx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
+    SSQ_HIP(hipMemcpy((cpx<T>*)Sx + map_sig * b0, d_Sx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
+    if (tau) SSQ_HIP(hipMemcpy((T*)tau + map_sig * b0, d_tau, sizeof(T) * map_sig * nb, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+struct TsstEvents {
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  ~TsstEvents() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+template <typename T>
+int tsst_exec_typed(const TsstShape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
+                    int64_t hop, int padtype, int variant, void* d_Tx, void* d_Sx, void* d_tau, void* d_work,
+                    float* kernel_ms) {
+  HostCallBufs d;
+  TsstEvents t;
+  TsstDev<T> p;
+  TsstScat<T> sc;
+  if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
+  // the workspace: (float32 calls) the widened signals, then the relative targets
+  double* d_xd = (double*)d_work;
+  short* d_rel = (short*)((char*)d_work + (sizeof(T) == 4 ? sizeof(double) * (size_t)batch * (size_t)n_signal : 0));
+  if (int rc = tsst_out_block<T>(d, s, hop, d_Sx, d_tau, d_rel, &p)) return rc;
+  if (kernel_ms) {
+    for (hipEvent_t& e : t.ev) SSQ_HIP(hipEventCreate(&e));
+    SSQ_HIP(hipEventRecord(t.ev[0], nullptr));
+  }
+  SSQ_HIP(tsst_run<T>(p, sc, s, (const T*)d_x, batch, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, d_rel, d_xd, kernel_ms ? t.ev[1] : nullptr));
+  if (kernel_ms) {
+    SSQ_HIP(hipEventRecord(t.ev[2], nullptr));
+    SSQ_HIP(hipEventSynchronize(t.ev[2]));
+    SSQ_HIP(hipEventElapsedTime(&kernel_ms[0], t.ev[0], t.ev[1]));
+    SSQ_HIP(hipEventElapsedTime(&kernel_ms[1], t.ev[1], t.ev[2]));
+  } else {
+    SSQ_HIP(hipDeviceSynchronize());
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ssq_tssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                       int64_t hop, double fs, int padtype, int order, double gamma, int variant, void* Tx, void* Sx,
+                       void* tau) {
+  if (!x || !window || !Tx || !Sx) SSQ_FAIL("NULL argument");
+  TsstShape s;
+  if (int rc = tsst_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, order, gamma, &s)) return rc;
+  if (int rc = require_device()) return rc;
+  return dtype == SSQ_F32 ? tsst_host_typed<float>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, Tx, Sx, tau)
+                          : tsst_host_typed<double>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, Tx, Sx, tau);
+}
+
+int64_t ssq_tssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop) {
+  TsstShape s;
+  if (tsst_shape(dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, 2, -1.0, &s)) return -1;
+  return (dtype == SSQ_F32 ? 8 * batch * n_signal : 0) + 2 * batch * s.n_freqs * s.n_frames;
+}
+
+int ssq_tssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                       int64_t hop, double fs, int padtype, int order, double gamma, int variant, void* d_Tx, void* d_Sx,
+                       void* d_tau, void* d_workspace, int64_t workspace_bytes, float* kernel_ms) {
+  if (!d_x || !window || !d_Tx || !d_Sx || !d_workspace) SSQ_FAIL("NULL argument");
+  TsstShape s;
+  if (int rc = tsst_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, order, gamma, &s)) return rc;
+  if (workspace_bytes < ssq_tssq_stft_workspace_bytes(dtype, batch, n_signal, n_fft, hop))
+    SSQ_FAIL("tssq_stft: workspace smaller than ssq_tssq_stft_workspace_bytes");
+  if (int rc = require_device()) return rc;
+  return dtype == SSQ_F32 ? tsst_exec_typed<float>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, variant, d_Tx, d_Sx,
+                                                   d_tau, d_workspace, kernel_ms)
+                          : tsst_exec_typed<double>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, variant, d_Tx, d_Sx,
+                                                    d_tau, d_workspace, kernel_ms);
+}
+
+}  // extern "C"

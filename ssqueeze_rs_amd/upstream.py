@@ -39,6 +39,11 @@ Supported subset (anything else raises ValueError naming the option):
     project's: DESIGN 4.11, csrc/stft_sst2.hip): the conventions of `ssq_stft` (ndarray window, the five padtypes,
     'sum' / 'lebesgue', `flipud`, `modulated`, batches) with a power-of-two `n_fft` from 16 to 4096; its `Tx` inverts
     through `issq_stft` like a first-order one;
+  * `tssq_stft`: the time-reassigned synchrosqueezed STFT (orders 1 and 2), which upstream does not have (the definition
+    is this project's: DESIGN 4.13, csrc/stft_tsst.hip): every coefficient moves along time to its group delay, which
+    concentrates impulses and fast chirps; the conventions of `ssq_stft2` (ndarray window, the five padtypes,
+    `modulated`, batches, a power-of-two `n_fft` from 16 to 4096); no inverse (its row sums give the spectrum at n_fft
+    points only);
   * `ssq_cwt2`: the second-order synchrosqueezed CWT, which upstream does not have either (the definition is this
     project's: DESIGN 4.12, csrc/cwt_sst2.hip): the conventions of `ssq_cwt` (ndarray scales of the three grids,
     `ssq_freqs` None / a string / an array, maprange 'peak' / 'maximal', 'sum' / 'lebesgue', the five padtypes, `flipud`,
@@ -396,6 +401,68 @@ def ssq_stft2(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=No
     out = [Tx if batched else Tx[0], Sx if batched else Sx[0], f.astype(rdt), Sfs]
     if get_w:
         out.append(w2 if batched else w2[0])
+    return tuple(out)
+
+
+def tssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
+              order=2, gamma=None, get_tau=False):
+    """Time-reassigned synchrosqueezed STFT -> (Tx, Sx, times, Sfs[, tau]); not in upstream (He, Tu, Bao, Hu and Zhang
+    2019), conventions of `ssq_stft2`.  Where `ssq_stft` and `ssq_stft2` move energy along frequency, this moves every
+    coefficient along TIME to its estimated group delay: an impulse, a fast chirp or a dispersive arrival, whose ridge
+    runs along frequency, lands on its own column.
+
+    With n = n_fft, the five windows of `ssq_stft2` (g, its spectral derivatives g1 and g2, tg = u g, tg1 = u g1,
+    u = sample index - n // 2), V, V1, V2, Vt, Vt1 the STFTs of `x` with them and frame m centred on sample m hop_len,
+    per sample and in fp64 for either dtype:
+        d1 = Re(Vt / V)          D = Vt V1 - Vt1 V          num = V2 V - V1^2          d2 = Re(Vt / V + V1 D / (V num))
+    d1 is the first-order group-delay offset; d2 is the time at which the locally fitted linear chirp crosses frequency
+    k / n, exact for linear group delay.  `order=2` uses d2 where |num| > gamma^2, d2 is finite and |d2| <= n / 2, else
+    (and always with `order=1`, which computes V and Vt only) d1; the offset is clamped to [-n / 2, n / 2].  `tau`
+    (get_tau=True) is offset / fs in seconds, relative to the frame's own time, +inf where a bin is not kept; bins with
+    |V| > gamma (default 10 eps of the dtype) are kept.  The target column comes from the reported `tau` in its dtype:
+        r = rint(tau / (hop_len / fs))  (0 where not finite)          m' = clip(m + r, 0, n_frames - 1)
+        Tx[k, m'] += Sx[k, m] exp(-2 pi i ((k (m - m') hop_len) mod n) / n)
+    The factor re-references the phase from the source frame's centre to the target's (the same for `modulated=False`):
+    with it an impulse at t0 lands on column t0 with magnitude sum(g) in every row; without it its contributions cancel.
+    Every cell is the sum of its contributions in ascending source frame (a compensated fp64 sum, no atomics), so the
+    result does not depend on the batch or on the kernel's tiling.  `Sx` equals `stft(x, ...)`; `times` =
+    arange(n_frames) hop_len / fs.  There is no inverse: for every row k
+        sum_m' Tx[k, m'] e^(-2 pi i k m' hop_len / n)  =  sum_(kept m) Sx[k, m] e^(-2 pi i k m hop_len / n),
+    the signal's spectrum at n_fft points, which determines it only modulo n_fft samples.
+
+    `n_fft` must be a power of two from 16 to 4096 and `order` 1 or 2 (ValueError otherwise, before any GPU work).  Every
+    (dtype, n_fft, order) is built without register spills or scratch (profiles/tsst_resources.txt)."""
+    lib = _lib.load()
+    if isinstance(order, (bool, np.bool_)) or order not in (1, 2):
+        raise ValueError(f"order {order!r}: tssq_stft builds orders 1 and 2")
+    xa, batched, code = _signal(x)
+    batch, N = xa.shape
+    fs = 1.0 / _dt(fs, t, N)
+    n_fft = n_fft or min(N // hop_len, 512)
+    if (not isinstance(n_fft, (int, np.integer)) or isinstance(n_fft, (bool, np.bool_))
+            or not SST2_MIN_N_FFT <= n_fft <= SST2_MAX_N_FFT or n_fft & (n_fft - 1)):
+        raise ValueError(f"n_fft {n_fft!r}: tssq_stft takes a power of two from {SST2_MIN_N_FFT} to {SST2_MAX_N_FFT}")
+    n_fft = int(n_fft)
+    if gamma is not None and math.isnan(float(gamma)):
+        raise ValueError("gamma is NaN")
+    if win_len is None:
+        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
+    win = get_window(window, win_len, n_fft)
+    pad = _pad_code(padtype)
+    _lib.require_gpu()
+    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0)
+    n_freqs, n_frames = n_fft // 2 + 1, (N - 1) // hop_len + 1
+    shape = (batch, n_freqs, n_frames)
+    cdt, rdt = _cdtype(code), _rdtype(code)
+    Tx, Sx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
+    tau = _lib.pinned_empty(shape, rdt) if get_tau else None
+    _call(lib.ssq_tssq_stft_host(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, pad, int(order),
+                                 -1.0 if gamma is None else float(gamma), variant, _ptr(Tx), _ptr(Sx), _ptr(tau)))
+    times = (np.arange(n_frames) * hop_len / fs).astype(rdt)
+    Sfs = np.linspace(0, .5 * fs, n_freqs, dtype=rdt)
+    out = [Tx if batched else Tx[0], Sx if batched else Sx[0], times, Sfs]
+    if get_tau:
+        out.append(tau if batched else tau[0])
     return tuple(out)
 
 
