@@ -224,6 +224,34 @@ int64_t ssq_tssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal
 int ssq_tssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
                        int64_t hop, double fs, int padtype, int order, double gamma, int variant, void* d_Tx, void* d_Sx,
                        void* d_tau, void* d_workspace, int64_t workspace_bytes, float* kernel_ms);
+/* Reassigned spectrogram, `upstream.reassign_stft` (csrc/stft_reassign.hip; Kodera et al. 1978; Auger and
+ * Flandrin 1995; upstream has no such transform): every bin's energy |Sx|^2 moves along frequency AND time at once, to
+ * its instantaneous frequency and its group delay (first order only).  window [n_fft] already sized, padtype SSQ_PAD_*,
+ * gamma < 0: 10 eps of the dtype (NaN is refused), variant: the SSQ_VARIANT_MODULATED bit (the others are ignored).
+ * n_fft must be a power of two from 16 to 4096.  Per-sample, with the window tables g, g1, tg and the STFTs V, V1, Vt of
+ * ssq_ssq_stft2_host, frame m centred on sample m hop, in fp64 for either dtype:
+ *   w = fs |k/n_fft - Im(V1/V)/(2 pi)|,  tau = clamp(Re(Vt/V), +- n_fft/2) / fs, each rounded once to `dtype`, +inf where
+ *   |V| <= gamma;  k' = ssq_ssq_stft2_host's bin rule on w (np.linspace(0, fs/2, n_freqs), no flip);
+ *   m' = clip(m + rint(tau / (hop/fs)), 0, n_frames - 1) in `dtype`;  Rx[k'][m'] += |Sx[k][m]|^2 (of the reported Sx, in
+ *   fp64), accumulated in 64-bit fixed point with the quantum P 2^-38, P the smallest power of two >= the signal's
+ *   max |Sx|^2: integer adds commute, so signal b's result does not depend on `batch`, the tiling or the order.
+ * Rx: [batch][n_freqs][n_frames] REAL of `dtype`; Sx: the same shape, complex of `dtype`; w, tau (each may be NULL):
+ * REAL of `dtype`, Hz and seconds relative to the frame's own time.  Synchronous; the batch goes through the device in
+ * slices sized from its free memory. */
+int ssq_reassign_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                           int64_t hop, double fs, int padtype, double gamma, int variant, void* Rx, void* Sx, void* w,
+                           void* tau);
+/* Device bytes of the workspace ssq_reassign_stft_exec needs (for SSQ_F32 the signals widened to fp64, then 8 bytes a
+ * signal for its max |Sx|^2 and one packed 4-byte target per bin), computed on the host; -1 on a shape
+ * ssq_reassign_stft_host refuses. */
+int64_t ssq_reassign_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop);
+/* The same transform on device buffers: d_x [batch][N], d_Rx, d_Sx, d_w and d_tau (each may be NULL) as above,
+ * d_workspace of at least ssq_reassign_stft_workspace_bytes bytes; `window` on the host.  Synchronous.  kernel_ms (may be
+ * NULL): TWO floats, the time of the operator kernel (with the widening of a float32 call) and of the scatter, from HIP
+ * events around the launches with the tables set up before them. */
+int ssq_reassign_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                           int64_t hop, double fs, int padtype, double gamma, int variant, void* d_Rx, void* d_Sx,
+                           void* d_w, void* d_tau, void* d_workspace, int64_t workspace_bytes, float* kernel_ms);
 /* ssqueezepy.issq_stft / issq_cwt, full inverse (_ssq_stft.py:139-198, _ssq_cwt.py:313-378):
  * x_out[j] = scale * sum_rows row_scale[row] * Re Tx[row][j]   (scale = 2 / window[n_fft/2]  resp.  2 / adm_ssq;
  * row_scale NULL = 1; the one-integral icwt of _cwt.py:477-492 is the same sum with 1/sqrt(a) rows for the L2 norm).

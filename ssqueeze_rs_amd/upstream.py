@@ -44,6 +44,10 @@ Supported subset (anything else raises ValueError naming the option):
     concentrates impulses and fast chirps; the conventions of `ssq_stft2` (ndarray window, the five padtypes,
     `modulated`, batches, a power-of-two `n_fft` from 16 to 4096); no inverse (its row sums give the spectrum at n_fft
     points only);
+  * `reassign_stft`: the reassigned spectrogram (Kodera et al.; Auger and Flandrin 1995), which upstream does not have
+    (the definition is this project's: DESIGN 4.14, csrc/stft_reassign.hip): every bin's energy |Sx|^2 moves along
+    frequency and time at once, to its instantaneous frequency and group delay (first order); the conventions of
+    `tssq_stft`; real, non-negative, energy-conserving, accumulated in fixed point (`REASSIGN_QUANTUM_LOG2`); no inverse;
   * `ssq_cwt2`: the second-order synchrosqueezed CWT, which upstream does not have either (the definition is this
     project's: DESIGN 4.12, csrc/cwt_sst2.hip): the conventions of `ssq_cwt` (ndarray scales of the three grids,
     `ssq_freqs` None / a string / an array, maprange 'peak' / 'maximal', 'sum' / 'lebesgue', the five padtypes, `flipud`,
@@ -463,6 +467,80 @@ def tssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=No
     out = [Tx if batched else Tx[0], Sx if batched else Sx[0], times, Sfs]
     if get_tau:
         out.append(tau if batched else tau[0])
+    return tuple(out)
+
+
+# csrc/stft_reassign.hip: kReassignQuantumLog2.  `reassign_stft` accumulates |Sx|^2 in 64-bit fixed point with the quantum
+# q = P 2^REASSIGN_QUANTUM_LOG2, P the smallest power of two >= the signal's max |Sx|^2.
+REASSIGN_QUANTUM_LOG2 = -38
+
+
+def reassign_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True,
+                  padtype="reflect", gamma=None, get_w=False, get_tau=False):
+    """Reassigned spectrogram -> (Rx, Sx, times, Sfs[, w][, tau]); not in upstream (Kodera, Gendrin and de Villedary 1978;
+    Auger and Flandrin 1995: `librosa.reassigned_spectrogram`, MATLAB's `spectrogram(..., 'reassigned')`), conventions
+    of `tssq_stft`.  Where `ssq_stft` / `ssq_stft2` move STFT coefficients along frequency and `tssq_stft` along time,
+    this moves every bin's ENERGY |Sx|^2 in both directions at once, to its instantaneous frequency and its group delay:
+    ridges that run along time and ridges that run along frequency (a sweep with clicks on it) sharpen together.
+
+    With n = n_fft, F = n // 2 + 1, g the sized window, g1 its spectral derivative (Nyquist term zeroed), tg = u g
+    (u = sample index - n // 2), V, V1, Vt the STFTs of `x` with them and frame m centred on sample m hop_len, per sample
+    and in fp64 for either dtype:
+        w   = fs |k / n - Im(V1 / V) / (2 pi)|             (`ssq_stft2`'s first-order frequency)
+        tau = clamp(Re(Vt / V), -n / 2, n / 2) / fs        (`tssq_stft`'s order-1 group-delay offset, seconds)
+    each rounded once to the call's dtype; a bin is kept where |V| > gamma (default 10 eps of the dtype), and `w`
+    (get_w=True) and `tau` (get_tau=True) are +inf where it is not.  The targets come from the reported maps, in their
+    dtype:
+        k' = `ssq_stft2`'s bin rule on w: clamped round-half-even on Sfs = np.linspace(0, fs / 2, F), no flip
+        m' = clip(m + rint(tau / (hop_len / fs)), 0, n_frames - 1)
+        Rx[k', m'] += |Sx[k, m]|^2                         (of the reported Sx, formed in fp64)
+    First order only, on purpose: (m + tau, w) is the centroid of the smoothed Wigner distribution, which lies ON the
+    line of a linear chirp for any window, so there is no chirp-rate bias to remove; the two second-order operators of
+    `ssq_stft2` and `tssq_stft` do not compose (one is a frequency at the frame's time, the other a time at the row's
+    frequency: the pair is off the line).
+
+    `Rx` is real and non-negative, in the call's real dtype, and conserves energy: sum(Rx) = sum of |Sx|^2 over the kept
+    bins.  It is accumulated in 64-bit fixed point with the quantum q = P 2^-38 (`REASSIGN_QUANTUM_LOG2`), P the smallest
+    power of two >= the signal's max |Sx|^2 -- about 2^-38 of the signal's peak energy, roughly -114 dB: every
+    contribution is rounded to a multiple of q, and the integer adds commute, so a cell's bits do not depend on the order
+    of the adds, the kernel's tiling or the batch.  `Sx` equals `stft(x, ...)`; `times` = arange(n_frames) hop_len / fs.
+    There is no inverse (the phase is gone).
+
+    `n_fft` must be a power of two from 16 to 4096 (ValueError otherwise, and for a NaN `gamma` or an unknown `padtype`,
+    before any GPU work).  Every (dtype, n_fft) is built without register spills or scratch
+    (profiles/reassign_resources.txt)."""
+    lib = _lib.load()
+    xa, batched, code = _signal(x)
+    batch, N = xa.shape
+    fs = 1.0 / _dt(fs, t, N)
+    n_fft = n_fft or min(N // hop_len, 512)
+    if (not isinstance(n_fft, (int, np.integer)) or isinstance(n_fft, (bool, np.bool_))
+            or not SST2_MIN_N_FFT <= n_fft <= SST2_MAX_N_FFT or n_fft & (n_fft - 1)):
+        raise ValueError(f"n_fft {n_fft!r}: reassign_stft takes a power of two from {SST2_MIN_N_FFT} to {SST2_MAX_N_FFT}")
+    n_fft = int(n_fft)
+    if gamma is not None and math.isnan(float(gamma)):
+        raise ValueError("gamma is NaN")
+    if win_len is None:
+        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
+    win = get_window(window, win_len, n_fft)
+    pad = _pad_code(padtype)
+    _lib.require_gpu()
+    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0)
+    n_freqs, n_frames = n_fft // 2 + 1, (N - 1) // hop_len + 1
+    shape = (batch, n_freqs, n_frames)
+    cdt, rdt = _cdtype(code), _rdtype(code)
+    Rx, Sx = _lib.pinned_empty(shape, rdt), _lib.pinned_empty(shape, cdt)
+    w = _lib.pinned_empty(shape, rdt) if get_w else None
+    tau = _lib.pinned_empty(shape, rdt) if get_tau else None
+    _call(lib.ssq_reassign_stft_host(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, pad,
+                                     -1.0 if gamma is None else float(gamma), variant, _ptr(Rx), _ptr(Sx), _ptr(w),
+                                     _ptr(tau)))
+    times = (np.arange(n_frames) * hop_len / fs).astype(rdt)
+    Sfs = np.linspace(0, .5 * fs, n_freqs, dtype=rdt)
+    out = [Rx if batched else Rx[0], Sx if batched else Sx[0], times, Sfs]
+    for a in (w, tau):
+        if a is not None:
+            out.append(a if batched else a[0])
     return tuple(out)
 
 
