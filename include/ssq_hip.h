@@ -349,6 +349,40 @@ int ssq_ssq_cwt2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
 /* The two fp64 tables of one scale on the host (no GPU), by the functions the kernel evaluates them with
  * (csrc/cwt_sst2_wavelets.h): T0, T1 [P], zero above P/2.  P a power of two. */
 int ssq_ssq_cwt2_tables(int wavelet, double p0, double p1, double scale, int64_t P, double* T0, double* T1);
+/* Reassigned scalogram, `upstream.reassign_cwt` (csrc/cwt_reassign.hip; Auger and Flandrin 1995, III;
+ * upstream has no such transform): every coefficient's energy |Wx|^2 moves along frequency AND time at once, to its
+ * instantaneous frequency and its group delay (first order only).  Arguments as ssq_ssq_cwt2_host without row weights
+ * and squeezing (variant: the SSQ_VARIANT_FLIPUD bit; gamma < 0: 10 eps of the dtype, NaN is refused).  Per-sample, with
+ * P, xh, xi_k, T0, T1 of ssq_ssq_cwt2_host, in fp64 for either dtype:
+ *   W = F^-1[xh T0], W1 = F^-1[xh i xi T0], Wt = F^-1[xh (-i) T1];
+ *   w = |Im(W1/W)| / (2 pi dt),  tau = clamp(Re(Wt/W), +- n_signal) dt, each rounded once to `dtype`, +inf where
+ *   |W| < gamma;  k' = ssq_ssqueeze_w_exec's bin rule on the reported w in `dtype` (flipped with the variant bit);
+ *   m' = clip(j + rint(tau / dt), 0, n_signal - 1) in `dtype`;  Rx[k'][m'] += |Wx[i][j]|^2 (of the reported Wx, in fp64),
+ *   accumulated by 64-bit integer atomic adds in fixed point with the quantum Pmax 2^-S, S = min(38, 62 -
+ *   ceil(log2(na n_signal))), Pmax the smallest power of two >= the signal's max |Wx|^2: integer adds commute, so signal
+ *   b's result depends neither on `batch`, nor on the chunking, nor on the order.  na * n_signal <= 2^40.
+ * Rx: [batch][na][n_signal] REAL of `dtype`; Wx: the same shape, complex of `dtype` (ssq_ssq_cwt2_host's Wx); w, tau
+ * (each may be NULL): REAL of `dtype`, Hz and seconds relative to the column's own time; kk, mm (each may be NULL): int32,
+ * the targets k' and m', -1 where a bin is not kept.
+ * Workspace: 16 ceil(batch / 2) + 16 batch na n_signal bytes (the maxima, the accumulators, the targets), then
+ * 16 P (batch + 6 R) for chunks of R rows; a row's result does not depend on R or on the batch.  work_limit_bytes: 0 for
+ * the preferred size, else at least min_bytes. */
+int ssq_reassign_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                          const double* scales, int64_t na, double dt, const double* ssq_freqs_asc, int freq_kind,
+                          int64_t freq_transition, int padtype, double gamma, int variant, int64_t work_limit_bytes,
+                          void* Rx, void* Wx, void* w, void* tau, void* kk, void* mm);
+/* Device bytes of the workspace: returns the preferred size (every row in one chunk, the chunk area capped at 2 GiB) and
+ * stores the least one (one row per chunk) in *min_bytes (may be NULL); computed on the host; -1 on a bad shape. */
+int64_t ssq_reassign_cwt_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int64_t* min_bytes);
+/* The same transform on device buffers: d_x [batch][n_signal], d_Rx, d_Wx (required), d_w, d_tau, d_kk, d_mm (each may be
+ * NULL) as above, d_workspace of workspace_bytes >= min_bytes (its size sets R); scales, ssq_freqs_asc on the host.
+ * Synchronous on `stream`.  kernel_ms (may be NULL): TWO floats, the time of all the kernels and of the scatter kernel
+ * alone, from HIP events around the launches. */
+int ssq_reassign_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                          const double* scales, int64_t na, double dt, const double* ssq_freqs_asc, int freq_kind,
+                          int64_t freq_transition, int padtype, double gamma, int variant, void* d_Rx, void* d_Wx,
+                          void* d_w, void* d_tau, void* d_kk, void* d_mm, void* d_workspace, int64_t workspace_bytes,
+                          void* stream, float* kernel_ms);
 
 /* ---- plans: device-resident batch pipelines -------------------------------- */
 typedef struct ssq_stft_plan ssq_stft_plan;

@@ -52,6 +52,11 @@ Supported subset (anything else raises ValueError naming the option):
     project's: DESIGN 4.12, csrc/cwt_sst2.hip): the conventions of `ssq_cwt` (ndarray scales of the three grids,
     `ssq_freqs` None / a string / an array, maprange 'peak' / 'maximal', 'sum' / 'lebesgue', the five padtypes, `flipud`,
     batches) for the order-0 'gmw' and 'morlet' wavelets; its `Tx` inverts through `issq_cwt` like a first-order one;
+  * `reassign_cwt`: the reassigned scalogram (Auger and Flandrin 1995, III), which upstream does not have (the definition
+    is this project's: DESIGN 4.15, csrc/cwt_reassign.hip): every coefficient's energy |Wx|^2 moves along frequency and
+    time at once, to its instantaneous frequency and group delay (first order); the conventions of `ssq_cwt2` without
+    row weights and `squeezing`; real, non-negative, energy-conserving, accumulated by 64-bit integer atomic adds in
+    fixed point (`reassign_cwt_quantum_log2`); no inverse;
   * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
     serial backward trace (`parallel` is accepted and ignored).
 dtype: float64 in -> complex128 (upstream's 'float64'); float32 in -> complex64 (upstream's default 'float32').
@@ -917,6 +922,96 @@ def ssq_cwt2(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None,
     out = [Tx if batched else Tx[0], Wx if batched else Wx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]
     if get_w:
         out.append(w2 if batched else w2[0])
+    return tuple(out)
+
+
+REASSIGN_CWT_QUANTUM_LOG2_MAX = 38      # csrc/cwt_reassign.hip: kCwtRQuantumBitsMax
+REASSIGN_CWT_MAX_CELLS = 1 << 40        # na * N of one signal
+
+
+def reassign_cwt_quantum_log2(na, N):
+    """log2 of `reassign_cwt`'s quantum relative to Pmax, the smallest power of two >= the signal's max |Wx|^2:
+    -min(38, 62 - L) with L = ceil(log2(na N)).  A contribution is at most 2^min(38, 62 - L) quanta and a cell takes at
+    most na N <= 2^L of them, so a cell stays below 2^62."""
+    cells = int(na) * int(N)
+    if cells < 1:
+        raise ValueError("`na` and `N` must be positive")
+    L = (cells - 1).bit_length()
+    return -min(REASSIGN_CWT_QUANTUM_LOG2_MAX, 62 - L)
+
+
+def reassign_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, ssq_freqs=None, padtype="reflect",
+                 maprange="peak", gamma=None, flipud=True, get_w=False, get_tau=False, get_targets=False):
+    """Reassigned scalogram -> (Rx, Wx, ssq_freqs, scales[, w][, tau][, kk, mm]); not in upstream (Auger and Flandrin
+    1995, III), conventions of `ssq_cwt2`.  Where `ssq_cwt` / `ssq_cwt2` move CWT coefficients along frequency, this
+    moves every coefficient's ENERGY |Wx|^2 along frequency and time at once, to its instantaneous frequency and its
+    group delay: a click's cone, which widens with scale in the scalogram and in both synchrosqueezed CWTs, collapses
+    onto the click's own column, and a sweep sharpens as under `ssq_cwt`.
+
+    Per sample, with P, n1, n2 = p2up(N), xh, xi_k, T0 and T1 those of `ssq_cwt2`, in fp64 for either dtype:
+        W = F^-1[xh T0]     W1 = F^-1[xh i xi T0]     Wt = F^-1[xh (-i) T1]        (columns n1 .. n1 + N - 1)
+        w   = |Im(W1 / W)| / (2 pi dt)                     (`ssq_cwt`'s first-order frequency)
+        tau = clamp(Re(Wt / W), -N, N) dt                  (the group-delay offset, seconds; t0 - b for an impulse at t0)
+    each rounded once to the call's dtype; a bin is kept unless |W| < gamma (default 10 eps of the dtype), and `w`
+    (get_w=True) and `tau` (get_tau=True) are +inf where it is not.  The targets come from the reported maps, in their
+    dtype:
+        k' = `ssqueeze`'s bin rule on w, on the `ssq_freqs` grid ('log', 'linear', 'log-piecewise'), flipped by `flipud`
+        m' = clip(j + rint(tau / dt), 0, N - 1)
+        Rx[k', m'] += |Wx[i, j]|^2                         (of the reported Wx, formed in fp64; no row weights)
+    `kk`, `mm` (get_targets=True) are the int32 maps of k' and m', -1 where a bin is not kept.
+
+    First order only, on purpose, for `reassign_stft`'s reason: (b + tau, w) is the centroid of the signal's smoothed
+    Wigner distribution (here the affine smoothing by the wavelet's), which lies ON the line of a linear chirp, so there
+    is no chirp-rate bias to remove; the second-order operators of `ssq_cwt2` (a frequency at the column's time) and its
+    time counterpart (a time at the row's frequency) do not compose: the pair is off the line.
+
+    `Rx` is real and non-negative, in the call's real dtype, and conserves energy: sum(Rx) = sum of |Wx|^2 over the kept
+    bins.  It is accumulated by 64-bit integer atomic adds in device memory, in fixed point with the quantum
+    q = Pmax 2^`reassign_cwt_quantum_log2(na, N)`, Pmax the smallest power of two >= the signal's max |Wx|^2: every
+    contribution is rounded to a multiple of q, and the integer adds commute, so a cell's bits depend neither on the
+    order of the adds, nor on the chunking, nor on the batch.  A signal of zeros gives an all-zero `Rx`; so does one with
+    a non-finite sample (its `Wx`, `w` and `tau` are NaN and no energy is defined).  `Wx` equals `ssq_cwt2`'s.  There is
+    no inverse (the phase is gone).
+
+    Built: what `ssq_cwt2` builds (wavelets 'gmw' order 0 and 'morlet'; an ndarray `scales` of any of the three grids;
+    `ssq_freqs` None, a string or an array; maprange 'peak' / 'maximal'; the five padtypes; 1-D or batched 2-D `x`) with
+    na N <= 2^40.  Anything else raises ValueError before any GPU work."""
+    lib = _lib.load()
+    xa, batched, code = _signal(x)
+    batch, N = xa.shape
+    if N < 2:
+        raise ValueError("`x` must hold at least 2 samples")
+    dt = _dt(fs, t, N)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError("`fs` / `t` must give a positive sampling period")
+    wcode, p0, p1 = _wavelet(wavelet)
+    if not p0 > 0 or (wcode == WAVELET["gmw"] and not p1 > 0):
+        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
+    if isinstance(scales, np.ndarray) and scales.dtype.kind in "fiu" and not (np.isfinite(scales).all() and (scales > 0).all()):
+        raise ValueError("`scales` must be positive and finite")
+    s, _, f_asc, scaletype, f_idx = _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt)
+    if not np.isfinite(f_asc).all():
+        raise ValueError("`ssq_freqs` must be finite")
+    if gamma is not None and math.isnan(float(gamma)):
+        raise ValueError("`gamma` is NaN")
+    pad = _pad_code(padtype)
+    if lib.ssq_reassign_cwt_workspace_bytes(code, batch, N, len(s), None) < 0:       # the C entry's shape checks (no GPU)
+        raise ValueError(lib.ssq_last_error().decode("utf-8", "replace"))
+    _lib.require_gpu()
+    shape = (batch, len(s), N)
+    cdt, rdt = _cdtype(code), _rdtype(code)
+    Rx, Wx = _lib.pinned_empty(shape, rdt), _lib.pinned_empty(shape, cdt)
+    w = _lib.pinned_empty(shape, rdt) if get_w else None
+    tau = _lib.pinned_empty(shape, rdt) if get_tau else None
+    kk, mm = (_lib.pinned_empty(shape, np.int32) for _ in range(2)) if get_targets else (None, None)
+    _call(lib.ssq_reassign_cwt_host(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, _ptr(f_asc),
+                                    FREQS[scaletype], f_idx or 0, pad, -1.0 if gamma is None else float(gamma),
+                                    VARIANT_FLIPUD if flipud else 0, 0, _ptr(Rx), _ptr(Wx), _ptr(w), _ptr(tau), _ptr(kk),
+                                    _ptr(mm)))
+    out = [Rx if batched else Rx[0], Wx if batched else Wx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]
+    for a in (w, tau, kk, mm):
+        if a is not None:
+            out.append(a if batched else a[0])
     return tuple(out)
 
 
