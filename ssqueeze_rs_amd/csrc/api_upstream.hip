@@ -78,17 +78,6 @@ __global__ void issq_colsum_batch_kernel(const cpx<T>* __restrict__ Tx_all, long
   x[j] = (T)(acc * scale);
 }
 
-// signals of `per_signal` device bytes each that fit beside `fixed` bytes: most of the free memory, at most `cap`
-long long slice_signals(long long batch, double per_signal, double fixed, long long cap) {
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)1 << 30;
-  double room = 0.8 * (double)free_b - fixed;
-  long long s = room > per_signal ? (long long)(room / per_signal) : 1;      // one signal is always tried: hipMalloc reports the rest
-  if (s > cap) s = cap;
-  if (s > batch) s = batch;
-  return s < 1 ? 1 : s;
-}
-
 // the three kernels of one signal on device buffers: d_Z [n_frames][n], d_work fft_work_elems(n, n_frames) elements
 template <typename T>
 hipError_t istft_three_dev(const cpx<T>* d_S, int64_t n_frames, const double* d_wp, const double* d_wn, int64_t n, int64_t hop,
@@ -188,15 +177,6 @@ int issq_batch_typed(const void* Tx, int64_t batch, int64_t rows, int64_t cols, 
   return 0;
 }
 
-// the two timing events of ssq_istft_batch_exec, released on every path
-struct TimingEvents {
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~TimingEvents() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
-};
-
 // The inverse of a batch that already lives on the device (d_Sx, d_x), by the path asked for; the kernels' own time
 // (HIP events around the launches, tables and workspace set up before) goes to *kernel_ms when it is not NULL.
 template <typename T>
@@ -207,7 +187,6 @@ int istft_batch_exec_typed(const void* d_Sx, int64_t batch, int64_t n_frames, co
   const cpx<T>* d_S = (const cpx<T>*)d_Sx;
   T* d_x = (T*)d_x_out;
   HostCallBufs d;
-  TimingEvents t;
   void *d_wp, *d_wn, *d_tw = nullptr, *d_Z = nullptr, *d_work = nullptr;
   SSQ_HIP(d.upload(&d_wp, wpow.data(), sizeof(double) * n));
   SSQ_HIP(d.upload(&d_wn, wnorm.data(), sizeof(double) * n));
@@ -219,30 +198,20 @@ int istft_batch_exec_typed(const void* d_Sx, int64_t batch, int64_t n_frames, co
     SSQ_HIP(d.alloc(&d_Z, sizeof(cpx<T>) * n * n_frames));
     SSQ_HIP(d.alloc(&d_work, sizeof(cpx<T>) * (we > 0 ? we : 1)));
   }
-  if (kernel_ms) {
-    SSQ_HIP(hipEventCreate(&t.ev0));
-    SSQ_HIP(hipEventCreate(&t.ev1));
-    SSQ_HIP(hipEventRecord(t.ev0, nullptr));
-  }
-  if (fused) {
-    for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
-      const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
-      SSQ_HIP(launch_istft_fused<T>(pl, d_S + b0 * nf * n_frames, nb, N, modulated, (const cpx<T>*)d_tw, (const double*)d_wp,
-                                    (const double*)d_wn, d_x + b0 * N, nullptr));
+  return run_timed(kernel_ms, false, [&](hipEvent_t) -> int {
+    if (fused) {
+      for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+        const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
+        SSQ_HIP(launch_istft_fused<T>(pl, d_S + b0 * nf * n_frames, nb, N, modulated, (const cpx<T>*)d_tw, (const double*)d_wp,
+                                      (const double*)d_wn, d_x + b0 * N, nullptr));
+      }
+    } else {
+      for (int64_t b = 0; b < batch; ++b)
+        SSQ_HIP(istft_three_dev<T>(d_S + b * nf * n_frames, n_frames, (const double*)d_wp, (const double*)d_wn, n, hop, N,
+                                   modulated, (cpx<T>*)d_Z, (cpx<T>*)d_work, d_x + b * N));
     }
-  } else {
-    for (int64_t b = 0; b < batch; ++b)
-      SSQ_HIP(istft_three_dev<T>(d_S + b * nf * n_frames, n_frames, (const double*)d_wp, (const double*)d_wn, n, hop, N,
-                                 modulated, (cpx<T>*)d_Z, (cpx<T>*)d_work, d_x + b * N));
-  }
-  if (kernel_ms) {
-    SSQ_HIP(hipEventRecord(t.ev1, nullptr));
-    SSQ_HIP(hipEventSynchronize(t.ev1));
-    SSQ_HIP(hipEventElapsedTime(kernel_ms, t.ev0, t.ev1));
-  } else {
-    SSQ_HIP(hipDeviceSynchronize());
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // The argument checks the three ssq_istft_* entry points share, in their order (batch: 1 for the single-signal form)

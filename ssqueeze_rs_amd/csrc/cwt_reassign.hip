@@ -10,9 +10,9 @@
 //   m'  = clip(j + rint(tau / dt), 0, N - 1) in the call's dtype
 //   Rx[k', m'] += |Wx[i, j]|^2              of the REPORTED Wx, formed in fp64; no row weights
 //
-//   cwt_reassign_pad_kernel, cwt_reassign_spectra_kernel : COPIES of cwt_sst2.hip's two (so that ssq_cwt2's machine code
-//                              stays what it is) with three product spectra a row instead of five; the transforms
-//                              between them are fft_any_batched's.
+//   cwt_pad_kernel (cwt_pad.h), cwt_reassign_spectra_kernel : cwt_sst2.hip's first two steps, the second with three
+//                              product spectra a row instead of five; the transforms between them are
+//                              fft_any_batched's.
 //   cwt_reassign_operator_kernel : one thread per (row, column), lanes along time: the three values, 1 / P, 1 / |W|^2
 //                              once; Wx, optionally w and tau, and the two int32 targets (k', m'; -1 where the bin is
 //                              not kept), formed from the values AS ROUNDED to the call's dtype.  It also reduces
@@ -31,34 +31,21 @@
 // Transforms and operator run in fp64 for float32 calls too (the decision of DESIGN 4.11 and 4.12, taken over).  A row is
 // transformed on its own by every kernel, so its result depends neither on the chunk it is in nor on the batch.
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 #include "../../include/ssq_hip.h"
+#include "bin_rule.h"
+#include "cwt_pad.h"
 #include "cwt_sst2_wavelets.h"
 #include "dev_buffers.h"
 #include "fft_generic.h"
 #include "host_math.h"
-#include "pad_index.h"
 
 namespace ssq {
 
 constexpr int kCwtRThreads = 256;
-constexpr int kCwtRMaxGridY = 65535;
 constexpr int kCwtRMaps = 3;                                  // W, W1, Wt
 constexpr int kCwtRQuantumBitsMax = 38;                       // upstream.REASSIGN_CWT_QUANTUM_LOG2_MAX
-
-// xh[b][m] = (x[b][pad_index(m - n1)], 0) in fp64, m < P.  grid (ceil(P / 256), min(batch, 65535))
-template <typename O>
-__global__ __launch_bounds__(kCwtRThreads) void cwt_reassign_pad_kernel(const O* __restrict__ x, cpx<double>* __restrict__ xh,
-                                                                        long long batch, long long N, long long P,
-                                                                        long long n1, int padtype) {
-  const long long m = (long long)blockIdx.x * kCwtRThreads + threadIdx.x;
-  if (m >= P) return;
-  const long long src = pad_index(padtype, m - n1, N);
-  for (long long b = blockIdx.y; b < batch; b += gridDim.y)
-    xh[b * P + m] = {src >= 0 ? (double)x[b * N + src] : 0.0, 0.0};
-}
 
 struct CwtRSpecDev {
   const cpx<double>* xh;     // [batch][P]: the forward DFTs
@@ -95,45 +82,6 @@ __global__ __launch_bounds__(kCwtRThreads) void cwt_reassign_spectra_kernel(cons
   }
 }
 
-// ssqueeze.hip's BinRule / bin_of, COPIED (ssqueeze.hip keeps its object code): the bin rule of algos.py for a finite w,
-// clamped round-half-even on 'log' / 'linear' frequencies, the two-segment map on 'log-piecewise' ones; NaN lands in row 0
-template <typename T>
-struct CwtRBinRule {
-  T bin_min, bin_step;       // log2 f[0], log2 f[1] - log2 f[0]  (linear: f[0], f[1] - f[0])
-  T vlmin1, dvl1;            // log-piecewise: the second segment
-  int idx1;
-  int kind;                  // SSQ_FREQS_*
-  int omax;                  // rows - 1
-  int flipud;
-};
-
-template <typename T>
-__device__ __forceinline__ int cwt_reassign_bin_of(const CwtRBinRule<T>& r, T w) {
-  int bin;
-  if (r.kind == SSQ_FREQS_LOG_PIECEWISE) {
-    const T wl = log2(w);
-    T v;
-    if (wl > r.vlmin1) v = rint((wl - r.vlmin1) / r.dvl1) + (T)r.idx1;
-    else v = rint(fmax((wl - r.bin_min) / r.bin_step, (T)0));
-    bin = (v >= (T)r.omax) ? r.omax : (v == v ? (int)v : 0);
-  } else {
-    const T v = fmax(((r.kind == SSQ_FREQS_LOG ? log2(w) : w) - r.bin_min) / r.bin_step, (T)0);
-    bin = (v >= (T)r.omax) ? r.omax : (int)rint(v);
-    if (!(v == v)) bin = 0;
-  }
-  return r.flipud ? (r.omax - bin) : bin;
-}
-
-// |Wx|^2 of a REPORTED coefficient in fp64: the one expression the operator's maximum and the scatter use, so that no
-// contribution of the scatter exceeds the maximum the operator kernel reduced
-template <typename O>
-__device__ __forceinline__ double cwt_reassign_energy(cpx<O> S) {
-  const double a = (double)S.x, b = (double)S.y;
-  return fma(a, a, b * b);
-}
-
-__device__ __forceinline__ double cwt_reassign_clamp(double d, double h) { return d < -h ? -h : (d > h ? h : d); }   // keeps a NaN
-
 template <typename O>
 struct CwtROpDev {
   const cpx<double>* maps;   // [rows][3][P]: the unnormalised inverse transforms
@@ -147,7 +95,7 @@ struct CwtROpDev {
   int na;
   double inv_P, gamma, inv_two_pi_dt, dt;
   O dt_o;                    // dt in the call's dtype: the time rule runs on the tau the call reports
-  CwtRBinRule<O> rule;       // the bin rule runs on the w the call reports
+  BinRule<O> rule;           // the bin rule (bin_rule.h) runs on the w the call reports
 };
 
 // max over the workgroup of a non-negative value, then one integer atomic max on its bit pattern (non-negative doubles
@@ -196,8 +144,8 @@ __global__ __launch_bounds__(kCwtRThreads) void cwt_reassign_operator_kernel(con
     int kk = -1, mm = -1;
     if (keep) {
       w = (O)(fabs(im1) * p.inv_two_pi_dt);
-      tau = (O)(cwt_reassign_clamp(re_t, (T)p.N) * p.dt);
-      kk = isinf(w) ? -1 : cwt_reassign_bin_of(p.rule, w);
+      tau = (O)(clamp_keep_nan(re_t, (T)p.N) * p.dt);
+      kk = isinf(w) ? -1 : bin_of(p.rule, w);
       // the time rule on the reported tau.  |tau / dt| <= N (1 + eps), the offset being clamped; the bound below only
       // keeps the quotient of an extreme dt inside the integer
       const O vt = tau / p.dt_o;
@@ -214,15 +162,9 @@ __global__ __launch_bounds__(kCwtRThreads) void cwt_reassign_operator_kernel(con
     if (p.tau) p.tau[o] = kk < 0 ? (O)INFINITY : tau;
     p.kk[o] = kk;
     p.mm[o] = mm;
-    mx = fmax(mx, cwt_reassign_energy<O>(Wo));                                // (a NaN is not a maximum)
+    mx = fmax(mx, energy_f64<O>(Wo));                                // (a NaN is not a maximum)
   }
   if (b_cur >= 0) cwt_reassign_flush_max(mx, red, p.emax + b_cur);
-}
-
-// round-to-nearest-even of 0 <= v <= 2^50 as an integer (stft_fused_kernel.h's to_fixed: one fp64 add, one subtract)
-__device__ __forceinline__ long long cwt_reassign_to_fixed(double v) {
-  constexpr double kMagic = 6755399441055744.0;
-  return __double_as_longlong(v + kMagic) - __double_as_longlong(kMagic);
 }
 
 // the signal's scale: Pmax = the smallest power of two >= max |Wx|^2, quantum q = Pmax 2^-qbits (exponent clamped so
@@ -269,9 +211,9 @@ __global__ __launch_bounds__(kCwtRThreads) void cwt_reassign_scatter_kernel(cons
       if (kk < 0) continue;
       const int mm = p.mm[base + i];
       if (kk >= p.na || mm < 0 || mm >= p.N) continue;                    // (never: the operator kernel clips both)
-      const double e = cwt_reassign_energy<O>(p.Wx[base + i]);
+      const double e = energy_f64<O>(p.Wx[base + i]);
       if (!(e == e)) continue;                                            // a NaN coefficient carries no energy
-      const long long f = cwt_reassign_to_fixed(fmin(e * inv_q, cap));    // <= 2^qbits quanta
+      const long long f = to_fixed_f64(fmin(e * inv_q, cap));    // <= 2^qbits quanta
       atomicAdd(p.acc + base + (long long)kk * p.N + mm, (unsigned long long)f);
     }
   }
@@ -360,44 +302,12 @@ int cwtr_check(int dtype, int64_t batch, int64_t N, int wavelet, double p0, doub
   return 0;
 }
 
-// ssqueeze.hip's bin_rule, copied with the struct: algos.py:341-370 and :84-90 in fp64
-template <typename T>
-void cwtr_bin_rule(const double* f, int64_t rows, int kind, int64_t idx, int flipud, CwtRBinRule<T>& r) {
-  std::memset(&r, 0, sizeof(r));
-  const bool lg = kind != SSQ_FREQS_LINEAR;
-  const double vmin = lg ? std::log2(f[0]) : f[0];
-  double dv = lg ? std::log2(f[1]) - std::log2(f[0]) : f[1] - f[0];
-  if (kind == SSQ_FREQS_LOG_PIECEWISE) {
-    r.idx1 = (int)idx - 1;
-    r.vlmin1 = (T)std::log2(f[idx - 1]);
-    r.dvl1 = (T)std::max(std::log2(f[idx]) - std::log2(f[idx - 1]), 2.220446049250313e-16);
-    dv = std::max(dv, 2.220446049250313e-16);
-  }
-  r.bin_min = (T)vmin;
-  r.bin_step = (T)dv;
-  r.kind = kind;
-  r.omax = (int)rows - 1;
-  r.flipud = flipud ? 1 : 0;
-}
-
 struct CwtRCall {
   int dtype, wavelet, freq_kind, padtype, variant;
   int64_t batch, N, na, freq_transition;
   double p0, p1, dt;
   const double *scales, *f_asc;
 };
-
-struct CwtREvents {
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  ~CwtREvents() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
-inline dim3 cwtr_grid(int64_t cols, int64_t rows) {
-  return dim3((unsigned)((cols + kCwtRThreads - 1) / kCwtRThreads), (unsigned)std::min<int64_t>(rows, kCwtRMaxGridY));
-}
 
 // The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the rows per chunk.  d_w, d_tau, d_kk, d_mm may
 // be nullptr (the targets then live in the workspace alone).  Synchronous.  kernel_ms: two floats, all kernels and the
@@ -406,13 +316,10 @@ template <typename T>
 int cwtr_run(const CwtRCall& c, const CwtRShape& s, const void* d_x, void* d_Rx, void* d_Wx, void* d_w, void* d_tau,
              void* d_kk, void* d_mm, void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
   HostCallBufs d;
-  CwtREvents t;
+  TimingEvents t;
   void* d_scales = nullptr;
   SSQ_HIP(d.upload(&d_scales, c.scales, sizeof(double) * (size_t)c.na));
-  if (kernel_ms) {
-    for (hipEvent_t& e : t.ev) SSQ_HIP(hipEventCreate(&e));
-    SSQ_HIP(hipEventRecord(t.ev[0], st));
-  }
+  if (kernel_ms) SSQ_HIP(t.start(4, st));
   const int64_t P = s.P;
   int64_t R = (work_bytes - s.fixed_bytes - 16 * P * c.batch) / (16 * P * 2 * kCwtRMaps);
   if (R > s.rows) R = s.rows;
@@ -425,10 +332,7 @@ int cwtr_run(const CwtRCall& c, const CwtRShape& s, const void* d_x, void* d_Rx,
   cpx<double>* spec = xh + c.batch * P;                        // [R][3][P]
   cpx<double>* pong = spec + R * kCwtRMaps * P;                // [R][3][P]
   SSQ_HIP(hipMemsetAsync(head, 0, (size_t)(cwtr_emax_bytes(c.batch) + 8 * c.batch * s.plane), st));
-  hipLaunchKernelGGL((cwt_reassign_pad_kernel<T>), cwtr_grid(P, c.batch), dim3(kCwtRThreads), 0, st,
-                     static_cast<const T*>(d_x), xh, (long long)c.batch, (long long)c.N, (long long)P, (long long)s.n1,
-                     c.padtype);
-  SSQ_HIP(hipGetLastError());
+  SSQ_HIP(cwt_pad<T>(static_cast<const T*>(d_x), xh, c.batch, c.N, P, s.n1, c.padtype, st));
   const int64_t fb = 2 * kCwtRMaps * R;                        // signals per forward call: the chunk area is its ping-pong
   for (int64_t b0 = 0; b0 < c.batch; b0 += fb)
     SSQ_HIP(fft_any_batched<double>(xh + b0 * P, spec, P, std::min<int64_t>(fb, c.batch - b0), -1, st));
@@ -451,12 +355,13 @@ int cwtr_run(const CwtRCall& c, const CwtRShape& s, const void* d_x, void* d_Rx,
   op.inv_two_pi_dt = 1.0 / (6.283185307179586 * c.dt);
   op.dt = c.dt;
   op.dt_o = (T)c.dt;
-  cwtr_bin_rule<T>(c.f_asc, c.na, c.freq_kind, c.freq_transition, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, op.rule);
+  if (int rc = bin_rule<T>(c.f_asc, c.na, c.freq_kind, c.freq_transition, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, op.rule))
+    return rc;                                                 // (cwtr_check has made each of its checks already)
   for (int64_t r0 = 0; r0 < s.rows; r0 += R) {
     const int64_t nr = std::min<int64_t>(R, s.rows - r0);
     sp.r0 = r0;
     sp.rows = nr;
-    hipLaunchKernelGGL(cwt_reassign_spectra_kernel, cwtr_grid(P, nr), dim3(kCwtRThreads), 0, st, sp);
+    hipLaunchKernelGGL(cwt_reassign_spectra_kernel, cwt_rows_grid(P, nr), dim3(kCwtRThreads), 0, st, sp);
     SSQ_HIP(hipGetLastError());
     SSQ_HIP(fft_any_batched<double>(spec, pong, P, kCwtRMaps * nr, +1, st));
     op.Wx = static_cast<cpx<T>*>(d_Wx) + r0 * c.N;
@@ -466,7 +371,7 @@ int cwtr_run(const CwtRCall& c, const CwtRShape& s, const void* d_x, void* d_Rx,
     op.mm = mm + r0 * c.N;
     op.r0 = r0;
     op.rows = nr;
-    hipLaunchKernelGGL((cwt_reassign_operator_kernel<T>), cwtr_grid(c.N, nr), dim3(kCwtRThreads), 0, st, op);
+    hipLaunchKernelGGL((cwt_reassign_operator_kernel<T>), cwt_rows_grid(c.N, nr), dim3(kCwtRThreads), 0, st, op);
     SSQ_HIP(hipGetLastError());
   }
   CwtRScatDev<T> sc{};
@@ -482,7 +387,7 @@ int cwtr_run(const CwtRCall& c, const CwtRShape& s, const void* d_x, void* d_Rx,
   sc.na = (int)c.na;
   sc.qbits = s.qbits;
   const dim3 grid((unsigned)std::min<int64_t>((s.plane + kCwtRThreads - 1) / kCwtRThreads, 0x7fffffffLL),
-                  (unsigned)std::min<int64_t>(c.batch, kCwtRMaxGridY));
+                  (unsigned)std::min<int64_t>(c.batch, 65535));
   if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
   hipLaunchKernelGGL((cwt_reassign_scatter_kernel<T>), grid, dim3(kCwtRThreads), 0, st, sc);
   SSQ_HIP(hipGetLastError());

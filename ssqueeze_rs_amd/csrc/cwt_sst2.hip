@@ -8,8 +8,8 @@
 //   w2 = |Im om2| / (2 pi dt) where |D| > gamma^2 and Im om2 is finite, else |Im om1| / (2 pi dt) (ssq_cwt's w);
 //   +inf where |W| < gamma (phase_one's rule, ssqueeze.hip).
 // A self-contained pipeline beside the tuned CWT plan (api_cwt.hip and its kernels are not involved):
-//   cwt2_pad_kernel       pads (pad_index.h, no padded real copy) and widens the signals to complex fp64; the forward
-//                         DFT is fft_any_batched's.
+//   cwt_pad_kernel        (cwt_pad.h) pads and widens the signals to complex fp64; the forward DFT is
+//                         fft_any_batched's.
 //   cwt2_spectra_kernel   for a chunk of (signal, scale) rows: T0, T1 in fp64 in the kernel and the five product spectra
 //                         into the workspace, one thread per bin k, coalesced along k, zeros above P/2.
 //   (fft_any_batched)     the 5 x rows inverse transforms of the chunk: the generic streaming passes, not the tile FFTs
@@ -25,29 +25,16 @@
 #include <vector>
 
 #include "../../include/ssq_hip.h"
+#include "cwt_pad.h"
 #include "cwt_sst2_wavelets.h"
 #include "dev_buffers.h"
 #include "fft_generic.h"
 #include "host_math.h"
-#include "pad_index.h"
 
 namespace ssq {
 
 constexpr int kCwt2Threads = 256;
-constexpr int kCwt2MaxGridY = 65535;
 constexpr int kCwt2Maps = 5;                                  // W, W1, W2, Wt, Wt1
-
-// xh[b][m] = (x[b][pad_index(m - n1)], 0) in fp64, m < P.  grid (ceil(P / 256), min(batch, 65535))
-template <typename O>
-__global__ __launch_bounds__(kCwt2Threads) void cwt2_pad_kernel(const O* __restrict__ x, cpx<double>* __restrict__ xh,
-                                                                long long batch, long long N, long long P, long long n1,
-                                                                int padtype) {
-  const long long m = (long long)blockIdx.x * kCwt2Threads + threadIdx.x;
-  if (m >= P) return;
-  const long long src = pad_index(padtype, m - n1, N);
-  for (long long b = blockIdx.y; b < batch; b += gridDim.y)
-    xh[b * P + m] = {src >= 0 ? (double)x[b * N + src] : 0.0, 0.0};
-}
 
 struct Cwt2SpecDev {
   const cpx<double>* xh;     // [batch][P]: the forward DFTs
@@ -194,44 +181,26 @@ struct Cwt2Call {
   const double *scales, *row_const, *f_asc;
 };
 
-struct Cwt2Events {
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~Cwt2Events() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
-};
-
-inline dim3 cwt2_grid(int64_t cols, int64_t rows) {
-  return dim3((unsigned)((cols + kCwt2Threads - 1) / kCwt2Threads), (unsigned)std::min<int64_t>(rows, kCwt2MaxGridY));
-}
-
 // The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the rows per chunk.  Synchronous.
 template <typename T>
 int cwt2_run(const Cwt2Call& c, const Cwt2Shape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_w2, void* d_work,
              int64_t work_bytes, hipStream_t st, float* kernel_ms) {
   HostCallBufs d;
-  Cwt2Events t;
+  TimingEvents t;
   void *d_scales = nullptr, *d_rc = nullptr;
   SSQ_HIP(d.upload(&d_scales, c.scales, sizeof(double) * (size_t)c.na));
   {
     const std::vector<T> rc(c.row_const, c.row_const + c.na);
     SSQ_HIP(d.upload(&d_rc, rc.data(), sizeof(T) * (size_t)c.na));
   }
-  if (kernel_ms) {
-    SSQ_HIP(hipEventCreate(&t.ev0));
-    SSQ_HIP(hipEventCreate(&t.ev1));
-    SSQ_HIP(hipEventRecord(t.ev0, st));
-  }
+  if (kernel_ms) SSQ_HIP(t.start(2, st));
   const int64_t P = s.P;
   int64_t R = (work_bytes - 16 * P * c.batch) / (16 * P * 2 * kCwt2Maps);
   if (R > s.rows) R = s.rows;
   cpx<double>* xh = static_cast<cpx<double>*>(d_work);
   cpx<double>* spec = xh + c.batch * P;                        // [R][5][P]
   cpx<double>* pong = spec + R * kCwt2Maps * P;                // [R][5][P]
-  hipLaunchKernelGGL((cwt2_pad_kernel<T>), cwt2_grid(P, c.batch), dim3(kCwt2Threads), 0, st, static_cast<const T*>(d_x), xh,
-                     (long long)c.batch, (long long)c.N, (long long)P, (long long)s.n1, c.padtype);
-  SSQ_HIP(hipGetLastError());
+  SSQ_HIP(cwt_pad<T>(static_cast<const T*>(d_x), xh, c.batch, c.N, P, s.n1, c.padtype, st));
   const int64_t fb = 2 * kCwt2Maps * R;                        // signals per forward call: the chunk area is its ping-pong
   for (int64_t b0 = 0; b0 < c.batch; b0 += fb)
     SSQ_HIP(fft_any_batched<double>(xh + b0 * P, spec, P, std::min<int64_t>(fb, c.batch - b0), -1, st));
@@ -255,22 +224,22 @@ int cwt2_run(const Cwt2Call& c, const Cwt2Shape& s, const void* d_x, void* d_Tx,
     const int64_t nr = std::min<int64_t>(R, s.rows - r0);
     sp.r0 = r0;
     sp.rows = nr;
-    hipLaunchKernelGGL(cwt2_spectra_kernel, cwt2_grid(P, nr), dim3(kCwt2Threads), 0, st, sp);
+    hipLaunchKernelGGL(cwt2_spectra_kernel, cwt_rows_grid(P, nr), dim3(kCwt2Threads), 0, st, sp);
     SSQ_HIP(hipGetLastError());
     SSQ_HIP(fft_any_batched<double>(spec, pong, P, kCwt2Maps * nr, +1, st));
     op.Wx = static_cast<cpx<T>*>(d_Wx) + r0 * c.N;
     op.w2 = static_cast<T*>(d_w2) + r0 * c.N;
     op.rows = nr;
-    hipLaunchKernelGGL((cwt2_operator_kernel<T>), cwt2_grid(c.N, nr), dim3(kCwt2Threads), 0, st, op);
+    hipLaunchKernelGGL((cwt2_operator_kernel<T>), cwt_rows_grid(c.N, nr), dim3(kCwt2Threads), 0, st, op);
     SSQ_HIP(hipGetLastError());
   }
   if (int rc = ssq_ssqueeze_w_exec(c.dtype, d_Wx, d_w2, c.batch, c.na, c.N, d_rc, c.f_asc, c.freq_kind, c.freq_transition,
                                    c.squeezing, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, d_Tx, st))
     return rc;
   if (kernel_ms) {
-    SSQ_HIP(hipEventRecord(t.ev1, st));
-    SSQ_HIP(hipEventSynchronize(t.ev1));
-    SSQ_HIP(hipEventElapsedTime(kernel_ms, t.ev0, t.ev1));
+    SSQ_HIP(hipEventRecord(t.ev[1], st));
+    SSQ_HIP(hipEventSynchronize(t.ev[1]));
+    SSQ_HIP(hipEventElapsedTime(kernel_ms, t.ev[0], t.ev[1]));
   }
   SSQ_HIP(hipStreamSynchronize(st));                           // (the tables above are freed on return)
   return 0;

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <string>
 
+#include "fft_passes.h"   // num_passes, pass_radix, pass_ns
+
 namespace ssq {
 
 // ---------------------------------------------------------------- errors ----
@@ -177,15 +179,22 @@ __host__ __device__ __forceinline__ void dft_strided(cpx<T> (&v)[16]) {
   }
 }
 
-// ----------------------------------------------------------- pass tables ----
-// N = 2^LOGN points handled by L = N/16 threads holding E = 16 elements each
-// (thread t owns elements t + L*q).  Radix list: 16,16,..., then the remainder.
-__host__ __device__ constexpr int num_passes(int logn) { return (logn + 3) / 4; }
-__host__ __device__ constexpr int pass_radix(int logn, int p) {
-  return (p < logn / 4) ? 16 : (1 << (logn % 4));
+// -------------------------------------------- small fp64 device helpers ----
+__device__ __forceinline__ double clamp_keep_nan(double d, double h) { return d < -h ? -h : (d > h ? h : d); }
+
+// |S|^2 of a REPORTED coefficient in fp64: the one expression a kernel that reduces the maximum and the scatter that
+// scales by it both use, so that no contribution of the scatter exceeds the maximum the other reduced
+template <typename O>
+__device__ __forceinline__ double energy_f64(cpx<O> S) {
+  const double a = (double)S.x, b = (double)S.y;
+  return fma(a, a, b * b);
 }
-__host__ __device__ constexpr int pass_ns(int logn, int p) {   // product of earlier radices
-  return 1 << (4 * p);
+
+// round-to-nearest-even of |v| <= 2^50 as an integer: adding 1.5 * 2^52 leaves it in the low mantissa bits -- one fp64
+// add and one 64-bit subtract instead of the ~18-instruction f64 -> i64 conversion (there is no native one)
+__device__ __forceinline__ long long to_fixed_f64(double v) {
+  constexpr double kMagic = 6755399441055744.0;
+  return __double_as_longlong(v + kMagic) - __double_as_longlong(kMagic);
 }
 
 }  // namespace ssq

@@ -112,12 +112,7 @@ __device__ __forceinline__ T from_int(std::conditional_t<sizeof(T) == 4, int, lo
 template <typename T>
 __device__ __forceinline__ std::conditional_t<sizeof(T) == 4, int, long long> to_fixed(T v) {
   if constexpr (sizeof(T) == 4) return cvt_round_i32(v);      // floor(v + 1/2): one instruction
-  else {
-    // |v| <= 2^50 (FRAC): adding 1.5 * 2^52 leaves round-to-nearest-even(v) in the low mantissa bits -- one fp64 add and
-    // one 64-bit subtract instead of the ~18-instruction f64 -> i64 conversion (there is no native one)
-    constexpr double kMagic = 6755399441055744.0;
-    return __double_as_longlong(v + kMagic) - __double_as_longlong(kMagic);
-  }
+  else return to_fixed_f64(v);                                // |v| <= 2^50 (FRAC)
 }
 // the way back for |i| < 2^51: exact
 template <typename T>

@@ -11,7 +11,7 @@
 //   Rx[k', m'] += |Sx[k, m]|^2                   of the REPORTED Sx, formed in fp64
 //
 //   reassign_operator_kernel : stft_tsst.hip's frame ownership, loader, packed fp64 transforms, split and LDS transpose
-//                              (a COPY, so that tssq_stft's and ssq_stft2's machine code stay what they are): TWO
+//                              (the shared pieces are stft_frames64.h's): TWO
 //                              transforms a frame, x (g + i g1) and x tg; both operators per bin; Sx, optionally w and tau,
 //                              and one packed 4-byte target per bin (int16 r = m' - m, kReassignNone where the bin is not
 //                              kept, above uint16 k') out along frames.  It also reduces max |Sx|^2 per signal: a
@@ -30,14 +30,11 @@
 
 #include "../../include/ssq_hip.h"
 #include "dev_buffers.h"
-#include "fft_core.h"
-#include "host_math.h"
-#include "stft_kernels.h"
+#include "sst_tables.h"
+#include "stft_frames64.h"
 
 namespace ssq {
 
-constexpr int kReassignThreads = 256;
-constexpr int kReassignRoundsPerTile = 4;      // store tiles one workgroup of the operator kernel walks
 constexpr int kReassignNone = -32768;          // the relative time target of a bin that is not kept
 constexpr int kReassignQuantumLog2 = -38;      // q = P 2^-38 (upstream.REASSIGN_QUANTUM_LOG2)
 constexpr int kReassignScatterThreads = 1024;
@@ -62,7 +59,7 @@ struct ReassignOut {
 
 template <typename O>
 struct ReassignDev {
-  const double* x;             // [batch][n_signal], widened by reassign_widen_kernel for a float32 call
+  const double* x;             // [batch][n_signal], widened (widen_f64) for a float32 call
   const cpx<double>* tw;       // the passes' twiddle tables, passes 1, 2, .. back to back
   const cpx<double>* wa;       // (g, g1 a1)      a*: powers of two that level the channels
   const double* wb;            // tg at
@@ -72,56 +69,6 @@ struct ReassignDev {
   double gamma;
   double h1, it;               // 0.5 / a1, 1 / at
 };
-
-template <int LOGN>
-struct ReassignCfg {
-  static constexpr int N = 1 << LOGN, L = N / 16, FPR = kReassignThreads / L, ROW = N + N / 16, F = N / 2 + 1;
-  static constexpr bool MULTI = L > 64;
-  static constexpr int TFS = FPR, SP = TFS >= 8 ? TFS + 1 : TFS;
-};
-
-__device__ __forceinline__ int reassign_opaque_zero() {
-  int z;
-  asm volatile("s_mov_b32 %0, 0" : "=s"(z));
-  return z;
-}
-
-// The 16 samples of a lane (stft_sst2.hip's loader: an edge frame goes through the pad index map in a rolled loop)
-template <typename O, int LOGN>
-__device__ __forceinline__ void reassign_samples(const ReassignDev<O>& p, const double* __restrict__ xs, long long pos0,
-                                                 int t, bool valid, bool interior, double* row, double (&xv)[16]) {
-  constexpr int N = 1 << LOGN, L = N / 16;
-  if (interior) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) xv[q] = xs[pos0 + ((t + L * q + p.rot) & (N - 1))];
-  } else {
-#pragma unroll 1
-    for (int q = 0; q < 16; ++q)
-      row[t + L * q] = load_padded_flat(xs, pos0 + ((t + L * q + p.rot) & (N - 1)), p.n_signal, p.padtype, valid);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) xv[q] = row[t + L * q];
-  }
-}
-
-// Z = A + i B of two real-input spectra -> A[k] h_a, B[k] h_b for the lane's bins t + L q, q <= 8
-template <typename T, int LOGN, bool MULTI>
-__device__ __forceinline__ void reassign_split(const cpx<T> (&v)[16], cpx<T>* exch, int t, T h_a, T h_b, cpx<T> (&A)[9],
-                                               cpx<T> (&B)[9]) {
-  constexpr int N = 1 << LOGN, L = N / 16;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) exch[exch_phys(t + L * q)] = v[q];
-  frame_sync<MULTI>();
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    const int idx = t + L * q;
-    const cpx<T> zp = exch[exch_phys((N - idx) & (N - 1))];
-    A[q] = {(v[q].x + zp.x) * h_a, (v[q].y - zp.y) * h_a};
-    B[q] = {(v[q].y + zp.y) * h_b, (zp.x - v[q].x) * h_b};
-  }
-  frame_sync<MULTI>();
-}
-
-__device__ __forceinline__ double reassign_clamp(double d, double h) { return d < -h ? -h : (d > h ? h : d); }   // keeps a NaN
 
 // both first-order operators of one bin, per sample: (|k/n - Im(V1/V)/(2 pi)|, clamp(Re(Vt/V))), or (inf, inf) where the
 // bin is not kept
@@ -134,27 +81,19 @@ __device__ __forceinline__ cpx<double> reassign_operator(const ReassignDev<O>& p
   const T re1 = eta - (V1.y * V.x - V1.x * V.y) / (den * two_pi);          // ssq_stft2's Re w1
   const T d1 = (Vt.x * V.x + Vt.y * V.y) / den;                            // tssq_stft's order-1 offset
   const bool keep = hypot(V.x, V.y) > p.gamma;
-  return {keep ? fabs(re1) : (T)INFINITY, keep ? reassign_clamp(d1, half) : (T)INFINITY};
-}
-
-// |Sx|^2 of a REPORTED coefficient in fp64: the one expression both kernels use, so that no contribution of the scatter
-// exceeds the maximum the operator kernel reduced
-template <typename O>
-__device__ __forceinline__ double reassign_energy(cpx<O> S) {
-  const double a = (double)S.x, b = (double)S.y;
-  return fma(a, a, b * b);
+  return {keep ? fabs(re1) : (T)INFINITY, keep ? clamp_keep_nan(d1, half) : (T)INFINITY};
 }
 
 template <typename O, int LOGN>
-__global__ __launch_bounds__(kReassignThreads) void reassign_operator_kernel(const ReassignDev<O> p) {
+__global__ __launch_bounds__(kFrameThreads) void reassign_operator_kernel(const ReassignDev<O> p) {
   using T = double;
-  using C = ReassignCfg<LOGN>;
+  using C = FrameCfg<LOGN>;
   constexpr int N = C::N, L = C::L, FPR = C::FPR, ROW = C::ROW, F = C::F, TFS = C::TFS, SP = C::SP;
   constexpr bool MULTI = C::MULTI;
   __shared__ __attribute__((aligned(16))) cpx<T> exch_all[FPR * ROW];
   __shared__ __attribute__((aligned(16))) cpx<T> st_s[F * SP];
   __shared__ __attribute__((aligned(16))) cpx<T> st_m[F * SP];      // V1, then (|Re w1| or inf, offset or inf)
-  __shared__ T mx_s[kReassignThreads];                              // every lane's own running max |Sx|^2
+  __shared__ T mx_s[kFrameThreads];                              // every lane's own running max |Sx|^2
 
   const int tid = threadIdx.x;
   int g = tid / L;                                         // frame slot of the round
@@ -174,19 +113,19 @@ __global__ __launch_bounds__(kReassignThreads) void reassign_operator_kernel(con
       const int f = fr0 + g;
       const bool valid = f < f_end;                                      // (a frame past the end transforms zeros)
       const long long pos0 = (long long)f * p.hop - N / 2;              // the larger half of the n - 1 pad samples on the left
-      const T* __restrict__ xs = p.x + (b + reassign_opaque_zero()) * p.n_signal;   // (formed per round, not held)
+      const T* __restrict__ xs = p.x + (b + opaque_zero()) * p.n_signal;   // (formed per round, not held)
       const bool interior = valid && pos0 >= 0 && pos0 + N <= p.n_signal;
       T xv[16];
-      reassign_samples<O, LOGN>(p, xs, pos0, t + reassign_opaque_zero(), valid, interior, reinterpret_cast<T*>(exch), xv);
+      frame_samples<LOGN>(p, xs, pos0, t + opaque_zero(), valid, interior, reinterpret_cast<T*>(exch), xv);
       frame_sync<MULTI>();      // (an edge frame's samples went through the row: all read before the first exchange writes it)
       const int slot = g;
       cpx<T> v[16];
-      // Two transforms, with stft_sst2.hip's opaque offsets and scheduling barriers (the loop-invariant table loads stay
+      // Two transforms, with stft_frames64.h's opaque offsets and stft_sst2.hip's scheduling barriers (the loop-invariant table loads stay
       // where they are used): (g, g1) first, V into the store tile and V1 parked in the lane's own map slots (the lane
       // reads back what it wrote: no ordering point); tg alone (real input: its spectrum is the transform itself).
       {
         cpx<T> V[9], V1[9];
-        const int z = reassign_opaque_zero(), tz = t + z;
+        const int z = opaque_zero(), tz = t + z;
         const cpx<T>* __restrict__ wa = p.wa + z;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
@@ -194,7 +133,7 @@ __global__ __launch_bounds__(kReassignThreads) void reassign_operator_kernel(con
           v[q] = {xv[q] * w.x, xv[q] * w.y};
         }
         fft_pass_compact<T, LOGN, 0, MULTI>(v, exch, p.tw + z, tz);
-        reassign_split<T, LOGN, MULTI>(v, exch, tz, (T)0.5, p.h1, V, V1);
+        frame_split<T, LOGN, MULTI>(v, exch, tz, (T)0.5, p.h1, V, V1);
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
           const int k = tz + L * q;
@@ -206,14 +145,14 @@ __global__ __launch_bounds__(kReassignThreads) void reassign_operator_kernel(con
       }
       __builtin_amdgcn_sched_barrier(0);
       {
-        const int z = reassign_opaque_zero(), tz = t + z;
+        const int z = opaque_zero(), tz = t + z;
         const T* __restrict__ wb = p.wb + z;
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = {xv[q] * wb[(tz + L * q + p.rot) & (N - 1)], (T)0};
         fft_pass_compact<T, LOGN, 0, MULTI>(v, exch, p.tw + z, tz);
       }
       __builtin_amdgcn_sched_barrier(0);
-      const int te = t + reassign_opaque_zero();
+      const int te = t + opaque_zero();
 #pragma unroll
       for (int q = 0; q < 9; ++q) {
         const int k = te + L * q;
@@ -225,7 +164,7 @@ __global__ __launch_bounds__(kReassignThreads) void reassign_operator_kernel(con
     }
     __syncthreads();
     // the outputs' addresses are fetched and formed here, so that no pointer is held across the transforms
-    const ReassignOut<O> po = p.out[reassign_opaque_zero()];
+    const ReassignOut<O> po = p.out[opaque_zero()];
     const long long ob = b * (long long)F * nfr;
     cpx<O>* __restrict__ Sx = po.Sx + ob;
     O* __restrict__ w_out = po.w ? po.w + ob : nullptr;
@@ -233,14 +172,14 @@ __global__ __launch_bounds__(kReassignThreads) void reassign_operator_kernel(con
     unsigned* __restrict__ tgt_out = po.tgt + ob;
     const int nft = f_end - fr0 < TFS ? f_end - fr0 : TFS;
     T mx = mx_s[tid];
-    for (int e = tid; e < F * TFS; e += kReassignThreads) {              // neighbouring lanes: neighbouring frames of a bin
+    for (int e = tid; e < F * TFS; e += kFrameThreads) {              // neighbouring lanes: neighbouring frames of a bin
       const int k = e / TFS, fl = e % TFS;
       if (fl < nft) {
         const long long m = (long long)fr0 + fl, o = (long long)k * nfr + m;
         const cpx<T> S = st_s[k * SP + fl];
         const cpx<O> So = {(O)S.x, (O)S.y};
         Sx[o] = So;
-        mx = fmax(mx, reassign_energy<O>(So));
+        mx = fmax(mx, energy_f64<O>(So));
         const cpx<T> M = st_m[k * SP + fl];
         O w = (O)INFINITY, tau = (O)INFINITY;
         unsigned pk = (unsigned)(kReassignNone & 0xffff) << 16;
@@ -270,19 +209,14 @@ __global__ __launch_bounds__(kReassignThreads) void reassign_operator_kernel(con
   }
   // max |Sx|^2 of the workgroup's bins, then one integer atomic max on the bit pattern (non-negative doubles order as
   // their bit patterns do; max is order-independent)
-  for (int s = kReassignThreads / 2; s > 0; s >>= 1) {
+  for (int s = kFrameThreads / 2; s > 0; s >>= 1) {
     if (tid < s) mx_s[tid] = fmax(mx_s[tid], mx_s[tid + s]);
     __syncthreads();
   }
   if (tid == 0) {
-    const ReassignOut<O> po = p.out[reassign_opaque_zero()];
+    const ReassignOut<O> po = p.out[opaque_zero()];
     atomicMax(po.emax + b, (unsigned long long)__double_as_longlong(mx_s[0]));
   }
-}
-
-__global__ void reassign_widen_kernel(const float* __restrict__ in, double* __restrict__ out, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (double)in[i];
 }
 
 template <typename O>
@@ -294,12 +228,6 @@ struct ReassignScat {
   long long n_frames;
   int n_freqs, reach, tile;          // reach = H; n_freqs * tile <= kReassignCells
 };
-
-// round-to-nearest-even of 0 <= v <= 2^50 as an integer (stft_fused_kernel.h's to_fixed: one fp64 add, one subtract)
-__device__ __forceinline__ long long reassign_to_fixed(double v) {
-  constexpr double kMagic = 6755399441055744.0;
-  return __double_as_longlong(v + kMagic) - __double_as_longlong(kMagic);
-}
 
 template <typename O>
 __global__ __launch_bounds__(kReassignScatterThreads) void reassign_scatter_kernel(const ReassignScat<O> p) {
@@ -336,8 +264,8 @@ __global__ __launch_bounds__(kReassignScatterThreads) void reassign_scatter_kern
       const long long mt = s0 + i + r;
       const int kk = (int)(pk & 0xffffu);
       if (r != kReassignNone && mt >= t0 && mt < t1 && kk < F) {
-        const double e = fmin(reassign_energy<O>(p.Sx[o]) * inv_q, 274877906944.0);      // <= 2^38 quanta
-        atomicAdd(&reassign_cells[kk * T + (int)(mt - t0)], (unsigned long long)reassign_to_fixed(e));
+        const double e = fmin(energy_f64<O>(p.Sx[o]) * inv_q, 274877906944.0);      // <= 2^38 quanta
+        atomicAdd(&reassign_cells[kk * T + (int)(mt - t0)], (unsigned long long)to_fixed_f64(e));
       }
       k += dk;
       i += di;
@@ -363,30 +291,15 @@ __global__ __launch_bounds__(kReassignScatterThreads) void reassign_scatter_kern
   }
 }
 
-template <typename T, int LOGN>
-static hipError_t reassign_launch_one(ReassignDev<T> p, long long batch, hipStream_t stream) {
-  p.tile_frames = ReassignCfg<LOGN>::TFS * kReassignRoundsPerTile;
-  const long long tiles = (p.n_frames + p.tile_frames - 1) / p.tile_frames;
-  if (tiles > 0x7fffffffLL || batch > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((reassign_operator_kernel<T, LOGN>), dim3((unsigned)tiles, (unsigned)batch), dim3(kReassignThreads), 0,
-                     stream, p);
-  return hipGetLastError();
-}
-
 template <typename T>
-static hipError_t reassign_launch(const ReassignDev<T>& p, int logn, long long batch, hipStream_t stream) {
-  switch (logn) {
-    case 4: return reassign_launch_one<T, 4>(p, batch, stream);
-    case 5: return reassign_launch_one<T, 5>(p, batch, stream);
-    case 6: return reassign_launch_one<T, 6>(p, batch, stream);
-    case 7: return reassign_launch_one<T, 7>(p, batch, stream);
-    case 8: return reassign_launch_one<T, 8>(p, batch, stream);
-    case 9: return reassign_launch_one<T, 9>(p, batch, stream);
-    case 10: return reassign_launch_one<T, 10>(p, batch, stream);
-    case 11: return reassign_launch_one<T, 11>(p, batch, stream);
-    case 12: return reassign_launch_one<T, 12>(p, batch, stream);
-  }
-  return hipErrorInvalidValue;
+static hipError_t reassign_launch(ReassignDev<T> p, int logn, long long batch, hipStream_t stream) {
+  return dispatch_logn(logn, [&](auto ln) {
+    constexpr int LOGN = decltype(ln)::value;
+    dim3 grid;
+    if (hipError_t e = frame_grid<LOGN>(p.n_frames, batch, &p.tile_frames, &grid); e != hipSuccess) return e;
+    hipLaunchKernelGGL((reassign_operator_kernel<T, LOGN>), grid, dim3(kFrameThreads), 0, stream, p);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace ssq
@@ -395,47 +308,21 @@ using namespace ssq;
 
 namespace {
 
-// a power of two a with a * max|tab| within a factor two of `level` (exact to apply and to undo)
-double reassign_level_scale(const std::vector<double>& tab, double level) {
-  double m = 0;
-  for (double v : tab) m = std::fmax(m, std::fabs(v));
-  if (!(m > 0) || !(level > 0) || !std::isfinite(level / m)) return 1.0;
-  int e = 0;
-  std::frexp(level / m, &e);
-  return std::ldexp(1.0, e - 1);
-}
-
-struct ReassignShape {
-  int logn = 0, reach = 1, tile = 1;
-  int64_t n_freqs = 0, n_frames = 0;
-  double fs = 1.0, gamma = 0.0, dw = 0.0;
+struct ReassignShape : FrameShape {
+  int tile = 1;
+  double dw = 0.0;
 };
 
 // The argument checks of the three entry points, and the shape they work on (sets the error and returns non-zero)
 int reassign_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop, double fs, int padtype,
                    double gamma, ReassignShape* s) {
-  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
-  if (batch < 1) SSQ_FAIL("batch must be >= 1");
-  if (n_fft < 16 || n_fft > 4096 || (n_fft & (n_fft - 1)) != 0)
-    SSQ_FAIL("reassign_stft: n_fft must be a power of two from 16 to 4096");
-  if (n_signal < 1 || hop < 1) SSQ_FAIL("reassign_stft: n_signal and hop must be >= 1");
-  if (hop > 0x7fffffffLL) SSQ_FAIL("reassign_stft: hop does not fit an int");
-  if (padtype < SSQ_PAD_REFLECT || padtype > 4) SSQ_FAIL("reassign_stft: unknown padtype");
-  if (gamma != gamma) SSQ_FAIL("reassign_stft: gamma is NaN");
-  if (!(fs > 0) || !std::isfinite(fs)) SSQ_FAIL("reassign_stft: fs must be positive");
-  s->logn = 0;
-  while ((1LL << s->logn) < n_fft) ++s->logn;
-  s->n_freqs = n_fft / 2 + 1;
-  s->n_frames = (n_signal - 1) / hop + 1;
-  if (s->n_frames > (1LL << 30)) SSQ_FAIL("reassign_stft: too many frames");
-  s->reach = (int)((n_fft / 2 + hop - 1) / hop);              // H = ceil(n / (2 hop)) <= 2048
+  if (int rc = frame_shape("reassign_stft", true, nullptr, dtype, batch, n_signal, n_fft, hop, fs, padtype, gamma, s))
+    return rc;
   // target frames of a scatter workgroup: what kReassignCells accumulators hold of all F rows (1024 ... 7)
   int64_t tile = kReassignCells / s->n_freqs;
   if (tile > kReassignMaxTile) tile = kReassignMaxTile;
   if (tile > s->n_frames) tile = s->n_frames;
   s->tile = (int)tile;
-  s->fs = fs;
-  s->gamma = gamma < 0 ? 10.0 * (dtype == SSQ_F64 ? 2.2204460492503131e-16 : 1.1920928955078125e-07) : gamma;
   const std::vector<double> sfs = host::np_linspace(0.0, 0.5 * fs, s->n_freqs);
   s->dw = sfs[1] - sfs[0];
   return 0;
@@ -445,32 +332,12 @@ int reassign_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, in
 template <typename T>
 int reassign_tables(HostCallBufs& d, const ReassignShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
                     int padtype, int variant, ReassignDev<T>* p, ReassignScat<T>* sc) {
-  const std::vector<double> g(window, window + n);
-  const std::vector<double> g1 = host::diff_window(window, n, true);
-  std::vector<double> tg((size_t)n);
-  for (int64_t j = 0; j < n; ++j) tg[j] = (double)(j - n / 2) * window[j];
-  double mg = 0;
-  for (double v : g) mg = std::fmax(mg, std::fabs(v));
-  const double a1 = reassign_level_scale(g1, mg), at = reassign_level_scale(tg, mg);
-  std::vector<cpx<double>> wa((size_t)n), tw;
-  std::vector<double> wb((size_t)n);
-  for (int64_t j = 0; j < n; ++j) {
-    wa[j] = {g[j], g1[j] * a1};
-    wb[j] = tg[j] * at;
-  }
-  for (int P = 1; P < num_passes(s.logn); ++P) {             // read coalesced by fft_pass_compact
-    const int R = pass_radix(s.logn, P), NS = pass_ns(s.logn, P);
-    for (int m = 0; m < R; ++m)
-      for (int k = 0; k < NS; ++k) {
-        const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)((long long)k * m) /
-                                (long double)((long long)NS * R);
-        tw.push_back({(double)cosl(ang), (double)(-sinl(ang))});
-      }
-  }
+  const host::SstTables t = host::sst_level_tables(window, n, host::kSstFirst);
+  const std::vector<double> tw = host::pass_twiddles(s.logn);
   void *d_tw, *d_wa, *d_wb;
-  SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(cpx<double>) * tw.size()));
-  SSQ_HIP(d.upload(&d_wa, wa.data(), sizeof(cpx<double>) * n));
-  SSQ_HIP(d.upload(&d_wb, wb.data(), sizeof(double) * n));
+  SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(double) * tw.size()));
+  SSQ_HIP(d.upload(&d_wa, t.wa.data(), sizeof(cpx<double>) * n));
+  SSQ_HIP(d.upload(&d_wb, t.wb.data(), sizeof(double) * n));
   *p = ReassignDev<T>{};
   p->tw = (const cpx<double>*)d_tw;
   p->wa = (const cpx<double>*)d_wa;
@@ -481,8 +348,8 @@ int reassign_tables(HostCallBufs& d, const ReassignShape& s, const double* windo
   p->padtype = padtype;
   p->rot = (variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
   p->gamma = s.gamma;
-  p->h1 = 0.5 / a1;
-  p->it = 1.0 / at;
+  p->h1 = t.h1;
+  p->it = t.it;
   *sc = ReassignScat<T>{};
   sc->n_frames = s.n_frames;
   sc->n_freqs = (int)s.n_freqs;
@@ -520,10 +387,7 @@ hipError_t reassign_run(ReassignDev<T> p, ReassignScat<T> sc, const ReassignShap
   if (e != hipSuccess) return e;
   const double* xd;
   if constexpr (sizeof(T) == 4) {
-    const long long n = (long long)nb * p.n_signal;
-    hipLaunchKernelGGL(reassign_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const float*)d_x, d_xd,
-                       n);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = widen_f64((const float*)d_x, d_xd, (long long)nb * p.n_signal, nullptr)) != hipSuccess) return e;
     xd = d_xd;
   } else {
     xd = (const double*)d_x;
@@ -561,15 +425,10 @@ int reassign_host_typed(const ReassignShape& s, const void* x, int64_t batch, in
   ReassignScat<T> sc;
   if (int rc = reassign_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
   const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  // signals per slice: most of the free memory (a signal's result does not depend on the slice it is in)
   const double per = (double)(sizeof(T) == 4 ? 12 : 8) * (double)n_signal + 8.0 +
                      (double)map_sig * (sizeof(cpx<T>) + sizeof(T) + sizeof(unsigned) + (w ? sizeof(T) : 0) +
                                         (tau ? sizeof(T) : 0));
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)1 << 30;
-  int64_t slice = (int64_t)(0.8 * (double)free_b / per);
-  if (slice > batch) slice = batch;
-  if (slice < 1) slice = 1;                                  // one signal is always tried: hipMalloc reports the rest
+  const int64_t slice = slice_signals(batch, per, 0.0, batch);
   void *d_x, *d_Rx, *d_Sx, *d_tgt, *d_emax, *d_w = nullptr, *d_tau = nullptr, *d_xd = nullptr;
   SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)n_signal * slice));
   if (sizeof(T) == 4) SSQ_HIP(d.alloc(&d_xd, sizeof(double) * (size_t)n_signal * slice));
@@ -593,14 +452,6 @@ int reassign_host_typed(const ReassignShape& s, const void* x, int64_t batch, in
   return 0;
 }
 
-struct ReassignEvents {
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  ~ReassignEvents() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
 // the workspace of the device entry point: (float32 calls) the widened signals, the signals' maxima, the packed targets
 int64_t reassign_workspace_xd(int dtype, int64_t batch, int64_t n_signal) {
   return dtype == SSQ_F32 ? 8 * batch * n_signal : 0;
@@ -611,7 +462,6 @@ int reassign_exec_typed(const ReassignShape& s, const void* d_x, int64_t batch, 
                         int64_t n, int64_t hop, int padtype, int variant, void* d_Rx, void* d_Sx, void* d_w, void* d_tau,
                         void* d_work, float* kernel_ms) {
   HostCallBufs d;
-  ReassignEvents t;
   ReassignDev<T> p;
   ReassignScat<T> sc;
   if (int rc = reassign_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
@@ -620,21 +470,10 @@ int reassign_exec_typed(const ReassignShape& s, const void* d_x, int64_t batch, 
   unsigned long long* d_emax = (unsigned long long*)after;
   unsigned* d_tgt = (unsigned*)(after + 8 * batch);
   if (int rc = reassign_out_block<T>(d, s, hop, d_Sx, d_w, d_tau, d_tgt, d_emax, &p)) return rc;
-  if (kernel_ms) {
-    for (hipEvent_t& e : t.ev) SSQ_HIP(hipEventCreate(&e));
-    SSQ_HIP(hipEventRecord(t.ev[0], nullptr));
-  }
-  SSQ_HIP(reassign_run<T>(p, sc, s, (const T*)d_x, batch, (T*)d_Rx, (cpx<T>*)d_Sx, d_tgt, d_emax, d_xd,
-                          kernel_ms ? t.ev[1] : nullptr));
-  if (kernel_ms) {
-    SSQ_HIP(hipEventRecord(t.ev[2], nullptr));
-    SSQ_HIP(hipEventSynchronize(t.ev[2]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[0], t.ev[0], t.ev[1]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[1], t.ev[1], t.ev[2]));
-  } else {
-    SSQ_HIP(hipDeviceSynchronize());
-  }
-  return 0;
+  return run_timed(kernel_ms, true, [&](hipEvent_t mid) -> int {
+    SSQ_HIP(reassign_run<T>(p, sc, s, (const T*)d_x, batch, (T*)d_Rx, (cpx<T>*)d_Sx, d_tgt, d_emax, d_xd, mid));
+    return 0;
+  });
 }
 
 }  // namespace

@@ -9,9 +9,10 @@
 //   r = rint(tau / (hop/fs)) in the call's dtype (0 where not finite)      m' = clip(m + r, 0, n_frames - 1)
 //   Tx[k, m'] += Sx[k, m] exp(-2 pi i ((k (m - m') hop) mod n) / n)         in ascending source frame m
 //
-//   tsst_operator_kernel : stft_sst2.hip's frame ownership and transforms (a COPY, so that ssq_stft2's machine code
-//                          stays what it is): 256 lanes own a tile of consecutive frames, n/16 lanes a frame, three
-//                          packed fp64 transforms for order 2, ONE (x (g + i tg)) for order 1; the time operator per
+//   tsst_operator_kernel : stft_sst2.hip's frame ownership and transforms (the shared pieces are stft_frames64.h's,
+//                          the transform block is written out here in its order): 256 lanes own a tile of
+//                          consecutive frames, n/16 lanes a frame, three packed fp64 transforms for order 2, ONE
+//                          (x (g + i tg)) for order 1; the time operator per
 //                          bin; Sx, tau and the relative target r (int16, kTsstNone where the bin is not kept) out
 //                          through the LDS transpose, so that global stores run along frames.
 //   tsst_scatter_kernel  : a workgroup owns a tile of target frames of one row and stages the int16 targets of the
@@ -27,14 +28,12 @@
 
 #include "../../include/ssq_hip.h"
 #include "dev_buffers.h"
-#include "fft_core.h"
-#include "host_math.h"
-#include "stft_kernels.h"
+#include "sst_tables.h"
+#include "stft_frames64.h"
 
 namespace ssq {
 
-constexpr int kTsstThreads = 256;
-constexpr int kTsstRoundsPerTile = 4;      // store tiles one workgroup of the operator kernel walks
+constexpr int kTsstThreads = 256;          // the scatter kernel's workgroup
 constexpr int kTsstNone = -32768;          // the relative target of a bin that is not kept
 constexpr int kTsstMaxReach = 2048;        // H at n_fft = 4096, hop 1
 constexpr int kTsstMaxTile = 4096;         // target frames of one scatter workgroup
@@ -55,7 +54,7 @@ struct TsstOut {
 
 template <typename O>
 struct TsstDev {
-  const double* x;         // [batch][n_signal], widened by tsst_widen_kernel for a float32 call
+  const double* x;         // [batch][n_signal], widened (widen_f64) for a float32 call
   const cpx<double>* tw;   // the passes' twiddle tables, passes 1, 2, .. back to back
   const cpx<double>* wa;   // order 2: (g, g1 a1); order 1: (g, tg at)      a*: powers of two that level the channels
   const double* wb;        // order 2: tg at
@@ -67,62 +66,12 @@ struct TsstDev {
   double h1, it, ht1, h2;  // 0.5 / a1, 1 / at (order 1: 0.5 / at), 0.5 / at1, 0.5 / a2
 };
 
-template <int LOGN>
-struct TsstCfg {
-  static constexpr int N = 1 << LOGN, L = N / 16, FPR = kTsstThreads / L, ROW = N + N / 16, F = N / 2 + 1;
-  static constexpr bool MULTI = L > 64;
-  static constexpr int TFS = FPR, SP = TFS >= 8 ? TFS + 1 : TFS;
-};
-
-__device__ __forceinline__ int tsst_opaque_zero() {
-  int z;
-  asm volatile("s_mov_b32 %0, 0" : "=s"(z));
-  return z;
-}
-
-// The 16 samples of a lane (stft_sst2.hip's loader: an edge frame goes through the pad index map in a rolled loop)
-template <typename O, int LOGN>
-__device__ __forceinline__ void tsst_samples(const TsstDev<O>& p, const double* __restrict__ xs, long long pos0, int t,
-                                             bool valid, bool interior, double* row, double (&xv)[16]) {
-  constexpr int N = 1 << LOGN, L = N / 16;
-  if (interior) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) xv[q] = xs[pos0 + ((t + L * q + p.rot) & (N - 1))];
-  } else {
-#pragma unroll 1
-    for (int q = 0; q < 16; ++q)
-      row[t + L * q] = load_padded_flat(xs, pos0 + ((t + L * q + p.rot) & (N - 1)), p.n_signal, p.padtype, valid);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) xv[q] = row[t + L * q];
-  }
-}
-
-// Z = A + i B of two real-input spectra -> A[k] h_a, B[k] h_b for the lane's bins t + L q, q <= 8
-template <typename T, int LOGN, bool MULTI>
-__device__ __forceinline__ void tsst_split(const cpx<T> (&v)[16], cpx<T>* exch, int t, T h_a, T h_b, cpx<T> (&A)[9],
-                                           cpx<T> (&B)[9]) {
-  constexpr int N = 1 << LOGN, L = N / 16;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) exch[exch_phys(t + L * q)] = v[q];
-  frame_sync<MULTI>();
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    const int idx = t + L * q;
-    const cpx<T> zp = exch[exch_phys((N - idx) & (N - 1))];
-    A[q] = {(v[q].x + zp.x) * h_a, (v[q].y - zp.y) * h_a};
-    B[q] = {(v[q].y + zp.y) * h_b, (zp.x - v[q].x) * h_b};
-  }
-  frame_sync<MULTI>();
-}
-
-__device__ __forceinline__ double tsst_clamp(double d, double h) { return d < -h ? -h : (d > h ? h : d); }   // keeps a NaN
-
 // first order: the group-delay offset Re(Vt / V) in samples, or +inf where the bin is not kept
 template <typename O>
 __device__ __forceinline__ double tsst_operator1(const TsstDev<O>& p, double half, cpx<double> V, cpx<double> Vt) {
   const double den = V.x * V.x + V.y * V.y;
   const double d1 = (Vt.x * V.x + Vt.y * V.y) / den;
-  return hypot(V.x, V.y) > p.gamma ? tsst_clamp(d1, half) : (double)INFINITY;
+  return hypot(V.x, V.y) > p.gamma ? clamp_keep_nan(d1, half) : (double)INFINITY;
 }
 
 // second order: Re(Vt/V + V1 D / (V num)) where the chirp fit is usable, else the first-order offset
@@ -137,13 +86,13 @@ __device__ __forceinline__ double tsst_operator2(const TsstDev<O>& p, double hal
   const cpx<T> a = cmul(V1, D), b = cmul(V, num);
   const T d2 = d1 + (a.x * b.x + a.y * b.y) / (b.x * b.x + b.y * b.y);     // Re(a / b)
   const bool second = hypot(num.x, num.y) > p.gamma_sq && isfinite(d2) && fabs(d2) <= half;
-  return hypot(V.x, V.y) > p.gamma ? tsst_clamp(second ? d2 : d1, half) : (T)INFINITY;
+  return hypot(V.x, V.y) > p.gamma ? clamp_keep_nan(second ? d2 : d1, half) : (T)INFINITY;
 }
 
 template <typename O, int LOGN, int ORDER>
-__global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstDev<O> p) {
+__global__ __launch_bounds__(kFrameThreads) void tsst_operator_kernel(const TsstDev<O> p) {
   using T = double;
-  using C = TsstCfg<LOGN>;
+  using C = FrameCfg<LOGN>;
   constexpr int N = C::N, L = C::L, FPR = C::FPR, ROW = C::ROW, F = C::F, TFS = C::TFS, SP = C::SP;
   constexpr bool MULTI = C::MULTI;
   __shared__ __attribute__((aligned(16))) cpx<T> exch_all[FPR * ROW];
@@ -166,17 +115,17 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstD
       const int f = fr0 + g;
       const bool valid = f < f_end;                                      // (a frame past the end transforms zeros)
       const long long pos0 = (long long)f * p.hop - N / 2;              // the larger half of the n - 1 pad samples on the left
-      const T* __restrict__ xs = p.x + (b + tsst_opaque_zero()) * p.n_signal;   // (formed per round, not held)
+      const T* __restrict__ xs = p.x + (b + opaque_zero()) * p.n_signal;   // (formed per round, not held)
       const bool interior = valid && pos0 >= 0 && pos0 + N <= p.n_signal;
       T xv[16];
-      tsst_samples<O, LOGN>(p, xs, pos0, t + tsst_opaque_zero(), valid, interior, reinterpret_cast<T*>(exch), xv);
+      frame_samples<LOGN>(p, xs, pos0, t + opaque_zero(), valid, interior, reinterpret_cast<T*>(exch), xv);
       frame_sync<MULTI>();      // (an edge frame's samples went through the row: all read before the first exchange writes it)
       const int slot = g;
       cpx<T> v[16];
       if constexpr (ORDER == 1) {
         // one packed transform x (g + i tg): V and Vt are all the first-order offset needs
         cpx<T> V[9], Vt[9];
-        const int z = tsst_opaque_zero(), tz = t + z;
+        const int z = opaque_zero(), tz = t + z;
         const cpx<T>* __restrict__ wa = p.wa + z;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
@@ -184,7 +133,7 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstD
           v[q] = {xv[q] * w.x, xv[q] * w.y};
         }
         fft_pass_compact<T, LOGN, 0, MULTI>(v, exch, p.tw + z, tz);
-        tsst_split<T, LOGN, MULTI>(v, exch, tz, (T)0.5, p.it, V, Vt);
+        frame_split<T, LOGN, MULTI>(v, exch, tz, (T)0.5, p.it, V, Vt);
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
           const int k = tz + L * q;
@@ -194,13 +143,13 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstD
           }
         }
       } else {
-        // The three transforms of stft_sst2.hip, in its order and with its opaque offsets and scheduling barriers (what
-        // keeps the kernel inside 256 registers): (g, g1) first, V into the store tile and V1 parked in the
-        // lane's own map slots; tg alone; (tg1, g2) last.
+        // The three transforms of stft_sst2.hip, in its order and with its opaque offsets (stft_frames64.h) and
+        // scheduling barriers (what keeps the kernel inside 256 registers): (g, g1) first, V into the store
+        // tile and V1 parked in the lane's own map slots; tg alone; (tg1, g2) last.
         cpx<T> Vt[9], Vt1[9], V2[9];
         {
           cpx<T> V[9], V1[9];
-          const int z = tsst_opaque_zero(), tz = t + z;
+          const int z = opaque_zero(), tz = t + z;
           const cpx<T>* __restrict__ wa = p.wa + z;
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
@@ -208,7 +157,7 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstD
             v[q] = {xv[q] * w.x, xv[q] * w.y};
           }
           fft_pass_compact<T, LOGN, 0, MULTI>(v, exch, p.tw + z, tz);
-          tsst_split<T, LOGN, MULTI>(v, exch, tz, (T)0.5, p.h1, V, V1);
+          frame_split<T, LOGN, MULTI>(v, exch, tz, (T)0.5, p.h1, V, V1);
 #pragma unroll
           for (int q = 0; q < 9; ++q) {
             const int k = tz + L * q;
@@ -220,7 +169,7 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstD
         }
         __builtin_amdgcn_sched_barrier(0);
         {
-          const int z = tsst_opaque_zero(), tz = t + z;
+          const int z = opaque_zero(), tz = t + z;
           const T* __restrict__ wb = p.wb + z;                           // real input: its spectrum is the transform itself
 #pragma unroll
           for (int q = 0; q < 16; ++q) v[q] = {xv[q] * wb[(tz + L * q + p.rot) & (N - 1)], (T)0};
@@ -230,7 +179,7 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstD
         }
         __builtin_amdgcn_sched_barrier(0);
         {
-          const int z = tsst_opaque_zero(), tz = t + z;
+          const int z = opaque_zero(), tz = t + z;
           const cpx<T>* __restrict__ wc = p.wc + z;
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
@@ -238,10 +187,10 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstD
             v[q] = {xv[q] * w.x, xv[q] * w.y};
           }
           fft_pass_compact<T, LOGN, 0, MULTI>(v, exch, p.tw + z, tz);
-          tsst_split<T, LOGN, MULTI>(v, exch, tz, p.ht1, p.h2, Vt1, V2);
+          frame_split<T, LOGN, MULTI>(v, exch, tz, p.ht1, p.h2, Vt1, V2);
         }
         __builtin_amdgcn_sched_barrier(0);
-        const int te = t + tsst_opaque_zero();
+        const int te = t + opaque_zero();
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
           const int k = te + L * q;
@@ -254,13 +203,13 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstD
     }
     __syncthreads();
     // the outputs' addresses are fetched and formed here, so that no pointer is held across the transforms
-    const TsstOut<O> po = p.out[tsst_opaque_zero()];
+    const TsstOut<O> po = p.out[opaque_zero()];
     const long long ob = b * (long long)F * nfr;
     cpx<O>* __restrict__ Sx = po.Sx + ob;
     O* __restrict__ tau_out = po.tau ? po.tau + ob : nullptr;
     short* __restrict__ rel_out = po.rel + ob;
     const int nft = f_end - fr0 < TFS ? f_end - fr0 : TFS;
-    for (int e = tid; e < F * TFS; e += kTsstThreads) {                  // neighbouring lanes: neighbouring frames of a bin
+    for (int e = tid; e < F * TFS; e += kFrameThreads) {                  // neighbouring lanes: neighbouring frames of a bin
       const int k = e / TFS, fl = e % TFS;
       if (fl < nft) {
         const long long m = (long long)fr0 + fl, o = (long long)k * nfr + m;
@@ -286,11 +235,6 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_operator_kernel(const TsstD
     }
     __syncthreads();
   }
-}
-
-__global__ void tsst_widen_kernel(const float* __restrict__ in, double* __restrict__ out, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (double)in[i];
 }
 
 template <typename O>
@@ -384,33 +328,18 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_scatter_kernel(const TsstSc
   }
 }
 
-template <typename T, int LOGN>
-static hipError_t tsst_launch_one(TsstDev<T> p, int order, long long batch, hipStream_t stream) {
-  p.tile_frames = TsstCfg<LOGN>::TFS * kTsstRoundsPerTile;
-  const long long tiles = (p.n_frames + p.tile_frames - 1) / p.tile_frames;
-  if (tiles > 0x7fffffffLL || batch > 65535) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)tiles, (unsigned)batch), block(kTsstThreads);
-  if (order == 1)
-    hipLaunchKernelGGL((tsst_operator_kernel<T, LOGN, 1>), grid, block, 0, stream, p);
-  else
-    hipLaunchKernelGGL((tsst_operator_kernel<T, LOGN, 2>), grid, block, 0, stream, p);
-  return hipGetLastError();
-}
-
 template <typename T>
-static hipError_t tsst_launch(const TsstDev<T>& p, int logn, int order, long long batch, hipStream_t stream) {
-  switch (logn) {
-    case 4: return tsst_launch_one<T, 4>(p, order, batch, stream);
-    case 5: return tsst_launch_one<T, 5>(p, order, batch, stream);
-    case 6: return tsst_launch_one<T, 6>(p, order, batch, stream);
-    case 7: return tsst_launch_one<T, 7>(p, order, batch, stream);
-    case 8: return tsst_launch_one<T, 8>(p, order, batch, stream);
-    case 9: return tsst_launch_one<T, 9>(p, order, batch, stream);
-    case 10: return tsst_launch_one<T, 10>(p, order, batch, stream);
-    case 11: return tsst_launch_one<T, 11>(p, order, batch, stream);
-    case 12: return tsst_launch_one<T, 12>(p, order, batch, stream);
-  }
-  return hipErrorInvalidValue;
+static hipError_t tsst_launch(TsstDev<T> p, int logn, int order, long long batch, hipStream_t stream) {
+  return dispatch_logn(logn, [&](auto ln) {
+    constexpr int LOGN = decltype(ln)::value;
+    dim3 grid;
+    if (hipError_t e = frame_grid<LOGN>(p.n_frames, batch, &p.tile_frames, &grid); e != hipSuccess) return e;
+    if (order == 1)
+      hipLaunchKernelGGL((tsst_operator_kernel<T, LOGN, 1>), grid, dim3(kFrameThreads), 0, stream, p);
+    else
+      hipLaunchKernelGGL((tsst_operator_kernel<T, LOGN, 2>), grid, dim3(kFrameThreads), 0, stream, p);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace ssq
@@ -419,45 +348,18 @@ using namespace ssq;
 
 namespace {
 
-// a power of two a with a * max|tab| within a factor two of `level` (exact to apply and to undo)
-double tsst_level_scale(const std::vector<double>& tab, double level) {
-  double m = 0;
-  for (double v : tab) m = std::fmax(m, std::fabs(v));
-  if (!(m > 0) || !(level > 0) || !std::isfinite(level / m)) return 1.0;
-  int e = 0;
-  std::frexp(level / m, &e);
-  return std::ldexp(1.0, e - 1);
-}
-
-struct TsstShape {
-  int logn = 0, order = 2, reach = 1, tile = 1024;
-  int64_t n_freqs = 0, n_frames = 0;
-  double fs = 1.0, gamma = 0.0;
+struct TsstShape : FrameShape {
+  int order = 2, tile = 1024;
 };
 
 // The argument checks of the three entry points, and the shape they work on (sets the error and returns non-zero)
 int tsst_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop, double fs, int padtype, int order,
                double gamma, TsstShape* s) {
-  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
-  if (batch < 1) SSQ_FAIL("batch must be >= 1");
-  if (n_fft < 16 || n_fft > 4096 || (n_fft & (n_fft - 1)) != 0)
-    SSQ_FAIL("tssq_stft: n_fft must be a power of two from 16 to 4096");
-  if (n_signal < 1 || hop < 1) SSQ_FAIL("tssq_stft: n_signal and hop must be >= 1");
-  if (hop > 0x7fffffffLL) SSQ_FAIL("tssq_stft: hop does not fit an int");
-  if (padtype < SSQ_PAD_REFLECT || padtype > 4) SSQ_FAIL("tssq_stft: unknown padtype");
-  if (order != 1 && order != 2) SSQ_FAIL("tssq_stft: order must be 1 or 2");
-  if (gamma != gamma) SSQ_FAIL("tssq_stft: gamma is NaN");
-  if (!(fs > 0) || !std::isfinite(fs)) SSQ_FAIL("tssq_stft: fs must be positive");
-  s->logn = 0;
-  while ((1LL << s->logn) < n_fft) ++s->logn;
+  if (int rc = frame_shape("tssq_stft", true, order == 1 || order == 2 ? nullptr : "order must be 1 or 2", dtype, batch,
+                           n_signal, n_fft, hop, fs, padtype, gamma, s))
+    return rc;
   s->order = order;
-  s->n_freqs = n_fft / 2 + 1;
-  s->n_frames = (n_signal - 1) / hop + 1;
-  if (s->n_frames > (1LL << 30)) SSQ_FAIL("tssq_stft: too many frames");
-  s->reach = (int)((n_fft / 2 + hop - 1) / hop);              // H = ceil(n / (2 hop)) <= kTsstMaxReach
   s->tile = 2 * s->reach < 1024 ? 1024 : (2 * s->reach + 255) / 256 * 256;   // halo re-read (tile + 2 H) / tile <= 2
-  s->fs = fs;
-  s->gamma = gamma < 0 ? 10.0 * (dtype == SSQ_F64 ? 2.2204460492503131e-16 : 1.1920928955078125e-07) : gamma;
   return 0;
 }
 
@@ -465,42 +367,18 @@ int tsst_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_
 template <typename T>
 int tsst_tables(HostCallBufs& d, const TsstShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
                 int padtype, int variant, TsstDev<T>* p, TsstScat<T>* sc) {
-  const std::vector<double> g(window, window + n);
-  std::vector<double> g1 = host::diff_window(window, n, true);
-  std::vector<double> g2 = host::diff_window(g1.data(), n, true);
-  std::vector<double> tg((size_t)n), tg1((size_t)n);
+  const host::SstTables t = host::sst_level_tables(window, n, s.order == 1 ? host::kSstTimeFirst : host::kSstSecond);
+  const std::vector<double> tw = host::pass_twiddles(s.logn);
+  std::vector<cpx<double>> rot((size_t)n);
   for (int64_t j = 0; j < n; ++j) {
-    const double u = (double)(j - n / 2);
-    tg[j] = u * window[j];
-    tg1[j] = u * g1[j];
-  }
-  double mg = 0;
-  for (double v : g) mg = std::fmax(mg, std::fabs(v));
-  const double a1 = tsst_level_scale(g1, mg), a2 = tsst_level_scale(g2, mg), at = tsst_level_scale(tg, mg),
-               at1 = tsst_level_scale(tg1, mg);
-  std::vector<cpx<double>> wa((size_t)n), wc((size_t)n), tw, rot((size_t)n);
-  std::vector<double> wb((size_t)n);
-  for (int64_t j = 0; j < n; ++j) {
-    wa[j] = s.order == 1 ? cpx<double>{g[j], tg[j] * at} : cpx<double>{g[j], g1[j] * a1};
-    wb[j] = tg[j] * at;
-    wc[j] = {tg1[j] * at1, g2[j] * a2};
     const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)j / (long double)n;
     rot[j] = {(double)cosl(ang), (double)(-sinl(ang))};
   }
-  for (int P = 1; P < num_passes(s.logn); ++P) {             // read coalesced by fft_pass_compact
-    const int R = pass_radix(s.logn, P), NS = pass_ns(s.logn, P);
-    for (int m = 0; m < R; ++m)
-      for (int k = 0; k < NS; ++k) {
-        const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)((long long)k * m) /
-                                (long double)((long long)NS * R);
-        tw.push_back({(double)cosl(ang), (double)(-sinl(ang))});
-      }
-  }
   void *d_tw, *d_wa, *d_wb, *d_wc, *d_rot;
-  SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(cpx<double>) * tw.size()));
-  SSQ_HIP(d.upload(&d_wa, wa.data(), sizeof(cpx<double>) * n));
-  SSQ_HIP(d.upload(&d_wb, wb.data(), sizeof(double) * n));
-  SSQ_HIP(d.upload(&d_wc, wc.data(), sizeof(cpx<double>) * n));
+  SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(double) * tw.size()));
+  SSQ_HIP(d.upload(&d_wa, t.wa.data(), sizeof(cpx<double>) * n));
+  SSQ_HIP(d.upload(&d_wb, t.wb.data(), sizeof(double) * n));
+  SSQ_HIP(d.upload(&d_wc, t.wc.data(), sizeof(cpx<double>) * n));
   SSQ_HIP(d.upload(&d_rot, rot.data(), sizeof(cpx<double>) * n));
   *p = TsstDev<T>{};
   p->tw = (const cpx<double>*)d_tw;
@@ -514,10 +392,10 @@ int tsst_tables(HostCallBufs& d, const TsstShape& s, const double* window, int64
   p->rot = (variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
   p->gamma = s.gamma;
   p->gamma_sq = s.gamma * s.gamma;
-  p->h1 = 0.5 / a1;
-  p->it = s.order == 1 ? 0.5 / at : 1.0 / at;
-  p->ht1 = 0.5 / at1;
-  p->h2 = 0.5 / a2;
+  p->h1 = t.h1;
+  p->it = t.it;
+  p->ht1 = t.ht1;
+  p->h2 = t.h2;
   *sc = TsstScat<T>{};
   sc->rot = (const cpx<double>*)d_rot;
   sc->n_frames = s.n_frames;
@@ -552,9 +430,7 @@ hipError_t tsst_run(TsstDev<T> p, TsstScat<T> sc, const TsstShape& s, const T* d
   hipError_t e;
   const double* xd;
   if constexpr (sizeof(T) == 4) {
-    const long long n = (long long)nb * p.n_signal;
-    hipLaunchKernelGGL(tsst_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const float*)d_x, d_xd, n);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = widen_f64((const float*)d_x, d_xd, (long long)nb * p.n_signal, nullptr)) != hipSuccess) return e;
     xd = d_xd;
   } else {
     xd = (const double*)d_x;
@@ -587,14 +463,9 @@ int tsst_host_typed(const TsstShape& s, const void* x, int64_t batch, int64_t n_
   TsstScat<T> sc;
   if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
   const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  // signals per slice: most of the free memory (a signal's result does not depend on the slice it is in)
   const double per = (double)(sizeof(T) == 4 ? 12 : 8) * (double)n_signal +
                      (double)map_sig * (2.0 * sizeof(cpx<T>) + sizeof(short) + (tau ? sizeof(T) : 0));
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)1 << 30;
-  int64_t slice = (int64_t)(0.8 * (double)free_b / per);
-  if (slice > batch) slice = batch;
-  if (slice < 1) slice = 1;                                  // one signal is always tried: hipMalloc reports the rest
+  const int64_t slice = slice_signals(batch, per, 0.0, batch);
   void *d_x, *d_Tx, *d_Sx, *d_rel, *d_tau = nullptr, *d_xd = nullptr;
   SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)n_signal * slice));
   if (sizeof(T) == 4) SSQ_HIP(d.alloc(&d_xd, sizeof(double) * (size_t)n_signal * slice));
@@ -614,20 +485,11 @@ int tsst_host_typed(const TsstShape& s, const void* x, int64_t batch, int64_t n_
   return 0;
 }
 
-struct TsstEvents {
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  ~TsstEvents() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
 template <typename T>
 int tsst_exec_typed(const TsstShape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
                     int64_t hop, int padtype, int variant, void* d_Tx, void* d_Sx, void* d_tau, void* d_work,
                     float* kernel_ms) {
   HostCallBufs d;
-  TsstEvents t;
   TsstDev<T> p;
   TsstScat<T> sc;
   if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
@@ -635,20 +497,10 @@ int tsst_exec_typed(const TsstShape& s, const void* d_x, int64_t batch, int64_t 
   double* d_xd = (double*)d_work;
   short* d_rel = (short*)((char*)d_work + (sizeof(T) == 4 ? sizeof(double) * (size_t)batch * (size_t)n_signal : 0));
   if (int rc = tsst_out_block<T>(d, s, hop, d_Sx, d_tau, d_rel, &p)) return rc;
-  if (kernel_ms) {
-    for (hipEvent_t& e : t.ev) SSQ_HIP(hipEventCreate(&e));
-    SSQ_HIP(hipEventRecord(t.ev[0], nullptr));
-  }
-  SSQ_HIP(tsst_run<T>(p, sc, s, (const T*)d_x, batch, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, d_rel, d_xd, kernel_ms ? t.ev[1] : nullptr));
-  if (kernel_ms) {
-    SSQ_HIP(hipEventRecord(t.ev[2], nullptr));
-    SSQ_HIP(hipEventSynchronize(t.ev[2]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[0], t.ev[0], t.ev[1]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[1], t.ev[1], t.ev[2]));
-  } else {
-    SSQ_HIP(hipDeviceSynchronize());
-  }
-  return 0;
+  return run_timed(kernel_ms, true, [&](hipEvent_t mid) -> int {
+    SSQ_HIP(tsst_run<T>(p, sc, s, (const T*)d_x, batch, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, d_rel, d_xd, mid));
+    return 0;
+  });
 }
 
 }  // namespace
