@@ -383,6 +383,39 @@ int ssq_reassign_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_s
                           int64_t freq_transition, int padtype, double gamma, int variant, void* d_Rx, void* d_Wx,
                           void* d_w, void* d_tau, void* d_kk, void* d_mm, void* d_workspace, int64_t workspace_bytes,
                           void* stream, float* kernel_ms);
+/* Time-reassigned synchrosqueezed CWT, `upstream.tssq_cwt` (csrc/cwt_tsst.hip; upstream has no such
+ * transform): every complex coefficient moves along TIME inside its own row, to its group delay, rotated so that its
+ * phase refers to the target column.  scales, wavelet, p0, p1, dt, padtype, gamma as ssq_ssq_cwt2_host (gamma < 0: 10 eps
+ * of the dtype, NaN is refused); row_freqs [na]: nu_i = wc / (2 pi scales[i]) cycles/sample in fp64, positive and finite,
+ * the caller's (`upstream.tssq_cwt_row_freqs`); order 1 or 2.  Per-sample, with P, xh, xi_k, T0, T1 and the five maps
+ * W, W1, W2, Wt, Wt1 of ssq_ssq_cwt2_host (order 1 forms W and Wt alone), in fp64 for either dtype:
+ *   d1 = Re(Wt/W);  D = W^2 + Wt1 W - Wt W1;  num = W2 W - W1^2;  d2 = d1 - Im((D/num) (2 pi nu_i + i W1/W));
+ *   off = d2 where order = 2, |num| > gamma^2, d2 is finite and |d2| <= n_signal, else d1; clamped to +- n_signal;
+ *   tau = off dt rounded once to `dtype`, +inf where |W| < gamma;  m' = clip(j + rint(tau / dt), 0, n_signal - 1) in
+ *   `dtype`;  Tx[i][m'] += Wx[i][j] exp(-2 pi i frac(nu_i (j - m'))) (of the reported Wx, in fp64), accumulated by two
+ *   64-bit integer atomic adds in fixed point with the quantum A 2^-S, S = min(38, 61 - ceil(log2 n_signal)), A the
+ *   smallest power of two >= sqrt(Pmax), Pmax the smallest power of two >= the signal's max |Wx|^2: integer adds
+ *   commute, so signal b's result depends neither on `batch`, nor on the chunking, nor on the order.
+ *   na * n_signal <= 2^40.
+ * Tx, Wx: [batch][na][n_signal] complex of `dtype` (Wx: ssq_ssq_cwt2_host's); tau (may be NULL): REAL of `dtype`, seconds
+ * relative to the column's own time; mm (may be NULL): int32, the target m', -1 where a bin is not kept.
+ * Workspace: 16 ceil(batch / 2) + 20 batch na n_signal bytes (to a multiple of 16: the maxima, the accumulators, the
+ * targets), then 16 P (batch + 2 M R) for chunks of R rows, M = 2 (order 1) or 5 (order 2); a row's result does not
+ * depend on R or on the batch.  work_limit_bytes: 0 for the preferred size, else at least min_bytes. */
+int ssq_tssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                      const double* scales, const double* row_freqs, int64_t na, double dt, int padtype, int order,
+                      double gamma, int64_t work_limit_bytes, void* Tx, void* Wx, void* tau, void* mm);
+/* Device bytes of the workspace: returns the preferred size (every row in one chunk, the chunk area capped at 2 GiB) and
+ * stores the least one (one row per chunk) in *min_bytes (may be NULL); computed on the host; -1 on a bad shape. */
+int64_t ssq_tssq_cwt_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int order, int64_t* min_bytes);
+/* The same transform on device buffers: d_x [batch][n_signal], d_Tx, d_Wx (required), d_tau, d_mm (each may be NULL) as
+ * above, d_workspace of workspace_bytes >= min_bytes (its size sets R); scales, row_freqs on the host.  Synchronous on
+ * `stream`.  kernel_ms (may be NULL): THREE floats, the time of all the kernels, of the scatter kernel alone and of
+ * everything before the scatter, from HIP events around the launches. */
+int ssq_tssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                      const double* scales, const double* row_freqs, int64_t na, double dt, int padtype, int order,
+                      double gamma, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm, void* d_workspace,
+                      int64_t workspace_bytes, void* stream, float* kernel_ms);
 
 /* ---- plans: device-resident batch pipelines -------------------------------- */
 typedef struct ssq_stft_plan ssq_stft_plan;

@@ -57,6 +57,11 @@ Supported subset (anything else raises ValueError naming the option):
     time at once, to its instantaneous frequency and group delay (first order); the conventions of `ssq_cwt2` without
     row weights and `squeezing`; real, non-negative, energy-conserving, accumulated by 64-bit integer atomic adds in
     fixed point (`reassign_cwt_quantum_log2`); no inverse;
+  * `tssq_cwt`: the time-reassigned synchrosqueezed CWT (orders 1 and 2), which upstream does not have (the definition
+    is this project's: DESIGN 4.16, csrc/cwt_tsst.hip): every complex coefficient moves along time inside its own row,
+    to its group delay, rotated to keep its phase reference, so clicks and fast sweeps concentrate and add coherently;
+    the conventions of `ssq_cwt2` without `ssq_freqs`, `maprange`, `squeezing`, `flipud` and row weights; accumulated by
+    64-bit integer atomic adds in fixed point (`tssq_cwt_quantum_log2`); no inverse (a per-row marginal identity);
   * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
     serial backward trace (`parallel` is accepted and ignored).
 dtype: float64 in -> complex128 (upstream's 'float64'); float32 in -> complex64 (upstream's default 'float32').
@@ -1010,6 +1015,114 @@ def reassign_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=N
                                     _ptr(mm)))
     out = [Rx if batched else Rx[0], Wx if batched else Wx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]
     for a in (w, tau, kk, mm):
+        if a is not None:
+            out.append(a if batched else a[0])
+    return tuple(out)
+
+
+TSSQ_CWT_QUANTUM_LOG2_MAX = 38          # csrc/cwt_tsst.hip: kCwtTQuantumBitsMax
+TSSQ_CWT_MAX_CELLS = 1 << 40            # na * N of one signal
+TSSQ_CWT_MAX_N = 1 << 26                # samples of one signal (the limit of the `ssq_cwt2` pipeline)
+
+
+def tssq_cwt_quantum_log2(N):
+    """log2 of `tssq_cwt`'s quantum relative to A, the smallest power of two >= sqrt(Pmax), Pmax the smallest power of two
+    >= the signal's max |Wx|^2: -min(38, 61 - ceil(log2 N)).  A part of a contribution is at most 2^min(38, 61 - L)
+    quanta and a cell takes at most N <= 2^L of them (one row), so a cell stays below 2^61."""
+    N = int(N)
+    if N < 1:
+        raise ValueError("`N` must be positive")
+    return -min(TSSQ_CWT_QUANTUM_LOG2_MAX, 61 - (N - 1).bit_length())
+
+
+def tssq_cwt_row_freqs(wavelet, scales):
+    """nu [na] float64, cycles/sample: the frequency of every row of `tssq_cwt`, wc / (2 pi scale) with the wavelet's peak
+    wc = (beta / gamma)^(1 / gamma) for 'gmw' and mu for 'morlet' -- the values the library is given."""
+    wcode, p0, p1 = _wavelet(wavelet)
+    if not (p0 > 0 and math.isfinite(p0)) or (wcode == WAVELET["gmw"] and not (p1 > 0 and math.isfinite(p1))):
+        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
+    s = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
+    if not (np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError("`scales` must be positive and finite")
+    wc = (p1 / p0) ** (1 / p0) if wcode == WAVELET["gmw"] else p0
+    return np.ascontiguousarray(wc / (2 * np.pi * s))
+
+
+def tssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, padtype="reflect", order=2, gamma=None,
+             get_tau=False, get_targets=False, work_limit_bytes=None):
+    """Time-reassigned synchrosqueezed CWT -> (Tx, Wx, scales, row_freqs[, tau][, mm]); not in upstream, conventions of
+    `ssq_cwt2`.  Where `ssq_cwt` / `ssq_cwt2` move CWT coefficients along frequency, this moves every complex coefficient
+    along TIME inside its own row, to its group delay: a click's cone collapses onto the click's column (as under
+    `reassign_cwt`), but the coefficients keep their phase and add coherently, and a fast sweep is put on the column where
+    it crosses each row.
+
+    Per sample, with P, n1, n2 = p2up(N), xh, xi_k, T0, T1 and the five maps those of `ssq_cwt2`, in fp64 for either dtype
+    (order 1 forms W and Wt alone), and nu_i = wc / (2 pi scales[i]) cycles/sample (`tssq_cwt_row_freqs`):
+        d1  = Re(Wt / W)                                   (the group-delay offset; t0 - b for an impulse at t0)
+        D   = W^2 + Wt1 W - Wt W1        num = W2 W - W1^2
+        d2  = d1 - Im((D / num) (2 pi nu_i + i W1 / W))    (the time at which the locally fitted chirp crosses nu_i)
+        off = d2 where order = 2, |num| > gamma^2, d2 is finite and |d2| <= N, else d1; clamped to [-N, N]
+        tau = off dt, rounded once to the call's dtype; +inf where |W| < gamma (default 10 eps of the dtype)
+        m'  = clip(j + rint(tau / dt), 0, N - 1)           in the call's dtype, on the reported tau
+        Tx[i, m'] += Wx[i, j] exp(-2 pi i frac(nu_i (j - m')))       (of the reported Wx, the product in fp64)
+    d2 is exact for a linear chirp under any wavelet (the dual of `ssq_cwt2`'s frequency).  The rotation re-references a
+    coefficient's phase from column j to column m' at the row's frequency; without it an impulse's contributions would
+    sum to psih(0) = 0.  Rows do not mix: `Tx` is [na, N] on the scale rows of `Wx`, and there are no `ssq_freqs`, row
+    weights, `maprange`, `squeezing` or `flipud`.  `row_freqs` is nu / dt in Hz, in the call's real dtype.  `tau`
+    (get_tau=True) is in seconds, +inf where a bin is not kept; `mm` (get_targets=True) is the int32 map of m', -1 there.
+
+    `Tx` is accumulated by 64-bit integer atomic adds in device memory, in fixed point with the quantum
+    q = A 2^`tssq_cwt_quantum_log2(N)`, A the smallest power of two >= sqrt(Pmax), Pmax the smallest power of two >= the
+    signal's max |Wx|^2: both parts of every contribution are rounded to a multiple of q, and the integer adds commute, so
+    a cell's bits depend neither on the order of the adds, nor on the chunking (`work_limit_bytes`), nor on the batch.  A
+    signal of zeros gives an all-zero `Tx`; so does one with a non-finite sample.  `Wx` equals `ssq_cwt2`'s.
+
+    There is no inverse; what stands in for one is a marginal identity per row:
+    sum_m' Tx[i, m'] exp(-2 pi i nu_i m') = sum over the kept j of Wx[i, j] exp(-2 pi i nu_i j).
+
+    Built: wavelets 'gmw' (order 0, bandpass norm) and 'morlet'; an ndarray `scales` of any of the three grids; the five
+    padtypes; orders 1 and 2; 1-D or batched 2-D `x`; N <= 2^26 and na N <= 2^40.  Anything else raises ValueError before
+    any GPU work."""
+    lib = _lib.load()
+    if isinstance(order, (bool, np.bool_)) or order not in (1, 2):
+        raise ValueError(f"order {order!r}: 1 and 2 are built")
+    xa, batched, code = _signal(x)
+    batch, N = xa.shape
+    if N < 2:
+        raise ValueError("`x` must hold at least 2 samples")
+    dt = _dt(fs, t, N)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError("`fs` / `t` must give a positive sampling period")
+    wcode, p0, p1 = _wavelet(wavelet)
+    if not (p0 > 0 and math.isfinite(p0)) or (wcode == WAVELET["gmw"] and not (p1 > 0 and math.isfinite(p1))):
+        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
+    if isinstance(scales, np.ndarray) and scales.dtype.kind in "fiu" and not (np.isfinite(scales).all() and (scales > 0).all()):
+        raise ValueError("`scales` must be positive and finite")
+    s, scaletype, _nv, _ = _scales(scales)
+    if scaletype == "log" and nv is not None and nv != _nv:
+        raise ValueError("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))
+    nu = tssq_cwt_row_freqs(wavelet, s)
+    if not (np.isfinite(nu).all() and (nu > 0).all()):
+        raise ValueError("`scales` give row frequencies that are not positive and finite")
+    if gamma is not None and math.isnan(float(gamma)):
+        raise ValueError("`gamma` is NaN")
+    pad = _pad_code(padtype)
+    mn = C.c_int64(0)
+    if lib.ssq_tssq_cwt_workspace_bytes(code, batch, N, len(s), int(order), C.byref(mn)) < 0:   # the shape checks (no GPU)
+        raise ValueError(lib.ssq_last_error().decode("utf-8", "replace"))
+    limit = 0 if work_limit_bytes is None else int(work_limit_bytes)
+    if work_limit_bytes is not None and limit < mn.value:
+        raise ValueError(f"`work_limit_bytes` must be at least {mn.value} for this shape")
+    _lib.require_gpu()
+    shape = (batch, len(s), N)
+    cdt, rdt = _cdtype(code), _rdtype(code)
+    Tx, Wx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
+    tau = _lib.pinned_empty(shape, rdt) if get_tau else None
+    mm = _lib.pinned_empty(shape, np.int32) if get_targets else None
+    _call(lib.ssq_tssq_cwt_host(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), _ptr(nu), len(s), dt, pad, int(order),
+                                -1.0 if gamma is None else float(gamma), limit, _ptr(Tx), _ptr(Wx), _ptr(tau), _ptr(mm)))
+    out = [Tx if batched else Tx[0], Wx if batched else Wx[0], s.astype(rdt), (nu / dt).astype(rdt)]
+    for a in (tau, mm):
         if a is not None:
             out.append(a if batched else a[0])
     return tuple(out)
