@@ -198,6 +198,40 @@ int64_t ssq_ssq_stft2_workspace_bytes(int dtype, int64_t batch, int64_t n_signal
 int ssq_ssq_stft2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
                        int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, void* d_Tx, void* d_Sx,
                        void* d_w2, void* d_workspace, int64_t workspace_bytes, float* kernel_ms);
+/* Multisynchrosqueezed STFT, `upstream.mssq_stft` (csrc/stft_msst.hip; Yu, Wang and Zhao 2019; upstream has
+ * no such transform): ssq_ssq_stft2_host whose frequency map is asked again at the bin a coefficient landed on, n_iter
+ * steps in all.  Arguments, conventions and the n_fft range of ssq_ssq_stft2_host; order 1 or 2, n_iter 1 .. 64.  Per
+ * column, with F = n_freqs and m[k] the one-step bin of row k -- ssq_ssq_stft2_host's bin rule on the frequency w the
+ * call reports, BEFORE any flip, -1 where |V| <= gamma; order 2: that entry's w2 (with its fallback to w1), order 1:
+ * fs |Re w1| on every bin (the same three transforms run for either order):
+ *   c1[k] = m[k];   c(i+1)[k] = m[ci[k]] if ci[k] >= 0 and m[ci[k]] >= 0, else ci[k]        (i = 1 .. n_iter - 1)
+ *   Tx[r(c_n[k])] += Sx[k] dw (SUM) or dw / F (LEBESGUE) for every kept k, rows ascending, in `dtype`, no atomics;
+ *   r(b) = F - 1 - b with FLIPUD, else b.
+ * A chain stops on a bin without a map of its own and on a fixed point; a cycle turns until n_iter runs out.  n_iter = 1,
+ * order 2 is ssq_ssq_stft2_host bit for bit.  Tx, Sx, ssq_freqs as there; w (may be NULL): the ONE-step frequency map,
+ * REAL of `dtype`, +inf where a bin is not kept; bins (may be NULL): [batch][n_freqs][n_frames] int32, the row of Tx each
+ * coefficient went to (r applied), -1 where it was not kept.  Synchronous, sliced like ssq_ssq_stft2_host. */
+int ssq_mssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                       int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, int order, int n_iter,
+                       void* Tx, double* ssq_freqs, void* Sx, void* w, int32_t* bins);
+/* Device bytes of the workspace ssq_mssq_stft_exec needs (ssq_ssq_stft2_workspace_bytes': the packed map and, for SSQ_F32,
+ * the widened signals), computed on the host; -1 on a shape ssq_mssq_stft_host refuses. */
+int64_t ssq_mssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop);
+/* The same transform on device buffers: d_x [batch][N], d_Tx, d_Sx, d_w and d_bins (each may be NULL) as above,
+ * d_workspace of at least ssq_mssq_stft_workspace_bytes bytes; `window` on the host.  Synchronous.  kernel_ms (may be
+ * NULL): THREE floats, the time of the operator kernel (with the widening of a float32 call), of the walk kernel, and of
+ * clearing Tx with the scatter, from HIP events around the launches with the tables set up before them. */
+int ssq_mssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                       int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, int order, int n_iter,
+                       void* d_Tx, void* d_Sx, void* d_w, int32_t* d_bins, void* d_workspace, int64_t workspace_bytes,
+                       float* kernel_ms);
+/* The walk of ssq_mssq_stft_host alone, on maps the caller holds (the same kernel): bins_in, bins_out
+ * [batch][n_rows][n_cols] int32 on the host, a target indexes the row axis itself, -1: no map.  n_rows 1 .. 2049,
+ * n_iter 1 .. 64; a target outside -1 .. n_rows - 1 is refused on the host.  Synchronous. */
+int ssq_msst_walk_host(const int32_t* bins_in, int64_t batch, int64_t n_rows, int64_t n_cols, int n_iter, int32_t* bins_out);
+/* Columns of the tile one workgroup of the walk kernel holds in LDS for maps of n_rows rows (16 .. 256; host only), -1
+ * outside 1 .. 2049. */
+int ssq_msst_tile_cols(int64_t n_rows);
 /* Time-reassigned synchrosqueezed STFT, `upstream.tssq_stft` (csrc/stft_tsst.hip; He, Tu, Bao, Hu and Zhang
  * 2019; upstream has no such transform): every coefficient moves along TIME to its estimated group delay.  window [n_fft]
  * already sized, padtype SSQ_PAD_*, order 1 or 2, gamma < 0: 10 eps of the dtype (NaN is refused), variant: the

@@ -81,6 +81,13 @@ _SIGNATURES = {
     "ssq_ssq_stft2_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64]),
     "ssq_ssq_stft2_exec": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_double,
                                      C.c_int, vp, vp, vp, vp, i64, C.POINTER(C.c_float)]),
+    "ssq_mssq_stft_host": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_double,
+                                     C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "ssq_mssq_stft_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64]),
+    "ssq_mssq_stft_exec": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_double,
+                                     C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, C.POINTER(C.c_float)]),
+    "ssq_msst_walk_host": (C.c_int, [vp, i64, i64, i64, C.c_int, vp]),
+    "ssq_msst_tile_cols": (C.c_int, [i64]),
     "ssq_tssq_stft_host": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_double,
                                      C.c_int, vp, vp, vp]),
     "ssq_tssq_stft_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64]),

@@ -18,7 +18,8 @@
 //   sst2_scatter_kernel  : one thread per time column, rows ascending (reassign_cols_kernel's order), no atomics:
 //                          the result does not depend on batch size or tiling.
 // The frame ownership, the loader, the split and the tables are stft_frames64.h's and sst_tables.h's, shared with
-// stft_tsst.hip and stft_reassign.hip.
+// stft_tsst.hip and stft_reassign.hip.  stft_msst.hip (mssq_stft) runs both kernels of this file through stft_sst2.h, with
+// its walk between them; its order 1 is gamma_sq = +inf (|D| > gamma_sq nowhere: every bin reports fs |Re w1|).
 #include <cmath>
 #include <vector>
 
@@ -26,27 +27,9 @@
 #include "dev_buffers.h"
 #include "sst_tables.h"
 #include "stft_frames64.h"
+#include "stft_sst2.h"
 
 namespace ssq {
-
-// O: the dtype of the call (float or double: x in, Sx / map / Tx / w2 out).  The transforms and the operator always run
-// in fp64: the operator is a quotient of two differences of products, and with fp32 transforms of 1024 points and more
-// over one strong bin in a thousand lands in another bin than the fp64 result.
-template <typename O>
-struct Sst2Dev {
-  const double* x;         // [batch][n_signal], widened (widen_f64) for a float32 call
-  const cpx<double>* tw;   // the passes' twiddle tables [m][k] = exp(-2 pi i k m / (NS R)), passes 1, 2, .. back to back
-  const cpx<double>* wa;   // (g, g1 a1)          by frame sample j; a*: powers of two that level the channels
-  const double* wb;        // tg at
-  const cpx<double>* wc;   // (tg1 at1, g2 a2)
-  cpx<O>* Sx;              // [batch][F][n_frames]
-  cpx<O>* map;             // [batch][F][n_frames]  (w2 or inf, bin or -1)
-  long long n_signal, n_frames;
-  int hop, pad_left, padtype, rot, flip, tile_frames;
-  double gamma, gamma_sq, fs;
-  O dw;                    // Sfs[1] - Sfs[0] in the call's dtype: the bin rule runs on the w2 the call reports
-  double h1, it, ht1, h2;  // 0.5 / a1, 1 / at, 0.5 / at1, 0.5 / a2
-};
 
 // the operator of one bin in fp64 -> (fs |Re w|, or inf where the bin is not kept; unused)
 template <typename O>
@@ -228,24 +211,12 @@ static hipError_t sst2_launch(Sst2Dev<T> p, int logn, long long batch, hipStream
   });
 }
 
-}  // namespace ssq
-
-using namespace ssq;
-
-namespace {
-
-struct Sst2Shape : FrameShape {
-  double dw = 0.0;
-  std::vector<double> sfs;
-};
-
-// The argument checks of the three entry points, and the shape they work on (sets the error and returns non-zero)
-int sst2_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop, double fs, int padtype, int squeezing,
-               double gamma, Sst2Shape* s) {
+// The argument checks of the entry points, and the shape they work on (sets the error and returns non-zero)
+int sst2_shape(const char* name, const char* own_fail, int dtype, int64_t batch, int64_t n_signal, int64_t n_fft,
+               int64_t hop, double fs, int padtype, int squeezing, double gamma, Sst2Shape* s) {
   const bool sq_ok = squeezing == SSQ_SQUEEZE_SUM || squeezing == SSQ_SQUEEZE_LEBESGUE;
-  if (int rc = frame_shape("ssq_stft2", false, sq_ok ? nullptr : "squeezing must be 'sum' or 'lebesgue'", dtype, batch,
-                           n_signal, n_fft, hop, fs, padtype, gamma, s))
-    return rc;
+  if (!own_fail && !sq_ok) own_fail = "squeezing must be 'sum' or 'lebesgue'";
+  if (int rc = frame_shape(name, false, own_fail, dtype, batch, n_signal, n_fft, hop, fs, padtype, gamma, s)) return rc;
   s->sfs = host::np_linspace(0.0, 0.5 * fs, s->n_freqs);
   s->dw = s->sfs[1] - s->sfs[0];
   return 0;
@@ -285,13 +256,12 @@ int sst2_tables(HostCallBufs& d, const Sst2Shape& s, const double* window, int64
   return 0;
 }
 
-// both kernels of `nb` signals on device buffers (Tx is zeroed here)
+// the operator kernel of `nb` signals on device buffers
 template <typename T>
-hipError_t sst2_run(Sst2Dev<T> p, const Sst2Shape& s, int squeezing, const T* d_x, int64_t nb, cpx<T>* d_Tx, cpx<T>* d_Sx,
-                    T* d_w, cpx<T>* d_map, double* d_xd /* float32 calls: [nb][n_signal] */) {
+hipError_t sst2_operator_run(Sst2Dev<T> p, const Sst2Shape& s, const T* d_x, int64_t nb, cpx<T>* d_Sx, cpx<T>* d_map,
+                             double* d_xd /* float32 calls: [nb][n_signal] */) {
   const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  hipError_t e = hipMemsetAsync(d_Tx, 0, sizeof(cpx<T>) * map_sig * (size_t)nb, nullptr);
-  if (e != hipSuccess) return e;
+  hipError_t e;
   const double* xd;
   if constexpr (sizeof(T) == 4) {
     if ((e = widen_f64((const float*)d_x, d_xd, (long long)nb * p.n_signal, nullptr)) != hipSuccess) return e;
@@ -306,13 +276,49 @@ hipError_t sst2_run(Sst2Dev<T> p, const Sst2Shape& s, int squeezing, const T* d_
     p.map = d_map + map_sig * b0;
     e = sst2_launch<T>(p, s.logn, n1, nullptr);
     if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// Tx zeroed, then the scatter of `nb` signals on device buffers
+template <typename T>
+hipError_t sst2_scatter_run(const Sst2Shape& s, int squeezing, T dw, int64_t nb, const cpx<T>* d_Sx, const cpx<T>* d_map,
+                            cpx<T>* d_Tx, T* d_w) {
+  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
+  hipError_t e = hipMemsetAsync(d_Tx, 0, sizeof(cpx<T>) * map_sig * (size_t)nb, nullptr);
+  if (e != hipSuccess) return e;
+  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
+    const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
     hipLaunchKernelGGL(sst2_scatter_kernel<T>, dim3((unsigned)((s.n_frames + 255) / 256), (unsigned)n1), dim3(256), 0, nullptr,
-                       (const cpx<T>*)p.Sx, (const cpx<T>*)p.map, d_Tx + map_sig * b0, d_w ? d_w + map_sig * b0 : (T*)nullptr,
-                       (int)s.n_freqs, (long long)s.n_frames, squeezing, p.dw, (T)((T)s.dw / (T)s.n_freqs));
+                       d_Sx + map_sig * b0, d_map + map_sig * b0, d_Tx + map_sig * b0, d_w ? d_w + map_sig * b0 : (T*)nullptr,
+                       (int)s.n_freqs, (long long)s.n_frames, squeezing, dw, (T)((T)s.dw / (T)s.n_freqs));
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+#define SSQ_SST2_INSTANTIATE(T)                                                                                          \
+  template int sst2_tables<T>(HostCallBufs&, const Sst2Shape&, const double*, int64_t, int64_t, int64_t, int, int,        \
+                              Sst2Dev<T>*);                                                                              \
+  template hipError_t sst2_operator_run<T>(Sst2Dev<T>, const Sst2Shape&, const T*, int64_t, cpx<T>*, cpx<T>*, double*);   \
+  template hipError_t sst2_scatter_run<T>(const Sst2Shape&, int, T, int64_t, const cpx<T>*, const cpx<T>*, cpx<T>*, T*);
+SSQ_SST2_INSTANTIATE(float)
+SSQ_SST2_INSTANTIATE(double)
+#undef SSQ_SST2_INSTANTIATE
+
+}  // namespace ssq
+
+using namespace ssq;
+
+namespace {
+
+// both kernels of `nb` signals on device buffers (Tx is zeroed here)
+template <typename T>
+hipError_t sst2_run(Sst2Dev<T> p, const Sst2Shape& s, int squeezing, const T* d_x, int64_t nb, cpx<T>* d_Tx, cpx<T>* d_Sx,
+                    T* d_w, cpx<T>* d_map, double* d_xd /* float32 calls: [nb][n_signal] */) {
+  if (hipError_t e = sst2_operator_run<T>(p, s, d_x, nb, d_Sx, d_map, d_xd); e != hipSuccess) return e;
+  return sst2_scatter_run<T>(s, squeezing, p.dw, nb, d_Sx, d_map, d_Tx, d_w);
 }
 
 template <typename T>
@@ -366,7 +372,7 @@ int ssq_ssq_stft2_host(int dtype, const void* x, int64_t batch, int64_t n_signal
                        double* ssq_freqs, void* Sx, void* w2) {
   if (!x || !window || !Tx || !Sx) SSQ_FAIL("NULL argument");
   Sst2Shape s;
-  if (int rc = sst2_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, squeezing, gamma, &s)) return rc;
+  if (int rc = sst2_shape("ssq_stft2", nullptr, dtype, batch, n_signal, n_fft, hop, fs, padtype, squeezing, gamma, &s)) return rc;
   if (ssq_freqs)
     for (int64_t i = 0; i < s.n_freqs; ++i) ssq_freqs[i] = (variant & SSQ_VARIANT_FLIPUD) ? s.sfs[s.n_freqs - 1 - i] : s.sfs[i];
   if (int rc = require_device()) return rc;
@@ -391,7 +397,7 @@ int ssq_ssq_stft2_window_tables(const double* window, int64_t n_fft, double* g1,
 
 int64_t ssq_ssq_stft2_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop) {
   Sst2Shape s;
-  if (sst2_shape(dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, SSQ_SQUEEZE_SUM, -1.0, &s)) return -1;
+  if (sst2_shape("ssq_stft2", nullptr, dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, SSQ_SQUEEZE_SUM, -1.0, &s)) return -1;
   return (int64_t)(dtype == SSQ_F32 ? 8 : 16) * batch * s.n_freqs * s.n_frames + (dtype == SSQ_F32 ? 8 * batch * n_signal : 0);
 }
 
@@ -400,7 +406,7 @@ int ssq_ssq_stft2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_sign
                        void* d_w2, void* d_workspace, int64_t workspace_bytes, float* kernel_ms) {
   if (!d_x || !window || !d_Tx || !d_Sx || !d_workspace) SSQ_FAIL("NULL argument");
   Sst2Shape s;
-  if (int rc = sst2_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, squeezing, gamma, &s)) return rc;
+  if (int rc = sst2_shape("ssq_stft2", nullptr, dtype, batch, n_signal, n_fft, hop, fs, padtype, squeezing, gamma, &s)) return rc;
   if (workspace_bytes < ssq_ssq_stft2_workspace_bytes(dtype, batch, n_signal, n_fft, hop))
     SSQ_FAIL("ssq_stft2: workspace smaller than ssq_ssq_stft2_workspace_bytes");
   if (int rc = require_device()) return rc;

@@ -39,6 +39,11 @@ Supported subset (anything else raises ValueError naming the option):
     project's: DESIGN 4.11, csrc/stft_sst2.hip): the conventions of `ssq_stft` (ndarray window, the five padtypes,
     'sum' / 'lebesgue', `flipud`, `modulated`, batches) with a power-of-two `n_fft` from 16 to 4096; its `Tx` inverts
     through `issq_stft` like a first-order one;
+  * `mssq_stft`: the multisynchrosqueezed STFT (Yu, Wang and Zhao 2019; orders 1 and 2), which upstream does not have
+    (the definition is this project's: DESIGN 4.17, csrc/stft_msst.hip): `ssq_stft2`'s frequency map asked again at the
+    bin a coefficient landed on, `n_iter` steps in all (1 .. 64), which narrows the ridge of a signal whose modulation is
+    not linear inside the window; the conventions of `ssq_stft2`; its `Tx` keeps every column's sum, so it inverts
+    through `issq_stft` like a first-order one; `msst_walk` runs the walk alone on an int32 map the caller holds;
   * `tssq_stft`: the time-reassigned synchrosqueezed STFT (orders 1 and 2), which upstream does not have (the definition
     is this project's: DESIGN 4.13, csrc/stft_tsst.hip): every coefficient moves along time to its group delay, which
     concentrates impulses and fast chirps; the conventions of `ssq_stft2` (ndarray window, the five padtypes,
@@ -416,6 +421,115 @@ def ssq_stft2(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=No
     if get_w:
         out.append(w2 if batched else w2[0])
     return tuple(out)
+
+
+MSST_MAX_ITER = 64                      # csrc/stft_msst.hip: kWalkMaxIter, a bound on work (not a measured number)
+MSST_MAX_ROWS = 2049                    # csrc/stft_msst.hip: kWalkMaxRows, the rows of n_fft = 4096
+
+
+def _n_iter(n_iter):
+    if (not isinstance(n_iter, (int, np.integer)) or isinstance(n_iter, (bool, np.bool_))
+            or not 1 <= n_iter <= MSST_MAX_ITER):
+        raise ValueError(f"n_iter {n_iter!r}: an int from 1 to {MSST_MAX_ITER}")
+    return int(n_iter)
+
+
+def mssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
+              squeezing="sum", gamma=None, flipud=False, order=2, n_iter=4, get_w=False, get_bins=False):
+    """Multisynchrosqueezed STFT -> (Tx, Sx, ssq_freqs, Sfs[, w][, bins]); not in upstream (Yu, Wang and Zhao 2019),
+    conventions of `ssq_stft2`.  Where `ssq_stft2` applies its frequency map once, this asks the map again at the bin a
+    coefficient landed on, `n_iter` steps in all: on a signal whose modulation is not linear inside the window the
+    one-step estimate taken off the ridge is biased, and the estimate taken where it points is closer.
+
+    Per column, with F = n_fft // 2 + 1 rows, let m[k] be the one-step bin of row k: the clamped round-half-even bin of
+    the reported frequency `w` on np.linspace(0, fs / 2, F) (the rule of `ssq_stft2`), taken in the call's dtype from the
+    `w` the call reports and before any `flipud`; m[k] = -1 where the bin is not kept (|V| <= gamma).  `order=2` uses the
+    w2 of `ssq_stft2`, including its fallback to w1 where |D| <= gamma^2; `order=1` uses fs |Re w1| on every bin (it runs
+    the same three transforms as order 2 and costs the same).  The walk:
+        c1[k] = m[k]
+        c(i+1)[k] = m[ci[k]]  if ci[k] >= 0 and m[ci[k]] >= 0,  else ci[k]          (i = 1 .. n_iter - 1)
+    A chain stops on a bin that has no map of its own and on a fixed point; a cycle keeps turning until `n_iter` runs
+    out.  Then, for every kept k, rows ascending inside a column, in the call's dtype and without atomics:
+        Tx[r(c_n[k]), j] += Sx[k, j] dw  ('sum')    or    dw / F  ('lebesgue');        r(b) = F - 1 - b under `flipud`, else b
+    `n_iter=1`, `order=2` is `ssq_stft2` bit for bit.  Coefficients move along frequency only and keep their phase, so
+    every column keeps its sum: `issq_stft`, `extract_ridges` and the component inversion take `Tx` unchanged.
+
+    `Sx` equals `stft(x, ...)`; `w` (get_w=True) is the ONE-step frequency map, +inf where a bin is not kept; `bins`
+    (get_bins=True) is int32: the row of `Tx` each coefficient went to, -1 where it was not kept.  `msst_walk` runs the
+    walk alone on a map the caller holds.
+
+    `n_fft` must be a power of two from 16 to 4096, `order` 1 or 2, `n_iter` an int from 1 to 64 (a bound on work: the
+    model signals of DESIGN 4.17 stopped moving by 32) and `squeezing` 'sum' or 'lebesgue' (ValueError otherwise, before
+    any GPU work).  The walk runs out of LDS, a tile of columns at a time (csrc/stft_msst.hip); its kernel and every
+    instantiation of the operator are built without register spills or scratch (profiles/msst_resources.txt,
+    profiles/sst2_resources.txt)."""
+    lib = _lib.load()
+    if isinstance(order, (bool, np.bool_)) or order not in (1, 2):
+        raise ValueError(f"order {order!r}: mssq_stft builds orders 1 and 2")
+    n_iter = _n_iter(n_iter)
+    if squeezing not in SQUEEZE:
+        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
+    xa, batched, code = _signal(x)
+    batch, N = xa.shape
+    fs = 1.0 / _dt(fs, t, N)
+    n_fft = n_fft or min(N // hop_len, 512)
+    if (not isinstance(n_fft, (int, np.integer)) or isinstance(n_fft, (bool, np.bool_))
+            or not SST2_MIN_N_FFT <= n_fft <= SST2_MAX_N_FFT or n_fft & (n_fft - 1)):
+        raise ValueError(f"n_fft {n_fft!r}: mssq_stft takes a power of two from {SST2_MIN_N_FFT} to {SST2_MAX_N_FFT}")
+    n_fft = int(n_fft)
+    if win_len is None:
+        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
+    win = get_window(window, win_len, n_fft)
+    pad = _pad_code(padtype)
+    _lib.require_gpu()
+    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0) | (VARIANT_FLIPUD if flipud else 0)
+    n_freqs, n_frames = n_fft // 2 + 1, (N - 1) // hop_len + 1
+    shape = (batch, n_freqs, n_frames)
+    cdt, rdt = _cdtype(code), _rdtype(code)
+    Tx, Sx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
+    w = _lib.pinned_empty(shape, rdt) if get_w else None
+    bins = _lib.pinned_empty(shape, np.int32) if get_bins else None
+    f = np.empty(n_freqs, dtype=np.float64)
+    _call(lib.ssq_mssq_stft_host(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, pad, SQUEEZE[squeezing],
+                                 -1.0 if gamma is None else float(gamma), variant, int(order), n_iter, _ptr(Tx), _ptr(f),
+                                 _ptr(Sx), _ptr(w), _ptr(bins)))
+    Sfs = np.linspace(0, .5 * fs, n_freqs, dtype=rdt)
+    out = [Tx if batched else Tx[0], Sx if batched else Sx[0], f.astype(rdt), Sfs]
+    if get_w:
+        out.append(w if batched else w[0])
+    if get_bins:
+        out.append(bins if batched else bins[0])
+    return tuple(out)
+
+
+def msst_walk(bins, n_iter):
+    """The walk of `mssq_stft` alone, on a map the caller holds -> int32, same shape.  `bins`: int32 [F, n] or
+    [B, F, n] (F <= 2049), a target indexes the row axis itself and -1 means no map; per column
+        c1[k] = bins[k];   c(i+1)[k] = bins[ci[k]] if ci[k] >= 0 and bins[ci[k]] >= 0, else ci[k]     (i = 1 .. n_iter - 1)
+    and the result is c_n.  Runs the kernel of `mssq_stft` (csrc/stft_msst.hip); a non-int32 array, targets outside
+    -1 .. F - 1 and an `n_iter` that is not an int from 1 to 64 raise ValueError before any GPU work."""
+    lib = _lib.load()
+    n_iter = _n_iter(n_iter)
+    if not isinstance(bins, np.ndarray) or bins.dtype != np.int32 or bins.ndim not in (2, 3):
+        raise ValueError("`bins` must be an int32 ndarray [F, n] or [B, F, n]")
+    b3 = np.ascontiguousarray(bins if bins.ndim == 3 else bins[None])
+    B, F, n = b3.shape
+    if not 1 <= F <= MSST_MAX_ROWS or B < 1 or n < 1:
+        raise ValueError(f"`bins` of shape {bins.shape}: 1 .. {MSST_MAX_ROWS} rows, and no empty axis")
+    if b3.min() < -1 or b3.max() >= F:
+        raise ValueError(f"`bins` holds targets outside -1 .. F - 1 = {F - 1}")
+    _lib.require_gpu()
+    out = np.empty_like(b3)
+    _call(lib.ssq_msst_walk_host(_ptr(b3), B, F, n, n_iter, _ptr(out)))
+    return out if bins.ndim == 3 else out[0]
+
+
+def msst_tile_cols(n_rows):
+    """Columns of the LDS tile one workgroup of the walk kernel owns for maps of `n_rows` rows (no GPU needed)."""
+    c = _lib.load().ssq_msst_tile_cols(int(n_rows))
+    if c < 0:
+        raise ValueError(f"n_rows {n_rows!r}: 1 .. {MSST_MAX_ROWS}")
+    return int(c)
 
 
 def tssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
