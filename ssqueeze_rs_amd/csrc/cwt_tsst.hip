@@ -1,25 +1,21 @@
 // cwt_tsst.hip -- the time-reassigned synchrosqueezed CWT, `upstream.tssq_cwt`.  Upstream has no such
 // transform: the definition is the project's own, restated in numpy by tests/helpers/tssq_cwt_ref.py.  Every complex
 // coefficient moves along TIME inside its own row, to its group delay, and is rotated to keep its phase reference; rows do
-// not mix.  Per-sample units, dt enters at the end.  With P, n1, n2 = p2up(N), xh, xi_k, T0 and T1 exactly those of
-// cwt_sst2.hip, on columns n1 .. n1 + N - 1:
-//   W = F^-1[xh T0]   W1 = F^-1[xh i xi T0]   W2 = F^-1[xh (-xi^2) T0]   Wt = F^-1[xh (-i) T1]   Wt1 = F^-1[xh xi T1]
+// not mix.  dt enters at the end.  With the maps of cwt_maps64.h (order 1: W and Wt; order 2: all five) on columns
+// n1 .. n1 + N - 1:
 //   nu_i = wc / (2 pi a_i) cycles/sample: the row's frequency, an argument [na] (the library never derives it)
 //   d1  = Re(Wt / W)
 //   D   = W^2 + Wt1 W - Wt W1      num = W2 W - W1^2
 //   d2  = d1 - Im((D / num) (2 pi nu_i + i W1 / W))        the group delay of the locally fitted log-quadratic spectrum
 //   off = d2 where order = 2, |num| > gamma^2, d2 is finite and |d2| <= N, else d1; clamped to [-N, N] (a NaN stays)
 //   tau = off dt, fp64 rounded once to the call's dtype; +inf where |W| < gamma
-//   m'  = clip(j + rint(tau / dt), 0, N - 1) in the call's dtype, on the REPORTED tau (cwt_reassign.hip's time rule)
+//   m'  = clip(j + rint(tau / dt), 0, N - 1) in the call's dtype, on the REPORTED tau (cwt_maps64.h's time rule)
 //   Tx[i, m'] += Wx[i, j] exp(-2 pi i frac(nu_i (j - m')))  of the REPORTED Wx, the product in fp64
-//
-//   cwt_pad_kernel (cwt_pad.h), cwt_tsst_spectra_kernel<ORDER> : cwt_sst2.hip's first two steps; order 1 forms two product
-//                              spectra a row (W, Wt), order 2 the five.  The transforms between them are fft_any_batched's.
+// The pipeline up to the operator is cwt_maps64.h's.  Then:
 //   cwt_tsst_operator_kernel<O, ORDER> : one thread per (row, column), lanes along time: the values, 1 / P, 1 / |W|^2 and
 //                              1 / |num|^2 once; Wx, optionally tau, and the int32 target m' (-1 where the bin is not
 //                              kept), formed from the values AS ROUNDED to the call's dtype.  It also reduces max |Wx|^2
-//                              per signal as cwt_reassign.hip does: a wave reduction, a four-value step through LDS, then
-//                              ONE 64-bit integer atomic max per workgroup on the bit pattern of the non-negative double.
+//                              per signal (cwt_flush_max).
 //   cwt_tsst_scatter_kernel<O> : after all chunks (the scale is per signal).  One thread per source bin, 64-bit flat index,
 //                              lanes along time; a kept bin loads Wx, rotates it in fp64, converts both parts to fixed
 //                              point (quantum q = A 2^-S, S = min(38, 61 - ceil(log2 N)), A the smallest power of two >=
@@ -34,72 +30,18 @@
 //                              every cell of Tx exactly once.
 // The rotation's angle is formed in turns: t = nu r with the product's rounding error recovered by an fma, then
 // t - rint(t) (exact) plus that remainder, and sinpi / cospi: its error does not grow with |r| <= N.
-// Transforms and operator run in fp64 for float32 calls too (the decision of DESIGN 4.11 and 4.12, taken over).  A row is
-// transformed on its own by every kernel, so its result depends neither on the chunk it is in nor on the batch.
+// The head of the workspace: the signals' maxima [batch] (to a multiple of 16 bytes), the accumulators [batch][na][N][2]
+// and the int32 target map [batch][na][N] (to a multiple of 16 bytes).
 #include <cmath>
-#include <vector>
 
-#include "../../include/ssq_hip.h"
-#include "cwt_pad.h"
-#include "cwt_sst2_wavelets.h"
-#include "dev_buffers.h"
-#include "fft_generic.h"
-#include "host_math.h"
+#include "cwt_maps64.h"
 
 namespace ssq {
 
-constexpr int kCwtTThreads = 256;
 constexpr int kCwtTQuantumBitsMax = 38;                       // upstream.TSSQ_CWT_QUANTUM_LOG2_MAX
 
-constexpr int cwt_tsst_maps(int order) { return order == 2 ? 5 : 2; }   // W, Wt | W, W1, W2, Wt, Wt1
-
-struct CwtTSpecDev {
-  const cpx<double>* xh;     // [batch][P]: the forward DFTs
-  const double* scales;      // [na]
-  cpx<double>* spec;         // [rows][maps][P]: the chunk's product spectra (then, in place, their inverse transforms)
-  long long P, r0, rows;     // the chunk: rows r0 .. r0 + rows - 1 of the batch x na
-  int na;
-  Cwt2Wavelet wv;
-};
-
-// grid (ceil(P / 256), min(rows, 65535)): thread k of row r0 + rl
-template <int ORDER>
-__global__ __launch_bounds__(kCwtTThreads) void cwt_tsst_spectra_kernel(const CwtTSpecDev p) {
-  constexpr int M = cwt_tsst_maps(ORDER);
-  const long long k = (long long)blockIdx.x * kCwtTThreads + threadIdx.x;
-  if (k >= p.P) return;
-  const bool live = 2 * k <= p.P;
-  for (long long rl = blockIdx.y; rl < p.rows; rl += gridDim.y) {
-    const long long r = p.r0 + rl;
-    const long long b = r / p.na;
-    const double a = p.scales[r - b * p.na];
-    cpx<double>* __restrict__ out = p.spec + rl * M * p.P + k;
-    cpx<double> s0 = {0.0, 0.0}, s1 = s0, s2 = s0, s3 = s0, s4 = s0;
-    if (live) {
-      double xi, T0, T1;
-      cwt2_tables_at(p.wv, a, k, p.P, &xi, &T0, &T1);
-      const cpx<double> X = p.xh[b * p.P + k];
-      s0 = {X.x * T0, X.y * T0};
-      s3 = {X.y * T1, -X.x * T1};                             // X (-i) T1
-      if constexpr (ORDER == 2) {
-        const double xT0 = xi * T0;
-        s1 = {-X.y * xT0, X.x * xT0};                         // X i xi T0
-        s2 = {-X.x * (xi * xT0), -X.y * (xi * xT0)};          // X (-xi^2) T0
-        s4 = {X.x * (xi * T1), X.y * (xi * T1)};              // X xi T1
-      }
-    }
-    if constexpr (ORDER == 2) {
-      out[0] = s0;
-      out[p.P] = s1;
-      out[2 * p.P] = s2;
-      out[3 * p.P] = s3;
-      out[4 * p.P] = s4;
-    } else {
-      out[0] = s0;
-      out[p.P] = s3;
-    }
-  }
-}
+constexpr unsigned cwt_tsst_map_set(int order) { return order == 2 ? kMapsAll : kMapW | kMapWt; }
+constexpr int cwt_tsst_maps(int order) { return cwt_map_count(cwt_tsst_map_set(order)); }
 
 template <typename O>
 struct CwtTOpDev {
@@ -115,37 +57,20 @@ struct CwtTOpDev {
   O dt_o;                    // dt in the call's dtype: the time rule runs on the tau the call reports
 };
 
-// max over the workgroup of a non-negative value, then one integer atomic max on its bit pattern (non-negative doubles
-// order as their bit patterns do; max is order-independent).  Called by every thread of the workgroup.
-__device__ __forceinline__ void cwt_tsst_flush_max(double mx, double* red, unsigned long long* dst) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) mx = fmax(mx, __shfl_xor(mx, s, 64));
-  __syncthreads();                                           // (the previous flush's reads of `red` are over)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double v = red[0];
-#pragma unroll
-    for (int i = 1; i < kCwtTThreads / 64; ++i) v = fmax(v, red[i]);
-    if (v > 0.0) atomicMax(dst, (unsigned long long)__double_as_longlong(v));
-  }
-}
-
-// grid (ceil(N / 256), min(rows, 65535)): thread = column j of row rl.  No thread leaves early: the maximum's reduction
-// has workgroup barriers, and the signal a row belongs to is the same for the whole workgroup.
+// grid (ceil(N / 256), min(rows, 65535)): thread = column j of row rl.  No thread leaves early (cwt_flush_max).
 template <typename O, int ORDER>
-__global__ __launch_bounds__(kCwtTThreads) void cwt_tsst_operator_kernel(const CwtTOpDev<O> p) {
+__global__ __launch_bounds__(kCwtThreads) void cwt_tsst_operator_kernel(const CwtTOpDev<O> p) {
   using T = double;
   constexpr int M = cwt_tsst_maps(ORDER);
-  __shared__ T red[kCwtTThreads / 64];
-  const long long j = (long long)blockIdx.x * kCwtTThreads + threadIdx.x;
+  __shared__ T red[kCwtThreads / 64];
+  const long long j = (long long)blockIdx.x * kCwtThreads + threadIdx.x;
   const bool live = j < p.N;
   T mx = (T)0;
   long long b_cur = -1;
   for (long long rl = blockIdx.y; rl < p.rows; rl += gridDim.y) {
     const long long b = (p.r0 + rl) / p.na;
     if (b != b_cur) {
-      if (b_cur >= 0) cwt_tsst_flush_max(mx, red, p.emax + b_cur);
+      if (b_cur >= 0) cwt_flush_max(mx, red, p.emax + b_cur);
       mx = (T)0;
       b_cur = b;
     }
@@ -174,14 +99,7 @@ __global__ __launch_bounds__(kCwtTThreads) void cwt_tsst_operator_kernel(const C
     if (keep) {
       tau = (O)(clamp_keep_nan(off, (T)p.N) * p.dt);
       if (!isinf(tau)) {                                                      // (an offset that overflows: not a target)
-        // the time rule on the reported tau.  |tau / dt| <= N (1 + eps), the offset being clamped; the bound below only
-        // keeps the quotient of an extreme dt inside the integer
-        const O vt = tau / p.dt_o;
-        const O rv = isfinite(vt) ? rint(vt) : (O)0;
-        const long long r = (long long)(rv < (O)-134217728 ? (O)-134217728 : (rv > (O)134217728 ? (O)134217728 : rv));
-        long long mt = j + r;
-        mt = mt < 0 ? 0 : (mt > p.N - 1 ? p.N - 1 : mt);
-        mm = (int)mt;
+        cwt_time_target(tau, p.dt_o, j, p.N, mm);
       } else {
         tau = (O)INFINITY;
       }
@@ -192,19 +110,16 @@ __global__ __launch_bounds__(kCwtTThreads) void cwt_tsst_operator_kernel(const C
     p.mm[o] = mm;
     mx = fmax(mx, energy_f64<O>(Wo));                                // (a NaN is not a maximum)
   }
-  if (b_cur >= 0) cwt_tsst_flush_max(mx, red, p.emax + b_cur);
+  if (b_cur >= 0) cwt_flush_max(mx, red, p.emax + b_cur);
 }
 
 // the signal's scale: Pmax = the smallest power of two >= max |Wx|^2, A = the smallest power of two >= sqrt(Pmax), quantum
 // q = A 2^-qbits (both q and 1 / q normal numbers; a signal of zeros, or one whose energy is not finite, gets q = 0)
 __device__ __forceinline__ void cwt_tsst_quantum(unsigned long long bits, int qbits, double* q, double* inv_q) {
-  const double mx = __longlong_as_double((long long)bits);
   *q = 0.0;
   *inv_q = 0.0;
-  if (mx > 0.0 && mx <= 1.7976931348623157e308) {
-    int ex;
-    const double fr = frexp(mx, &ex);                                    // mx = fr 2^ex, fr in [0.5, 1)
-    const int lp = fr == 0.5 ? ex - 1 : ex;                              // Pmax = 2^lp, |lp| <= 1075
+  int lp;
+  if (cwt_pow2_above(bits, &lp)) {
     const int la = (lp + 1) >> 1;                                        // ceil(lp / 2): A = 2^la
     *q = ldexp(1.0, la - qbits);
     *inv_q = ldexp(1.0, qbits - la);
@@ -226,8 +141,8 @@ struct CwtTScatDev {
 // grid (min(ceil(plane / 256), 2^31 - 1), min(batch, 65535)): 64-bit flat index i over a signal's na x N bins, lanes
 // along time, the x blocks stride over the plane and the y blocks over the signals
 template <typename O>
-__global__ __launch_bounds__(kCwtTThreads) void cwt_tsst_scatter_kernel(const CwtTScatDev<O> p) {
-  const long long stride = (long long)gridDim.x * kCwtTThreads;
+__global__ __launch_bounds__(kCwtThreads) void cwt_tsst_scatter_kernel(const CwtTScatDev<O> p) {
+  const long long stride = (long long)gridDim.x * kCwtThreads;
   const double cap = ldexp(1.0, p.qbits);
   for (long long b = blockIdx.y; b < p.batch; b += gridDim.y) {
     double q, inv_q;
@@ -236,7 +151,7 @@ __global__ __launch_bounds__(kCwtTThreads) void cwt_tsst_scatter_kernel(const Cw
     const long long base = b * p.plane;
     const int lane = threadIdx.x & 63;
     // the loop is uniform over the wave (start and stride are multiples of 64): every lane takes part in the shuffles
-    for (long long i = (long long)blockIdx.x * kCwtTThreads + threadIdx.x; i - lane < p.plane; i += stride) {
+    for (long long i = (long long)blockIdx.x * kCwtThreads + threadIdx.x; i - lane < p.plane; i += stride) {
       long long cellno = -1, fr = 0, fi = 0;                               // cellno -1: nothing to add
       if (i < p.plane) {
         const int mm = p.mm[base + i];
@@ -284,13 +199,13 @@ __global__ __launch_bounds__(kCwtTThreads) void cwt_tsst_scatter_kernel(const Cw
 }
 
 template <typename O>
-__global__ __launch_bounds__(kCwtTThreads) void cwt_tsst_readout_kernel(const CwtTScatDev<O> p) {
-  const long long stride = (long long)gridDim.x * kCwtTThreads;
+__global__ __launch_bounds__(kCwtThreads) void cwt_tsst_readout_kernel(const CwtTScatDev<O> p) {
+  const long long stride = (long long)gridDim.x * kCwtThreads;
   for (long long b = blockIdx.y; b < p.batch; b += gridDim.y) {
     double q, inv_q;
     cwt_tsst_quantum(p.emax[b], p.qbits, &q, &inv_q);
     const long long base = b * p.plane;
-    for (long long i = (long long)blockIdx.x * kCwtTThreads + threadIdx.x; i < p.plane; i += stride) {
+    for (long long i = (long long)blockIdx.x * kCwtThreads + threadIdx.x; i < p.plane; i += stride) {
       const unsigned long long* cell = p.acc + 2 * (base + i);
       p.Tx[base + i] = {(O)((double)(long long)cell[0] * q), (O)((double)(long long)cell[1] * q)};
     }
@@ -303,141 +218,75 @@ using namespace ssq;
 
 namespace {
 
-constexpr int64_t kCwtTDefaultWorkBytes = (int64_t)2 << 30;   // the chunk area of the preferred workspace is capped here
-
-struct CwtTShape {
-  int64_t P = 0, n1 = 0, n2 = 0, rows = 0, plane = 0;
-  int qbits = 0, maps = 0;
-  double gamma = 0.0;
-  int64_t fixed_bytes = 0, min_bytes = 0, pref_bytes = 0;
-};
-
-// workspace: first what does not depend on R -- the signals' maxima [batch] (to a multiple of 16 bytes), the accumulators
-// [batch][na][N][2] and the int32 target map [batch][na][N] (to a multiple of 16 bytes) -- then xh [batch][P] and a chunk
-// area of R rows ([R][maps][P] spectra and as much again for the transforms' ping-pong)
-int64_t cwtt_chunk_bytes(int64_t batch, int64_t P, int64_t R, int maps) { return 16 * P * (batch + 2 * maps * R); }
-int64_t cwtt_emax_bytes(int64_t batch) { return (8 * batch + 15) / 16 * 16; }
-int64_t cwtt_fixed_bytes(int64_t batch, int64_t plane) {
-  return cwtt_emax_bytes(batch) + 16 * batch * plane + (4 * batch * plane + 15) / 16 * 16;
-}
-
-int cwtt_shape_only(int dtype, int64_t batch, int64_t N, int64_t na, int order, CwtTShape* s) {
-  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
-  if (batch < 1) SSQ_FAIL("batch must be >= 1");
-  if (order != 1 && order != 2) SSQ_FAIL("tssq_cwt: order must be 1 or 2");
-  if (N < 2 || N > ((int64_t)1 << 26)) SSQ_FAIL("tssq_cwt: n_signal must be in [2, 2^26]");
-  if (na < 2 || na > 32767) SSQ_FAIL("tssq_cwt: na must be in [2, 32767]");
-  if (na * N > ((int64_t)1 << 40)) SSQ_FAIL("tssq_cwt: na * n_signal must be <= 2^40");
-  host::p2up(N, &s->P, &s->n1, &s->n2);
-  if (s->P < N || (s->P & (s->P - 1)) != 0) SSQ_FAIL("tssq_cwt: bad padded length");
-  if ((double)batch * (double)na * (double)N * 20.0 > 4.0e18 || (double)batch * (double)s->P * 16.0 > 4.0e18)
-    SSQ_FAIL("tssq_cwt: transform too large");
-  s->rows = batch * na;
-  s->plane = na * N;
-  s->maps = cwt_tsst_maps(order);
-  int L = 0;
-  while (((int64_t)1 << L) < N) ++L;                          // ceil(log2 N) <= 26
-  s->qbits = std::min(kCwtTQuantumBitsMax, 61 - L);
-  s->fixed_bytes = cwtt_fixed_bytes(batch, s->plane);
-  s->min_bytes = cwtt_chunk_bytes(batch, s->P, 1, s->maps) + s->fixed_bytes;
-  int64_t R = (kCwtTDefaultWorkBytes - 16 * s->P * batch) / (16 * s->P * 2 * s->maps);
-  if (R > s->rows) R = s->rows;
-  if (R < 1) R = 1;
-  s->pref_bytes = cwtt_chunk_bytes(batch, s->P, R, s->maps) + s->fixed_bytes;
-  return 0;
-}
-
-// every argument check of the entry points (sets the error and returns non-zero): nothing here touches the GPU
-int cwtt_check(int dtype, int64_t batch, int64_t N, int wavelet, double p0, double p1, const double* scales,
-               const double* nu, int64_t na, double dt, int padtype, int order, double gamma, CwtTShape* s) {
-  if (int rc = cwtt_shape_only(dtype, batch, N, na, order, s)) return rc;
-  if (wavelet != SSQ_WAVELET_GMW && wavelet != SSQ_WAVELET_MORLET) SSQ_FAIL("tssq_cwt: unknown wavelet");
-  if (!(p0 > 0) || !std::isfinite(p0)) SSQ_FAIL("tssq_cwt: wavelet parameter p0 must be positive");
-  if (wavelet == SSQ_WAVELET_GMW && (!(p1 > 0) || !std::isfinite(p1)))
-    SSQ_FAIL("tssq_cwt: wavelet parameter p1 must be positive");
-  if (!scales || !nu) SSQ_FAIL("NULL argument");
-  for (int64_t i = 0; i < na; ++i) {
-    if (!(scales[i] > 0) || !std::isfinite(scales[i])) SSQ_FAIL("tssq_cwt: scales must be positive and finite");
-    if (!(nu[i] > 0) || !std::isfinite(nu[i])) SSQ_FAIL("tssq_cwt: row_freqs must be positive and finite");
-  }
-  if (!(dt > 0) || !std::isfinite(dt)) SSQ_FAIL("tssq_cwt: dt must be positive");
-  if (padtype < SSQ_PAD_REFLECT || padtype > SSQ_PAD_WRAP) SSQ_FAIL("tssq_cwt: unknown padtype");
-  if (std::isnan(gamma)) SSQ_FAIL("tssq_cwt: gamma is NaN");
-  s->gamma = gamma < 0 ? 10.0 * (dtype == SSQ_F64 ? 2.2204460492503131e-16 : 1.1920928955078125e-07) : gamma;
-  return 0;
-}
+// the head: 16 bytes of accumulator and one int32 target per cell
+constexpr CwtMapsKind kCwtTKind = {"tssq_cwt", "ssq_tssq_cwt_workspace_bytes", 20.0, 4.0e18, 20};
 
 struct CwtTCall {
-  int dtype, wavelet, padtype, order;
-  int64_t batch, N, na;
-  double p0, p1, dt;
-  const double *scales, *nu;
+  CwtMapsCall m;
+  int order;
+  const double* nu;
 };
+
+const char* cwtt_order_fail(int order) { return order != 1 && order != 2 ? "order must be 1 or 2" : nullptr; }
+
+int cwtt_check(const CwtTCall& c, CwtMapsShape* s) {
+  const auto rows = [&]() -> int {
+    if (!c.m.scales || !c.nu) SSQ_FAIL("NULL argument");
+    for (int64_t i = 0; i < c.m.na; ++i) {
+      if (!(c.m.scales[i] > 0) || !std::isfinite(c.m.scales[i])) SSQ_FAIL("tssq_cwt: scales must be positive and finite");
+      if (!(c.nu[i] > 0) || !std::isfinite(c.nu[i])) SSQ_FAIL("tssq_cwt: row_freqs must be positive and finite");
+    }
+    return 0;
+  };
+  return cwt_maps_check(kCwtTKind, cwt_tsst_maps(c.order), cwtt_order_fail(c.order), c.m, rows, nullptr, 0, nullptr, s);
+}
 
 // The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the rows per chunk.  d_tau, d_mm may be nullptr
 // (the targets then live in the workspace alone).  Synchronous.  kernel_ms: three floats, all kernels, the scatter kernel
 // alone, and everything before the scatter.
 template <typename T, int ORDER>
-int cwtt_run(const CwtTCall& c, const CwtTShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm,
+int cwtt_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm,
              void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
-  constexpr int M = cwt_tsst_maps(ORDER);
+  const int64_t batch = c.m.batch, N = c.m.N, na = c.m.na;
   HostCallBufs d;
   TimingEvents t;
   void *d_scales = nullptr, *d_nu = nullptr;
-  SSQ_HIP(d.upload(&d_scales, c.scales, sizeof(double) * (size_t)c.na));
-  SSQ_HIP(d.upload(&d_nu, c.nu, sizeof(double) * (size_t)c.na));
+  SSQ_HIP(d.upload(&d_scales, c.m.scales, sizeof(double) * (size_t)na));
+  SSQ_HIP(d.upload(&d_nu, c.nu, sizeof(double) * (size_t)na));
   if (kernel_ms) SSQ_HIP(t.start(4, st));
-  const int64_t P = s.P;
-  int64_t R = (work_bytes - s.fixed_bytes - 16 * P * c.batch) / (16 * P * 2 * M);
-  if (R > s.rows) R = s.rows;
-  const int64_t cells = c.batch * s.plane;
+  const int64_t cells = batch * s.plane;
   char* head = static_cast<char*>(d_work);
   unsigned long long* emax = reinterpret_cast<unsigned long long*>(head);                                  // [batch]
-  unsigned long long* acc = reinterpret_cast<unsigned long long*>(head + cwtt_emax_bytes(c.batch));       // [cells][2]
+  unsigned long long* acc = reinterpret_cast<unsigned long long*>(head + cwt_emax_bytes(batch));          // [cells][2]
   int* mm = d_mm ? static_cast<int*>(d_mm) : reinterpret_cast<int*>(acc + 2 * cells);
-  cpx<double>* xh = reinterpret_cast<cpx<double>*>(head + s.fixed_bytes);
-  cpx<double>* spec = xh + c.batch * P;                        // [R][M][P]
-  cpx<double>* pong = spec + R * M * P;                        // [R][M][P]
-  SSQ_HIP(hipMemsetAsync(head, 0, (size_t)(cwtt_emax_bytes(c.batch) + 16 * cells), st));
-  SSQ_HIP(cwt_pad<T>(static_cast<const T*>(d_x), xh, c.batch, c.N, P, s.n1, c.padtype, st));
-  const int64_t fb = 2 * M * R;                                // signals per forward call: the chunk area is its ping-pong
-  for (int64_t b0 = 0; b0 < c.batch; b0 += fb)
-    SSQ_HIP(fft_any_batched<double>(xh + b0 * P, spec, P, std::min<int64_t>(fb, c.batch - b0), -1, st));
-  CwtTSpecDev sp{};
-  sp.xh = xh;
-  sp.scales = static_cast<const double*>(d_scales);
-  sp.spec = spec;
-  sp.P = P;
-  sp.na = (int)c.na;
-  sp.wv = cwt2_wavelet(c.wavelet, c.p0, c.p1);
+  SSQ_HIP(hipMemsetAsync(head, 0, (size_t)(cwt_emax_bytes(batch) + 16 * cells), st));
   CwtTOpDev<T> op{};
-  op.maps = spec;
   op.nu = static_cast<const double*>(d_nu);
   op.emax = emax;
-  op.P = P;
-  op.N = c.N;
+  op.P = s.P;
+  op.N = N;
   op.n1 = s.n1;
-  op.na = (int)c.na;
-  op.inv_P = 1.0 / (double)P;
+  op.na = (int)na;
+  op.inv_P = 1.0 / (double)s.P;
   op.gamma = s.gamma;
   op.gamma_sq = s.gamma * s.gamma;
-  op.dt = c.dt;
-  op.dt_o = (T)c.dt;
-  for (int64_t r0 = 0; r0 < s.rows; r0 += R) {
-    const int64_t nr = std::min<int64_t>(R, s.rows - r0);
-    sp.r0 = r0;
-    sp.rows = nr;
-    hipLaunchKernelGGL((cwt_tsst_spectra_kernel<ORDER>), cwt_rows_grid(P, nr), dim3(kCwtTThreads), 0, st, sp);
-    SSQ_HIP(hipGetLastError());
-    SSQ_HIP(fft_any_batched<double>(spec, pong, P, M * nr, +1, st));
-    op.Wx = static_cast<cpx<T>*>(d_Wx) + r0 * c.N;
-    op.tau = d_tau ? static_cast<T*>(d_tau) + r0 * c.N : nullptr;
-    op.mm = mm + r0 * c.N;
+  op.dt = c.m.dt;
+  op.dt_o = (T)c.m.dt;
+  const auto launch_op = [&](const cpx<double>* maps, int64_t r0, int64_t nr) -> int {
+    op.maps = maps;
+    op.Wx = static_cast<cpx<T>*>(d_Wx) + r0 * N;
+    op.tau = d_tau ? static_cast<T*>(d_tau) + r0 * N : nullptr;
+    op.mm = mm + r0 * N;
     op.r0 = r0;
     op.rows = nr;
-    hipLaunchKernelGGL((cwt_tsst_operator_kernel<T, ORDER>), cwt_rows_grid(c.N, nr), dim3(kCwtTThreads), 0, st, op);
+    hipLaunchKernelGGL((cwt_tsst_operator_kernel<T, ORDER>), cwt_rows_grid(N, nr), dim3(kCwtThreads), 0, st, op);
     SSQ_HIP(hipGetLastError());
-  }
+    return 0;
+  };
+  if (int rc = cwt_maps_chunks<T, cwt_tsst_map_set(ORDER)>(c.m, s, d_x, d_scales, d_work, work_bytes, st, launch_op))
+    return rc;
+  int L = 0;
+  while (((int64_t)1 << L) < N) ++L;                          // ceil(log2 N) <= 26
   CwtTScatDev<T> sc{};
   sc.Wx = static_cast<const cpx<T>*>(d_Wx);
   sc.mm = mm;
@@ -445,17 +294,17 @@ int cwtt_run(const CwtTCall& c, const CwtTShape& s, const void* d_x, void* d_Tx,
   sc.emax = emax;
   sc.acc = acc;
   sc.Tx = static_cast<cpx<T>*>(d_Tx);
-  sc.batch = c.batch;
+  sc.batch = batch;
   sc.plane = s.plane;
-  sc.N = c.N;
-  sc.qbits = s.qbits;
-  const dim3 grid((unsigned)std::min<int64_t>((s.plane + kCwtTThreads - 1) / kCwtTThreads, 0x7fffffffLL),
-                  (unsigned)std::min<int64_t>(c.batch, 65535));
+  sc.N = N;
+  sc.qbits = std::min(kCwtTQuantumBitsMax, 61 - L);
+  const dim3 grid((unsigned)std::min<int64_t>((s.plane + kCwtThreads - 1) / kCwtThreads, 0x7fffffffLL),
+                  (unsigned)std::min<int64_t>(batch, 65535));
   if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
-  hipLaunchKernelGGL((cwt_tsst_scatter_kernel<T>), grid, dim3(kCwtTThreads), 0, st, sc);
+  hipLaunchKernelGGL((cwt_tsst_scatter_kernel<T>), grid, dim3(kCwtThreads), 0, st, sc);
   SSQ_HIP(hipGetLastError());
   if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[2], st));
-  hipLaunchKernelGGL((cwt_tsst_readout_kernel<T>), grid, dim3(kCwtTThreads), 0, st, sc);
+  hipLaunchKernelGGL((cwt_tsst_readout_kernel<T>), grid, dim3(kCwtThreads), 0, st, sc);
   SSQ_HIP(hipGetLastError());
   if (kernel_ms) {
     SSQ_HIP(hipEventRecord(t.ev[3], st));
@@ -469,19 +318,19 @@ int cwtt_run(const CwtTCall& c, const CwtTShape& s, const void* d_x, void* d_Tx,
 }
 
 template <typename T>
-int cwtt_run_order(const CwtTCall& c, const CwtTShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm,
-                   void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
+int cwtt_run_order(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau,
+                   void* d_mm, void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
   return c.order == 2 ? cwtt_run<T, 2>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_work, work_bytes, st, kernel_ms)
                       : cwtt_run<T, 1>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_work, work_bytes, st, kernel_ms);
 }
 
 template <typename T>
-int cwtt_host_typed(const CwtTCall& c, const CwtTShape& s, const void* x, int64_t work_bytes, void* Tx, void* Wx, void* tau,
-                    void* mm) {
+int cwtt_host_typed(const CwtTCall& c, const CwtMapsShape& s, const void* x, int64_t work_bytes, void* Tx, void* Wx,
+                    void* tau, void* mm) {
   HostCallBufs d;
-  const size_t n = (size_t)s.rows * (size_t)c.N;
+  const size_t n = (size_t)s.rows * (size_t)c.m.N;
   void *d_x, *d_Tx, *d_Wx, *d_work, *d_tau = nullptr;
-  SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.batch * (size_t)c.N));
+  SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));
   SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * n));
   SSQ_HIP(d.alloc(&d_Wx, sizeof(cpx<T>) * n));
   if (tau) SSQ_HIP(d.alloc(&d_tau, sizeof(T) * n));
@@ -492,7 +341,7 @@ int cwtt_host_typed(const CwtTCall& c, const CwtTShape& s, const void* x, int64_
   if (tau) SSQ_HIP(hipMemcpy(tau, d_tau, sizeof(T) * n, hipMemcpyDeviceToHost));
   // the targets of the workspace: behind the maxima and the accumulators at its head
   if (mm)
-    SSQ_HIP(hipMemcpy(mm, static_cast<const char*>(d_work) + cwtt_emax_bytes(c.batch) + 16 * n, sizeof(int) * n,
+    SSQ_HIP(hipMemcpy(mm, static_cast<const char*>(d_work) + cwt_emax_bytes(c.m.batch) + 16 * n, sizeof(int) * n,
                       hipMemcpyDeviceToHost));
   return 0;
 }
@@ -502,8 +351,8 @@ int cwtt_host_typed(const CwtTCall& c, const CwtTShape& s, const void* x, int64_
 extern "C" {
 
 int64_t ssq_tssq_cwt_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int order, int64_t* min_bytes) {
-  CwtTShape s;
-  if (cwtt_shape_only(dtype, batch, n_signal, na, order, &s)) return -1;
+  CwtMapsShape s;
+  if (cwt_maps_shape(kCwtTKind, cwt_tsst_maps(order), cwtt_order_fail(order), dtype, batch, n_signal, na, &s)) return -1;
   if (min_bytes) *min_bytes = s.min_bytes;
   return s.pref_bytes;
 }
@@ -513,12 +362,11 @@ int ssq_tssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
                       double gamma, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm, void* d_workspace,
                       int64_t workspace_bytes, void* stream, float* kernel_ms) {
   if (!d_x || !d_Tx || !d_Wx || !d_workspace) SSQ_FAIL("NULL argument");
-  CwtTShape s;
-  if (int rc = cwtt_check(dtype, batch, n_signal, wavelet, p0, p1, scales, row_freqs, na, dt, padtype, order, gamma, &s))
-    return rc;
-  if (workspace_bytes < s.min_bytes) SSQ_FAIL("tssq_cwt: workspace smaller than the min_bytes of ssq_tssq_cwt_workspace_bytes");
+  const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales}, order, row_freqs};
+  CwtMapsShape s;
+  if (int rc = cwtt_check(c, &s)) return rc;
+  if (int rc = cwt_exec_bytes(kCwtTKind, s, workspace_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  const CwtTCall c{dtype, wavelet, padtype, order, batch, n_signal, na, p0, p1, dt, scales, row_freqs};
   hipStream_t st = static_cast<hipStream_t>(stream);
   return dtype == SSQ_F32
              ? cwtt_run_order<float>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_workspace, workspace_bytes, st, kernel_ms)
@@ -529,16 +377,12 @@ int ssq_tssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal,
                       const double* scales, const double* row_freqs, int64_t na, double dt, int padtype, int order,
                       double gamma, int64_t work_limit_bytes, void* Tx, void* Wx, void* tau, void* mm) {
   if (!x || !Tx || !Wx) SSQ_FAIL("NULL argument");
-  CwtTShape s;
-  if (int rc = cwtt_check(dtype, batch, n_signal, wavelet, p0, p1, scales, row_freqs, na, dt, padtype, order, gamma, &s))
-    return rc;
-  if (work_limit_bytes < 0 || (work_limit_bytes > 0 && work_limit_bytes < s.min_bytes))
-    SSQ_FAIL("tssq_cwt: work_limit_bytes below the min_bytes of ssq_tssq_cwt_workspace_bytes");
+  const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales}, order, row_freqs};
+  CwtMapsShape s;
+  int64_t work = 0;
+  if (int rc = cwtt_check(c, &s)) return rc;
+  if (int rc = cwt_host_bytes(kCwtTKind, s, batch, work_limit_bytes, &work)) return rc;
   if (int rc = require_device()) return rc;
-  const int64_t work = work_limit_bytes > 0
-                           ? std::min(work_limit_bytes, cwtt_chunk_bytes(batch, s.P, s.rows, s.maps) + s.fixed_bytes)
-                           : s.pref_bytes;
-  const CwtTCall c{dtype, wavelet, padtype, order, batch, n_signal, na, p0, p1, dt, scales, row_freqs};
   return dtype == SSQ_F32 ? cwtt_host_typed<float>(c, s, x, work, Tx, Wx, tau, mm)
                           : cwtt_host_typed<double>(c, s, x, work, Tx, Wx, tau, mm);
 }
