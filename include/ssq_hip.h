@@ -450,6 +450,43 @@ int ssq_tssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
                       const double* scales, const double* row_freqs, int64_t na, double dt, int padtype, int order,
                       double gamma, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm, void* d_workspace,
                       int64_t workspace_bytes, void* stream, float* kernel_ms);
+/* ConceFT, the multitaper synchrosqueezed CWT, `upstream.conceft_cwt` (csrc/cwt_conceft.hip; Daubechies,
+ * Wang and Wu 2016; upstream has no such transform).  The wavelets are the GMWs (gmw_gamma, gmw_beta; bandpass norm) of
+ * n_orders distinct orders, coeffs [n_orders][n_coeffs] their polynomials as for ssq_cwt_host_gmwk (1 <= n_orders <= 8,
+ * na * n_orders <= 32767); vectors [n_draws][n_orders] complex (interleaved, fp64), the caller's unit vectors already
+ * gauged (`upstream.conceft_vectors`), 1 <= n_draws <= 256; scale: C_0 / sum_m c_m > 0 (`upstream.gmw_adm_ssq`).  scales,
+ * dt, row_const, ssq_freqs_asc, freq_kind, freq_transition, padtype as ssq_ssq_cwt_host_rows; gamma < 0: 10 eps of the
+ * dtype, NaN is refused; variant: the SSQ_VARIANT_FLIPUD bit.  With W_g, dW_g the planes of ssq_cwt_host_gmwk (l1_norm,
+ * not rpadded), in `dtype`:
+ *   W^(m) = sum_g vectors[m][g] W_g, dW^(m) likewise (g ascending);  k = the bin of ssq_ssq_cwt_host_rows' rule on
+ *   (W^(m), dW^(m)), kept where |W^(m)| > gamma;  Tx[k][n] += W^(m)[i][n] * (row_const[i] * scale rounded to `dtype`).
+ * One thread owns a column: no atomics, the additions into a cell in a fixed order (draws in chunks of 8; chunks, then
+ * rows, then draws ascending; a draw's run of rows in one bin is summed first), so a signal's result depends neither on
+ * `batch` nor on the workspace.  Squeezing 'sum' only.
+ * Tx: [batch][na][n_signal] complex of `dtype`; Wx (may be NULL): [batch][n_orders][na][n_signal] complex, the planes W_g;
+ * w (may be NULL): [batch][n_draws][na][n_signal] REAL of `dtype`, every draw's phase transform, +inf where not kept.
+ * Workspace: 32 (fp32: 16) n_orders na n_signal bytes per signal of a slice (to a multiple of 256).  work_limit_bytes:
+ * 0 for the preferred size, else at least min_bytes. */
+int ssq_conceft_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, double gmw_gamma, double gmw_beta,
+                         const double* coeffs, int64_t n_coeffs, int64_t n_orders, const double* vectors, int64_t n_draws,
+                         double scale, const double* scales, int64_t na, double dt, const double* row_const,
+                         const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition, int padtype, double gamma,
+                         int variant, int64_t work_limit_bytes, void* Tx, void* Wx, void* w);
+/* Device bytes of the workspace: returns the preferred size (the whole batch in one slice, capped at 1 GiB but never
+ * below one signal) and stores the least one (one signal per slice) in *min_bytes (may be NULL); computed on the host;
+ * -1 on a bad shape. */
+int64_t ssq_conceft_cwt_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int64_t n_orders,
+                                        int64_t* min_bytes);
+/* The same transform on device buffers: d_x [batch][n_signal], d_Tx (required), d_Wx, d_w (each may be NULL) as above,
+ * d_workspace of workspace_bytes >= min_bytes (its size sets the signals per slice); coeffs, vectors, scales, row_const,
+ * ssq_freqs_asc on the host.  Synchronous on `stream`.  kernel_ms (may be NULL): ONE float, the time of the squeeze
+ * kernel alone (summed over the slices), from HIP events around its launches. */
+int ssq_conceft_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, double gmw_gamma, double gmw_beta,
+                         const double* coeffs, int64_t n_coeffs, int64_t n_orders, const double* vectors, int64_t n_draws,
+                         double scale, const double* scales, int64_t na, double dt, const double* row_const,
+                         const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition, int padtype, double gamma,
+                         int variant, void* d_Tx, void* d_Wx, void* d_w, void* d_workspace, int64_t workspace_bytes,
+                         void* stream, float* kernel_ms);
 
 /* ---- plans: device-resident batch pipelines -------------------------------- */
 typedef struct ssq_stft_plan ssq_stft_plan;

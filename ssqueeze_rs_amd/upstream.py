@@ -67,6 +67,13 @@ Supported subset (anything else raises ValueError naming the option):
     to its group delay, rotated to keep its phase reference, so clicks and fast sweeps concentrate and add coherently;
     the conventions of `ssq_cwt2` without `ssq_freqs`, `maprange`, `squeezing`, `flipud` and row weights; accumulated by
     64-bit integer atomic adds in fixed point (`tssq_cwt_quantum_log2`); no inverse (a per-row marginal identity);
+  * `conceft_cwt`: ConceFT, the multitaper synchrosqueezed CWT (Daubechies, Wang and Wu 2016), which upstream does not
+    have (the definition is this project's: DESIGN 4.18, csrc/cwt_conceft.hip): `ssq_cwt` under M random unit
+    combinations of the GMWs of J orders (`conceft_vectors`, gauged by the orders' admittances `gmw_adm_ssq`), averaged,
+    which keeps a ridge sharp where noise scatters the single-wavelet reassignment; the 2 J planes of
+    `cwt_higher_order` are computed once and every draw is formed, binned and summed from them in one fused kernel, no
+    atomics, bitwise the same whatever the batch; the conventions of `ssq_cwt` for the 'gmw' wavelet and squeezing
+    'sum'; its `Tx` inverts through `issq_cwt` like a first-order one;
   * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
     serial backward trace (`parallel` is accepted and ignored).
 dtype: float64 in -> complex128 (upstream's 'float64'); float32 in -> complex64 (upstream's default 'float32').
@@ -1237,6 +1244,188 @@ def tssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None,
                                 -1.0 if gamma is None else float(gamma), limit, _ptr(Tx), _ptr(Wx), _ptr(tau), _ptr(mm)))
     out = [Tx if batched else Tx[0], Wx if batched else Wx[0], s.astype(rdt), (nu / dt).astype(rdt)]
     for a in (tau, mm):
+        if a is not None:
+            out.append(a if batched else a[0])
+    return tuple(out)
+
+
+CONCEFT_MAX_ORDERS = 8                  # csrc/cwt_conceft.hip: kConceftMaxOrders
+CONCEFT_MAX_DRAWS = 256                 # csrc/cwt_conceft.hip: kConceftMaxDraws
+CONCEFT_MIN_ADMITTANCE = 1e-6           # a draw's c_m relative to sum_j |r_mj| |C_kj| below which it is refused
+
+
+def gmw_adm_ssq(gamma, beta, k):
+    """The admittance of the order-k GMW (bandpass norm), C_k = int_0^inf psih_k(w) / w dw, in closed form:
+    A sum_m kc[m] 2^m Gamma(beta / gamma + m) / gamma with kc = `gmw_k_constants(gamma, beta, k)`, wc = (beta / gamma)^(1 /
+    gamma) and A = exp(-beta ln wc + wc^gamma).  C_0 is `adm_ssq(('gmw', ...))`, the constant `issq_cwt` divides by."""
+    gamma, beta, k = float(gamma), float(beta), int(k)
+    if not (gamma > 0 and beta > 0 and math.isfinite(gamma) and math.isfinite(beta)):
+        raise ValueError("gmw_adm_ssq: gamma and beta must be positive and finite")
+    if not 0 <= k <= GMW_MAX_ORDER:
+        raise ValueError(f"gmw_adm_ssq: order {k!r} outside 0 .. {GMW_MAX_ORDER}")
+    kc = gmw_k_constants(gamma, beta, k)
+    q = beta / gamma
+    ln_a = q - q * math.log(q)                               # -beta ln wc + wc^gamma
+    if q + k < 170 and abs(ln_a) < 700:                       # Gamma itself: the alternating sum cancels several digits
+        return float(math.exp(ln_a) * sum(kc[m] * 2.0 ** m * math.gamma(q + m) for m in range(k + 1)) / gamma)
+    return float(sum(kc[m] * 2.0 ** m * math.exp(math.lgamma(q + m) + ln_a) for m in range(k + 1)) / gamma)
+
+
+def _conceft_gauge(r, adm):
+    """Rows of `r` [M, J] normalised and turned by the unit phase that makes c_m = sum_j r_mj adm[j] real and positive
+    -> (r complex128 [M, J], c float64 [M]).  Formed in extended precision and rounded once, so that equivalent inputs
+    (a row times any unit phase, or a row that is gauged already) agree to the last place or so."""
+    r = np.array(r, dtype=np.complex128)
+    adm = np.asarray(adm, dtype=np.float64).reshape(-1)
+    if r.ndim != 2 or r.shape[1] != len(adm) or r.shape[0] < 1:
+        raise ValueError(f"`vectors` must be [n_draws, {len(adm)}] (one column per order); got shape {r.shape}")
+    if not np.isfinite(r.view(np.float64)).all():
+        raise ValueError("`vectors` must be finite")
+    rl, al = r.astype(np.clongdouble), adm.astype(np.longdouble)
+    norm = np.sqrt((rl.real ** 2 + rl.imag ** 2).sum(axis=1))
+    if (norm == 0).any():
+        raise ValueError("`vectors`: draw %d is the zero vector" % int(np.argmax(norm == 0)))
+    rl = rl / norm[:, None]
+    c = (rl * al[None, :]).sum(axis=1)
+    floor = CONCEFT_MIN_ADMITTANCE * (np.abs(rl) * np.abs(al)[None, :]).sum(axis=1)
+    bad = ~(np.abs(c) > floor)
+    if bad.any():
+        m = int(np.argmax(bad))
+        raise ValueError("`vectors`: draw %d is degenerate, its admittance |sum_j r_j C_kj| = %.3g is not above %.3g "
+                         "(the draw's wavelet has no usable reconstruction constant)" % (m, float(abs(c[m])), float(floor[m])))
+    rl = rl * (np.conj(c) / np.abs(c))[:, None]
+    return np.ascontiguousarray(rl.astype(np.complex128)), np.abs(c).astype(np.float64)
+
+
+def _conceft_draws(n_draws, n_orders, seed):
+    """The raw draws: `default_rng(seed)` complex normals [n_draws, n_orders] with unit rows; every refusal of the counts."""
+    for name, v in (("n_draws", n_draws), ("n_orders", n_orders)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} {v!r}: must be an int")
+    M, J = int(n_draws), int(n_orders)
+    if not 1 <= M <= CONCEFT_MAX_DRAWS:
+        raise ValueError(f"n_draws {n_draws!r}: 1 .. {CONCEFT_MAX_DRAWS} are built")
+    if not 1 <= J <= CONCEFT_MAX_ORDERS:
+        raise ValueError(f"n_orders {n_orders!r}: 1 .. {CONCEFT_MAX_ORDERS} are built")
+    rng = np.random.default_rng(seed)
+    r = rng.standard_normal((M, J)) + 1j * rng.standard_normal((M, J))
+    return r / np.linalg.norm(r, axis=1, keepdims=True)
+
+
+def conceft_vectors(n_draws, n_orders, seed, adm):
+    """The random unit vectors of `conceft_cwt`: complex normal draws from `np.random.default_rng(seed)`, normalised, each
+    turned by the unit phase that makes c_m = sum_j r_mj adm[j] real and positive (`adm`: the orders' `gmw_adm_ssq`)
+    -> complex128 [n_draws, n_orders]."""
+    r = _conceft_draws(n_draws, n_orders, seed)
+    if len(np.asarray(adm).reshape(-1)) != r.shape[1]:
+        raise ValueError(f"`adm` must hold one admittance per order ({r.shape[1]})")
+    return _conceft_gauge(r, adm)[0]
+
+
+def conceft_cwt(x, wavelet="gmw", scales="log-piecewise", orders=3, n_draws=20, seed=0, vectors=None, nv=None, fs=None,
+                t=None, ssq_freqs=None, padtype="reflect", maprange="peak", gamma=None, flipud=True, get_Wx=False,
+                get_w=False, squeezing="sum"):
+    """ConceFT, the multitaper synchrosqueezed CWT (Daubechies, Wang and Wu 2016) -> (Tx, ssq_freqs, scales[, Wx][, w]);
+    not in upstream, conventions of `ssq_cwt`.  The answer to noise: the J orthogonal wavelets of a Morse family are the
+    GMWs of orders k_0 .. k_{J-1}; M random unit vectors r_m in C^J each give a wavelet sum_j r_mj psi_kj, and the M
+    synchrosqueezed transforms are averaged.  The signal's ridge is where every draw agrees, the noise-driven
+    reassignments differ from draw to draw and average down; a plain multitaper average widens the ridge, this does not.
+
+    With W_j, dW_j the planes of `cwt_higher_order(x, wavelet, order=orders, average=False, derivative=True)` (one forward
+    FFT per signal) and C_k = `gmw_adm_ssq(gamma, beta, k)`:
+        gauge      r_m times the unit phase that makes c_m = sum_j r_mj C_kj real and positive (a global phase of the
+                   wavelet moves no bin; the draws then add coherently and every column sum of Tx stays a positive
+                   multiple of the analytic signal); a draw with c_m <= 1e-6 sum_j |r_mj| |C_kj| is refused
+        per draw   W^(m) = sum_j r_mj W_j, dW^(m) = sum_j r_mj dW_j (j ascending, in the call's dtype); the phase
+                   transform and the bin by `ssq_cwt`'s rule, kept where |W^(m)| > gamma (default 10 eps of the dtype);
+                   Tx[k, n] += W^(m)[i, n] row_const[i]
+        scale      Tx *= C_0 / sum_m c_m, so `issq_cwt(Tx, wavelet)` inverts it as it inverts `ssq_cwt`'s; with
+                   vectors = [[1, 0, ...]] the scale is exactly 1 and Tx is `ssq_cwt`'s
+    The combinations are linear, so the 2 J planes are computed once and every draw is formed from them on the device in
+    one fused kernel (csrc/cwt_conceft.hip): one thread owns a column of Tx, no atomics, the additions into a cell in a
+    fixed order, so the result is bitwise the same run to run and whatever the batch.
+
+    `orders`: an int J (the orders 0 .. J-1) or a tuple of distinct orders within 0 .. 16, at most 8.  `vectors`
+    [M, J] complex overrides `n_draws` (1 .. 256) and `seed` (`conceft_vectors`); its rows are normalised and gauged here.
+    `ssq_freqs` are the order-0 wavelet's, as for `ssq_cwt(order=)`.  `Wx` (get_Wx=True): the J planes [J, na, N]; `w`
+    (get_w=True): every draw's phase transform [M, na, N], real, +inf where not kept.  A batch [B, N] gives a leading B.
+
+    Built: wavelet 'gmw' with bandpass norm; an ndarray `scales` of any of the three grids; `ssq_freqs` None, a string or
+    an array; maprange 'peak' / 'maximal'; squeezing 'sum'; the five padtypes; `flipud`; J na <= 32767.  Anything else
+    raises ValueError before any GPU work."""
+    lib = _lib.load()
+    if squeezing != "sum":
+        raise ValueError(f"squeezing {squeezing!r}: conceft_cwt builds 'sum' only")
+    if _wavelet_name(wavelet) != "gmw":
+        raise ValueError("conceft_cwt: the wavelet must be GMW, whose higher orders are the orthogonal tapers (got %r)"
+                         % (wavelet,))
+    wcode, p0, p1 = _wavelet(wavelet)
+    if not (p0 > 0 and math.isfinite(p0) and p1 > 0 and math.isfinite(p1)):
+        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
+    if isinstance(orders, (bool, np.bool_)):
+        raise ValueError(f"`orders` must be an int or a tuple / list / range of ints (got {orders!r})")
+    if isinstance(orders, (int, np.integer)):
+        if not 1 <= orders <= CONCEFT_MAX_ORDERS:
+            raise ValueError(f"`orders` {orders!r}: 1 .. {CONCEFT_MAX_ORDERS} orders are built")
+        orders = tuple(range(int(orders)))
+    elif isinstance(orders, (tuple, list, range)):
+        orders = tuple(orders)
+    else:
+        raise ValueError(f"`orders` must be an int or a tuple / list / range of ints (got {orders!r})")
+    for k in orders:
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"`orders` must hold ints (got {orders!r})")
+        if not 0 <= k <= GMW_MAX_ORDER:
+            raise ValueError(f"`orders` must lie within 0 .. {GMW_MAX_ORDER} (got {orders!r})")
+    if not 1 <= len(orders) <= CONCEFT_MAX_ORDERS:
+        raise ValueError(f"`orders`: 1 .. {CONCEFT_MAX_ORDERS} orders are built (got {len(orders)})")
+    if len(set(orders)) != len(orders):
+        raise ValueError(f"`orders` must be distinct (got {orders!r})")
+    orders = tuple(int(k) for k in orders)
+    J = len(orders)
+    adm = np.array([gmw_adm_ssq(p0, p1, k) for k in orders])
+    if vectors is None:
+        r, c = _conceft_gauge(_conceft_draws(n_draws, J, seed), adm)
+    else:
+        vectors = np.asarray(vectors)
+        if vectors.ndim != 2 or vectors.shape[1] != J or vectors.dtype.kind not in "fiuc":
+            raise ValueError(f"`vectors` must be a numeric array [n_draws, {J}] (one column per order); got shape "
+                             f"{vectors.shape}")
+        if not 1 <= vectors.shape[0] <= CONCEFT_MAX_DRAWS:
+            raise ValueError(f"`vectors`: 1 .. {CONCEFT_MAX_DRAWS} draws are built (got {vectors.shape[0]})")
+        r, c = _conceft_gauge(vectors, adm)
+    M = r.shape[0]
+    scale = float(gmw_adm_ssq(p0, p1, 0) / c.sum())         # (vectors = e_0 of order 0: C_0 / C_0, exactly 1)
+    xa, batched, code = _signal(x)
+    batch, N = xa.shape
+    if N < 2:
+        raise ValueError("`x` must hold at least 2 samples")
+    dt = _dt(fs, t, N)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError("`fs` / `t` must give a positive sampling period")
+    if isinstance(scales, np.ndarray) and scales.dtype.kind in "fiu" and not (np.isfinite(scales).all() and (scales > 0).all()):
+        raise ValueError("`scales` must be positive and finite")
+    s, row_const, f_asc, scaletype, f_idx = _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt)
+    if not np.isfinite(f_asc).all():
+        raise ValueError("`ssq_freqs` must be finite")
+    if gamma is not None and math.isnan(float(gamma)):
+        raise ValueError("`gamma` is NaN")
+    pad = _pad_code(padtype)
+    na = len(s)
+    if lib.ssq_conceft_cwt_workspace_bytes(code, batch, N, na, J, None) < 0:              # the shape checks (no GPU)
+        raise ValueError(lib.ssq_last_error().decode("utf-8", "replace"))
+    polys = np.ascontiguousarray(gmw_order_coefficients(p0, p1, orders, average=False))
+    _lib.require_gpu()
+    cdt, rdt = _cdtype(code), _rdtype(code)
+    Tx = _lib.pinned_empty((batch, na, N), cdt)
+    Wx = _lib.pinned_empty((batch, J, na, N), cdt) if get_Wx else None
+    w = _lib.pinned_empty((batch, M, na, N), rdt) if get_w else None
+    _call(lib.ssq_conceft_cwt_host(code, _ptr(xa), batch, N, p0, p1, _ptr(polys), polys.shape[1], J, _ptr(r), M, scale,
+                                   _ptr(s), na, dt, _ptr(row_const), _ptr(f_asc), FREQS[scaletype], f_idx or 0, pad,
+                                   -1.0 if gamma is None else float(gamma), VARIANT_FLIPUD if flipud else 0, 0, _ptr(Tx),
+                                   _ptr(Wx), _ptr(w)))
+    out = [Tx if batched else Tx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]
+    for a in (Wx, w):
         if a is not None:
             out.append(a if batched else a[0])
     return tuple(out)
