@@ -543,6 +543,8 @@ int ssq_chunks_relayout(int dtype, const void* d_in, int64_t channels, int64_t c
                         int64_t out_col_base, int64_t out_channels, int64_t ch_base, void* stream);
 
 typedef struct ssq_cwt_plan ssq_cwt_plan;
+/* na <= 32767 (with a higher-order GMW: na * n_groups <= 32767): the scale rows sit on grid.y of the table kernels, and a
+ * plan with more is refused at creation ("too many scales (max 32767)"), as are the *_host calls that build one. */
 int ssq_cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wavelet,
                         const double* scales, int64_t na, double dt, int padtype);
 /* the same with a numerics variant (SSQ_VARIANT_*) and the upstream wavelet's parameters (p0, p1) = (gamma, beta) of

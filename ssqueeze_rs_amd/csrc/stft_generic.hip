@@ -73,13 +73,13 @@ hipError_t launch_fft_frames(const StftDev<T>& p, long long sig, int n_fft, cons
 }
 
 template <typename T>
-__global__ void dft_frames_kernel(StftDev<T> p, int n_fft, GenericTabs tabs, cpx<T>* __restrict__ Sx,
+__global__ void dft_frames_kernel(StftDev<T> p, long long b0, int n_fft, GenericTabs tabs, cpx<T>* __restrict__ Sx,
                                   cpx<T>* __restrict__ dSx) {
   const long long n_signal = p.n_signal;
   const int hop = p.hop, pad_left = p.pad_left, padtype = p.padtype, n_frames = p.n_frames, n_freqs = p.n_freqs;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;   // frame
   const int k = blockIdx.y * blockDim.y + threadIdx.y;   // bin
-  const long long b = blockIdx.z;
+  const long long b = b0 + blockIdx.z;                   // (grid.z holds one slice of at most 65535 signals)
   if (j >= n_frames || k >= n_freqs) return;
   const T* xs = sig_base(p, b);
   const long long pos0 = (long long)j * hop - pad_left;
@@ -106,10 +106,10 @@ __global__ void dft_frames_kernel(StftDev<T> p, int n_fft, GenericTabs tabs, cpx
 }
 
 template <typename T>
-__global__ void reassign_cols_kernel(StftDev<T> p, const cpx<T>* __restrict__ Sx,
+__global__ void reassign_cols_kernel(StftDev<T> p, long long b0, const cpx<T>* __restrict__ Sx,
                                      const cpx<T>* __restrict__ dSx) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  const long long b = blockIdx.y;
+  const long long b = b0 + blockIdx.y;
   if (j >= p.n_frames) return;
   const long long base = b * (long long)p.n_freqs * p.n_frames + j;
   for (int i = 0; i < p.n_freqs; ++i) {
@@ -134,22 +134,34 @@ __global__ void reassign_cols_kernel(StftDev<T> p, const cpx<T>* __restrict__ Sx
   }
 }
 
+constexpr long long kMaxGridYZ = 65535;
+
 template <typename T>
 hipError_t launch_dft_frames(const StftDev<T>& p, long long batch, int n_fft, const GenericTabs& tabs,
                              cpx<T>* Sx, cpx<T>* dSx, hipStream_t stream) {
   dim3 block(64, 4, 1);
-  dim3 grid((p.n_frames + 63) / 64, (p.n_freqs + 3) / 4, (unsigned)batch);
-  hipLaunchKernelGGL(dft_frames_kernel<T>, grid, block, 0, stream, p, n_fft, tabs, Sx, dSx);
-  return hipGetLastError();
+  // a grid's y and z stop at 65535: slices of signals, the slice's first signal handed to the kernel (which indexes the
+  // signals through sig_base, so a strided batch slices the same way)
+  for (long long b0 = 0; b0 < batch; b0 += kMaxGridYZ) {
+    const long long n1 = batch - b0 < kMaxGridYZ ? batch - b0 : kMaxGridYZ;
+    dim3 grid((p.n_frames + 63) / 64, (p.n_freqs + 3) / 4, (unsigned)n1);
+    hipLaunchKernelGGL(dft_frames_kernel<T>, grid, block, 0, stream, p, b0, n_fft, tabs, Sx, dSx);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  return hipSuccess;
 }
 
 template <typename T>
 hipError_t launch_reassign_cols(const StftDev<T>& p, const cpx<T>* Sx, const cpx<T>* dSx,
                                 long long batch, hipStream_t stream) {
   dim3 block(64, 1, 1);
-  dim3 grid((p.n_frames + 63) / 64, (unsigned)batch, 1);
-  hipLaunchKernelGGL(reassign_cols_kernel<T>, grid, block, 0, stream, p, Sx, dSx);
-  return hipGetLastError();
+  for (long long b0 = 0; b0 < batch; b0 += kMaxGridYZ) {
+    const long long n1 = batch - b0 < kMaxGridYZ ? batch - b0 : kMaxGridYZ;
+    dim3 grid((p.n_frames + 63) / 64, (unsigned)n1, 1);
+    hipLaunchKernelGGL(reassign_cols_kernel<T>, grid, block, 0, stream, p, b0, Sx, dSx);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  return hipSuccess;
 }
 
 template hipError_t launch_dft_frames<float>(const StftDev<float>&, long long, int, const GenericTabs&, cpx<float>*,

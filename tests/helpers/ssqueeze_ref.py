@@ -28,7 +28,10 @@ def phase_stft(Sx, dSx, Sfs, gamma):
 def transition_idx(v):
     """utils/cwt_utils.py:375-395 (`logscale_transition_idx`)."""
     from ssqueeze_rs_amd.upstream_scales import logscale_transition_idx
-    return logscale_transition_idx(np.asarray(v))
+    v = np.asarray(v)
+    if v.size < 3:                      # no second difference, so no transition (upstream's argmax of nothing raises)
+        return None
+    return logscale_transition_idx(v)
 
 
 def bin_params(ssq_freqs, logscale):
