@@ -561,6 +561,13 @@ int64_t ssq_cwt_plan_workspace_bytes(const ssq_cwt_plan* plan, int64_t batch);
 /* How many scales of an ssq exec the cwt_os families serve (time tiles, decimated, analytic-input and full-circle
  * tiles).  0: the naive / tile / two-step / big kernels alone, which is what every upstream-variant plan gets. */
 int ssq_cwt_plan_tiled_rows(const ssq_cwt_plan* plan);
+/* Which scales each cwt_os family of an fp32 ssq exec serves, as half-open row ranges read from the fields the launcher
+ * itself uses: out = {os_a0, os_s0, os_mid, os_s1, os_d1, os_z0, os_z1, reg}.  [os_a0, os_s0): analytic-input tiles,
+ * [os_s0, os_mid): 4096-point tiles, [os_mid, os_s1): 8192-point tiles, [os_s1, os_d1): 16-fold decimated tiles,
+ * [os_z0, os_z1): full-circle phase blocks; reg: the other two-step scales run on the register core.  Rows in front of
+ * the first tiled one are reassigned before the tiles (plain stores into the cleared Tx), rows behind it after them
+ * (read-modify-write).  An empty range: that family is not launched. */
+int ssq_cwt_plan_tile_segments(const ssq_cwt_plan* plan, int32_t out[8]);
 /* cwt: d_Wx/d_dWx [batch][na][cols]; d_dWx may be NULL */
 int ssq_cwt_plan_exec_cwt(ssq_cwt_plan* plan, const void* d_x, int64_t batch, int l1_norm,
                           int rpadded, void* d_Wx, void* d_dWx,

@@ -159,6 +159,7 @@ _SIGNATURES = {
     "ssq_cwt_plan_destroy": (C.c_int, [vp]),
     "ssq_cwt_plan_workspace_bytes": (i64, [vp, i64]),
     "ssq_cwt_plan_tiled_rows": (C.c_int, [vp]),
+    "ssq_cwt_plan_tile_segments": (C.c_int, [vp, C.POINTER(C.c_int32)]),
     "ssq_cwt_plan_exec_cwt": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, i64, vp]),
     "ssq_cwt_plan_exec_ssq": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                         vp, vp, vp, vp, vp, i64, vp]),

@@ -1009,10 +1009,15 @@ static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int
         if (d1 - best1 >= 4) pl->os_d1 = d1;
         // in front of them the finest scales, whose psih is NOT negligible at Nyquist, on tiles of the analytic signal
         // (register-core plans compute it with one extra transform); the continued spectrum must vanish by 2 pi:
-        // Morlet a >= 1.97, GMW a >= 0.64 (profiles/r02_ab_cwt_os_analytic.txt)
+        // Morlet a >= 1.97, GMW a >= 0.64 (profiles/r02_ab_cwt_os_analytic.txt) -- and must PEAK below the Nyquist
+        // frequency: the fp32 analytic signal carries rounding noise (2^-24 of the signal) in the half of its spectrum
+        // that should be empty, and the continued wavelet multiplies it by its gain THERE.  With the peak at
+        // w_c / a > pi (GMW: w_c = 20^(1/3) = 2.714, a < 0.864) that gain exceeds every gain the signal itself meets:
+        // a = 0.707 on a tone at 0.05 cycles per sample came out 6.8e-4 of the row maximum off the oracle where the
+        // frequency-domain path is 6.6e-6 off.  Morlet: 6 / 1.97 < pi already
         pl->os_a0 = best0;
         if (pl->reg) {
-          const double a_ext = wavelet == SSQ_WAVELET_MORLET ? 1.97 : 0.64;
+          const double a_ext = wavelet == SSQ_WAVELET_MORLET ? 1.97 : 0.87;
           int a0 = best0;
           while (a0 > 0 && scales[a0 - 1] >= a_ext && pl->zoom_logq[(size_t)(a0 - 1)] == 0) --a0;
           pl->os_a0 = a0;
@@ -1118,6 +1123,21 @@ int ssq_cwt_plan_tiled_rows(const ssq_cwt_plan* pl) {
   int rows = 0;
   for (const auto m : pl->os_mask) rows += m ? 1 : 0;
   return rows;
+}
+
+int ssq_cwt_plan_tile_segments(const ssq_cwt_plan* pl, int32_t out[8]) {
+  if (!pl) SSQ_FAIL("plan is NULL");
+  if (!out) SSQ_FAIL("out is NULL");
+  // the fields exec_ssq_typed launches from, in its launch order
+  out[0] = pl->os_a0;
+  out[1] = pl->os_s0;
+  out[2] = pl->os_mid;
+  out[3] = pl->os_s1;
+  out[4] = pl->os_d1;
+  out[5] = pl->os_z0;
+  out[6] = pl->os_z1;
+  out[7] = pl->reg ? 1 : 0;
+  return 0;
 }
 
 int64_t ssq_cwt_plan_workspace_bytes(const ssq_cwt_plan* pl, int64_t batch) {

@@ -44,6 +44,21 @@ def test_launch_info_is_declared_bound_and_rejects_bad_arguments():
     assert b"plan is NULL" in lib.ssq_last_error()
 
 
+def test_tile_segments_query_is_declared_bound_and_rejects_bad_arguments():
+    """ssq_cwt_plan_tile_segments: in the header with the argument list of the ctypes table, and NULL arguments are
+    errors with a message (the query itself needs a plan, hence a GPU: tests/test_gpu_cwt_tiles.py)."""
+    lib = _lib.load()
+    assert "ssq_cwt_plan_tile_segments" in _lib.header_symbols()
+    res, args = _lib._SIGNATURES["ssq_cwt_plan_tile_segments"]
+    assert res is C.c_int and args == [C.c_void_p, C.POINTER(C.c_int32)]
+    with open(_lib.HEADER_PATH) as f:
+        decl = f.read().split("int ssq_cwt_plan_tile_segments(", 1)[1].split(");", 1)[0]
+    assert [a.strip() for a in decl.split(",")] == ["const ssq_cwt_plan* plan", "int32_t out[8]"]
+    out = (C.c_int32 * 8)(*([7] * 8))
+    assert lib.ssq_cwt_plan_tile_segments(None, out) != 0 and list(out) == [7] * 8
+    assert b"plan is NULL" in lib.ssq_last_error()
+
+
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 

@@ -10,6 +10,7 @@ import pytest
 
 from oracle import ssq_oracle as o
 from ssqueeze_rs_amd import _rs
+from tests.helpers.cwt_scatter_check import assert_scatter_cells
 
 pytestmark = pytest.mark.gpu
 
@@ -112,18 +113,10 @@ def _check_ssq_cwt(x, tol_w, **kw):
         assert (np.abs(np.abs(v - np.trunc(v)) - 0.5) < tie_tol).all(), f"{mism.sum()} unexplained"
         assert mism.mean() <= (1e-4 if x.dtype == np.float64 else 1e-5)
     keep = dbg["k"] >= 0
-    # scatter: re-accumulate with the kernel's own bins (no dw factor in the CWT path)
-    Tx_re = np.zeros_like(Tx_o)
-    cols = np.arange(x.shape[0])
+    # scatter: re-accumulate with the kernel's own bins (no dw factor in the CWT path), cell by cell: empty cells exactly
+    # zero, single terms bitwise, sums to the recursive-summation bound (tests/helpers/cwt_scatter_check.py)
     leb = kw.get("squeezing") == "lebesgue"
-    Wg = dbg["Wx"].astype(np.complex128)
-    for i in range(na):
-        m = keep[i]
-        if leb:
-            Tx_re[dbg["k"][i, m], cols[m]] += 1.0 / na
-        else:
-            Tx_re[dbg["k"][i, m], cols[m]] += Wg[i, m]
-    assert np.abs(Tx - Tx_re).max() <= (1e-10 if x.dtype == np.float64 else 2e-5) * max(np.abs(Tx_re).max(), 1e-300)
+    assert_scatter_cells(Tx, dbg["Wx"], dbg["k"], leb, x.dtype)
     # end to end: column sums are invariant under bin flips (not under keep/drop flips)
     # keep/drop may only differ where Wx is rounding noise (the un-normalised GMW leaves ~1e17*eps there)
     flips = keep != im["valid"]
