@@ -1,6 +1,7 @@
 // stft_fused.hip -- launches of the fused STFT / synchrosqueezed-STFT kernel (stft_fused_kernel.h) for power-of-two
 // n_fft, and the 16-wave kernel for fp32 n_fft = 1024 (the headline path).
 #include "stft_fused_kernel.h"
+#include "tx1024_lds_layout.h"
 
 namespace ssq {
 
@@ -12,7 +13,9 @@ namespace ssq {
 //     8 values; lanes 32-63 write, all read the other 8) -- the DS unit runs a wave's ops in order;
 //   * exchange 2 is a 4x4 transpose between the four 16-lane rows and the low two bits of the register
 //     index: v_permlane32_swap + v_permlane16_swap, no LDS;
-//   * twiddles come from an LDS copy of the W_1024 table, samples are prefetched one tile ahead.
+//   * twiddles come from an LDS copy of the W_1024 table, samples are prefetched one tile ahead;
+//   * window, twiddles and the exchange-1 row are laid out (tx1024_lds_layout.h) so that the two elements a lane
+//     consumes together are adjacent: every such read is one ds_read_b128.
 // One tile = one frame per wave, so the tile barrier comes once per frame per wave.
 // ---------------------------------------------------------------------------------------------
 // (Measured and not kept: the FFT on packed fp32 -- 25 % fewer vector instructions, same time, because two waves already
@@ -23,14 +26,24 @@ struct Hi1024 {
   static constexpr int N = 1024, L = 64, NF = 513, W = 16, F = 16, PITCH = F + 1, THREADS = W * 64;
   static constexpr int PLANE = NF * PITCH;
   static constexpr int TILE_BYTES = (((2 * PLANE + F) * 4 + 15) / 16) * 16;
-  // the register-half exchange lays a half row out as 64 writers x (8 values + 1 pad)
-  static constexpr int EXH_ELEMS = 64 * 9;
+  // the register-half exchange lays a half row out as 32 blocks (r, g) of 8 values x 2 writers (+ pads)
+  static constexpr int EXH_ELEMS = tx1024::EXCH_ELEMS;
   static constexpr int EXH_BYTES = W * EXH_ELEMS * 8;
-  static constexpr int TAB_BYTES = N * 8;                   // window table; twiddle tables [16][16] + [3][256] (+pad)
-  static constexpr int LDS_BYTES = TILE_BYTES + EXH_BYTES + 2 * TAB_BYTES;
+  static constexpr int TAB_BYTES = tx1024::TAB_ELEMS * 8;   // window table [8][64][2]; twiddle tables [16][18] + [6][64][2]
+  static constexpr int LDS_BYTES = TILE_BYTES + EXH_BYTES + TAB_BYTES;
   static constexpr int FRAC = 30, EMIN = -90;
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+  static_assert(N == tx1024::N && NF == tx1024::NF && W == tx1024::W && F == tx1024::F && PITCH == tx1024::PITCH &&
+                    TILE_BYTES == tx1024::TILE_BYTES && LDS_BYTES == tx1024::LDS_BYTES,
+                "tx1024_lds_layout.h describes this kernel's image (and asserts the 16-byte alignment of its parts)");
 };
+
+// two adjacent complex elements at a 16-byte aligned LDS address: one ds_read_b128
+__device__ __forceinline__ void lds_pair(const cpx<float>* q, cpx<float>& a, cpx<float>& b) {
+  const float4 w = *reinterpret_cast<const float4*>(q);
+  a = {w.x, w.y};
+  b = {w.z, w.w};
+}
 
 // 4x4 transpose of R[0..3] across the four 16-lane rows of the wave (one dword per lane per register)
 __device__ __forceinline__ void rows_transpose4(float& r0, float& r1, float& r2, float& r3) {
@@ -57,8 +70,9 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
   float* col_scale = reinterpret_cast<float*>(tile_re + 2 * H::PLANE);
   cpx<T>* exch_all = reinterpret_cast<cpx<T>*>(smem + H::TILE_BYTES);
   cpx<T>* win_lds = reinterpret_cast<cpx<T>*>(smem + H::TILE_BYTES + H::EXH_BYTES);
-  cpx<T>* tw1 = win_lds + N;        // pass 1: [m = 0..15][k = 0..15]   W_256^(k m)
-  cpx<T>* tw2 = tw1 + 256;          // pass 2: [m = 0..2][j = 0..255]   W_1024^(j (m+1))  (row m+1 of the compact layout)
+  namespace X = tx1024;
+  cpx<T>* tw1 = win_lds + X::WIN_ELEMS;   // pass 1: [k = 0..15][m = 1..15, filler | 2 pad]   W_256^(k m)
+  cpx<T>* tw2 = tw1 + X::TW1_ELEMS;       // pass 2: [pair i = 0..5][t = 0..63][2]   W_1024^((t + 64 b) m), (b, m) b-major
 
   const int tid = threadIdx.x;
   const int t = tid & 63;          // lane = position inside the frame
@@ -67,9 +81,11 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
   const int fl = __builtin_amdgcn_readfirstlane(tid >> 6);         // wave = frame inside the tile
   cpx<T>* exch = exch_all + fl * H::EXH_ELEMS;
 
-  for (int i = tid; i < N; i += THREADS) win_lds[i] = p.win2[i];
-  if (tid < 256) tw1[tid] = p.tw[((tid & 15) * (tid >> 4) * 4) & (N - 1)];
-  for (int i = tid; i < 768; i += THREADS) tw2[i] = p.tw[((i & 255) * ((i >> 8) + 1)) & (N - 1)];
+  // table fill in SLOT order: consecutive threads store consecutive LDS elements (no bank conflicts) and gather the
+  // 16 KiB of cached global tables instead; the pads of the pass-1 rows get W^0 like the filler
+  for (int s = tid; s < X::WIN_ELEMS; s += THREADS) win_lds[s] = p.win2[X::win_elem(s)];
+  for (int s = tid; s < X::TW1_ELEMS; s += THREADS) tw1[s] = p.tw[(X::tw1_k(s) * X::tw1_m(s) * 4) & (N - 1)];
+  for (int s = tid; s < X::TW2_ELEMS; s += THREADS) tw2[s] = p.tw[(X::tw2_j(s) * X::tw2_m(s)) & (N - 1)];
   // 64-bit cells start at RE = 2^31: RE + 2^31 stays in [0, 2^32), so no borrow ever reaches the high word and the
   // read-out takes IM = high word, RE = low word ^ 2^31 -- one instruction less per cell than undoing a borrow
   constexpr long long CELL0 = WKDBG ? 0LL : 0x80000000LL;
@@ -184,29 +200,31 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
     const bool has_next = nsig < n_sig;
     cpx<T> v[16];
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const cpx<T> wq = win_lds[t + L * q];
-      v[q] = {xn[q] * wq.x, xn[q] * wq.y};
+    for (int j = 0; j < 8; ++j) {
+      cpx<T> w0, w1;
+      lds_pair(win_lds + X::win_row(t, j), w0, w1);
+      v[2 * j] = {xn[2 * j] * w0.x, xn[2 * j] * w0.y};
+      v[2 * j + 1] = {xn[2 * j + 1] * w1.x, xn[2 * j + 1] * w1.y};
     }
 
     // ---- pass 0: radix 16 over elements t + 64q ----
-    fft_compute<T, 10, 0, false, false>(v, twr_unused, tw1, t);
+    fft_compute<T, 10, 0, false, false>(v, twr_unused, nullptr, t);
     // ---- exchange 1 by REGISTER halves: in phase ph EVERY lane writes its values u = 8 ph .. 8 ph + 7 (elements
     //      16 t + u) -- full-width stores -- and the lanes whose element residue (t & 15) lies in that half read all 16
     //      of their elements t + 64 q = 16 ((t >> 4) + 4 q) + (t & 15).
-    //      Row layout: writer lane t' at 9 t' + (u & 7): pitch 9 elements = 18 dwords keeps both the 16-lane store
-    //      groups and the 32-lane load groups on distinct banks.
+    //      Row layout (tx1024_lds_layout.h): the values of writers (t >> 4) + 8 g and + 8 g + 4 are adjacent, so the
+    //      16 loads are 8 of 16 bytes; store groups and load groups stay on distinct banks.
     {
       cpx<T> nv[16];
-      const int rbase = 9 * (t >> 4) + (t & 7);
+      const int sbase = X::exch_store_base(t), lbase = X::exch_load_base(t);
 #pragma unroll
       for (int ph = 0; ph < 2; ++ph) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) exch[9 * t + u] = v[8 * ph + u];
+        for (int u = 0; u < 8; ++u) exch[sbase + X::exch_val(u)] = v[8 * ph + u];
         frame_sync<false>();
         if (((t >> 3) & 1) == ph) {
 #pragma unroll
-          for (int q = 0; q < 16; ++q) nv[q] = exch[rbase + 36 * q];
+          for (int g = 0; g < 8; ++g) lds_pair(exch + lbase + X::exch_load_off(g), nv[2 * g], nv[2 * g + 1]);
         }
         frame_sync<false>();
       }
@@ -217,8 +235,19 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
     // register set of the frame are live, and 16 more registers in flight there push the kernel into scratch; the rest
     // of this tile (pass 1, pass 2, epilogue, read-out: > 10k cycles) still covers the HBM latency many times over
     if (has_next) load_frame(nsig, tile_frame0(njt), xn);
-    // ---- pass 1: twiddle W_256^(k m), radix 16 ----
-    fft_compute<T, 10, 1, false, false, true>(v, twr_unused, tw1, t);
+    // ---- pass 1: twiddle W_256^(k m), radix 16 (fft_compute's multiply order, the twiddles fetched in pairs) ----
+    {
+      const cpx<T>* row = tw1 + X::tw1_row(t & 15, 0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        cpx<T> w0, w1;
+        lds_pair(row + 2 * i, w0, w1);
+        v[2 * i + 1] = cmul(v[2 * i + 1], w0);
+        if (i < 7) v[2 * i + 2] = cmul(v[2 * i + 2], w1);       // (the pair of m = 15 is the filler)
+      }
+      constexpr int R = pass_radix(10, 1), NB = 16 / R;
+      butterflies<false, R, NB>(v, std::make_integer_sequence<int, NB>{});
+    }
     // ---- exchange 2: producer (row m, k), reg u = 4 uh + ul  ->  consumer (row ul, k), reg 4 m + uh ----
     {
 #pragma unroll
@@ -237,7 +266,19 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
 #undef SSQ_SWAP
     }
     // ---- pass 2: twiddle W_1024^((t + 64 b) m), four radix-4 butterflies ----
-    fft_compute<T, 10, 2, false, false, true>(v, twr_unused, tw2 - 256, t);   // compact index m*256 + j, m = 1..3
+    {
+      constexpr int R = pass_radix(10, 2), NB = 16 / R;
+      static_assert(R == 4 && NB == 4, "tw2 rows hold (b, m), b < 4, m = 1..3");
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        cpx<T> w0, w1;
+        lds_pair(tw2 + X::tw2_row(t, i), w0, w1);
+        const int e0 = 2 * i, e1 = 2 * i + 1;                  // entry e = 3 b + (m - 1) multiplies v[b + m NB]
+        v[e0 / 3 + (e0 % 3 + 1) * NB] = cmul(v[e0 / 3 + (e0 % 3 + 1) * NB], w0);
+        v[e1 / 3 + (e1 % 3 + 1) * NB] = cmul(v[e1 / 3 + (e1 % 3 + 1) * NB], w1);
+      }
+      butterflies<false, R, NB>(v, std::make_integer_sequence<int, NB>{});
+    }
     // lane t now holds Z[t + 64 q]
 
     // ---- partner Z[N-k] for the bins this lane owns ----
