@@ -89,6 +89,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import warnings
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -116,6 +117,47 @@ def _signal(x):
     batched = x.ndim == 2
     xa = np.ascontiguousarray(x if batched else x[None, :])
     return xa, batched, (SSQ_F32 if xa.dtype == np.float32 else SSQ_F64)
+
+
+def _rdtype(code):
+    return np.float32 if code == SSQ_F32 else np.float64
+
+
+def _ccode(dtype):
+    """The library's dtype code of a complex64 / complex128 map."""
+    return SSQ_F32 if dtype == np.complex64 else SSQ_F64
+
+
+def _eps(code):
+    return EPS32 if code == SSQ_F32 else EPS64
+
+
+def _gamma_arg(gamma):
+    """`gamma` as the library takes it: -1 asks for its default (10 eps of the dtype)."""
+    return -1.0 if gamma is None else float(gamma)
+
+
+def _unbatch(batched, *arrays):
+    """The arrays that are not None, without the batch axis where the call's input had none."""
+    return [a if batched else a[0] for a in arrays if a is not None]
+
+
+def _squeeze_code(squeezing):
+    if squeezing not in SQUEEZE:
+        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
+    return SQUEEZE[squeezing]
+
+
+def _order12(order, built):
+    if isinstance(order, (bool, np.bool_)) or order not in (1, 2):
+        raise ValueError(f"order {order!r}: {built}")
+    return int(order)
+
+
+def _shape_checked(lib, rc):
+    """A `*_workspace_bytes` result: negative is the C entry's refusal of the shape (made on the host, no GPU)."""
+    if rc < 0:
+        raise ValueError(lib.ssq_last_error().decode("utf-8", "replace"))
 
 
 def _pad_code(padtype):
@@ -281,27 +323,63 @@ def p2up(n):
 
 
 # --------------------------------------------------------------------------------------------------- STFT family ----
+SST2_MIN_N_FFT, SST2_MAX_N_FFT = 16, 4096     # csrc/stft_sst2.hip: one frame is held by n_fft / 16 lanes of a workgroup
+
+
+def _stft_front(x, window, n_fft, win_len, hop_len, fs, t, pow2_for=None):
+    """The front end of the STFT family: the signal, `fs`, the `n_fft` and `win_len` defaults, the sized window and
+    the dtypes of the results.  `pow2_for`: the name of a transform whose kernels take a
+    power-of-two `n_fft` only (None: any length)."""
+    f = SimpleNamespace()
+    f.xa, f.batched, f.code = _signal(x)
+    f.batch, f.N = f.xa.shape
+    f.fs = 1.0 / _dt(fs, t, f.N)
+    n_fft = n_fft or min(f.N // hop_len, 512)
+    if pow2_for is not None:
+        if (not isinstance(n_fft, (int, np.integer)) or isinstance(n_fft, (bool, np.bool_))
+                or not SST2_MIN_N_FFT <= n_fft <= SST2_MAX_N_FFT or n_fft & (n_fft - 1)):
+            raise ValueError(f"n_fft {n_fft!r}: {pow2_for} takes a power of two from {SST2_MIN_N_FFT} to {SST2_MAX_N_FFT}")
+        n_fft = int(n_fft)
+    if win_len is None:
+        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
+    f.n_fft, f.win = n_fft, get_window(window, win_len, n_fft)
+    f.n_freqs = n_fft // 2 + 1
+    f.cdt, f.rdt = _cdtype(f.code), _rdtype(f.code)
+    return f
+
+
+def _stft_shape(f, hop_len):
+    """The shape of the family's maps.  Its callers ask for the GPU first: `hop_len = 0` with an `n_fft` given divides by
+    zero here, after `require_gpu()`, as it always has."""
+    f.n_frames = (f.N - 1) // hop_len + 1
+    return f.batch, f.n_freqs, f.n_frames
+
+
+def _variant(modulated, flipud=False):
+    return VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0) | (VARIANT_FLIPUD if flipud else 0)
+
+
+def _Sfs(f):
+    return np.linspace(0, .5 * f.fs, f.n_freqs, dtype=f.rdt)               # _ssq_stft.py:248-257
+
+
+def _times(f, hop_len):
+    return (np.arange(f.n_frames) * hop_len / f.fs).astype(f.rdt)
+
+
 def stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, padtype="reflect", modulated=True,
          derivative=False, dtype=None):
     """ssqueezepy.stft (old/ssqueezepy/_stft.py:13-193) -> Sx, or (Sx, dSx) with derivative=True."""
     lib = _lib.load()
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    fs = 1.0 / _dt(fs, t, N)
-    n_fft = n_fft or min(N // hop_len, 512)
-    if win_len is None:
-        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
-    win = get_window(window, win_len, n_fft)
+    f = _stft_front(x, window, n_fft, win_len, hop_len, fs, t)
     _lib.require_gpu()
-    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0)
-    shape = (batch, n_fft // 2 + 1, (N - 1) // hop_len + 1)
-    Sx = _lib.pinned_empty(shape, _cdtype(code))
-    dSx = _lib.pinned_empty(shape, _cdtype(code)) if derivative else None
-    _call(lib.ssq_stft_host_v(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, _pad_code(padtype), variant,
-                              _ptr(Sx), _ptr(dSx)))
-    if not batched:
-        Sx, dSx = Sx[0], (dSx[0] if derivative else None)
-    return (Sx, dSx) if derivative else Sx
+    shape = _stft_shape(f, hop_len)
+    Sx = _lib.pinned_empty(shape, f.cdt)
+    dSx = _lib.pinned_empty(shape, f.cdt) if derivative else None
+    _call(lib.ssq_stft_host_v(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs,
+                              _pad_code(padtype), _variant(modulated), _ptr(Sx), _ptr(dSx)))   # (padtype: after the GPU)
+    out = _unbatch(f.batched, Sx, dSx)
+    return tuple(out) if derivative else out[0]
 
 
 def istft(Sx, window=None, n_fft=None, win_len=None, hop_len=1, N=None, modulated=True, win_exp=1):
@@ -319,7 +397,7 @@ def istft(Sx, window=None, n_fft=None, win_len=None, hop_len=1, N=None, modulate
     if Sx.ndim == 3 and Sx.shape[0] < 1:
         raise ValueError("`Sx` holds no signal (B == 0)")
     win = get_window(window, win_len, n_fft)
-    code = SSQ_F32 if Sx.dtype == np.complex64 else SSQ_F64
+    code = _ccode(Sx.dtype)
     _lib.require_gpu()
     Sc = np.ascontiguousarray(Sx)
     if Sx.ndim == 3:
@@ -327,7 +405,7 @@ def istft(Sx, window=None, n_fft=None, win_len=None, hop_len=1, N=None, modulate
         _call(lib.ssq_istft_batch_host(code, _ptr(Sc), Sc.shape[0], Sc.shape[2], _ptr(win), n_fft, hop_len, N,
                                        int(bool(modulated)), int(win_exp), _ptr(x)))
         return x
-    x = np.empty(N, dtype=np.float32 if code == SSQ_F32 else np.float64)
+    x = np.empty(N, dtype=_rdtype(code))
     _call(lib.ssq_istft_host(code, _ptr(Sc), Sc.shape[1], _ptr(win), n_fft, hop_len, N, int(bool(modulated)),
                              int(win_exp), _ptr(x)))
     return x
@@ -340,39 +418,19 @@ def ssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=Non
     lib = _lib.load()
     if ssq_freqs is not None:
         raise ValueError("`ssq_freqs` other than None (= Sfs, linear) is not built")
-    if squeezing not in SQUEEZE:
-        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    fs = 1.0 / _dt(fs, t, N)
-    n_fft = n_fft or min(N // hop_len, 512)
-    if win_len is None:
-        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
-    win = get_window(window, win_len, n_fft)
+    squeeze = _squeeze_code(squeezing)
+    f = _stft_front(x, window, n_fft, win_len, hop_len, fs, t)
     _lib.require_gpu()
-    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0) | (VARIANT_FLIPUD if flipud else 0)
-    n_freqs, n_frames = n_fft // 2 + 1, (N - 1) // hop_len + 1
-    shape = (batch, n_freqs, n_frames)
-    cdt = _cdtype(code)
-    Tx, Sx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
-    dSx = _lib.pinned_empty(shape, cdt) if get_dWx else None
-    wk = _lib.pinned_empty(shape, cdt) if get_w else None
-    f = np.empty(n_freqs, dtype=np.float64)
-    _call(lib.ssq_ssq_stft_host_v(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, _pad_code(padtype),
-                                  SQUEEZE[squeezing], -1.0 if gamma is None else float(gamma), variant, _ptr(Tx),
-                                  _ptr(f), _ptr(Sx), _ptr(dSx), _ptr(wk)))
-    rdt = np.float32 if code == SSQ_F32 else np.float64
-    Sfs = np.linspace(0, .5 * fs, n_freqs, dtype=rdt)                      # _ssq_stft.py:248-257
-    out = [Tx if batched else Tx[0], Sx if batched else Sx[0], f.astype(rdt), Sfs]
-    if get_w:
-        w = wk.real.copy()
-        out.append(w if batched else w[0])
-    if get_dWx:
-        out.append(dSx if batched else dSx[0])
-    return tuple(out)
-
-
-SST2_MIN_N_FFT, SST2_MAX_N_FFT = 16, 4096     # csrc/stft_sst2.hip: one frame is held by n_fft / 16 lanes of a workgroup
+    shape = _stft_shape(f, hop_len)
+    Tx, Sx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    dSx = _lib.pinned_empty(shape, f.cdt) if get_dWx else None
+    wk = _lib.pinned_empty(shape, f.cdt) if get_w else None
+    freqs = np.empty(f.n_freqs, dtype=np.float64)
+    _call(lib.ssq_ssq_stft_host_v(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs,
+                                  _pad_code(padtype), squeeze, _gamma_arg(gamma),     # (padtype: after the GPU)
+                                  _variant(modulated, flipud), _ptr(Tx), _ptr(freqs), _ptr(Sx), _ptr(dSx), _ptr(wk)))
+    w = wk.real.copy() if get_w else None
+    return (*_unbatch(f.batched, Tx, Sx), freqs.astype(f.rdt), _Sfs(f), *_unbatch(f.batched, w, dSx))
 
 
 def ssq_stft2(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
@@ -399,35 +457,18 @@ def ssq_stft2(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=No
     in that range is built without register spills or scratch (profiles/sst2_resources.txt), so none is refused on
     those grounds."""
     lib = _lib.load()
-    if squeezing not in SQUEEZE:
-        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    fs = 1.0 / _dt(fs, t, N)
-    n_fft = n_fft or min(N // hop_len, 512)
-    if (not isinstance(n_fft, (int, np.integer)) or isinstance(n_fft, (bool, np.bool_))
-            or not SST2_MIN_N_FFT <= n_fft <= SST2_MAX_N_FFT or n_fft & (n_fft - 1)):
-        raise ValueError(f"n_fft {n_fft!r}: ssq_stft2 takes a power of two from {SST2_MIN_N_FFT} to {SST2_MAX_N_FFT}")
-    n_fft = int(n_fft)
-    if win_len is None:
-        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
-    win = get_window(window, win_len, n_fft)
+    squeeze = _squeeze_code(squeezing)
+    f = _stft_front(x, window, n_fft, win_len, hop_len, fs, t, "ssq_stft2")
     pad = _pad_code(padtype)
     _lib.require_gpu()
-    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0) | (VARIANT_FLIPUD if flipud else 0)
-    n_freqs, n_frames = n_fft // 2 + 1, (N - 1) // hop_len + 1
-    shape = (batch, n_freqs, n_frames)
-    cdt, rdt = _cdtype(code), _rdtype(code)
-    Tx, Sx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
-    w2 = _lib.pinned_empty(shape, rdt) if get_w else None
-    f = np.empty(n_freqs, dtype=np.float64)
-    _call(lib.ssq_ssq_stft2_host(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, pad, SQUEEZE[squeezing],
-                                 -1.0 if gamma is None else float(gamma), variant, _ptr(Tx), _ptr(f), _ptr(Sx), _ptr(w2)))
-    Sfs = np.linspace(0, .5 * fs, n_freqs, dtype=rdt)
-    out = [Tx if batched else Tx[0], Sx if batched else Sx[0], f.astype(rdt), Sfs]
-    if get_w:
-        out.append(w2 if batched else w2[0])
-    return tuple(out)
+    shape = _stft_shape(f, hop_len)
+    Tx, Sx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    w2 = _lib.pinned_empty(shape, f.rdt) if get_w else None
+    freqs = np.empty(f.n_freqs, dtype=np.float64)
+    _call(lib.ssq_ssq_stft2_host(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs, pad,
+                                 squeeze, _gamma_arg(gamma), _variant(modulated, flipud), _ptr(Tx),
+                                 _ptr(freqs), _ptr(Sx), _ptr(w2)))
+    return (*_unbatch(f.batched, Tx, Sx), freqs.astype(f.rdt), _Sfs(f), *_unbatch(f.batched, w2))
 
 
 MSST_MAX_ITER = 64                      # csrc/stft_msst.hip: kWalkMaxIter, a bound on work (not a measured number)
@@ -471,42 +512,21 @@ def mssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=No
     instantiation of the operator are built without register spills or scratch (profiles/msst_resources.txt,
     profiles/sst2_resources.txt)."""
     lib = _lib.load()
-    if isinstance(order, (bool, np.bool_)) or order not in (1, 2):
-        raise ValueError(f"order {order!r}: mssq_stft builds orders 1 and 2")
+    order = _order12(order, "mssq_stft builds orders 1 and 2")
     n_iter = _n_iter(n_iter)
-    if squeezing not in SQUEEZE:
-        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    fs = 1.0 / _dt(fs, t, N)
-    n_fft = n_fft or min(N // hop_len, 512)
-    if (not isinstance(n_fft, (int, np.integer)) or isinstance(n_fft, (bool, np.bool_))
-            or not SST2_MIN_N_FFT <= n_fft <= SST2_MAX_N_FFT or n_fft & (n_fft - 1)):
-        raise ValueError(f"n_fft {n_fft!r}: mssq_stft takes a power of two from {SST2_MIN_N_FFT} to {SST2_MAX_N_FFT}")
-    n_fft = int(n_fft)
-    if win_len is None:
-        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
-    win = get_window(window, win_len, n_fft)
+    squeeze = _squeeze_code(squeezing)
+    f = _stft_front(x, window, n_fft, win_len, hop_len, fs, t, "mssq_stft")
     pad = _pad_code(padtype)
     _lib.require_gpu()
-    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0) | (VARIANT_FLIPUD if flipud else 0)
-    n_freqs, n_frames = n_fft // 2 + 1, (N - 1) // hop_len + 1
-    shape = (batch, n_freqs, n_frames)
-    cdt, rdt = _cdtype(code), _rdtype(code)
-    Tx, Sx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
-    w = _lib.pinned_empty(shape, rdt) if get_w else None
+    shape = _stft_shape(f, hop_len)
+    Tx, Sx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    w = _lib.pinned_empty(shape, f.rdt) if get_w else None
     bins = _lib.pinned_empty(shape, np.int32) if get_bins else None
-    f = np.empty(n_freqs, dtype=np.float64)
-    _call(lib.ssq_mssq_stft_host(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, pad, SQUEEZE[squeezing],
-                                 -1.0 if gamma is None else float(gamma), variant, int(order), n_iter, _ptr(Tx), _ptr(f),
-                                 _ptr(Sx), _ptr(w), _ptr(bins)))
-    Sfs = np.linspace(0, .5 * fs, n_freqs, dtype=rdt)
-    out = [Tx if batched else Tx[0], Sx if batched else Sx[0], f.astype(rdt), Sfs]
-    if get_w:
-        out.append(w if batched else w[0])
-    if get_bins:
-        out.append(bins if batched else bins[0])
-    return tuple(out)
+    freqs = np.empty(f.n_freqs, dtype=np.float64)
+    _call(lib.ssq_mssq_stft_host(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs, pad,
+                                 squeeze, _gamma_arg(gamma), _variant(modulated, flipud), order, n_iter,
+                                 _ptr(Tx), _ptr(freqs), _ptr(Sx), _ptr(w), _ptr(bins)))
+    return (*_unbatch(f.batched, Tx, Sx), freqs.astype(f.rdt), _Sfs(f), *_unbatch(f.batched, w, bins))
 
 
 def msst_walk(bins, n_iter):
@@ -528,7 +548,7 @@ def msst_walk(bins, n_iter):
     _lib.require_gpu()
     out = np.empty_like(b3)
     _call(lib.ssq_msst_walk_host(_ptr(b3), B, F, n, n_iter, _ptr(out)))
-    return out if bins.ndim == 3 else out[0]
+    return _unbatch(bins.ndim == 3, out)[0]
 
 
 def msst_tile_cols(n_rows):
@@ -568,37 +588,18 @@ def tssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=No
     `n_fft` must be a power of two from 16 to 4096 and `order` 1 or 2 (ValueError otherwise, before any GPU work).  Every
     (dtype, n_fft, order) is built without register spills or scratch (profiles/tsst_resources.txt)."""
     lib = _lib.load()
-    if isinstance(order, (bool, np.bool_)) or order not in (1, 2):
-        raise ValueError(f"order {order!r}: tssq_stft builds orders 1 and 2")
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    fs = 1.0 / _dt(fs, t, N)
-    n_fft = n_fft or min(N // hop_len, 512)
-    if (not isinstance(n_fft, (int, np.integer)) or isinstance(n_fft, (bool, np.bool_))
-            or not SST2_MIN_N_FFT <= n_fft <= SST2_MAX_N_FFT or n_fft & (n_fft - 1)):
-        raise ValueError(f"n_fft {n_fft!r}: tssq_stft takes a power of two from {SST2_MIN_N_FFT} to {SST2_MAX_N_FFT}")
-    n_fft = int(n_fft)
+    order = _order12(order, "tssq_stft builds orders 1 and 2")
+    f = _stft_front(x, window, n_fft, win_len, hop_len, fs, t, "tssq_stft")
     if gamma is not None and math.isnan(float(gamma)):
         raise ValueError("gamma is NaN")
-    if win_len is None:
-        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
-    win = get_window(window, win_len, n_fft)
     pad = _pad_code(padtype)
     _lib.require_gpu()
-    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0)
-    n_freqs, n_frames = n_fft // 2 + 1, (N - 1) // hop_len + 1
-    shape = (batch, n_freqs, n_frames)
-    cdt, rdt = _cdtype(code), _rdtype(code)
-    Tx, Sx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
-    tau = _lib.pinned_empty(shape, rdt) if get_tau else None
-    _call(lib.ssq_tssq_stft_host(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, pad, int(order),
-                                 -1.0 if gamma is None else float(gamma), variant, _ptr(Tx), _ptr(Sx), _ptr(tau)))
-    times = (np.arange(n_frames) * hop_len / fs).astype(rdt)
-    Sfs = np.linspace(0, .5 * fs, n_freqs, dtype=rdt)
-    out = [Tx if batched else Tx[0], Sx if batched else Sx[0], times, Sfs]
-    if get_tau:
-        out.append(tau if batched else tau[0])
-    return tuple(out)
+    shape = _stft_shape(f, hop_len)
+    Tx, Sx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    tau = _lib.pinned_empty(shape, f.rdt) if get_tau else None
+    _call(lib.ssq_tssq_stft_host(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs, pad, order,
+                                 _gamma_arg(gamma), _variant(modulated), _ptr(Tx), _ptr(Sx), _ptr(tau)))
+    return (*_unbatch(f.batched, Tx, Sx), _times(f, hop_len), _Sfs(f), *_unbatch(f.batched, tau))
 
 
 # csrc/stft_reassign.hip: kReassignQuantumLog2.  `reassign_stft` accumulates |Sx|^2 in 64-bit fixed point with the quantum
@@ -641,38 +642,18 @@ def reassign_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, 
     before any GPU work).  Every (dtype, n_fft) is built without register spills or scratch
     (profiles/reassign_resources.txt)."""
     lib = _lib.load()
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    fs = 1.0 / _dt(fs, t, N)
-    n_fft = n_fft or min(N // hop_len, 512)
-    if (not isinstance(n_fft, (int, np.integer)) or isinstance(n_fft, (bool, np.bool_))
-            or not SST2_MIN_N_FFT <= n_fft <= SST2_MAX_N_FFT or n_fft & (n_fft - 1)):
-        raise ValueError(f"n_fft {n_fft!r}: reassign_stft takes a power of two from {SST2_MIN_N_FFT} to {SST2_MAX_N_FFT}")
-    n_fft = int(n_fft)
+    f = _stft_front(x, window, n_fft, win_len, hop_len, fs, t, "reassign_stft")
     if gamma is not None and math.isnan(float(gamma)):
         raise ValueError("gamma is NaN")
-    if win_len is None:
-        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
-    win = get_window(window, win_len, n_fft)
     pad = _pad_code(padtype)
     _lib.require_gpu()
-    variant = VARIANT_UPSTREAM | (VARIANT_MODULATED if modulated else 0)
-    n_freqs, n_frames = n_fft // 2 + 1, (N - 1) // hop_len + 1
-    shape = (batch, n_freqs, n_frames)
-    cdt, rdt = _cdtype(code), _rdtype(code)
-    Rx, Sx = _lib.pinned_empty(shape, rdt), _lib.pinned_empty(shape, cdt)
-    w = _lib.pinned_empty(shape, rdt) if get_w else None
-    tau = _lib.pinned_empty(shape, rdt) if get_tau else None
-    _call(lib.ssq_reassign_stft_host(code, _ptr(xa), batch, N, _ptr(win), n_fft, hop_len, fs, pad,
-                                     -1.0 if gamma is None else float(gamma), variant, _ptr(Rx), _ptr(Sx), _ptr(w),
-                                     _ptr(tau)))
-    times = (np.arange(n_frames) * hop_len / fs).astype(rdt)
-    Sfs = np.linspace(0, .5 * fs, n_freqs, dtype=rdt)
-    out = [Rx if batched else Rx[0], Sx if batched else Sx[0], times, Sfs]
-    for a in (w, tau):
-        if a is not None:
-            out.append(a if batched else a[0])
-    return tuple(out)
+    shape = _stft_shape(f, hop_len)
+    Rx, Sx = _lib.pinned_empty(shape, f.rdt), _lib.pinned_empty(shape, f.cdt)
+    w = _lib.pinned_empty(shape, f.rdt) if get_w else None
+    tau = _lib.pinned_empty(shape, f.rdt) if get_tau else None
+    _call(lib.ssq_reassign_stft_host(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs, pad,
+                                     _gamma_arg(gamma), _variant(modulated), _ptr(Rx), _ptr(Sx), _ptr(w), _ptr(tau)))
+    return (*_unbatch(f.batched, Rx, Sx), _times(f, hop_len), _Sfs(f), *_unbatch(f.batched, w, tau))
 
 
 def issq_stft(Tx, window=None, cc=None, cw=None, n_fft=None, win_len=None, hop_len=1, modulated=True):
@@ -684,16 +665,12 @@ def issq_stft(Tx, window=None, cc=None, cw=None, n_fft=None, win_len=None, hop_l
     if hop_len != 1:
         raise ValueError("inversion with `hop_len != 1` is unsupported.")
     comp = _component_args(Tx, cc, cw)
-    if comp is not None:
-        n_fft = n_fft or (Tx.shape[-2] - 1) * 2
-        win_len = win_len or n_fft
-        win = get_window(window, win_len, n_fft)
-        return _issq_components(*comp, 2.0 / float(win[len(win) // 2]))
-    _full_map(Tx, "Tx")
+    if comp is None:
+        _full_map(Tx, "Tx")
     n_fft = n_fft or (Tx.shape[-2] - 1) * 2
-    win_len = win_len or n_fft
-    win = get_window(window, win_len, n_fft)
-    return _issq(Tx, 2.0 / float(win[len(win) // 2]))
+    win = get_window(window, win_len or n_fft, n_fft)
+    scale = 2.0 / float(win[len(win) // 2])
+    return _issq(Tx, scale) if comp is None else _issq_components(*comp, scale)
 
 
 class _RowCountError(AssertionError, ValueError):
@@ -712,7 +689,7 @@ def _issq(Tx, scale, row_scale=None):
     """scale * sum_rows row_scale[row] * Re Tx[row] -> [N], or [B, N] for a batched Tx (entry b bitwise the 2-D call)."""
     lib = _lib.load()
     _full_map(Tx, "Tx")
-    code = SSQ_F32 if Tx.dtype == np.complex64 else SSQ_F64
+    code = _ccode(Tx.dtype)
     _lib.require_gpu()
     Tc = np.ascontiguousarray(Tx)
     rs = None if row_scale is None else np.ascontiguousarray(row_scale, dtype=np.float64)
@@ -721,7 +698,7 @@ def _issq(Tx, scale, row_scale=None):
         _call(lib.ssq_issq_batch_host(code, _ptr(Tc), Tc.shape[0], Tc.shape[1], Tc.shape[2], float(scale), _ptr(rs),
                                       _ptr(x)))
         return x
-    x = np.empty(Tc.shape[1], dtype=np.float32 if code == SSQ_F32 else np.float64)
+    x = np.empty(Tc.shape[1], dtype=_rdtype(code))
     _call(lib.ssq_issq_host(code, _ptr(Tc), Tc.shape[0], Tc.shape[1], float(scale), _ptr(rs), _ptr(x)))
     return x
 
@@ -773,14 +750,14 @@ def _issq_components(Tb, cc, cw, batched, scale):
     lib = _lib.load()
     B, F, N = Tb.shape
     K = cc.shape[-1]
-    code = SSQ_F32 if Tb.dtype == np.complex64 else SSQ_F64
+    code = _ccode(Tb.dtype)
     _lib.require_gpu()
     Tc = np.ascontiguousarray(Tb)
     cc64 = np.ascontiguousarray(cc, dtype=np.int64).reshape(B, N, K)
     cw64 = np.ascontiguousarray(cw, dtype=np.int64).reshape(B, N, K)
     x = np.empty((B, K + 1, N), dtype=np.float64)
     _call(lib.ssq_issq_components_host(code, _ptr(Tc), B, F, N, _ptr(cc64), _ptr(cw64), 0, K, float(scale), _ptr(x)))
-    return x if batched else x[0]
+    return _unbatch(batched, x)[0]
 
 
 # ---------------------------------------------------------------------------------------------------- CWT family ----
@@ -816,16 +793,12 @@ def cwt_higher_order(x, wavelet="gmw", order=1, average=None, astensor=True, **k
 
 
 def _cwt(x, wavelet, scales, fs, t, nv, l1_norm, derivative, padtype, rpadded, order_args):
-    if isinstance(scales, np.ndarray):
-        nv = None                                            # _cwt.py:226-227
     lib = _lib.load()
     xa, batched, code = _signal(x)
     batch, N = xa.shape
     dt = _dt(fs, t, N)
     wcode, p0, p1 = _wavelet(wavelet)
-    s, scaletype, _nv, _ = _scales(scales)
-    if scaletype == "log" and nv is not None and nv != _nv:
-        raise Exception("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))   # cwt_utils.py:229-231
+    s = _scales(scales)[0]                                 # (`nv` is not read: an ndarray's own holds, _cwt.py:226-227)
     orders, average = order_args if order_args else ((0,), True)
     if all(k == 0 for k in orders) and (average or len(orders) == 1):
         order_args = None                                  # the order-0 wavelet itself: the plain table (code 2)
@@ -844,7 +817,7 @@ def _cwt(x, wavelet, scales, fs, t, nv, l1_norm, derivative, padtype, rpadded, o
         _call(lib.ssq_cwt_host_gmwk(code, _ptr(xa), batch, N, p0, p1, _ptr(polys), polys.shape[1], groups, _ptr(s),
                                     len(s), dt, int(bool(l1_norm)), _pad_code(padtype), int(bool(rpadded)),
                                     VARIANT_UPSTREAM, _ptr(Wx), _ptr(dWx)))
-    sc = s.astype(np.float32 if code == SSQ_F32 else np.float64)
+    sc = s.astype(_rdtype(code))
 
     def split(A):                                          # [batch, groups * na, cols] -> per order, batch axis dropped
         A = A.reshape(batch, groups, len(s), cols)
@@ -911,6 +884,30 @@ def _row_const(s, scaletype, nv):
     return np.ascontiguousarray((s[1] - s[0]) / s)
 
 
+def _freq_type(ssq_freqs, cwt_scaletype, maprange, generate):
+    """ssqueezing.py:172-194, the frequencies a transform is squeezed onto -> (f_asc float64 ascending, their scaletype,
+    f_idx: their 'log-piecewise' transition or None).  A string names the type, None takes the scales' (this mirror has
+    always binned exponential scales on 'log' frequencies) and `generate(scaletype)` makes them; an array has its type
+    inferred."""
+    if isinstance(ssq_freqs, np.ndarray):
+        f_own = _own_dtype(ssq_freqs)
+        scaletype, _ = infer_scaletype(f_own)                                                     # :193-194
+        f_asc = np.ascontiguousarray(f_own, dtype=np.float64)
+    elif ssq_freqs is None or isinstance(ssq_freqs, str):
+        scaletype = ssq_freqs if isinstance(ssq_freqs, str) else cwt_scaletype
+        if scaletype == "log-piecewise" and maprange == "maximal":
+            raise ValueError("can't have `ssq_scaletype = log-piecewise` or tuple with `maprange = 'maximal'` "
+                             "(got %s)" % str(maprange))                                          # :181-184
+        f_asc = f_own = np.ascontiguousarray(generate(scaletype), dtype=np.float64)   # (in float64, as upstream's)
+    else:
+        raise ValueError("`ssq_freqs` must be None, 'log', 'log-piecewise', 'linear' or an array")
+    # algos.py:356-370: the two-segment rule at the frequencies' transition, found in their own dtype; none: one segment
+    f_idx = logscale_transition_idx(f_own) if scaletype == "log-piecewise" else None
+    if scaletype == "log-piecewise" and f_idx is None:
+        scaletype = "log"
+    return f_asc, scaletype, f_idx
+
+
 def _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt):
     """The scale and frequency grids of `ssq_cwt` / `ssq_cwt2` -> (s float64 [na], row_const, f_asc float64 ascending,
     scaletype of the frequencies, f_idx: their 'log-piecewise' transition or None).  Every refusal of the two grids."""
@@ -918,29 +915,42 @@ def _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt):
     if cwt_scaletype == "log" and nv is not None and nv != _nv:
         raise Exception("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))
     row_const = _row_const(s, cwt_scaletype, _nv)
-    # ssqueezing.py:172-194: a string names the frequencies' type, None takes the scales' (this mirror has always binned
-    # exponential scales on 'log' frequencies), an array has its type inferred
-    if isinstance(ssq_freqs, np.ndarray):
-        f_asc = np.ascontiguousarray(ssq_freqs, dtype=np.float64).reshape(-1)
-        if len(f_asc) != len(s):
-            raise ValueError("`ssq_freqs` must have one frequency per scale (%s != %s)" % (len(f_asc), len(s)))
-        f_own = _own_dtype(ssq_freqs)
-        scaletype, _ = infer_scaletype(f_own)
-    elif ssq_freqs is None or isinstance(ssq_freqs, str):
-        scaletype = ssq_freqs if isinstance(ssq_freqs, str) else cwt_scaletype
-        if scaletype == "log-piecewise" and maprange == "maximal":
-            raise ValueError("can't have `ssq_scaletype = log-piecewise` or tuple with `maprange = 'maximal'` "
-                             "(got %s)" % str(maprange))                                          # :181-184
-        f_asc = np.ascontiguousarray(_ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype, s_own),
-                                     dtype=np.float64)
-        f_own = f_asc                                      # (computed in float64, as upstream's)
-    else:
-        raise ValueError("`ssq_freqs` must be None, 'log', 'log-piecewise', 'linear' or an array")
-    # algos.py:356-370: the two-segment rule at the frequencies' transition, found in their own dtype; none: one segment
-    f_idx = logscale_transition_idx(f_own) if scaletype == "log-piecewise" else None
-    if scaletype == "log-piecewise" and f_idx is None:
-        scaletype = "log"
+    if isinstance(ssq_freqs, np.ndarray) and ssq_freqs.size != len(s):
+        raise ValueError("`ssq_freqs` must have one frequency per scale (%s != %s)" % (ssq_freqs.size, len(s)))
+    f_asc, scaletype, f_idx = _freq_type(ssq_freqs, cwt_scaletype, maprange, lambda scaletype: _ssq_freqs(
+        s, N, wcode, p0, p1, dt, maprange, scaletype, s_own))
     return s, row_const, f_asc, scaletype, f_idx
+
+
+def _cwt_front(x, wavelet, scales, fs, t, gamma, padtype):
+    """The front end of `ssq_cwt2`, `reassign_cwt`, `tssq_cwt` and `conceft_cwt`: the signal, the sampling period, the
+    wavelet and the checks on them, on `scales`, `gamma` and `padtype` that all four make before their grids."""
+    f = SimpleNamespace()
+    f.xa, f.batched, f.code = _signal(x)
+    f.batch, f.N = f.xa.shape
+    if f.N < 2:
+        raise ValueError("`x` must hold at least 2 samples")
+    f.dt = _dt(fs, t, f.N)
+    if not (f.dt > 0 and math.isfinite(f.dt)):
+        raise ValueError("`fs` / `t` must give a positive sampling period")
+    f.wcode, f.p0, f.p1 = _wavelet(wavelet)
+    if not f.p0 > 0 or (f.wcode == WAVELET["gmw"] and not f.p1 > 0):
+        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
+    if isinstance(scales, np.ndarray) and scales.dtype.kind in "fiu" and not (np.isfinite(scales).all() and (scales > 0).all()):
+        raise ValueError("`scales` must be positive and finite")
+    if gamma is not None and math.isnan(float(gamma)):
+        raise ValueError("`gamma` is NaN")
+    f.gamma, f.pad = _gamma_arg(gamma), _pad_code(padtype)
+    f.cdt, f.rdt = _cdtype(f.code), _rdtype(f.code)
+    return f
+
+
+def _finite_freq_grid(f, scales, nv, ssq_freqs, maprange):
+    """`_cwt_freq_grid` for a front end's signal and wavelet, refusing frequencies that are not finite."""
+    grid = _cwt_freq_grid(scales, nv, ssq_freqs, maprange, f.N, f.wcode, f.p0, f.p1, f.dt)
+    if not np.isfinite(grid[2]).all():
+        raise ValueError("`ssq_freqs` must be finite")
+    return grid
 
 
 def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, ssq_freqs=None, padtype="reflect",
@@ -951,8 +961,7 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
     lib = _lib.load()
     if difftype != "trig":
         raise ValueError("only difftype='trig' is built")
-    if squeezing not in SQUEEZE:
-        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
+    squeeze = _squeeze_code(squeezing)
     # _ssq_cwt.py:228-241: Wx of the order (set) averaged, dWx by `trigdiff` of the padded Wx -- the derivative transform of
     # the averaged wavelet up to rounding; ssq_freqs below stay the order-0 wavelet's (ssqueeze gets `wavelet` itself)
     order_args = _order_args(order, isinstance(order, (tuple, list, range)), wavelet)
@@ -970,25 +979,21 @@ def ssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, 
     dWx = _lib.pinned_empty(shape, cdt) if get_dWx else None
     wk = _lib.pinned_empty(shape, cdt) if get_w else None
     variant = VARIANT_UPSTREAM | (VARIANT_FLIPUD if flipud else 0)
-    g = -1.0 if gamma is None else float(gamma)
+    g = _gamma_arg(gamma)
     if order_args is None:
         _call(lib.ssq_ssq_cwt_host_rows(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, _ptr(row_const),
                                         _ptr(f_asc), FREQS[scaletype], f_idx or 0, _pad_code(padtype),
-                                        SQUEEZE[squeezing], g, variant, _ptr(Tx), _ptr(Wx), _ptr(dWx), _ptr(wk)))
+                                        squeeze, g, variant, _ptr(Tx), _ptr(Wx), _ptr(dWx), _ptr(wk)))
     else:
         poly = np.ascontiguousarray(gmw_order_coefficients(p0, p1, *order_args))
         _call(lib.ssq_ssq_cwt_host_gmwk_rows(code, _ptr(xa), batch, N, p0, p1, _ptr(poly), poly.shape[1], 1, _ptr(s),
                                              len(s), dt, _ptr(row_const), _ptr(f_asc), FREQS[scaletype], f_idx or 0,
-                                             _pad_code(padtype), SQUEEZE[squeezing], g, variant, _ptr(Tx), _ptr(Wx),
+                                             _pad_code(padtype), squeeze, g, variant, _ptr(Tx), _ptr(Wx),
                                              _ptr(dWx), _ptr(wk)))
-    rdt = np.float32 if code == SSQ_F32 else np.float64
-    out = [Tx if batched else Tx[0], Wx if batched else Wx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]   # ssqueezing.py:199-205
-    if get_w:
-        w = wk.real.copy()
-        out.append(w if batched else w[0])
-    if get_dWx:
-        out.append(dWx if batched else dWx[0])
-    return tuple(out)
+    rdt = _rdtype(code)
+    w = wk.real.copy() if get_w else None
+    return (*_unbatch(batched, Tx, Wx), f_asc[::-1].astype(rdt), s.astype(rdt),                # ssqueezing.py:199-205
+            *_unbatch(batched, w, dWx))
 
 
 def ssq_cwt2(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, ssq_freqs=None, padtype="reflect",
@@ -1016,39 +1021,17 @@ def ssq_cwt2(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None,
     `ssq_freqs` None, a string or an array; maprange 'peak' / 'maximal'; 'sum' / 'lebesgue'; the five padtypes; 1-D or
     batched 2-D `x`.  Anything else raises ValueError before any GPU work."""
     lib = _lib.load()
-    if squeezing not in SQUEEZE:
-        raise ValueError(f"squeezing {squeezing!r}: 'sum' and 'lebesgue' are built")
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    if N < 2:
-        raise ValueError("`x` must hold at least 2 samples")
-    dt = _dt(fs, t, N)
-    if not (dt > 0 and math.isfinite(dt)):
-        raise ValueError("`fs` / `t` must give a positive sampling period")
-    wcode, p0, p1 = _wavelet(wavelet)
-    if not p0 > 0 or (wcode == WAVELET["gmw"] and not p1 > 0):
-        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
-    if isinstance(scales, np.ndarray) and scales.dtype.kind in "fiu" and not (np.isfinite(scales).all() and (scales > 0).all()):
-        raise ValueError("`scales` must be positive and finite")
-    s, row_const, f_asc, scaletype, f_idx = _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt)
-    if not np.isfinite(f_asc).all():
-        raise ValueError("`ssq_freqs` must be finite")
-    if gamma is not None and math.isnan(float(gamma)):
-        raise ValueError("`gamma` is NaN")
-    pad = _pad_code(padtype)
+    squeeze = _squeeze_code(squeezing)
+    f = _cwt_front(x, wavelet, scales, fs, t, gamma, padtype)
+    s, row_const, f_asc, scaletype, f_idx = _finite_freq_grid(f, scales, nv, ssq_freqs, maprange)
     _lib.require_gpu()
-    shape = (batch, len(s), N)
-    cdt, rdt = _cdtype(code), _rdtype(code)
-    Tx, Wx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
-    w2 = _lib.pinned_empty(shape, rdt) if get_w else None
-    _call(lib.ssq_ssq_cwt2_host(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, _ptr(row_const), _ptr(f_asc),
-                                FREQS[scaletype], f_idx or 0, pad, SQUEEZE[squeezing],
-                                -1.0 if gamma is None else float(gamma), VARIANT_FLIPUD if flipud else 0, 0, _ptr(Tx),
-                                _ptr(Wx), _ptr(w2)))
-    out = [Tx if batched else Tx[0], Wx if batched else Wx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]
-    if get_w:
-        out.append(w2 if batched else w2[0])
-    return tuple(out)
+    shape = (f.batch, len(s), f.N)
+    Tx, Wx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    w2 = _lib.pinned_empty(shape, f.rdt) if get_w else None
+    _call(lib.ssq_ssq_cwt2_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), len(s), f.dt,
+                                _ptr(row_const), _ptr(f_asc), FREQS[scaletype], f_idx or 0, f.pad, squeeze,
+                                f.gamma, VARIANT_FLIPUD if flipud else 0, 0, _ptr(Tx), _ptr(Wx), _ptr(w2)))
+    return (*_unbatch(f.batched, Tx, Wx), f_asc[::-1].astype(f.rdt), s.astype(f.rdt), *_unbatch(f.batched, w2))
 
 
 REASSIGN_CWT_QUANTUM_LOG2_MAX = 38      # csrc/cwt_reassign.hip: kCwtRQuantumBitsMax
@@ -1103,42 +1086,21 @@ def reassign_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=N
     `ssq_freqs` None, a string or an array; maprange 'peak' / 'maximal'; the five padtypes; 1-D or batched 2-D `x`) with
     na N <= 2^40.  Anything else raises ValueError before any GPU work."""
     lib = _lib.load()
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    if N < 2:
-        raise ValueError("`x` must hold at least 2 samples")
-    dt = _dt(fs, t, N)
-    if not (dt > 0 and math.isfinite(dt)):
-        raise ValueError("`fs` / `t` must give a positive sampling period")
-    wcode, p0, p1 = _wavelet(wavelet)
-    if not p0 > 0 or (wcode == WAVELET["gmw"] and not p1 > 0):
-        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
-    if isinstance(scales, np.ndarray) and scales.dtype.kind in "fiu" and not (np.isfinite(scales).all() and (scales > 0).all()):
-        raise ValueError("`scales` must be positive and finite")
-    s, _, f_asc, scaletype, f_idx = _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt)
-    if not np.isfinite(f_asc).all():
-        raise ValueError("`ssq_freqs` must be finite")
-    if gamma is not None and math.isnan(float(gamma)):
-        raise ValueError("`gamma` is NaN")
-    pad = _pad_code(padtype)
-    if lib.ssq_reassign_cwt_workspace_bytes(code, batch, N, len(s), None) < 0:       # the C entry's shape checks (no GPU)
-        raise ValueError(lib.ssq_last_error().decode("utf-8", "replace"))
+    f = _cwt_front(x, wavelet, scales, fs, t, gamma, padtype)
+    s, _, f_asc, scaletype, f_idx = _finite_freq_grid(f, scales, nv, ssq_freqs, maprange)
+    _shape_checked(lib, lib.ssq_reassign_cwt_workspace_bytes(f.code, f.batch, f.N, len(s), None))
     _lib.require_gpu()
-    shape = (batch, len(s), N)
-    cdt, rdt = _cdtype(code), _rdtype(code)
-    Rx, Wx = _lib.pinned_empty(shape, rdt), _lib.pinned_empty(shape, cdt)
-    w = _lib.pinned_empty(shape, rdt) if get_w else None
-    tau = _lib.pinned_empty(shape, rdt) if get_tau else None
+    shape = (f.batch, len(s), f.N)
+    Rx, Wx = _lib.pinned_empty(shape, f.rdt), _lib.pinned_empty(shape, f.cdt)
+    w = _lib.pinned_empty(shape, f.rdt) if get_w else None
+    tau = _lib.pinned_empty(shape, f.rdt) if get_tau else None
     kk, mm = (_lib.pinned_empty(shape, np.int32) for _ in range(2)) if get_targets else (None, None)
-    _call(lib.ssq_reassign_cwt_host(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), len(s), dt, _ptr(f_asc),
-                                    FREQS[scaletype], f_idx or 0, pad, -1.0 if gamma is None else float(gamma),
+    _call(lib.ssq_reassign_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), len(s), f.dt,
+                                    _ptr(f_asc), FREQS[scaletype], f_idx or 0, f.pad, f.gamma,
                                     VARIANT_FLIPUD if flipud else 0, 0, _ptr(Rx), _ptr(Wx), _ptr(w), _ptr(tau), _ptr(kk),
                                     _ptr(mm)))
-    out = [Rx if batched else Rx[0], Wx if batched else Wx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]
-    for a in (w, tau, kk, mm):
-        if a is not None:
-            out.append(a if batched else a[0])
-    return tuple(out)
+    return (*_unbatch(f.batched, Rx, Wx), f_asc[::-1].astype(f.rdt), s.astype(f.rdt),
+            *_unbatch(f.batched, w, tau, kk, mm))
 
 
 TSSQ_CWT_QUANTUM_LOG2_MAX = 38          # csrc/cwt_tsst.hip: kCwtTQuantumBitsMax
@@ -1205,48 +1167,29 @@ def tssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None,
     padtypes; orders 1 and 2; 1-D or batched 2-D `x`; N <= 2^26 and na N <= 2^40.  Anything else raises ValueError before
     any GPU work."""
     lib = _lib.load()
-    if isinstance(order, (bool, np.bool_)) or order not in (1, 2):
-        raise ValueError(f"order {order!r}: 1 and 2 are built")
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    if N < 2:
-        raise ValueError("`x` must hold at least 2 samples")
-    dt = _dt(fs, t, N)
-    if not (dt > 0 and math.isfinite(dt)):
-        raise ValueError("`fs` / `t` must give a positive sampling period")
-    wcode, p0, p1 = _wavelet(wavelet)
-    if not (p0 > 0 and math.isfinite(p0)) or (wcode == WAVELET["gmw"] and not (p1 > 0 and math.isfinite(p1))):
+    order = _order12(order, "1 and 2 are built")
+    f = _cwt_front(x, wavelet, scales, fs, t, gamma, padtype)
+    if not (math.isfinite(f.p0) and math.isfinite(f.p1)):                   # (the front end: positive; here finite too)
         raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
-    if isinstance(scales, np.ndarray) and scales.dtype.kind in "fiu" and not (np.isfinite(scales).all() and (scales > 0).all()):
-        raise ValueError("`scales` must be positive and finite")
     s, scaletype, _nv, _ = _scales(scales)
-    if scaletype == "log" and nv is not None and nv != _nv:
+    if scaletype == "log" and nv is not None and nv != _nv:                  # (a ValueError here, `_cwt_freq_grid`: Exception)
         raise ValueError("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))
     nu = tssq_cwt_row_freqs(wavelet, s)
     if not (np.isfinite(nu).all() and (nu > 0).all()):
         raise ValueError("`scales` give row frequencies that are not positive and finite")
-    if gamma is not None and math.isnan(float(gamma)):
-        raise ValueError("`gamma` is NaN")
-    pad = _pad_code(padtype)
     mn = C.c_int64(0)
-    if lib.ssq_tssq_cwt_workspace_bytes(code, batch, N, len(s), int(order), C.byref(mn)) < 0:   # the shape checks (no GPU)
-        raise ValueError(lib.ssq_last_error().decode("utf-8", "replace"))
+    _shape_checked(lib, lib.ssq_tssq_cwt_workspace_bytes(f.code, f.batch, f.N, len(s), order, C.byref(mn)))
     limit = 0 if work_limit_bytes is None else int(work_limit_bytes)
     if work_limit_bytes is not None and limit < mn.value:
         raise ValueError(f"`work_limit_bytes` must be at least {mn.value} for this shape")
     _lib.require_gpu()
-    shape = (batch, len(s), N)
-    cdt, rdt = _cdtype(code), _rdtype(code)
-    Tx, Wx = _lib.pinned_empty(shape, cdt), _lib.pinned_empty(shape, cdt)
-    tau = _lib.pinned_empty(shape, rdt) if get_tau else None
+    shape = (f.batch, len(s), f.N)
+    Tx, Wx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    tau = _lib.pinned_empty(shape, f.rdt) if get_tau else None
     mm = _lib.pinned_empty(shape, np.int32) if get_targets else None
-    _call(lib.ssq_tssq_cwt_host(code, _ptr(xa), batch, N, wcode, p0, p1, _ptr(s), _ptr(nu), len(s), dt, pad, int(order),
-                                -1.0 if gamma is None else float(gamma), limit, _ptr(Tx), _ptr(Wx), _ptr(tau), _ptr(mm)))
-    out = [Tx if batched else Tx[0], Wx if batched else Wx[0], s.astype(rdt), (nu / dt).astype(rdt)]
-    for a in (tau, mm):
-        if a is not None:
-            out.append(a if batched else a[0])
-    return tuple(out)
+    _call(lib.ssq_tssq_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), _ptr(nu), len(s), f.dt,
+                                f.pad, order, f.gamma, limit, _ptr(Tx), _ptr(Wx), _ptr(tau), _ptr(mm)))
+    return (*_unbatch(f.batched, Tx, Wx), s.astype(f.rdt), (nu / f.dt).astype(f.rdt), *_unbatch(f.batched, tau, mm))
 
 
 CONCEFT_MAX_ORDERS = 8                  # csrc/cwt_conceft.hip: kConceftMaxOrders
@@ -1359,8 +1302,9 @@ def conceft_cwt(x, wavelet="gmw", scales="log-piecewise", orders=3, n_draws=20, 
     if _wavelet_name(wavelet) != "gmw":
         raise ValueError("conceft_cwt: the wavelet must be GMW, whose higher orders are the orthogonal tapers (got %r)"
                          % (wavelet,))
-    wcode, p0, p1 = _wavelet(wavelet)
-    if not (p0 > 0 and math.isfinite(p0) and p1 > 0 and math.isfinite(p1)):
+    f = _cwt_front(x, wavelet, scales, fs, t, gamma, padtype)
+    p0, p1 = f.p0, f.p1
+    if not (math.isfinite(p0) and math.isfinite(p1)):                       # (the front end: positive; here finite too)
         raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
     if isinstance(orders, (bool, np.bool_)):
         raise ValueError(f"`orders` must be an int or a tuple / list / range of ints (got {orders!r})")
@@ -1396,39 +1340,18 @@ def conceft_cwt(x, wavelet="gmw", scales="log-piecewise", orders=3, n_draws=20, 
         r, c = _conceft_gauge(vectors, adm)
     M = r.shape[0]
     scale = float(gmw_adm_ssq(p0, p1, 0) / c.sum())         # (vectors = e_0 of order 0: C_0 / C_0, exactly 1)
-    xa, batched, code = _signal(x)
-    batch, N = xa.shape
-    if N < 2:
-        raise ValueError("`x` must hold at least 2 samples")
-    dt = _dt(fs, t, N)
-    if not (dt > 0 and math.isfinite(dt)):
-        raise ValueError("`fs` / `t` must give a positive sampling period")
-    if isinstance(scales, np.ndarray) and scales.dtype.kind in "fiu" and not (np.isfinite(scales).all() and (scales > 0).all()):
-        raise ValueError("`scales` must be positive and finite")
-    s, row_const, f_asc, scaletype, f_idx = _cwt_freq_grid(scales, nv, ssq_freqs, maprange, N, wcode, p0, p1, dt)
-    if not np.isfinite(f_asc).all():
-        raise ValueError("`ssq_freqs` must be finite")
-    if gamma is not None and math.isnan(float(gamma)):
-        raise ValueError("`gamma` is NaN")
-    pad = _pad_code(padtype)
+    s, row_const, f_asc, scaletype, f_idx = _finite_freq_grid(f, scales, nv, ssq_freqs, maprange)
     na = len(s)
-    if lib.ssq_conceft_cwt_workspace_bytes(code, batch, N, na, J, None) < 0:              # the shape checks (no GPU)
-        raise ValueError(lib.ssq_last_error().decode("utf-8", "replace"))
+    _shape_checked(lib, lib.ssq_conceft_cwt_workspace_bytes(f.code, f.batch, f.N, na, J, None))
     polys = np.ascontiguousarray(gmw_order_coefficients(p0, p1, orders, average=False))
     _lib.require_gpu()
-    cdt, rdt = _cdtype(code), _rdtype(code)
-    Tx = _lib.pinned_empty((batch, na, N), cdt)
-    Wx = _lib.pinned_empty((batch, J, na, N), cdt) if get_Wx else None
-    w = _lib.pinned_empty((batch, M, na, N), rdt) if get_w else None
-    _call(lib.ssq_conceft_cwt_host(code, _ptr(xa), batch, N, p0, p1, _ptr(polys), polys.shape[1], J, _ptr(r), M, scale,
-                                   _ptr(s), na, dt, _ptr(row_const), _ptr(f_asc), FREQS[scaletype], f_idx or 0, pad,
-                                   -1.0 if gamma is None else float(gamma), VARIANT_FLIPUD if flipud else 0, 0, _ptr(Tx),
-                                   _ptr(Wx), _ptr(w)))
-    out = [Tx if batched else Tx[0], f_asc[::-1].astype(rdt), s.astype(rdt)]
-    for a in (Wx, w):
-        if a is not None:
-            out.append(a if batched else a[0])
-    return tuple(out)
+    Tx = _lib.pinned_empty((f.batch, na, f.N), f.cdt)
+    Wx = _lib.pinned_empty((f.batch, J, na, f.N), f.cdt) if get_Wx else None
+    w = _lib.pinned_empty((f.batch, M, na, f.N), f.rdt) if get_w else None
+    _call(lib.ssq_conceft_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, p0, p1, _ptr(polys), polys.shape[1], J, _ptr(r), M,
+                                   scale, _ptr(s), na, f.dt, _ptr(row_const), _ptr(f_asc), FREQS[scaletype], f_idx or 0,
+                                   f.pad, f.gamma, VARIANT_FLIPUD if flipud else 0, 0, _ptr(Tx), _ptr(Wx), _ptr(w)))
+    return (*_unbatch(f.batched, Tx), f_asc[::-1].astype(f.rdt), s.astype(f.rdt), *_unbatch(f.batched, Wx, w))
 
 
 def issq_cwt(Tx, wavelet="gmw", cc=None, cw=None):
@@ -1485,7 +1408,7 @@ def _cmap(A, name):
     if not isinstance(A, np.ndarray) or A.ndim not in (2, 3) or A.dtype not in (np.complex64, np.complex128):
         raise TypeError(f"`{name}` must be a 2D [F, N] (or batched 3D [B, F, N]) complex64 / complex128 ndarray")
     batched = A.ndim == 3
-    return np.ascontiguousarray(A if batched else A[None]), batched, (SSQ_F32 if A.dtype == np.complex64 else SSQ_F64)
+    return np.ascontiguousarray(A if batched else A[None]), batched, _ccode(A.dtype)
 
 
 def _like(B, A, name):
@@ -1495,8 +1418,11 @@ def _like(B, A, name):
     return np.ascontiguousarray(B if B.ndim == 3 else B[None], dtype=A.dtype)
 
 
-def _rdtype(code):
-    return np.float32 if code == SSQ_F32 else np.float64
+def _sfs_rows(Sfs, F, rdt):
+    sfs = np.ascontiguousarray(np.asarray(Sfs).reshape(-1), dtype=rdt)
+    if len(sfs) != F:
+        raise ValueError(f"`Sfs` must have one frequency per row of `Sx` ({len(sfs)} != {F})")
+    return sfs
 
 
 def _phase(Wx, dWx, Sfs, gamma):
@@ -1504,16 +1430,12 @@ def _phase(Wx, dWx, Sfs, gamma):
     dWb = _like(dWx, Wx, "dWx")
     B, F, N = Wb.shape
     rdt = _rdtype(code)
-    sfs = None
-    if Sfs is not None:
-        sfs = np.ascontiguousarray(np.asarray(Sfs).reshape(-1), dtype=rdt)
-        if len(sfs) != F:
-            raise ValueError(f"`Sfs` must have one frequency per row of `Sx` ({len(sfs)} != {F})")
+    sfs = None if Sfs is None else _sfs_rows(Sfs, F, rdt)
     lib = _lib.load()
     _lib.require_gpu()
     w = np.empty((B, F, N), dtype=rdt)
     _call(lib.ssq_phase_host(code, _ptr(Wb), _ptr(dWb), _ptr(sfs), B, F, N, float(gamma), _ptr(w)))
-    return w if batched else w[0]
+    return _unbatch(batched, w)[0]
 
 
 def phase_cwt(Wx, dWx, difftype="trig", gamma=None, parallel=None):
@@ -1524,7 +1446,7 @@ def phase_cwt(Wx, dWx, difftype="trig", gamma=None, parallel=None):
         raise ValueError(f"difftype {difftype!r}: only 'trig' is built")
     _, _, code = _cmap(Wx, "Wx")
     if gamma is None:
-        gamma = math.sqrt(EPS32 if code == SSQ_F32 else EPS64)
+        gamma = math.sqrt(_eps(code))
     return _phase(Wx, dWx, None, gamma)
 
 
@@ -1533,7 +1455,7 @@ def phase_stft(Sx, dSx, Sfs, gamma=None, parallel=None):
     (2 pi)|, +inf where |Sx| < gamma; `gamma=None` is 10 eps of the dtype.  `parallel` is accepted and unused."""
     _, _, code = _cmap(Sx, "Sx")
     if gamma is None:
-        gamma = 10 * (EPS32 if code == SSQ_F32 else EPS64)
+        gamma = 10 * _eps(code)
     if Sfs is None:
         raise ValueError("`Sfs` must be given")
     return _phase(Sx, dSx, Sfs, gamma)
@@ -1578,7 +1500,7 @@ def ssqueeze(Wx, w=None, ssq_freqs=None, scales=None, Sfs=None, fs=None, t=None,
     if maprange not in ("peak", "maximal"):
         raise ValueError(f"maprange {maprange!r}: must be one of 'maximal', 'peak'")
     dt = _dt(fs, t, N)
-    f_idx = None
+    f_idx = Sfs_t = None
     if transform == "cwt":
         if scales is None:
             raise ValueError("`scales` can't be None if `transform == 'cwt'`")
@@ -1586,43 +1508,28 @@ def ssqueeze(Wx, w=None, ssq_freqs=None, scales=None, Sfs=None, fs=None, t=None,
         if len(s) != F:
             raise ValueError("`scales` must have one scale per row of `Wx` (%s != %s)" % (len(s), F))
         row_const = _row_const(s, cwt_scaletype, _nv)                                   # ssqueezing.py:122-127
-        if isinstance(ssq_freqs, np.ndarray):
-            f_own = _own_dtype(ssq_freqs)
-            scaletype, _ = infer_scaletype(f_own)                                        # :193-194
-        elif ssq_freqs is None or isinstance(ssq_freqs, str):
-            scaletype = ssq_freqs if isinstance(ssq_freqs, str) else cwt_scaletype      # :172-176
-            if scaletype == "log-piecewise" and maprange == "maximal":
-                raise ValueError("can't have `ssq_scaletype = log-piecewise` or tuple with `maprange = 'maximal'` "
-                                 "(got %s)" % str(maprange))                             # :178-182
+
+        def generate(scaletype):
             if maprange == "peak" and wavelet is None:
                 raise ValueError("`wavelet` must be given with maprange 'peak'")
             wcode, p0, p1 = _wavelet(wavelet) if wavelet is not None else (0, 0.0, 0.0)
-            f_own = np.asarray(_ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype, s_own, was_padded),
-                               dtype=np.float64)
-            ssq_freqs = f_own
-        else:
-            raise ValueError("`ssq_freqs` must be None, 'log', 'log-piecewise', 'linear' or an array")
-        f_idx = logscale_transition_idx(f_own) if scaletype == "log-piecewise" else None
-        if scaletype == "log-piecewise" and f_idx is None:
-            scaletype = "log"
-        Sfs_t = None
+            return _ssq_freqs(s, N, wcode, p0, p1, dt, maprange, scaletype, s_own, was_padded)
+        f_asc, scaletype, f_idx = _freq_type(ssq_freqs, cwt_scaletype, maprange, generate)
+        if not isinstance(ssq_freqs, np.ndarray):
+            ssq_freqs = f_asc
     else:
         if not isinstance(ssq_freqs, np.ndarray):
             raise ValueError("transform 'stft': `ssq_freqs` must be an array (ssq_stft passes Sfs)")
         f_own = _own_dtype(ssq_freqs)
-        scaletype = "linear"                                                             # :189-191
+        f_asc, scaletype = np.ascontiguousarray(f_own, dtype=np.float64), "linear"       # :189-191
         row_const = np.full(F, float(f_own[1] - f_own[0]))                               # :129-130
-        Sfs_t = None
         if w is None:
             if Sfs is None:
                 raise ValueError("transform 'stft' with `w=None`: `Sfs` must be given")
-            Sfs_t = np.ascontiguousarray(np.asarray(Sfs).reshape(-1), dtype=rdt)
-            if len(Sfs_t) != F:
-                raise ValueError(f"`Sfs` must have one frequency per row of `Sx` ({len(Sfs_t)} != {F})")
+            Sfs_t = _sfs_rows(Sfs, F, rdt)
             if Sfs_t[0] != rdt(f_own[0]):
                 raise ValueError("transform 'stft' with `w=None` bins from Sfs[0]: ssq_freqs[0] != Sfs[0] is not "
                                  "built; pass `w = phase_stft(Sx, dSx, Sfs)` instead")
-    f_asc = np.ascontiguousarray(f_own, dtype=np.float64)
     if len(f_asc) != F:
         raise ValueError("`ssq_freqs` must have one frequency per row of `Wx` (%s != %s)" % (len(f_asc), F))
     kind, trans = FREQS[scaletype], f_idx or 0
@@ -1645,7 +1552,7 @@ def ssqueeze(Wx, w=None, ssq_freqs=None, scales=None, Sfs=None, fs=None, t=None,
                                       _ptr(Tx)))
     else:
         dWb = _like(dWx, Wx, "dWx")
-        g = 10 * (EPS32 if code == SSQ_F32 else EPS64) if gamma is None else float(gamma)
+        g = 10 * _eps(code) if gamma is None else float(gamma)
         Tx = np.empty((B, F, N), dtype=Wb.dtype)
         _call(lib.ssq_ssqueeze_dwx_host(code, _ptr(Wb), _ptr(dWb), _ptr(Sfs_t), B, F, N, _ptr(row_const), _ptr(f_asc),
                                         kind, trans, SSQUEEZE_MODES[mode], int(bool(flipud)), g, _ptr(Tx)))
@@ -1653,7 +1560,7 @@ def ssqueeze(Wx, w=None, ssq_freqs=None, scales=None, Sfs=None, fs=None, t=None,
         Tx = np.ascontiguousarray(Tx.real)
     if transform == "cwt" or flipud:                                                     # :199-205
         ssq_freqs = ssq_freqs[::-1]
-    return (Tx if batched else Tx[0]), ssq_freqs
+    return _unbatch(batched, Tx)[0], ssq_freqs
 
 
 # ---------------------------------------------------------------------------------------------- ridge extraction ----
@@ -1682,7 +1589,7 @@ def extract_ridges(Tf, scales, penalty=2., n_ridges=1, bw=15, transform='cwt', g
         code, pcode, cplx, src = SSQ_F64, SSQ_F32, 0, Tb.astype(np.float64, copy=False)
     else:
         raise TypeError(f"`Tf` dtype {Tf.dtype}: complex64/128, float32/64 or integer are supported")
-    pdt = np.float64 if pcode == SSQ_F64 else np.float32
+    pdt = _rdtype(pcode)
     s = np.asarray(scales, dtype=pdt)
     if s.ndim > 2 or (s.ndim == 2 and s.shape[1] != 1) or s.size != F:
         raise ValueError(f"`scales` must have shape ({F},) or ({F}, 1) to match `Tf`, got {s.shape}")
@@ -1702,7 +1609,5 @@ def extract_ridges(Tf, scales, penalty=2., n_ridges=1, bw=15, transform='cwt', g
     ridge_e = np.empty((B, N, n_ridges), dtype=pdt) if get_params else None
     _call(lib.ssq_extract_ridges_host(code, pcode, cplx, _ptr(src), B, F, N, _ptr(metric), _ptr(scales_orig), pen,
                                       n_ridges, float(bw), _ptr(ridge_idxs), _ptr(ridge_f), _ptr(ridge_e), None))
-    if not batched:
-        ridge_idxs = ridge_idxs[0]
-        ridge_f, ridge_e = (ridge_f[0], ridge_e[0]) if get_params else (None, None)
-    return (ridge_idxs, ridge_f, ridge_e) if get_params else ridge_idxs
+    out = _unbatch(batched, ridge_idxs, ridge_f, ridge_e)
+    return tuple(out) if get_params else out[0]
