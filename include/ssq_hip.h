@@ -516,6 +516,21 @@ int ssq_stft_plan_launch_info(const ssq_stft_plan* plan, int out_kind, int64_t b
  * over the batch, blocks[i] its grid.  The arrays hold at least 2 entries; any pointer may be NULL. */
 int ssq_stft_plan_launch_list(const ssq_stft_plan* plan, int out_kind, int64_t batch, int* n_launch, int* edge,
                               int64_t* tiles, int64_t* blocks);
+/* Read-only: the kernel family ssq_stft_plan_exec launches for `out_kind`, read from the fields the launcher itself
+ * branches on.  DFT: direct sums (dft_frames_kernel); FFT_BATCHED: frames packed for the batched any-length device FFT;
+ * FUSED_POW2 / FUSED_SPLIT: stft_fused_kernel on a power of two (SPLIT: the fp64 n_fft = 1024 configuration);
+ * TX1024: stft_tx1024_kernel (fp32 n_fft = 1024, Tx and (w, k)); MIXED_RADIX / BLUESTEIN: the any-length modes of
+ * stft_fused_kernel.  Launches nothing. */
+enum {
+  SSQ_STFT_ROUTE_DFT = 0,
+  SSQ_STFT_ROUTE_FFT_BATCHED = 1,
+  SSQ_STFT_ROUTE_FUSED_POW2 = 2,
+  SSQ_STFT_ROUTE_FUSED_SPLIT = 3,
+  SSQ_STFT_ROUTE_TX1024 = 4,
+  SSQ_STFT_ROUTE_MIXED_RADIX = 5,
+  SSQ_STFT_ROUTE_BLUESTEIN = 6
+};
+int ssq_stft_plan_route(const ssq_stft_plan* plan, int out_kind, int* route);
 /* d_x: [batch][N]; d_out: [batch][n_freqs][n_frames] complex; async on `stream` (hipStream_t). */
 int ssq_stft_plan_exec(ssq_stft_plan* plan, int out_kind, const void* d_x, int64_t batch,
                        void* d_out, void* d_workspace, int64_t workspace_bytes, void* stream);

@@ -19,6 +19,8 @@ PAD = {"reflect": 0, "zero": 1}
 SQUEEZE = {"sum": 0, "lebesgue": 1}
 WAVELET = {"gmw": 0, "morlet": 1}
 OUT_TX, OUT_SX, OUT_DSX, OUT_WK = 0, 1, 2, 3
+# ssq_stft_plan_route: SSQ_STFT_ROUTE_* in declaration order
+STFT_ROUTES = ("DFT", "FFT_BATCHED", "FUSED_POW2", "FUSED_SPLIT", "TX1024", "MIXED_RADIX", "BLUESTEIN")
 
 
 class SsqHipError(RuntimeError):
@@ -151,6 +153,7 @@ _SIGNATURES = {
     "ssq_stft_plan_launch_info": (C.c_int, [vp, C.c_int, i64, C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(i64)]),
     "ssq_stft_plan_launch_list": (C.c_int, [vp, C.c_int, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64),
                                             C.POINTER(i64)]),
+    "ssq_stft_plan_route": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
     "ssq_stft_plan_exec": (C.c_int, [vp, C.c_int, vp, i64, vp, vp, i64, vp]),
     "ssq_stft_plan_exec_strided": (C.c_int, [vp, C.c_int, vp, i64, i64, i64, i64, vp, vp, i64, vp]),
     "ssq_chunk_halo_fill": (C.c_int, [C.c_int, vp, i64, i64, i64, C.c_int, vp]),

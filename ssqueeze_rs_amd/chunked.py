@@ -34,6 +34,7 @@ import numpy as np
 from . import _lib
 
 CHUNK_DEFAULT = 1_000_000            # tests/stft_ssq_test.py:302
+RELAYOUT_MAX_CHUNKS = 65535          # ssq_chunks_relayout puts the chunks on grid.z: longer runs go as several slabs
 
 
 def chunk_plan(samples: int, chunk: int) -> List[Tuple[int, int]]:
@@ -142,7 +143,7 @@ def _stft_family(data, out_kind, fs, n_fft, hop, window, squeezing, chunk, depth
                                                 hop, float(fs), 0, _lib.SQUEEZE.get(squeezing, 0), -1.0, 0))
             plans.append(plan)
             per = Cn * K * F * 2 * dev.esz                   # temp bytes of one chunk over all channels
-            slab = max(1, min(len(idx), temp_bytes // max(per, 1)))
+            slab = max(1, min(len(idx), temp_bytes // max(per, 1), RELAYOUT_MAX_CHUNKS))
             ws = int(lib.ssq_stft_plan_workspace_bytes(plan, Cn * slab, out_kind))
             d_ws = C.c_void_p()
             try:                                             # (allocations inside: a failing one must not leak the other)
@@ -234,7 +235,7 @@ def _cwt_family(data, ssq, fs, wavelet, scales, nv, padtype, squeezing, maprange
             plans.append(plan)
             wsb = int(lib.ssq_cwt_plan_workspace_bytes(plan, 1))
             per = Cn * na * n_ext * 2 * dev.esz
-            slab = max(1, min(len(idx), temp_bytes // max(per, 1)))
+            slab = max(1, min(len(idx), temp_bytes // max(per, 1), RELAYOUT_MAX_CHUNKS))
             d_ws = C.c_void_p()
             tmps = [C.c_void_p() for _ in range(n_out)]
             try:                                             # (allocations inside: a failing one must not leak the others)

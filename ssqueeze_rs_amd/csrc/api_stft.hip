@@ -465,6 +465,25 @@ int ssq_stft_plan_launch_list(const ssq_stft_plan* pl, int out_kind, int64_t bat
   return 0;
 }
 
+// which kernel family exec launches, from the fields exec_typed / launch_stft_fused / launch_one themselves branch on
+int ssq_stft_plan_route(const ssq_stft_plan* pl, int out_kind, int* route) {
+  if (!pl) SSQ_FAIL("plan is NULL");
+  if (!route) SSQ_FAIL("route is NULL");
+  if (out_kind < SSQ_OUT_TX || out_kind > SSQ_OUT_WK) SSQ_FAIL("bad out_kind");
+  if (!pl->fused) {
+    *route = pl->fft_path ? SSQ_STFT_ROUTE_FFT_BATCHED : SSQ_STFT_ROUTE_DFT;
+    return 0;
+  }
+  if (pl->blue || pl->mr_np > 0) {                           // make_dev: n_eff != fft_len -> launch_stft_anylen
+    *route = pl->mr_np > 0 ? SSQ_STFT_ROUTE_MIXED_RADIX : SSQ_STFT_ROUTE_BLUESTEIN;
+    return 0;
+  }
+  FusedLaunchShape shape;
+  if (int rc = plan_launch_shape(pl, out_kind, 1, shape)) return rc;
+  *route = shape.tx1024 ? SSQ_STFT_ROUTE_TX1024 : (shape.split ? SSQ_STFT_ROUTE_FUSED_SPLIT : SSQ_STFT_ROUTE_FUSED_POW2);
+  return 0;
+}
+
 int64_t ssq_stft_plan_workspace_bytes(const ssq_stft_plan* pl, int64_t batch, int out_kind) {
   if (!pl || pl->fused) return 0;
   const int64_t elem = (pl->dtype == SSQ_F32 ? 8 : 16);

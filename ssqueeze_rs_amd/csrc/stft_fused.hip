@@ -440,6 +440,7 @@ static FusedLaunchShape shape_one(const StftDev<T>& p0, int cu_count, long long 
   bool tx1024 = false;
   if constexpr (sizeof(T) == 4 && LOGN == 10) tx1024 = (p0.out_kind == 0 || p0.out_kind == 3) && p0.n_eff == C::N;
   s.tx1024 = tx1024;
+  s.split = C::SPLIT;
   const int TF = tx1024 ? Hi1024::F : C::F;   // frames per tile of the kernel that will run
   s.tile_frames = TF;
   // interior tiles [lo, hi): every frame of the tile reads only inside the signal

@@ -79,6 +79,7 @@ struct FusedLaunchShape {
   int tile_frames = 0;
   int n_launch = 0;
   bool tx1024 = false;           // fp32 n_fft = 1024 Tx / (w, k): the 16-wave kernel
+  bool split = false;            // fp64 n_fft = 1024: the 8-wave FusedCfg::SPLIT configuration of stft_fused_kernel
   struct Launch {
     int edge = 0;                // the edge-capable instantiation (padding by index mirroring)
     int ta0 = 0, ta_n = 0, tb0 = 0, tiles_per_signal = 0;

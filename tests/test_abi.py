@@ -44,6 +44,26 @@ def test_launch_info_is_declared_bound_and_rejects_bad_arguments():
     assert b"plan is NULL" in lib.ssq_last_error()
 
 
+def test_route_query_is_declared_bound_and_rejects_bad_arguments():
+    """ssq_stft_plan_route: in the header with the argument list of the ctypes table, the route names of _lib in the
+    header's order, and NULL arguments are errors with a message that leave `route` alone (the query itself needs a
+    plan, hence a GPU: tests/test_gpu_stft_strided.py)."""
+    lib = _lib.load()
+    assert "ssq_stft_plan_route" in _lib.header_symbols()
+    res, args = _lib._SIGNATURES["ssq_stft_plan_route"]
+    assert res is C.c_int and args == [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    with open(_lib.HEADER_PATH) as f:
+        src = f.read()
+    decl = src.split("int ssq_stft_plan_route(", 1)[1].split(");", 1)[0]
+    assert [a.strip() for a in decl.split(",")] == ["const ssq_stft_plan* plan", "int out_kind", "int* route"]
+    import re
+    names = re.findall(r"SSQ_STFT_ROUTE_([A-Z0-9_]+) = (\d+)", src)
+    assert [n for n, _ in names] == list(_lib.STFT_ROUTES) and [int(v) for _, v in names] == list(range(7))
+    route = C.c_int(77)
+    assert lib.ssq_stft_plan_route(None, _lib.OUT_TX, C.byref(route)) != 0 and route.value == 77
+    assert b"plan is NULL" in lib.ssq_last_error()
+
+
 def test_tile_segments_query_is_declared_bound_and_rejects_bad_arguments():
     """ssq_cwt_plan_tile_segments: in the header with the argument list of the ctypes table, and NULL arguments are
     errors with a message (the query itself needs a plan, hence a GPU: tests/test_gpu_cwt_tiles.py)."""
