@@ -487,6 +487,44 @@ int ssq_conceft_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_si
                          const double* ssq_freqs_asc, int freq_kind, int64_t freq_transition, int padtype, double gamma,
                          int variant, void* d_Tx, void* d_Wx, void* d_w, void* d_workspace, int64_t workspace_bytes,
                          void* stream, float* kernel_ms);
+/* ConceFT on the STFT, the multitaper synchrosqueezed STFT, `upstream.conceft_stft` (csrc/stft_conceft.hip, DESIGN 4.19;
+ * Daubechies, Wang and Wu 2016; upstream has no such transform).  tapers [n_tapers][n_fft]: real windows already sized
+ * to n_fft (1 <= n_tapers <= 8; n_fft a power of two from 16 to 4096); vectors [n_draws][n_tapers] complex (interleaved,
+ * fp64), the caller's unit vectors already gauged so that c_m = sum_j vectors[m][j] tapers[j][n_fft/2] > 0,
+ * 1 <= n_draws <= 256; scale: tapers[0][n_fft/2] / sum_m c_m > 0.  hop, fs, padtype as ssq_ssq_stft2_host; gamma < 0:
+ * 10 eps of the dtype, NaN is refused; variant: the SSQ_VARIANT_MODULATED and SSQ_VARIANT_FLIPUD bits.  With V_j, V1_j
+ * the STFTs of x with tapers[j] and its spectral derivative (Nyquist term zeroed), computed in fp64 and rounded once to
+ * `dtype`, then in `dtype`:
+ *   S = sum_j vectors[m][j] V_j, dS likewise from V1_j (j ascending);  w = fs |k/n_fft - Im(dS/S)/(2 pi)|, kept where
+ *   |S| > gamma;  b = ssq_ssq_stft2_host's bin of w on linspace(0, fs/2, F);  Tx[b][t] += S * (dw * scale rounded to
+ *   `dtype`), dw = the grid's step.
+ * One thread owns a column: no atomics, the additions into a cell in a fixed order (draws in chunks of 8; chunks, then
+ * rows, then draws ascending; a draw's run of rows in one bin is summed first), so a signal's result depends neither on
+ * `batch` nor on the workspace.
+ * Tx: [batch][F][n_frames] complex of `dtype`, F = n_fft/2 + 1, n_frames = (n_signal - 1)/hop + 1; ssq_freqs (may be
+ * NULL): F doubles; Sx, dSx (each may be NULL): [batch][n_tapers][F][n_frames] complex, the planes V_j, V1_j; w (may be
+ * NULL): [batch][n_draws][F][n_frames] REAL of `dtype`, every draw's frequency, +inf where not kept.
+ * Workspace: the 2 n_tapers planes of a slice, 32 (fp32: 16) n_tapers F bytes per frame, plus 8 n_signal bytes per
+ * signal of a slice for a float32 call; a slice is whole signals, or a run of whole store tiles (4096 / n_fft frames)
+ * of one signal.  work_limit_bytes: 0 for the preferred size, else at least min_bytes. */
+int ssq_conceft_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* tapers, int64_t n_tapers,
+                          int64_t n_fft, int64_t hop, double fs, int padtype, const double* vectors, int64_t n_draws,
+                          double scale, double gamma, int variant, int64_t work_limit_bytes, void* Tx, double* ssq_freqs,
+                          void* Sx, void* dSx, void* w);
+/* Device bytes of the workspace: returns the preferred size (whole signals up to 1 GiB; never below the least; the squeeze
+ * kernel runs one wave per 64 frames of a slice, so a larger workspace is faster until a slice holds some 200 000 frames)
+ * and stores the least one (one store tile of one signal) in *min_bytes (may be NULL); computed on the host; -1 on a bad
+ * shape. */
+int64_t ssq_conceft_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop,
+                                         int64_t n_tapers, int64_t* min_bytes);
+/* The same transform on device buffers: d_x [batch][n_signal], d_Tx (required), d_Sx, d_dSx, d_w (each may be NULL) as
+ * above, d_workspace of workspace_bytes >= min_bytes (its size sets the slices); tapers, vectors on the host.
+ * Synchronous on `stream`.  kernel_ms (may be NULL): TWO floats, the time of the squeeze kernel alone and of the plane
+ * kernel alone (each summed over the slices), from HIP events around their launches. */
+int ssq_conceft_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* tapers,
+                          int64_t n_tapers, int64_t n_fft, int64_t hop, double fs, int padtype, const double* vectors,
+                          int64_t n_draws, double scale, double gamma, int variant, void* d_Tx, void* d_Sx, void* d_dSx,
+                          void* d_w, void* d_workspace, int64_t workspace_bytes, void* stream, float* kernel_ms);
 
 /* ---- plans: device-resident batch pipelines -------------------------------- */
 typedef struct ssq_stft_plan ssq_stft_plan;

@@ -125,6 +125,12 @@ _SIGNATURES = {
     "ssq_conceft_cwt_exec": (C.c_int, [C.c_int, vp, i64, i64, C.c_double, C.c_double, vp, i64, i64, vp, i64, C.c_double,
                                        vp, i64, C.c_double, vp, vp, C.c_int, i64, C.c_int, C.c_double, C.c_int, vp, vp,
                                        vp, vp, i64, vp, C.POINTER(C.c_float)]),
+    "ssq_conceft_stft_host": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, i64, C.c_double, C.c_int, vp, i64,
+                                        C.c_double, C.c_double, C.c_int, i64, vp, vp, vp, vp, vp]),
+    "ssq_conceft_stft_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64, i64, C.POINTER(i64)]),
+    "ssq_conceft_stft_exec": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, i64, C.c_double, C.c_int, vp, i64,
+                                        C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp, i64, vp,
+                                        C.POINTER(C.c_float)]),
     "ssq_upstream_adm": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "ssq_upstream_center_frequency": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, i64, C.POINTER(C.c_double)]),
     "ssq_upstream_p2up": (C.c_int, [i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),

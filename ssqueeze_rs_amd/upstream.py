@@ -74,6 +74,14 @@ Supported subset (anything else raises ValueError naming the option):
     `cwt_higher_order` are computed once and every draw is formed, binned and summed from them in one fused kernel, no
     atomics, bitwise the same whatever the batch; the conventions of `ssq_cwt` for the 'gmw' wavelet and squeezing
     'sum'; its `Tx` inverts through `issq_cwt` like a first-order one;
+  * `conceft_stft`: ConceFT on the STFT, the multitaper synchrosqueezed STFT (Daubechies, Wang and Wu 2016), which
+    upstream does not have (the definition is this project's: DESIGN 4.19, csrc/stft_conceft.hip): the first-order
+    synchrosqueezed STFT under M random unit combinations of J tapers (an ndarray [J, win_len], or the orthonormal
+    Hermite windows of `hermite_windows`), gauged by the tapers' centre samples and averaged; the 2 J planes are computed
+    once in fp64 and every draw is formed, binned and summed from them in one kernel, no atomics, bitwise the same
+    whatever the batch and the workspace; the conventions of `ssq_stft2` (the five padtypes, `flipud`, `modulated`,
+    batches, a power-of-two `n_fft` from 16 to 4096) with squeezing 'sum'; its `Tx` inverts through
+    `issq_stft(Tx, window=tapers[0])`;
   * `extract_ridges` (ridge_extraction.py:11-233) on any 2-D (or batched 3-D) real, integer or complex map, with the
     serial backward trace (`parallel` is accepted and ignored).
 dtype: float64 in -> complex128 (upstream's 'float64'); float32 in -> complex64 (upstream's default 'float32').
@@ -1352,6 +1360,125 @@ def conceft_cwt(x, wavelet="gmw", scales="log-piecewise", orders=3, n_draws=20, 
                                    scale, _ptr(s), na, f.dt, _ptr(row_const), _ptr(f_asc), FREQS[scaletype], f_idx or 0,
                                    f.pad, f.gamma, VARIANT_FLIPUD if flipud else 0, 0, _ptr(Tx), _ptr(Wx), _ptr(w)))
     return (*_unbatch(f.batched, Tx), f_asc[::-1].astype(f.rdt), s.astype(f.rdt), *_unbatch(f.batched, Wx, w))
+
+
+def hermite_windows(n_fft, n_tapers, sigma=None):
+    """The first `n_tapers` orthonormal Hermite functions as windows of `n_fft` samples -> float64 [n_tapers, n_fft]: the
+    tapers of `conceft_stft` (Daubechies, Wang and Wu 2016, section 3).  psi_0(u) = pi^(-1/4) exp(-u^2 / 2) and the
+    three-term recurrence psi_{k+1} = sqrt(2 / (k + 1)) u psi_k - sqrt(k / (k + 1)) psi_{k-1}, sampled at
+    u = (i - n_fft // 2) / sigma and divided by sqrt(sigma), so that the rows are orthonormal in l2 once the window holds
+    them: with the default sigma = n_fft / 16 the Gram matrix of 8 tapers is within 1e-15 of the identity for n_fft >= 64
+    and within 3e-8 at n_fft = 32; at n_fft = 16 the higher tapers are cut off by the window and are NOT orthogonal (the
+    transform does not need orthogonality, only the gauge).  1 <= n_tapers <= 8."""
+    for name, v in (("n_fft", n_fft), ("n_tapers", n_tapers)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} {v!r}: must be an int")
+    if n_fft < 1:
+        raise ValueError(f"n_fft {n_fft!r}: must be positive")
+    if not 1 <= n_tapers <= CONCEFT_MAX_ORDERS:
+        raise ValueError(f"n_tapers {n_tapers!r}: 1 .. {CONCEFT_MAX_ORDERS} are built")
+    if sigma is None:
+        sigma = n_fft / 16
+    if (isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating))
+            or not math.isfinite(sigma) or not sigma > 0):
+        raise ValueError(f"sigma {sigma!r}: must be positive and finite")
+    sigma = float(sigma)
+    u = (np.arange(int(n_fft), dtype=np.float64) - int(n_fft) // 2) / sigma
+    h = np.empty((int(n_tapers), int(n_fft)), dtype=np.float64)
+    h[0] = math.pi ** -0.25 * np.exp(-0.5 * u * u)
+    for k in range(int(n_tapers) - 1):
+        h[k + 1] = math.sqrt(2.0 / (k + 1)) * u * h[k] - (math.sqrt(k / (k + 1.0)) * h[k - 1] if k else 0.0)
+    return h / math.sqrt(sigma)
+
+
+def conceft_stft(x, tapers=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
+                 n_tapers=3, n_draws=20, seed=0, vectors=None, gamma=None, flipud=False, get_planes=False, get_w=False):
+    """ConceFT on the STFT, the multitaper synchrosqueezed STFT (Daubechies, Wang and Wu 2016)
+    -> (Tx, ssq_freqs, Sfs[, Sx, dSx][, w]); not in upstream, conventions of `ssq_stft2`.  The form of ConceFT for noisy
+    band-limited data on a linear frequency grid: J orthonormal tapers h_j (default: `hermite_windows(n_fft, n_tapers)`),
+    M random unit vectors r_m in C^J that each give a window sum_j r_mj h_j, and the M first-order synchrosqueezed STFTs
+    averaged.  The signal's ridge is where every draw agrees; the noise-driven reassignments differ from draw to draw and
+    average down.
+
+    With c = n_fft // 2, V_j the STFT of `x` with h_j and V1_j the one with its spectral derivative (Nyquist term zeroed),
+    both run in fp64 for either dtype and rounded once to the call's dtype (padding, hop and `modulated` of `ssq_stft2`):
+        gauge      r_m normalised and turned by the unit phase that makes c_m = sum_j r_mj h_j[c] real and positive; a draw
+                   with c_m <= 1e-6 sum_j |r_mj| |h_j[c]| is refused
+        per draw   S = sum_j r_mj V_j, dS = sum_j r_mj V1_j (j ascending, in the call's dtype);
+                   w = fs |k / n_fft - Im(dS / S) / (2 pi)|, kept where |S| > gamma (default 10 eps of the dtype); the bin
+                   of w by `ssq_stft2`'s rule on np.linspace(0, fs / 2, F);  Tx[bin, t] += S dw h_0[c] / sum_m c_m
+    so `issq_stft(Tx, window=tapers[0])` inverts it at hop_len = 1; with vectors = [[1, 0, ...]] the factor is exactly dw
+    and Tx is the first-order squeeze with taper 0.  The 2 J planes are computed once per slice of frames and every draw
+    is formed, binned and summed from them in one kernel (csrc/stft_conceft.hip): one thread owns a column of Tx, no
+    atomics, the additions into a cell in a fixed order, so the result is bitwise the same run to run, whatever the batch
+    and the workspace.
+
+    `tapers`: an ndarray [J, win_len] of real windows (1 <= J <= 8), each sized to `n_fft` as `get_window` sizes one;
+    tapers[0][c] must be finite and non-zero.  `vectors` [M, J] complex overrides `n_draws` (1 .. 256) and `seed`; its rows
+    are normalised and gauged here.  `Sx`, `dSx` (get_planes=True): the planes V_j, V1_j [J, F, n_frames]; `w`
+    (get_w=True): every draw's frequency [M, F, n_frames], real, +inf where a bin is not kept.  A batch [B, N] gives a
+    leading B.  `n_fft` must be a power of two from 16 to 4096; the five padtypes.  Anything else raises ValueError
+    before any GPU work."""
+    lib = _lib.load()
+    if isinstance(hop_len, (bool, np.bool_)) or not isinstance(hop_len, (int, np.integer)) or hop_len < 1:
+        raise ValueError(f"hop_len {hop_len!r}: must be a positive int")
+    hop_len = int(hop_len)
+    if tapers is not None:
+        if (not isinstance(tapers, np.ndarray) or tapers.ndim != 2 or tapers.dtype.kind not in "fiu"
+                or not 1 <= tapers.shape[0] <= CONCEFT_MAX_ORDERS or tapers.shape[1] < 1):
+            raise ValueError(f"`tapers` must be a real ndarray [n_tapers, win_len] of 1 .. {CONCEFT_MAX_ORDERS} windows")
+        tapers = np.asarray(tapers, dtype=np.float64)
+        if not np.isfinite(tapers).all():
+            raise ValueError("`tapers` must be finite")
+        win0 = tapers[0]
+    else:
+        if isinstance(n_tapers, (bool, np.bool_)) or not isinstance(n_tapers, (int, np.integer)):
+            raise ValueError(f"n_tapers {n_tapers!r}: must be an int")
+        if not 1 <= n_tapers <= CONCEFT_MAX_ORDERS:
+            raise ValueError(f"n_tapers {n_tapers!r}: 1 .. {CONCEFT_MAX_ORDERS} are built")
+        win0 = np.zeros(win_len or 0)                        # (sized below, once n_fft is known)
+    f = _stft_front(x, win0, n_fft, win_len, hop_len, fs, t, "conceft_stft")
+    if not (math.isfinite(f.fs) and f.fs > 0):
+        raise ValueError(f"conceft_stft: fs must be positive and finite (got {f.fs!r})")
+    pad = _pad_code(padtype)
+    if tapers is None:
+        tapers = hermite_windows(win_len or f.n_fft, int(n_tapers))
+    wins = np.ascontiguousarray(np.stack([get_window(h, tapers.shape[1], f.n_fft) for h in tapers]))
+    J = wins.shape[0]
+    adm = wins[:, f.n_fft // 2].copy()
+    if not (math.isfinite(adm[0]) and adm[0] != 0):
+        raise ValueError("conceft_stft: tapers[0] at the window's centre (index n_fft // 2 once sized) must be finite and "
+                         f"non-zero (got {adm[0]!r}): it is the constant `issq_stft` divides by")
+    if vectors is None:
+        r, c = _conceft_gauge(_conceft_draws(n_draws, J, seed), adm)
+    else:
+        vectors = np.asarray(vectors)
+        if vectors.ndim != 2 or vectors.shape[1] != J or vectors.dtype.kind not in "fiuc":
+            raise ValueError(f"`vectors` must be a numeric array [n_draws, {J}] (one column per taper); got shape "
+                             f"{vectors.shape}")
+        if not 1 <= vectors.shape[0] <= CONCEFT_MAX_DRAWS:
+            raise ValueError(f"`vectors`: 1 .. {CONCEFT_MAX_DRAWS} draws are built (got {vectors.shape[0]})")
+        r, c = _conceft_gauge(vectors, adm)
+    M = r.shape[0]
+    scale = float(adm[0] / c.sum())                          # (vectors = e_0: h_0[c] / h_0[c], exactly 1)
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError("conceft_stft: tapers[0] at the window's centre must be positive under the gauge "
+                         f"(h_0[c] / sum_m c_m = {scale!r})")
+    g = _gamma_arg(gamma)
+    if g != g:
+        raise ValueError("conceft_stft: gamma is NaN")
+    _shape_checked(lib, lib.ssq_conceft_stft_workspace_bytes(f.code, f.batch, f.N, f.n_fft, hop_len, J, None))
+    _lib.require_gpu()
+    B, F, nfr = _stft_shape(f, hop_len)
+    Tx = _lib.pinned_empty((B, F, nfr), f.cdt)
+    Sx = _lib.pinned_empty((B, J, F, nfr), f.cdt) if get_planes else None
+    dSx = _lib.pinned_empty((B, J, F, nfr), f.cdt) if get_planes else None
+    w = _lib.pinned_empty((B, M, F, nfr), f.rdt) if get_w else None
+    freqs = np.empty(F, dtype=np.float64)
+    _call(lib.ssq_conceft_stft_host(f.code, _ptr(f.xa), f.batch, f.N, _ptr(wins), J, f.n_fft, hop_len, f.fs, pad, _ptr(r),
+                                    M, scale, g, _variant(modulated, flipud), 0, _ptr(Tx), _ptr(freqs), _ptr(Sx),
+                                    _ptr(dSx), _ptr(w)))
+    return (*_unbatch(f.batched, Tx), freqs.astype(f.rdt), _Sfs(f), *_unbatch(f.batched, Sx, dSx, w))
 
 
 def issq_cwt(Tx, wavelet="gmw", cc=None, cw=None):
