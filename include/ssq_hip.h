@@ -383,6 +383,47 @@ int ssq_ssq_cwt2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
 /* The two fp64 tables of one scale on the host (no GPU), by the functions the kernel evaluates them with
  * (csrc/cwt_sst2_wavelets.h): T0, T1 [P], zero above P/2.  P a power of two. */
 int ssq_ssq_cwt2_tables(int wavelet, double p0, double p1, double scale, int64_t P, double* T0, double* T1);
+/* Multisynchrosqueezed CWT, `upstream.mssq_cwt` (csrc/cwt_msst.hip; the CWT counterpart of
+ * ssq_mssq_stft_host; upstream has no such transform): ssq_ssq_cwt2_host whose frequency map is asked again at the row
+ * nearest to the bin a coefficient landed on, n_iter steps in all.  Arguments and conventions of ssq_ssq_cwt2_host; order
+ * 1 or 2, n_iter 1 .. 64, na 2 .. 2049.  Per column, with w[i] the one-step frequency of row i in `dtype` (order 2: that
+ * entry's w2 with its fallback; order 1: |Im om1| / (2 pi dt) on every element; +inf where |W| < gamma), b[i] the bin of
+ * w[i] by ssq_ssqueeze_w_exec's rule BEFORE any flip (-1 where w is infinite; NaN: bin 0) and row_of_bin [na] (host,
+ * every entry in 0 .. na - 1; `upstream.mssq_cwt_row_of_bin` builds the row nearest to each bin in log frequency):
+ *   r1[k] = k (kept k);   r(i+1)[k] = row_of_bin[b[ri[k]]] if b[row_of_bin[b[ri[k]]]] >= 0, else ri[k]   (i = 1 .. n_iter - 1)
+ *   w_n[k] = w[r_n[k]], +inf where k is not kept;   Tx = the scatter of Wx under w_n by ssq_ssqueeze_w_exec (FLIPUD there).
+ * A chain stops on a row without a map of its own and on a fixed point; a cycle turns until n_iter runs out.  n_iter = 1,
+ * order 2 is ssq_ssq_cwt2_host bit for bit.  Tx, Wx as there; w (may be NULL): the ONE-step frequency, REAL of `dtype`;
+ * rows (may be NULL): [batch][na][n_signal] int32, r_n, -1 where not kept; bins (may be NULL): int32, b.  Synchronous. */
+int ssq_mssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                      const double* scales, int64_t na, double dt, const double* row_const, const double* ssq_freqs_asc,
+                      int freq_kind, int64_t freq_transition, int padtype, int squeezing, double gamma, int variant,
+                      int64_t work_limit_bytes, int order, int n_iter, const int32_t* row_of_bin, void* Tx, void* Wx, void* w,
+                      int32_t* rows, int32_t* bins);
+/* Device bytes of the workspace ssq_mssq_cwt_exec needs: the plane of w_n ([batch][na][n_signal] REAL of `dtype`, to a
+ * multiple of 16 bytes) in front of ssq_ssq_cwt2_workspace_bytes' workspace.  Returns the preferred size and stores the
+ * least one in *min_bytes (may be NULL); computed on the host; -1 on a shape ssq_mssq_cwt_host refuses. */
+int64_t ssq_mssq_cwt_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int64_t* min_bytes);
+/* The same transform on device buffers: d_x [batch][n_signal], d_Tx, d_Wx, d_w (required), d_rows and d_bins (each may be
+ * NULL) as above, d_workspace of workspace_bytes >= min_bytes; scales, row_const, ssq_freqs_asc, row_of_bin on the host.
+ * n_iter = 1 with neither d_rows nor d_bins launches no walk kernel.  Synchronous on `stream`.  kernel_ms (may be NULL):
+ * THREE floats, the time of the pipeline with the operator, of the walk kernel, and of clearing Tx with the scatter, from
+ * HIP events around the launches with the tables set up before them. */
+int ssq_mssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                      const double* scales, int64_t na, double dt, const double* row_const, const double* ssq_freqs_asc,
+                      int freq_kind, int64_t freq_transition, int padtype, int squeezing, double gamma, int variant, int order,
+                      int n_iter, const int32_t* row_of_bin, void* d_Tx, void* d_Wx, void* d_w, int32_t* d_rows,
+                      int32_t* d_bins, void* d_workspace, int64_t workspace_bytes, void* stream, float* kernel_ms);
+/* The walk of ssq_mssq_cwt_host alone, on frequency maps the caller holds (the same kernel): w, w_n [batch][na][n_cols]
+ * REAL of `dtype` and rows, bins int32 of the same shape, all on the host and all required; +inf in w: not kept.  na
+ * 2 .. 2049, n_cols 1 .. 2^30, n_iter 1 .. 64; a row_of_bin entry outside 0 .. na - 1 is refused on the host.
+ * Synchronous. */
+int ssq_mssq_cwt_walk_host(int dtype, const void* w, int64_t batch, int64_t na, int64_t n_cols, const double* ssq_freqs_asc,
+                           int freq_kind, int64_t freq_transition, const int32_t* row_of_bin, int n_iter, int32_t* rows,
+                           int32_t* bins, void* w_n);
+/* Columns of the tile one workgroup of the walk kernel holds in LDS for `na` rows (16 .. 256; host only), -1 outside
+ * 2 .. 2049. */
+int ssq_mssq_cwt_tile_cols(int64_t na);
 /* Reassigned scalogram, `upstream.reassign_cwt` (csrc/cwt_reassign.hip; Auger and Flandrin 1995, III;
  * upstream has no such transform): every coefficient's energy |Wx|^2 moves along frequency AND time at once, to its
  * instantaneous frequency and its group delay (first order only).  Arguments as ssq_ssq_cwt2_host without row weights

@@ -107,6 +107,15 @@ _SIGNATURES = {
                                     C.c_int, i64, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, i64, vp,
                                     C.POINTER(C.c_float)]),
     "ssq_ssq_cwt2_tables": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, i64, vp, vp]),
+    "ssq_mssq_cwt_host": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, C.c_double, vp, vp,
+                                    C.c_int, i64, C.c_int, C.c_int, C.c_double, C.c_int, i64, C.c_int, C.c_int, vp, vp, vp,
+                                    vp, vp, vp]),
+    "ssq_mssq_cwt_workspace_bytes": (i64, [C.c_int, i64, i64, i64, C.POINTER(i64)]),
+    "ssq_mssq_cwt_exec": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, C.c_double, vp, vp,
+                                    C.c_int, i64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,
+                                    vp, vp, vp, i64, vp, C.POINTER(C.c_float)]),
+    "ssq_mssq_cwt_walk_host": (C.c_int, [C.c_int, vp, i64, i64, i64, vp, C.c_int, i64, vp, C.c_int, vp, vp, vp]),
+    "ssq_mssq_cwt_tile_cols": (C.c_int, [i64]),
     "ssq_reassign_cwt_host": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, C.c_double, vp,
                                         C.c_int, i64, C.c_int, C.c_double, C.c_int, i64, vp, vp, vp, vp, vp, vp]),
     "ssq_reassign_cwt_workspace_bytes": (i64, [C.c_int, i64, i64, i64, C.POINTER(i64)]),

@@ -9,15 +9,15 @@
 //                         1 / |W|^2 and 1 / |D|^2 formed once, Wx and w2 out in the call's dtype.
 //   ssq_ssqueeze_w_exec   the deterministic scatter of Wx under w2 (rows ascending, no atomics) into Tx.
 // Wx and w2 are rounded once on store, the scatter runs in the call's dtype on the rounded values, so Tx is the scatter
-// of what the call reports.  A first version with no time target (DESIGN 4.12 has the cost).
+// of what the call reports.  A first version with no time target (DESIGN 4.12 has the cost).  cwt_msst.hip (mssq_cwt)
+// runs both halves of this file, the operator half and the squeeze half, through cwt_sst2.h, with its walk kernel
+// between them; ssq_cwt2 calls the same two halves one after the other.
 #include <cmath>
 #include <vector>
 
-#include "cwt_maps64.h"
+#include "cwt_sst2.h"
 
 namespace ssq {
-
-constexpr int kCwt2Maps = cwt_map_count(kMapsAll);            // W, W1, W2, Wt, Wt1
 
 template <typename O>
 struct Cwt2OpDev {
@@ -57,57 +57,41 @@ __global__ __launch_bounds__(kCwtThreads) void cwt2_operator_kernel(const Cwt2Op
   }
 }
 
-}  // namespace ssq
-
-using namespace ssq;
-
-namespace {
-
-constexpr CwtMapsKind kCwt2Kind = {"ssq_cwt2", "ssq_ssq_cwt2_workspace_bytes", 16.0, 9.0e18, 0};   // no head
-
-struct Cwt2Call {
-  CwtMapsCall m;
-  int freq_kind, squeezing, variant;
-  int64_t freq_transition;
-  const double *row_const, *f_asc;
-};
-
-int cwt2_check(const Cwt2Call& c, CwtMapsShape* s) {
+int cwt2_check(const CwtMapsKind& k, const char* own_fail, const Cwt2Call& c, CwtMapsShape* s) {
+  const std::string pre = std::string(k.name) + ": ";
   const auto rows = [&]() -> int {
     if (!c.m.scales || !c.row_const || !c.f_asc) SSQ_FAIL("NULL argument");
     for (int64_t i = 0; i < c.m.na; ++i) {
-      if (!(c.m.scales[i] > 0) || !std::isfinite(c.m.scales[i])) SSQ_FAIL("ssq_cwt2: scales must be positive and finite");
-      if (!std::isfinite(c.row_const[i])) SSQ_FAIL("ssq_cwt2: row_const must be finite");
-      if (!std::isfinite(c.f_asc[i])) SSQ_FAIL("ssq_cwt2: ssq_freqs_asc must be finite");
+      if (!(c.m.scales[i] > 0) || !std::isfinite(c.m.scales[i])) SSQ_FAIL(pre + "scales must be positive and finite");
+      if (!std::isfinite(c.row_const[i])) SSQ_FAIL(pre + "row_const must be finite");
+      if (!std::isfinite(c.f_asc[i])) SSQ_FAIL(pre + "ssq_freqs_asc must be finite");
     }
     return 0;
   };
   const bool sq_ok = c.squeezing == SSQ_SQUEEZE_SUM || c.squeezing == SSQ_SQUEEZE_LEBESGUE;
-  return cwt_maps_check(kCwt2Kind, kCwt2Maps, nullptr, c.m, rows, &c.freq_kind, c.freq_transition,
+  return cwt_maps_check(k, kCwt2Maps, own_fail, c.m, rows, &c.freq_kind, c.freq_transition,
                         sq_ok ? nullptr : "squeezing must be 'sum' or 'lebesgue'", s);
 }
 
-// The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the rows per chunk.  Synchronous.
 template <typename T>
-int cwt2_run(const Cwt2Call& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_w2, void* d_work,
-             int64_t work_bytes, hipStream_t st, float* kernel_ms) {
-  const int64_t N = c.m.N, na = c.m.na;
-  HostCallBufs d;
-  TimingEvents t;
-  void *d_scales = nullptr, *d_rc = nullptr;
-  SSQ_HIP(d.upload(&d_scales, c.m.scales, sizeof(double) * (size_t)na));
-  {
-    const std::vector<T> rc(c.row_const, c.row_const + na);
-    SSQ_HIP(d.upload(&d_rc, rc.data(), sizeof(T) * (size_t)na));
-  }
-  if (kernel_ms) SSQ_HIP(t.start(2, st));
+int cwt2_tables(HostCallBufs& d, const Cwt2Call& c, void** d_scales, void** d_rc) {
+  SSQ_HIP(d.upload(d_scales, c.m.scales, sizeof(double) * (size_t)c.m.na));
+  const std::vector<T> rc(c.row_const, c.row_const + c.m.na);
+  SSQ_HIP(d.upload(d_rc, rc.data(), sizeof(T) * (size_t)c.m.na));
+  return 0;
+}
+
+template <typename T>
+int cwt2_operator_run(const Cwt2Call& c, const CwtMapsShape& s, double gamma_sq, const void* d_x, const void* d_scales,
+                      void* d_Wx, void* d_w2, void* d_work, int64_t work_bytes, hipStream_t st) {
+  const int64_t N = c.m.N;
   Cwt2OpDev<T> op{};
   op.P = s.P;
   op.N = N;
   op.n1 = s.n1;
   op.inv_P = 1.0 / (double)s.P;
   op.gamma = s.gamma;
-  op.gamma_sq = s.gamma * s.gamma;
+  op.gamma_sq = gamma_sq;
   op.inv_two_pi_dt = 1.0 / (6.283185307179586 * c.m.dt);
   const auto launch_op = [&](const cpx<double>* maps, int64_t r0, int64_t nr) -> int {
     op.maps = maps;
@@ -118,10 +102,40 @@ int cwt2_run(const Cwt2Call& c, const CwtMapsShape& s, const void* d_x, void* d_
     SSQ_HIP(hipGetLastError());
     return 0;
   };
-  if (int rc = cwt_maps_chunks<T, kMapsAll>(c.m, s, d_x, d_scales, d_work, work_bytes, st, launch_op)) return rc;
-  if (int rc = ssq_ssqueeze_w_exec(c.m.dtype, d_Wx, d_w2, c.m.batch, na, N, d_rc, c.f_asc, c.freq_kind, c.freq_transition,
-                                   c.squeezing, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, d_Tx, st))
-    return rc;
+  return cwt_maps_chunks<T, kMapsAll>(c.m, s, d_x, d_scales, d_work, work_bytes, st, launch_op);
+}
+
+int cwt2_squeeze_run(const Cwt2Call& c, const void* d_Wx, const void* d_w, const void* d_rc, void* d_Tx, hipStream_t st) {
+  return ssq_ssqueeze_w_exec(c.m.dtype, d_Wx, d_w, c.m.batch, c.m.na, c.m.N, d_rc, c.f_asc, c.freq_kind, c.freq_transition,
+                             c.squeezing, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, d_Tx, st);
+}
+
+template int cwt2_tables<float>(HostCallBufs&, const Cwt2Call&, void**, void**);
+template int cwt2_tables<double>(HostCallBufs&, const Cwt2Call&, void**, void**);
+template int cwt2_operator_run<float>(const Cwt2Call&, const CwtMapsShape&, double, const void*, const void*, void*, void*,
+                                      void*, int64_t, hipStream_t);
+template int cwt2_operator_run<double>(const Cwt2Call&, const CwtMapsShape&, double, const void*, const void*, void*, void*,
+                                       void*, int64_t, hipStream_t);
+
+}  // namespace ssq
+
+using namespace ssq;
+
+namespace {
+
+constexpr CwtMapsKind kCwt2Kind = {"ssq_cwt2", "ssq_ssq_cwt2_workspace_bytes", 16.0, 9.0e18, 0};   // no head
+
+// The whole transform on device buffers: the two halves, one after the other.  Synchronous.
+template <typename T>
+int cwt2_run(const Cwt2Call& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_w2, void* d_work,
+             int64_t work_bytes, hipStream_t st, float* kernel_ms) {
+  HostCallBufs d;
+  TimingEvents t;
+  void *d_scales = nullptr, *d_rc = nullptr;
+  if (int rc = cwt2_tables<T>(d, c, &d_scales, &d_rc)) return rc;
+  if (kernel_ms) SSQ_HIP(t.start(2, st));
+  if (int rc = cwt2_operator_run<T>(c, s, s.gamma * s.gamma, d_x, d_scales, d_Wx, d_w2, d_work, work_bytes, st)) return rc;
+  if (int rc = cwt2_squeeze_run(c, d_Wx, d_w2, d_rc, d_Tx, st)) return rc;
   if (kernel_ms) {
     SSQ_HIP(hipEventRecord(t.ev[1], st));
     SSQ_HIP(hipEventSynchronize(t.ev[1]));
@@ -184,7 +198,7 @@ int ssq_ssq_cwt2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
   const Cwt2Call c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales},
                    freq_kind, squeezing, variant, freq_transition, row_const, ssq_freqs_asc};
   CwtMapsShape s;
-  if (int rc = cwt2_check(c, &s)) return rc;
+  if (int rc = cwt2_check(kCwt2Kind, nullptr, c, &s)) return rc;
   if (int rc = cwt_exec_bytes(kCwt2Kind, s, workspace_bytes)) return rc;
   if (int rc = require_device()) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -201,7 +215,7 @@ int ssq_ssq_cwt2_host(int dtype, const void* x, int64_t batch, int64_t n_signal,
                    freq_kind, squeezing, variant, freq_transition, row_const, ssq_freqs_asc};
   CwtMapsShape s;
   int64_t work = 0;
-  if (int rc = cwt2_check(c, &s)) return rc;
+  if (int rc = cwt2_check(kCwt2Kind, nullptr, c, &s)) return rc;
   if (int rc = cwt_host_bytes(kCwt2Kind, s, batch, work_limit_bytes, &work)) return rc;
   if (int rc = require_device()) return rc;
   return dtype == SSQ_F32 ? cwt2_host_typed<float>(c, s, x, work, Tx, Wx, w2) : cwt2_host_typed<double>(c, s, x, work, Tx, Wx, w2);

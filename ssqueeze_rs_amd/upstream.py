@@ -57,6 +57,12 @@ Supported subset (anything else raises ValueError naming the option):
     project's: DESIGN 4.12, csrc/cwt_sst2.hip): the conventions of `ssq_cwt` (ndarray scales of the three grids,
     `ssq_freqs` None / a string / an array, maprange 'peak' / 'maximal', 'sum' / 'lebesgue', the five padtypes, `flipud`,
     batches) for the order-0 'gmw' and 'morlet' wavelets; its `Tx` inverts through `issq_cwt` like a first-order one;
+  * `mssq_cwt`: the multisynchrosqueezed CWT (orders 1 and 2), the CWT counterpart of `mssq_stft`, which upstream does not
+    have (the definition is this project's: DESIGN 4.20, csrc/cwt_msst.hip): `ssq_cwt2`'s frequency map asked again at
+    the row nearest in log frequency to the bin a coefficient landed on (`mssq_cwt_row_of_bin`), `n_iter` steps in all
+    (1 .. 64), for 2 .. 2049 scales; the conventions of `ssq_cwt2`; a coefficient keeps its own row weight and its phase,
+    so `Tx` keeps every column's weighted sum and inverts through `issq_cwt` like a first-order one; `mssq_cwt_walk` runs
+    the walk alone on a frequency map the caller holds;
   * `reassign_cwt`: the reassigned scalogram (Auger and Flandrin 1995, III), which upstream does not have (the definition
     is this project's: DESIGN 4.15, csrc/cwt_reassign.hip): every coefficient's energy |Wx|^2 moves along frequency and
     time at once, to its instantaneous frequency and group delay (first order); the conventions of `ssq_cwt2` without
@@ -1198,6 +1204,128 @@ def tssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None,
     _call(lib.ssq_tssq_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), _ptr(nu), len(s), f.dt,
                                 f.pad, order, f.gamma, limit, _ptr(Tx), _ptr(Wx), _ptr(tau), _ptr(mm)))
     return (*_unbatch(f.batched, Tx, Wx), s.astype(f.rdt), (nu / f.dt).astype(f.rdt), *_unbatch(f.batched, tau, mm))
+
+
+def mssq_cwt_row_of_bin(wavelet, scales, ssq_freqs_asc, fs=None):
+    """rho, int32 [na]: for every bin of the ascending `ssq_freqs_asc` the row of `scales` whose frequency
+    nu_i = `tssq_cwt_row_freqs(wavelet, scales)[i]` fs is nearest in log2 (rows are constant-Q, so log distance is used for
+    'linear' grids too); on a tie the lowest row; a bin with a frequency <= 0 takes the row of the lowest nu.  float64,
+    numpy, no GPU.  On a 'peak' log grid over log scales it is the reversal na - 1 - bin."""
+    nu = tssq_cwt_row_freqs(wavelet, scales) * (1.0 if fs is None else float(fs))
+    f = np.ascontiguousarray(ssq_freqs_asc, dtype=np.float64).reshape(-1)
+    if f.size != nu.size:
+        raise ValueError("`ssq_freqs_asc` must have one frequency per scale (%s != %s)" % (f.size, nu.size))
+    if not (np.isfinite(f).all() and np.isfinite(nu).all() and (nu > 0).all()):
+        raise ValueError("`ssq_freqs_asc` and the rows' frequencies must be finite (and the rows' positive)")
+    pos = f > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dist = np.abs(np.log2(nu)[None, :] - np.log2(np.where(pos, f, 1.0))[:, None])
+    return np.where(pos, dist.argmin(axis=1), int(nu.argmin())).astype(np.int32)
+
+
+def _mssq_cwt_rows(na):
+    if not 2 <= na <= MSST_MAX_ROWS:
+        raise ValueError(f"na = {na} scales: mssq_cwt builds 2 .. {MSST_MAX_ROWS} (the walk holds every row of a tile of "
+                         "columns in LDS)")
+
+
+def mssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, ssq_freqs=None, padtype="reflect",
+             squeezing="sum", maprange="peak", gamma=None, flipud=True, order=2, n_iter=4, get_w=False, get_rows=False,
+             get_bins=False):
+    """Multisynchrosqueezed CWT -> (Tx, Wx, ssq_freqs, scales[, w][, rows][, bins]); not in upstream (the CWT counterpart of
+    `mssq_stft`; Yu, Wang and Zhao 2019), conventions of `ssq_cwt2`.  Where `ssq_cwt2` applies its frequency map once, this
+    asks the map again at the row nearest to the bin a coefficient landed on, `n_iter` steps in all: on a signal whose
+    modulation is not linear inside the wavelet the one-step estimate taken off the ridge is biased, and the estimate
+    taken where it points is closer.
+
+    Per column, with na rows (scales ascending) and f_asc [na] the ascending bin frequencies the call squeezes onto:
+        w[i]    the one-step frequency of row i, in the call's dtype, as reported (get_w=True): `order=2` the w2 of
+                `ssq_cwt2`, including its fallback to the first-order frequency where |D| <= gamma^2; `order=1`
+                |Im om1| / (2 pi dt) on every element (it runs the same five transforms and costs the same); +inf where
+                |W| < gamma
+        b[i]    the one-step bin: `ssqueeze`'s bin rule on w[i], in the call's dtype, before any `flipud`; -1 where w is
+                infinite; NaN lands in bin 0, as `ssqueeze` has it
+        rho[k]  the row of bin k: `mssq_cwt_row_of_bin(wavelet, scales, f_asc, fs)`, the row nearest in log frequency
+                (the rows and the bins are different index sets; on a 'peak' log grid rho is the reversal na - 1 - k)
+    The walk, in row space:
+        r1[k] = k  (kept k)
+        r(i+1)[k] = rho[b[ri[k]]]  if b[rho[b[ri[k]]]] >= 0,  else ri[k]             (i = 1 .. n_iter - 1)
+    A chain stops on a row that has no map of its own and on a fixed point; a cycle keeps turning until `n_iter` runs
+    out.  Then w_n[k] = w[r_n[k]] (+inf where k is not kept) and `Tx` = `ssqueeze(Wx, w_n, ...)`: rows ascending inside a
+    column, no atomics, `flipud` applied there and nowhere else.  A coefficient lands on bin b[r_n[k]] with its OWN
+    row weight and keeps its phase, so every column keeps its weighted sum: `issq_cwt`, `extract_ridges` and the
+    component inversion take `Tx` unchanged.  `n_iter=1`, `order=2` is `ssq_cwt2` bit for bit.
+
+    `Wx` equals `ssq_cwt2`'s; `w` is the ONE-step map; `rows` (get_rows=True) is int32 r_n, -1 where an element is not
+    kept; `bins` (get_bins=True) is int32 b, the one-step bins the kernel computed.  `mssq_cwt_walk` runs the walk alone
+    on a frequency map the caller holds.
+
+    Built: what `ssq_cwt2` builds, with `order` 1 or 2, `n_iter` an int from 1 to 64 (the bound of `mssq_stft`), 2 .. 2049
+    scales and `squeezing` 'sum' or 'lebesgue'.  Anything else raises ValueError before any GPU work.  The walk runs out
+    of LDS, a tile of columns at a time (csrc/cwt_msst.hip); its kernel is built without register spills or scratch
+    (profiles/msst_cwt_resources.txt)."""
+    lib = _lib.load()
+    order = _order12(order, "mssq_cwt builds orders 1 and 2")
+    n_iter = _n_iter(n_iter)
+    squeeze = _squeeze_code(squeezing)
+    f = _cwt_front(x, wavelet, scales, fs, t, gamma, padtype)
+    s, row_const, f_asc, scaletype, f_idx = _finite_freq_grid(f, scales, nv, ssq_freqs, maprange)
+    _mssq_cwt_rows(len(s))
+    rho = mssq_cwt_row_of_bin(wavelet, s, f_asc, 1.0 / f.dt)
+    _lib.require_gpu()
+    shape = (f.batch, len(s), f.N)
+    Tx, Wx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    w = _lib.pinned_empty(shape, f.rdt) if get_w else None
+    rows = _lib.pinned_empty(shape, np.int32) if get_rows else None
+    bins = _lib.pinned_empty(shape, np.int32) if get_bins else None
+    _call(lib.ssq_mssq_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), len(s), f.dt,
+                                _ptr(row_const), _ptr(f_asc), FREQS[scaletype], f_idx or 0, f.pad, squeeze, f.gamma,
+                                VARIANT_FLIPUD if flipud else 0, 0, order, n_iter, _ptr(rho), _ptr(Tx), _ptr(Wx), _ptr(w),
+                                _ptr(rows), _ptr(bins)))
+    return (*_unbatch(f.batched, Tx, Wx), f_asc[::-1].astype(f.rdt), s.astype(f.rdt), *_unbatch(f.batched, w, rows, bins))
+
+
+def mssq_cwt_walk(w, ssq_freqs_asc, row_of_bin, n_iter):
+    """The walk of `mssq_cwt` alone, on a frequency map the caller holds -> (rows, bins, w_n).  `w`: float32 / float64
+    [na, n] or [B, na, n] (2 <= na <= 2049), +inf where an element is not kept; `ssq_freqs_asc` [na]: the ascending bin
+    frequencies, their type ('log', 'linear', 'log-piecewise') inferred as `ssqueeze` infers it; `row_of_bin` [na]: the
+    row of every bin.  `bins` is int32 b, the bin of every element by `ssqueeze`'s rule in w's dtype (-1 where w is
+    infinite); `rows` int32 r_n of the walk in `mssq_cwt`'s docstring (-1 where not kept); `w_n` = w[r_n], +inf where not
+    kept.  Runs the kernel of `mssq_cwt` (csrc/cwt_msst.hip); every refusal is a ValueError before any GPU work."""
+    lib = _lib.load()
+    n_iter = _n_iter(n_iter)
+    if not isinstance(w, np.ndarray) or w.dtype not in (np.float32, np.float64) or w.ndim not in (2, 3):
+        raise ValueError("`w` must be a float32 or float64 ndarray [na, n] or [B, na, n]")
+    w3 = np.ascontiguousarray(w if w.ndim == 3 else w[None])
+    B, na, n = w3.shape
+    if not 2 <= na <= MSST_MAX_ROWS or B < 1 or n < 1:
+        raise ValueError(f"`w` of shape {w.shape}: 2 .. {MSST_MAX_ROWS} rows, and no empty axis")
+    if not isinstance(ssq_freqs_asc, np.ndarray) or ssq_freqs_asc.shape != (na,) or ssq_freqs_asc.dtype.kind != "f":
+        raise ValueError("`ssq_freqs_asc` must be a float ndarray with one frequency per row of `w`")
+    if not (np.isfinite(ssq_freqs_asc).all() and (np.diff(ssq_freqs_asc) > 0).all()):
+        raise ValueError("`ssq_freqs_asc` must be finite and ascending")
+    if na == 2:                                            # (two frequencies have no second difference to infer from)
+        f_asc, scaletype, f_idx = np.ascontiguousarray(ssq_freqs_asc, dtype=np.float64), "linear", None
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f_asc, scaletype, f_idx = _freq_type(ssq_freqs_asc, None, None, None)
+    rho = np.asarray(row_of_bin)
+    if rho.shape != (na,) or rho.dtype.kind not in "iu" or rho.min() < 0 or rho.max() >= na:
+        raise ValueError(f"`row_of_bin` must hold one integer row from 0 to na - 1 = {na - 1} per bin")
+    rho = np.ascontiguousarray(rho, dtype=np.int32)
+    _lib.require_gpu()
+    rows, bins, w_n = np.empty(w3.shape, np.int32), np.empty(w3.shape, np.int32), np.empty_like(w3)
+    _call(lib.ssq_mssq_cwt_walk_host(SSQ_F32 if w3.dtype == np.float32 else SSQ_F64, _ptr(w3), B, na, n, _ptr(f_asc),
+                                     FREQS[scaletype], f_idx or 0, _ptr(rho), n_iter, _ptr(rows), _ptr(bins), _ptr(w_n)))
+    return tuple(_unbatch(w.ndim == 3, rows, bins, w_n))
+
+
+def mssq_cwt_tile_cols(na):
+    """Columns of the LDS tile one workgroup of `mssq_cwt`'s walk kernel owns for `na` scales (no GPU needed)."""
+    c = _lib.load().ssq_mssq_cwt_tile_cols(int(na))
+    if c < 0:
+        raise ValueError(f"na {na!r}: 2 .. {MSST_MAX_ROWS}")
+    return int(c)
 
 
 CONCEFT_MAX_ORDERS = 8                  # csrc/cwt_conceft.hip: kConceftMaxOrders
