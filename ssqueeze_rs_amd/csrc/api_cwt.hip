@@ -2,6 +2,7 @@
 // Replaces the PyO3 functions `cwt` / `cwt_simd` (rust/src/spectral/cwt.rs:46-144,
 // cwt_simd.rs:52-150) and `ssq_cwt` (rust/src/spectral/ssq_cwt.rs:244-493).
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -12,6 +13,7 @@
 #include <mutex>
 
 #include "cwt_kernels.h"
+#include "dev_buffers.h"
 #include "host_cache.h"
 #include "host_math.h"
 
@@ -24,22 +26,17 @@ struct ssq_cwt_plan {
   bool two_step = false, naive = false;
   bool big = false;            // P > 2^24: batched generic device FFT instead of the tile transforms
   int wavelet = 0, padtype = 0, na = 0;
+  DeviceBufs mem;              // owns every device table below (the d_* fields are views)
   // upstream-parity mode (SSQ_VARIANT_UPSTREAM; old/ssqueezepy): p2up padding, normalised wavelets (wavelet table codes
   // 2 = GMW(gamma = wp0, beta = wp1), 3 = Morlet(mu = wp0)) with a halved Nyquist bin, the generic transforms only.
-  // ups_freqs / ups_const: the ascending frequencies and the row weights (ssqueezing.py:122-133) the next ssq exec bins
-  // with; ups_rows: the weights differ between rows or the bins are log-piecewise (cwt_reassign_rows_kernel, weights in
-  // d_ups_const); ups_idx: the transition of log-piecewise frequencies (ups_freqs[:idx], ups_freqs[idx:])
+  // What an ssq exec of such a plan bins with is an argument of that exec (SsqBins), not a property of the plan
   int variant = 0, table_code = 0;
   double wp0 = 0.0, wp1 = 0.0;
   // higher-order upstream GMW (wavelet_table_gmwk_kernel): gmwk_groups polynomials of gmwk_n coefficients; the plan's
   // rows are the groups one after the other (row r: polynomial r / (na / gmwk_groups), scale scales[r]); empty = codes 2, 3
   std::vector<double> gmwk;
   int gmwk_n = 0, gmwk_groups = 1;
-  std::vector<double> ups_freqs;
-  std::vector<double> ups_const;
-  bool ups_rows = false;
-  int ups_idx = 0;
-  void* d_ups_const = nullptr; // [na] T
+  void* d_ups_const = nullptr; // [na] T: room for an exec's row weights (SsqBins::d_row_const), allocated on first need
   double dt = 1.0;
   std::vector<double> scales;
   void* d_psih = nullptr;      // wavelet table: scale s at psi_off[s], band[s] entries of T (zero beyond: not stored)
@@ -133,113 +130,87 @@ double upstream_support(int wavelet, double p0, double p1, int dtype, const doub
   return w;
 }
 
+// exp(-2 pi i num / den), evaluated in long double and rounded once to T
 template <typename T>
-int upload_tw(void** dst, long long n, long long P_total, long long stride) {
-  // dst[i] = exp(-2*pi*i * (i*stride) / P_total), i in [0, n)
-  std::vector<cpx<T>> h((size_t)(n > 0 ? n : 1));
-  for (long long i = 0; i < n; ++i) {
-    const long double ang = 2.0L * kPI * (long double)(i * stride) / (long double)P_total;
-    h[i] = {(T)cosl(ang), (T)(-sinl(ang))};
-  }
-  SSQ_HIP(hipMalloc(dst, sizeof(cpx<T>) * h.size()));
-  SSQ_HIP(hipMemcpy(*dst, h.data(), sizeof(cpx<T>) * h.size(), hipMemcpyHostToDevice));
+cpx<T> twiddle(long long num, long long den) {
+  const long double ang = 2.0L * kPI * (long double)num / (long double)den;
+  return {(T)cosl(ang), (T)(-sinl(ang))};
+}
+
+// dst[i] = exp(-2*pi*i * (i*stride) / P_total), i in [0, n)
+template <typename T>
+int upload_tw(ssq_cwt_plan* pl, void** dst, long long n, long long P_total, long long stride) {
+  std::vector<cpx<T>> h((size_t)n);
+  for (long long i = 0; i < n; ++i) h[(size_t)i] = twiddle<T>(i * stride, P_total);
+  SSQ_HIP(pl->mem.upload(dst, h));
   return 0;
+}
+
+// appends the W_M table (M = 2^logm) and behind it, for fp64 and 4 <= logm <= 12, the per-pass compact tables
+// [m][k] = exp(-2 pi i k m / (NS R)) of the tile transform (cwt_tw_compact_elems entries)
+template <typename T>
+void append_tw_tile(std::vector<cpx<T>>& h, int logm) {
+  const size_t h0 = h.size();
+  const long long M = 1LL << logm;
+  for (long long i = 0; i < M; ++i) h.push_back(twiddle<T>(i, M));
+  const bool compact = sizeof(T) == 8 && logm >= 4 && logm <= 12;
+  if (compact)
+    for (int P = 1; P < num_passes(logm); ++P) {
+      const int R = pass_radix(logm, P), NS = pass_ns(logm, P);
+      for (int m = 0; m < R; ++m)
+        for (int k = 0; k < NS; ++k) h.push_back(twiddle<T>((long long)k * m, (long long)NS * R));
+    }
+  assert((long long)(h.size() - h0) == M + (compact ? cwt_tw_compact_elems(logm) : 0));
+  (void)h0;
 }
 
 template <typename T>
 int build_tables(ssq_cwt_plan* pl) {
-  const long long P1 = 1LL << pl->log_p1, P2 = 1LL << pl->log_p2;
-  // W_M table, and behind it (fp64 plans) the per-pass compact tables [m][k] = exp(-2 pi i k m / (NS R)) of the tile transform
-  auto upload_tw_tile = [&](void** dst, int logm) -> int {
-    const long long M = 1LL << logm;
-    const long long extra = (sizeof(T) == 8 && logm >= 4 && logm <= 12) ? cwt_tw_compact_elems(logm) : 0;
-    std::vector<cpx<T>> h((size_t)(M + extra));
-    for (long long i = 0; i < M; ++i) {
-      const long double ang = 2.0L * kPI * (long double)i / (long double)M;
-      h[(size_t)i] = {(T)cosl(ang), (T)(-sinl(ang))};
-    }
-    if (extra > 0) {
-      long long off = M;
-      for (int P = 1; P < num_passes(logm); ++P) {
-        const int R = pass_radix(logm, P), NS = pass_ns(logm, P);
-        for (int m = 0; m < R; ++m)
-          for (int k = 0; k < NS; ++k) {
-            const long double ang = 2.0L * kPI * (long double)((long long)k * m) / (long double)((long long)NS * R);
-            h[(size_t)(off + (long long)m * NS + k)] = {(T)cosl(ang), (T)(-sinl(ang))};
-          }
-        off += (long long)R * NS;
-      }
-    }
-    SSQ_HIP(hipMalloc(dst, sizeof(cpx<T>) * h.size()));
-    SSQ_HIP(hipMemcpy(*dst, h.data(), sizeof(cpx<T>) * h.size(), hipMemcpyHostToDevice));
-    return 0;
-  };
-  if (int rc = upload_tw_tile(&pl->d_tw1, pl->log_p1)) return rc;
-  if (int rc = upload_tw_tile(&pl->d_tw2, pl->log_p2)) return rc;
+  DeviceBufs& mem = pl->mem;
+  const long long P1 = 1LL << pl->log_p1;
+  for (int step = 1; step <= 2; ++step) {
+    std::vector<cpx<T>> h;
+    append_tw_tile<T>(h, step == 1 ? pl->log_p1 : pl->log_p2);
+    SSQ_HIP(mem.upload(step == 1 ? &pl->d_tw1 : &pl->d_tw2, h));
+  }
   if (pl->two_step) {
-    // in-tile factors of the W_P twiddle (the other factor, W_P^(t0 k), is formed per tile in LDS)
-    auto upload_f2 = [&](void** dst, long long rows, long long cols, bool row_is_k) -> int {
+    // in-tile factors of the W_P twiddle (the other factor, W_P^(t0 k), is formed per tile in LDS): [rows][cols] W_P^(i j)
+    auto upload_f2 = [&](void** dst, long long rows, long long cols) -> int {
       std::vector<cpx<T>> h((size_t)(rows * cols));
       for (long long i = 0; i < rows; ++i)
-        for (long long j = 0; j < cols; ++j) {
-          const long double ang = 2.0L * kPI * (long double)(i * j) / (long double)pl->P;   // c*k either way
-          h[(size_t)(i * cols + j)] = {(T)cosl(ang), (T)(-sinl(ang))};
-        }
-      (void)row_is_k;
-      SSQ_HIP(hipMalloc(dst, sizeof(cpx<T>) * h.size()));
-      SSQ_HIP(hipMemcpy(*dst, h.data(), sizeof(cpx<T>) * h.size(), hipMemcpyHostToDevice));
+        for (long long j = 0; j < cols; ++j) h[(size_t)(i * cols + j)] = twiddle<T>(i * j, pl->P);
+      SSQ_HIP(mem.upload(dst, h));
       return 0;
     };
-    if (int rc = upload_f2(&pl->d_f2a, P1, cwt_tile_rows<T>(pl->log_p1), true)) return rc;
+    if (int rc = upload_f2(&pl->d_f2a, P1, cwt_tile_rows<T>(pl->log_p1))) return rc;
     for (int lq = 4; lq <= 12; ++lq) {
       bool used = false;
       for (int v : pl->zoom_logq) used = used || v == lq;
       if (!used) continue;
-      if (int rc = upload_f2(&pl->d_f2z[lq], cwt_tile_rows<T>(lq), 1LL << lq, false)) return rc;
+      if (int rc = upload_f2(&pl->d_f2z[lq], cwt_tile_rows<T>(lq), 1LL << lq)) return rc;
     }
     // W_Q for Q = 16 .. kZoomTabQ, each followed (fp64 plans) by its per-pass compact tables; pl->twz_off[log2 Q] says where
     std::vector<cpx<T>> hz;
     for (int lq = 4; (1LL << lq) <= kZoomTabQ; ++lq) {
-      const long long Q = 1LL << lq;
       pl->twz_off[lq] = (long long)hz.size();
-      for (long long i = 0; i < Q; ++i) {
-        const long double ang = 2.0L * kPI * (long double)i / (long double)Q;
-        hz.push_back({(T)cosl(ang), (T)(-sinl(ang))});
-      }
-      if (sizeof(T) == 8) {
-        for (int P = 1; P < num_passes(lq); ++P) {
-          const int R = pass_radix(lq, P), NS = pass_ns(lq, P);
-          for (int m = 0; m < R; ++m)
-            for (int k = 0; k < NS; ++k) {
-              const long double ang = 2.0L * kPI * (long double)((long long)k * m) / (long double)((long long)NS * R);
-              hz.push_back({(T)cosl(ang), (T)(-sinl(ang))});
-            }
-        }
-      }
+      append_tw_tile<T>(hz, lq);
     }
-    SSQ_HIP(hipMalloc(&pl->d_twz, sizeof(cpx<T>) * hz.size()));
-    SSQ_HIP(hipMemcpy(pl->d_twz, hz.data(), sizeof(cpx<T>) * hz.size(), hipMemcpyHostToDevice));
+    SSQ_HIP(mem.upload(&pl->d_twz, hz));
   }
   const long long nlo = pl->P < 4096 ? pl->P : 4096;
   const long long nhi = pl->P < 4096 ? 1 : pl->P / 4096;
-  if (int rc = upload_tw<T>(&pl->d_twlo, nlo, pl->P, 1)) return rc;
-  if (int rc = upload_tw<T>(&pl->d_twhi, nhi, pl->P, 4096)) return rc;
+  if (int rc = upload_tw<T>(pl, &pl->d_twlo, nlo, pl->P, 1)) return rc;
+  if (int rc = upload_tw<T>(pl, &pl->d_twhi, nhi, pl->P, 4096)) return rc;
   std::vector<T> s1((size_t)pl->na), s2((size_t)pl->na);
   const double norm = 1.0 / (double)pl->P;                              // cwt.rs:251
   for (int i = 0; i < pl->na; ++i) {
     s1[i] = (T)norm;
     s2[i] = (T)(norm * std::sqrt(pl->scales[i]));                       // cwt.rs:253
   }
-  SSQ_HIP(hipMalloc(&pl->d_scale_l1, sizeof(T) * (pl->na > 0 ? pl->na : 1)));
-  SSQ_HIP(hipMalloc(&pl->d_scale_l2, sizeof(T) * (pl->na > 0 ? pl->na : 1)));
-  SSQ_HIP(hipMalloc((void**)&pl->d_scales, sizeof(double) * (pl->na > 0 ? pl->na : 1)));
-  SSQ_HIP(hipMalloc((void**)&pl->d_band, sizeof(int) * (pl->na > 0 ? pl->na : 1)));
-  if (pl->na > 0) SSQ_HIP(hipMemcpy(pl->d_band, pl->band.data(), sizeof(int) * pl->na, hipMemcpyHostToDevice));
-  if (pl->na > 0) {
-    SSQ_HIP(hipMemcpy(pl->d_scale_l1, s1.data(), sizeof(T) * pl->na, hipMemcpyHostToDevice));
-    SSQ_HIP(hipMemcpy(pl->d_scale_l2, s2.data(), sizeof(T) * pl->na, hipMemcpyHostToDevice));
-    SSQ_HIP(hipMemcpy(pl->d_scales, pl->scales.data(), sizeof(double) * pl->na, hipMemcpyHostToDevice));
-  }
+  SSQ_HIP(mem.upload(&pl->d_scale_l1, s1));
+  SSQ_HIP(mem.upload(&pl->d_scale_l2, s2));
+  SSQ_HIP(mem.upload(&pl->d_scales, pl->scales));
+  SSQ_HIP(mem.upload(&pl->d_band, pl->band));
   std::vector<long long> off((size_t)(pl->na > 0 ? pl->na : 1), 0);
   long long total = 0;
   int max_band = 1;
@@ -248,9 +219,8 @@ int build_tables(ssq_cwt_plan* pl) {
     total += pl->band[(size_t)i];
     if (pl->band[(size_t)i] > max_band) max_band = pl->band[(size_t)i];
   }
-  SSQ_HIP(hipMalloc(&pl->d_psih, sizeof(T) * (size_t)(total > 0 ? total : 1)));
-  SSQ_HIP(hipMalloc((void**)&pl->d_psi_off, sizeof(long long) * off.size()));
-  SSQ_HIP(hipMemcpy(pl->d_psi_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
+  SSQ_HIP(mem.alloc(&pl->d_psih, sizeof(T) * (size_t)total));
+  SSQ_HIP(mem.upload(&pl->d_psi_off, off));
   if (pl->na > 0 && !pl->gmwk.empty()) {
     const int rows = pl->na / pl->gmwk_groups;
     for (int g = 0; g < pl->gmwk_groups; ++g) {
@@ -269,9 +239,11 @@ int build_tables(ssq_cwt_plan* pl) {
     SSQ_HIP(hipDeviceSynchronize());
   }
   if constexpr (sizeof(T) == 4) {
+    if ((pl->reg && pl->na > 0) || pl->os_s1 > pl->os_s0 || pl->os_z1 > pl->os_z0)   // register core and every tile family
+      if (int rc = upload_tw<float>(pl, &pl->d_tw1024, 1024, 1024, 1)) return rc;
     if (pl->os_s0 > pl->os_a0) {                               // analytic-input tiles (register-core plans only)
       const int nA = pl->os_s0 - pl->os_a0;
-      SSQ_HIP(hipMalloc(&pl->d_osHa, sizeof(float) * 4096 * (size_t)nA));
+      SSQ_HIP(mem.alloc(&pl->d_osHa, sizeof(float) * 4096 * (size_t)nA));
       SSQ_HIP(launch_cwt_os_table((float*)pl->d_osHa, pl->d_scales, pl->os_a0, nA, pl->wavelet, 4, 0, true, nullptr));
       const long long half = pl->P / 2;
       const long long bnd = half + 1 < (1LL << 20) ? half + 1 : (1LL << 20);
@@ -279,35 +251,27 @@ int build_tables(ssq_cwt_plan* pl) {
       std::vector<float> ones((size_t)A * 1024);
       for (int b = 0; b < 1024; ++b)
         for (int aa = 0; aa < A; ++aa) ones[(size_t)b * A + aa] = (1024LL * aa + b <= half) ? 1.0f : 0.0f;
-      SSQ_HIP(hipMalloc(&pl->d_xa_psiT, sizeof(float) * ones.size()));
-      SSQ_HIP(hipMemcpy(pl->d_xa_psiT, ones.data(), sizeof(float) * ones.size(), hipMemcpyHostToDevice));
-      const long long offs[2] = {0, -half};                    // psiT_off | psi_off: psih[psi_off + P/2] = entry 0 = 1
-      const int ints[2] = {A, (int)(half + 1)};                // A | band
-      const float sc = (float)(1.0 / (double)pl->P);
-      SSQ_HIP(hipMalloc((void**)&pl->d_xa_off, sizeof(offs)));
-      SSQ_HIP(hipMalloc((void**)&pl->d_xa_int, sizeof(ints)));
-      SSQ_HIP(hipMalloc((void**)&pl->d_xa_scale, sizeof(float)));
-      SSQ_HIP(hipMemcpy(pl->d_xa_off, offs, sizeof(offs), hipMemcpyHostToDevice));
-      SSQ_HIP(hipMemcpy(pl->d_xa_int, ints, sizeof(ints), hipMemcpyHostToDevice));
-      SSQ_HIP(hipMemcpy(pl->d_xa_scale, &sc, sizeof(float), hipMemcpyHostToDevice));
+      SSQ_HIP(mem.upload(&pl->d_xa_psiT, ones));
+      const std::vector<long long> offs = {0, -half};          // psiT_off | psi_off: psih[psi_off + P/2] = entry 0 = 1
+      const std::vector<int> ints = {A, (int)(half + 1)};      // A | band
+      const std::vector<float> sc = {(float)(1.0 / (double)pl->P)};
+      SSQ_HIP(mem.upload(&pl->d_xa_off, offs));
+      SSQ_HIP(mem.upload(&pl->d_xa_int, ints));
+      SSQ_HIP(mem.upload(&pl->d_xa_scale, sc));
       SSQ_HIP(hipDeviceSynchronize());
     }
     if (pl->os_z1 > pl->os_z0) {
       const int nz = pl->os_z1 - pl->os_z0;
-      SSQ_HIP(hipMalloc(&pl->d_osHz, sizeof(float) * 2048 * (size_t)nz));
+      SSQ_HIP(mem.alloc(&pl->d_osHz, sizeof(float) * 2048 * (size_t)nz));
       SSQ_HIP(launch_cwt_os_table((float*)pl->d_osHz, pl->d_scales, pl->os_z0, nz, pl->wavelet, 4, pl->logP - 12, false, nullptr));
       SSQ_HIP(hipDeviceSynchronize());
-      if (!pl->reg && !(pl->os_s1 > pl->os_s0))
-        if (int rc = upload_tw<float>(&pl->d_tw1024, 1024, 1024, 1)) return rc;
     }
     if (pl->os_s1 > pl->os_s0) {                               // time-tiled ssq path (any two-step fp32 plan)
       const int n4 = pl->os_mid - pl->os_s0, n8 = pl->os_s1 - pl->os_mid;
-      if (!pl->reg)
-        if (int rc = upload_tw<float>(&pl->d_tw1024, 1024, 1024, 1)) return rc;
-      SSQ_HIP(hipMalloc(&pl->d_osH4, sizeof(float) * 2048 * (size_t)(n4 > 0 ? n4 : 1)));
-      SSQ_HIP(hipMalloc(&pl->d_osH, sizeof(float) * 4096 * (size_t)(n8 > 0 ? n8 : 1)));
       const int nd = pl->os_d1 - pl->os_s1;
-      SSQ_HIP(hipMalloc(&pl->d_osHd, sizeof(float) * 4096 * (size_t)(nd > 0 ? nd : 1)));
+      SSQ_HIP(mem.alloc(&pl->d_osH4, sizeof(float) * 2048 * (size_t)n4));
+      SSQ_HIP(mem.alloc(&pl->d_osH, sizeof(float) * 4096 * (size_t)n8));
+      SSQ_HIP(mem.alloc(&pl->d_osHd, sizeof(float) * 4096 * (size_t)nd));
       SSQ_HIP(launch_cwt_os_table((float*)pl->d_osH4, pl->d_scales, pl->os_s0, n4, pl->wavelet, 4, 0, false, nullptr));
       SSQ_HIP(launch_cwt_os_table((float*)pl->d_osH, pl->d_scales, pl->os_mid, n8, pl->wavelet, 8, 0, false, nullptr));
       SSQ_HIP(launch_cwt_os_table((float*)pl->d_osHd, pl->d_scales, pl->os_s1, nd, pl->wavelet, 8, kOsLogDec, false, nullptr));
@@ -327,16 +291,13 @@ int build_tables(ssq_cwt_plan* pl) {
         totT += (long long)A[(size_t)i] * 1024;
         if (A[(size_t)i] > max_A) max_A = A[(size_t)i];
       }
-      SSQ_HIP(hipMalloc(&pl->d_psiT, sizeof(float) * (size_t)(totT > 0 ? totT : 1)));
-      SSQ_HIP(hipMalloc((void**)&pl->d_psiT_off, sizeof(long long) * A.size()));
-      SSQ_HIP(hipMalloc((void**)&pl->d_psiT_A, sizeof(int) * A.size()));
-      SSQ_HIP(hipMemcpy(pl->d_psiT_off, offT.data(), sizeof(long long) * A.size(), hipMemcpyHostToDevice));
-      SSQ_HIP(hipMemcpy(pl->d_psiT_A, A.data(), sizeof(int) * A.size(), hipMemcpyHostToDevice));
+      SSQ_HIP(mem.alloc(&pl->d_psiT, sizeof(float) * (size_t)totT));
+      SSQ_HIP(mem.upload(&pl->d_psiT_off, offT));
+      SSQ_HIP(mem.upload(&pl->d_psiT_A, A));
       SSQ_HIP(launch_cwt_reg_table((float*)pl->d_psiT, pl->d_psiT_off, pl->d_psiT_A, max_A, (const float*)pl->d_psih,
                                    pl->d_psi_off, pl->d_band, pl->na, nullptr));
       SSQ_HIP(hipDeviceSynchronize());
-      if (int rc = upload_tw<float>(&pl->d_tw1024, 1024, 1024, 1)) return rc;
-      if (int rc = upload_tw<float>(&pl->d_tw20, 1024, 1LL << 20, 1)) return rc;
+      if (int rc = upload_tw<float>(pl, &pl->d_tw20, 1024, 1LL << 20, 1)) return rc;
       int dev = 0;
       hipDeviceProp_t prop;
       if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
@@ -575,12 +536,69 @@ int analytic_signal(const ssq_cwt_plan* pl, const CwtDev<T>& p, char* ws, hipStr
   return 0;
 }
 
+// The time-tile families of one signal, in their fixed order and from the segments ssq_cwt_plan_tile_segments reports:
+// analytic-input, 4-row and 8-row tiles and, with `ssq`, the decimated and the full-circle groups.  ssq: the tiles
+// reassign straight into q.Tx (Wx / dWx: optional debug planes).  Store form (exec_cwt): the tiles store Wx / dWx,
+// times out_mul[s] if given, and mul scales every inv_F; its columns must be contiguous, which the decimated and
+// full-circle groups' 8-byte pieces are not.  p.xh must hold the forward transform.
+template <typename T>
+int launch_time_tiles(const ssq_cwt_plan* pl, const CwtDev<T>& p, const T* x, const CwtSsqDev<T>& q, cpx<T>* Wx,
+                      cpx<T>* dWx, bool ssq, const T* out_mul, double mul, char* ws, hipStream_t st) {
+  if constexpr (sizeof(T) == 4) {
+    const WsLayout L = ws_layout(pl);
+    CwtOsDev o;
+    std::memset(&o, 0, sizeof(o));
+    o.x = x;
+    o.xs = (cpx<float>*)(ws + L.os_xs);
+    o.tw1024 = (const cpx<float>*)pl->d_tw1024;
+    o.q = q;
+    o.dbg_Wx = Wx;
+    o.dbg_dWx = dWx;
+    o.store_only = ssq ? 0 : 1;
+    o.out_mul = out_mul;
+    o.n_signal = pl->N;
+    o.padtype = pl->padtype;
+    // one family: its table and scales, the frequency step and 1 / F of its F-point grid (in double, rounded once)
+    auto family = [&](const void* H, int s_begin, int s_end, double F) {
+      o.H = (const float*)H;
+      o.s_begin = s_begin;
+      o.s_end = s_end;
+      o.xi_step = (float)((2.0 * M_PI / F) / pl->dt);
+      o.inv_F = (float)(mul / F);
+    };
+    if (pl->os_s0 > pl->os_a0) {
+      if (int rc = analytic_signal<T>(pl, p, ws, st)) return rc;
+      o.xa = (const cpx<float>*)(ws + L.xa);
+      o.xa_off = pl->n1;
+      family(pl->d_osHa, pl->os_a0, pl->os_s0, 4096.0);
+      SSQ_HIP(launch_cwt_os_analytic(o, st));
+    }
+    for (int rows = 4; rows <= 8; rows += 4) {                 // ascending scales: the short tiles first
+      if (rows == 4) family(pl->d_osH4, pl->os_s0, pl->os_mid, 1024.0 * rows);
+      else family(pl->d_osH, pl->os_mid, pl->os_s1, 1024.0 * rows);
+      SSQ_HIP(launch_cwt_os(o, rows, 0, st));
+    }
+    if (ssq && pl->os_d1 > pl->os_s1) {
+      family(pl->d_osHd, pl->os_s1, pl->os_d1, (double)kOsF * (double)(1 << kOsLogDec));
+      SSQ_HIP(launch_cwt_os(o, 8, kOsLogDec, st));
+    }
+    if (ssq && pl->os_z1 > pl->os_z0) {                        // band-limited scales: full-circle phase blocks
+      family(pl->d_osHz, pl->os_z0, pl->os_z1, (double)pl->P);
+      o.xh = p.xh;
+      o.log_dec = pl->logP - 12;
+      o.full_n0 = pl->P / 4 - pl->n1;                          // <= 0: the emitted window covers [n1, n1 + N)
+      SSQ_HIP(launch_cwt_os_full(o, st));
+    }
+  }
+  return 0;
+}
+
 template <typename T>
 int exec_cwt_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, bool l1, bool rpadded, void* d_Wx,
                    void* d_dWx, char* ws, hipStream_t st) {
   const long long cols = rpadded ? pl->P : pl->N;
-  // The short-wavelet scales by time tiles that store Wx / dWx (contiguous columns: the analytic-input and the plain
-  // groups; the decimated and full-circle groups would write 8-byte pieces); SSQ_CWT_OS_STORE=0 keeps the transforms
+  // The short-wavelet scales by time tiles that store Wx / dWx (the analytic-input and the plain groups);
+  // SSQ_CWT_OS_STORE=0 keeps the transforms
   const char* es = std::getenv("SSQ_CWT_OS_STORE");
   const bool tiles = sizeof(T) == 4 && !rpadded && d_dWx && pl->os_s1 > pl->os_s0 && !(es && std::atoi(es) == 0);
   std::vector<char> mask;
@@ -588,73 +606,51 @@ int exec_cwt_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, bool l1, 
     mask.assign((size_t)pl->na, 0);
     for (int i = pl->os_a0; i < pl->os_s1; ++i) mask[(size_t)i] = 1;
   }
-  const WsLayout L = ws_layout(pl);
+  CwtSsqDev<T> q;                                              // (the store form reads the plane's shape alone)
+  std::memset(&q, 0, sizeof(q));
+  q.N = pl->N;
+  q.na = pl->na;
   for (long long b = 0; b < batch; ++b) {
     CwtDev<T> p = base_dev<T>(pl, ws);
-    if (int rc = run_forward<T>(pl, p, (const T*)d_x + b * pl->N, st)) return rc;
+    const T* x = (const T*)d_x + b * pl->N;
+    if (int rc = run_forward<T>(pl, p, x, st)) return rc;
     cpx<T>* W = (cpx<T>*)d_Wx + b * pl->na * cols;
     cpx<T>* dW = d_dWx ? (cpx<T>*)d_dWx + b * pl->na * cols : nullptr;
     if (int rc = run_inverse<T>(pl, p, W, dW, l1, rpadded, st, tiles ? mask.data() : nullptr)) return rc;
-    if constexpr (sizeof(T) == 4) {
-      if (tiles) {
-        CwtOsDev o;
-        std::memset(&o, 0, sizeof(o));
-        o.x = (const float*)d_x + b * pl->N;
-        o.xs = (cpx<float>*)(ws + L.os_xs);
-        o.tw1024 = (const cpx<float>*)pl->d_tw1024;
-        o.q.N = pl->N;
-        o.q.na = pl->na;
-        o.dbg_Wx = (cpx<float>*)W;
-        o.dbg_dWx = (cpx<float>*)dW;
-        o.store_only = 1;
-        o.out_mul = l1 ? nullptr : (const float*)pl->d_scale_l2;     // sqrt(a) / P: inv_F below carries the P
-        o.n_signal = pl->N;
-        o.padtype = pl->padtype;
-        const double mulP = l1 ? 1.0 : (double)pl->P;
-        if (pl->os_s0 > pl->os_a0) {
-          if (int rc = analytic_signal<T>(pl, p, ws, st)) return rc;
-          o.xa = (const cpx<float>*)(ws + L.xa);
-          o.xa_off = pl->n1;
-          o.H = (const float*)pl->d_osHa;
-          o.s_begin = pl->os_a0;
-          o.s_end = pl->os_s0;
-          o.xi_step = (float)((2.0 * M_PI / 4096.0) / pl->dt);
-          o.inv_F = (float)(mulP / 4096.0);
-          SSQ_HIP(launch_cwt_os_analytic(o, st));
-        }
-        for (int rows = 4; rows <= 8; rows += 4) {
-          const double F = 1024.0 * rows;
-          o.H = (const float*)(rows == 4 ? pl->d_osH4 : pl->d_osH);
-          o.s_begin = rows == 4 ? pl->os_s0 : pl->os_mid;
-          o.s_end = rows == 4 ? pl->os_mid : pl->os_s1;
-          o.xi_step = (float)((2.0 * M_PI / F) / pl->dt);
-          o.inv_F = (float)(mulP / F);
-          SSQ_HIP(launch_cwt_os(o, rows, 0, st));
-        }
-      }
-    }
+    // L2: out_mul = sqrt(a) / P, so inv_F carries the P
+    if (tiles)
+      if (int rc = launch_time_tiles<T>(pl, p, x, q, W, dW, false, l1 ? nullptr : (const T*)pl->d_scale_l2,
+                                        l1 ? 1.0 : (double)pl->P, ws, st))
+        return rc;
   }
   return 0;
 }
 
+// What one ssq exec of an upstream-variant plan bins with: arguments of that exec (ssq_cwt_host_impl builds them from
+// its caller's), which the public ssq_cwt_plan_exec_ssq cannot pass.
+struct SsqBins {
+  const double* freqs;         // [na] the ascending frequencies
+  const double* row_const;     // [na] the row weights (ssqueezing.py:122-133)
+  int idx;                     // the transition of log-piecewise frequencies (freqs[:idx], freqs[idx:])
+  bool rows;                   // the weights differ between rows or the bins are log-piecewise: cwt_reassign_rows_kernel ...
+  const void* d_row_const;     // ... with the weights on the device, [na] T
+};
+
+// the batch-invariant part of the reassignment's parameter blocks
 template <typename T>
-int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_dist, int maprange,
-                   int squeezing, int flipud, double gamma, void* d_Tx, void* d_dbg_Wx, void* d_dbg_dWx,
-                   void* d_dbg_wk, char* ws, hipStream_t st) {
-  const WsLayout L = ws_layout(pl);
-  std::vector<double> f((size_t)pl->na);
+int ssq_bin_params(const ssq_cwt_plan* pl, const SsqBins* bins, int freq_dist, int maprange, int squeezing, int flipud,
+                   double gamma, CwtSsqDev<T>& q, CwtRowsDev<T>& rows) {
+  const int n = pl->na;
   const bool ups = pl->variant != 0;
+  std::vector<double> f((size_t)n);
   if (ups) {
-    if ((int)pl->ups_freqs.size() != pl->na || (int)pl->ups_const.size() != pl->na)
-      SSQ_FAIL("upstream ssq exec: frequencies / row weights not set");
-    f = pl->ups_freqs;
-  } else if (int rc = ssq_cwt_ssq_freqs(pl->scales.data(), pl->na, pl->N, pl->dt, maprange, freq_dist, f.data())) {
+    if (!bins) SSQ_FAIL("upstream ssq exec: frequencies / row weights not set");
+    f.assign(bins->freqs, bins->freqs + n);
+  } else if (int rc = ssq_cwt_ssq_freqs(pl->scales.data(), n, pl->N, pl->dt, maprange, freq_dist, f.data())) {
     return rc;
   }
-  const int n = pl->na;
-  CwtSsqDev<T> q;
   std::memset(&q, 0, sizeof(q));
-  CwtRowsDev<T> rows{};
+  rows = CwtRowsDev<T>{};
   q.N = pl->N;
   q.na = n;
   q.is_log = (n > 1 && (f[1] / f[0] > 1.1)) ? 1 : 0;                      // ssq_cwt.rs:135-139
@@ -667,7 +663,7 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
     const double vmin = q.is_log ? std::log2(f[0]) : f[0];
     double dv = q.is_log ? std::log2(f[1]) - std::log2(f[0]) : f[1] - f[0];
     if (freq_dist == SSQ_FREQS_LOG_PIECEWISE) {                           // algos.py:364-370
-      const int idx = pl->ups_idx;                                        // found by the caller in the input's dtype
+      const int idx = bins->idx;                                          // found by the caller in the input's dtype
       if (idx < 2 || idx > n - 1) SSQ_FAIL("upstream ssq_cwt: freq_transition must be 2 .. na-1 for log-piecewise");
       rows.piecewise = 1;
       rows.idx1 = idx - 1;
@@ -679,18 +675,13 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
     q.bin_step = (T)dv;
     q.inv_bin_step = (T)(1.0 / dv);
     q.variant = 1;
-    q.tx_const = (T)pl->ups_const[0];                                     // ssqueezing.py:122-133
-    rows.row_const = (const T*)pl->d_ups_const;
-  } else if (q.is_log) {                                                  // :142-149
-    const double lmin = std::log2(f[0]);
-    const double lstep = n > 1 ? (std::log2(f[n - 1]) - lmin) / (double)(n - 1) : 1.0;
-    q.bin_min = (T)lmin;
-    q.bin_step = (T)lstep;
-    q.inv_bin_step = (T)(1.0 / lstep);
-  } else {                                                                // :150-157
-    const double lin_min = f[0];
-    const double lstep = n > 1 ? (f[n - 1] - lin_min) / (double)(n - 1) : 1.0;
-    q.bin_min = (T)lin_min;
+    q.tx_const = (T)bins->row_const[0];                                   // ssqueezing.py:122-133
+    rows.row_const = (const T*)bins->d_row_const;
+  } else {                                                                // log :142-149, linear :150-157
+    const double fmin = q.is_log ? std::log2(f[0]) : f[0];
+    const double fmax = q.is_log ? std::log2(f[n - 1]) : f[n - 1];
+    const double lstep = n > 1 ? (fmax - fmin) / (double)(n - 1) : 1.0;
+    q.bin_min = (T)fmin;
     q.bin_step = (T)lstep;
     q.inv_bin_step = (T)(1.0 / lstep);
   }
@@ -699,12 +690,25 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
   q.gamma = (T)(gamma < 0 ? 10.0 * 2.2204460492503131e-16 : gamma);       // ssq_cwt.rs:438-441
   if (ups && gamma < 0) q.gamma = (T)(10.0 * (sizeof(T) == 8 ? 2.2204460492503131e-16 : 1.1920928955078125e-07));
   q.leb_val = (T)(1.0 / (double)n);
+  return 0;
+}
+
+template <typename T>
+int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_dist, int maprange,
+                   int squeezing, int flipud, double gamma, void* d_Tx, void* d_dbg_Wx, void* d_dbg_dWx,
+                   void* d_dbg_wk, char* ws, hipStream_t st, const SsqBins* bins) {
+  const WsLayout L = ws_layout(pl);
+  const int n = pl->na;
+  CwtSsqDev<T> q;
+  CwtRowsDev<T> rows;
+  if (int rc = ssq_bin_params<T>(pl, bins, freq_dist, maprange, squeezing, flipud, gamma, q, rows)) return rc;
+  const CwtRowsDev<T>* by_rows = pl->variant != 0 && bins->rows ? &rows : nullptr;
   const long long plane = (long long)n * pl->N;
   // reassignment with a written-rows bitmap (first run of a row: plain store), Tx cleared beside the transforms (a
   // read-modify-write of a cleared Tx, or the kernel writing the untouched rows as zeros itself instead of the clear,
   // measured slower on C4: profiles/r02_ab_cwt_sweep.txt)
   const bool os = sizeof(T) == 4 && (pl->os_s1 > pl->os_s0 || pl->os_z1 > pl->os_z0);   // time-tile family
-  const bool sweep = !ups && !os && cwt_reassign_can_sweep<T>(n);
+  const bool sweep = pl->variant == 0 && !os && cwt_reassign_can_sweep<T>(n);
   const bool self_zero = sweep && !pl->clear_tx_aside();
   const bool side_clear = pl->clear_tx_aside() && !self_zero;   // clear Tx beside the transforms
   if (side_clear && !pl->side) {
@@ -712,204 +716,110 @@ int exec_ssq_typed(ssq_cwt_plan* pl, const void* d_x, long long batch, int freq_
     SSQ_HIP(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
     SSQ_HIP(hipEventCreateWithFlags(&pl->ev_join, hipEventDisableTiming));
   }
+  cpx<T>* W = (cpx<T>*)(ws + L.w);
+  cpx<T>* dW = (cpx<T>*)(ws + L.dw);
+  q.Wx = W;
+  q.dWx = dW;
+  cpx<T>* dbgW = nullptr;                                      // this signal's debug planes (nullptr: not asked for)
+  cpx<T>* dbgdW = nullptr;
+  auto copy_dbg = [&]() -> int {                               // ... filled from the workspaces
+    if (dbgW) SSQ_HIP(hipMemcpyAsync(dbgW, W, (size_t)plane * sizeof(cpx<T>), hipMemcpyDeviceToDevice, st));
+    if (dbgdW) SSQ_HIP(hipMemcpyAsync(dbgdW, dW, (size_t)plane * sizeof(cpx<T>), hipMemcpyDeviceToDevice, st));
+    return 0;
+  };
   for (long long b = 0; b < batch; ++b) {
     CwtDev<T> p = base_dev<T>(pl, ws);
+    const T* x = (const T*)d_x + b * pl->N;
     q.Tx = (cpx<T>*)d_Tx + b * plane;
+    q.wk = d_dbg_wk ? (cpx<T>*)d_dbg_wk + b * plane : nullptr;
+    dbgW = d_dbg_Wx ? (cpx<T>*)d_dbg_Wx + b * plane : nullptr;
+    dbgdW = d_dbg_dWx ? (cpx<T>*)d_dbg_dWx + b * plane : nullptr;
     if (side_clear) {
       SSQ_HIP(hipEventRecord(pl->ev_fork, st));
       SSQ_HIP(hipStreamWaitEvent(pl->side, pl->ev_fork, 0));
       SSQ_HIP(hipMemsetAsync(q.Tx, 0, (size_t)plane * sizeof(cpx<T>), pl->side));
       SSQ_HIP(hipEventRecord(pl->ev_join, pl->side));
     }
-    if (int rc = run_forward<T>(pl, p, (const T*)d_x + b * pl->N, st)) return rc;
-    cpx<T>* W = (cpx<T>*)(ws + L.w);
-    cpx<T>* dW = (cpx<T>*)(ws + L.dw);
-    q.Wx = W;
-    q.dWx = dW;
-    q.wk = d_dbg_wk ? (cpx<T>*)d_dbg_wk + b * plane : nullptr;
-    if (os) {
-      if constexpr (sizeof(T) == 4) {
-        // every other scale through the transforms into the workspaces ...
-        if (!pl->all_tiled) {
-          if (int rc = run_inverse<T>(pl, p, W, dW, true, false, st, pl->os_mask.data())) return rc;   // always L1 (:405)
-          if (d_dbg_Wx)
-            SSQ_HIP(hipMemcpyAsync((cpx<T>*)d_dbg_Wx + b * plane, W, (size_t)plane * sizeof(cpx<T>),
-                                   hipMemcpyDeviceToDevice, st));
-          if (d_dbg_dWx)
-            SSQ_HIP(hipMemcpyAsync((cpx<T>*)d_dbg_dWx + b * plane, dW, (size_t)plane * sizeof(cpx<T>),
-                                   hipMemcpyDeviceToDevice, st));
-        }
-        SSQ_HIP(hipStreamWaitEvent(st, pl->ev_join, 0));           // Tx is clear from here on
-        // the scales in FRONT of the tiled ones first, while Tx is still empty: with the written-rows bitmap their runs
-        // are plain stores (behind the tile kernels each would be a dependent read-modify-write chain per column)
-        int lead = 0;
-        while (lead < n && !pl->os_mask[(size_t)lead]) ++lead;
-        const bool lead_sweep = lead > 0 && lead < n && cwt_reassign_can_sweep<T>(n);
-        if (lead_sweep) {
-          q.s_begin = 0;
-          q.s_end = lead;
-          SSQ_HIP(launch_cwt_reassign_sweep<T>(q, st, false));
-        }
-        // ... the short-wavelet scales tile by tile straight into Tx (their Wx / dWx exist only on chip) ...
-        CwtOsDev o;
-        std::memset(&o, 0, sizeof(o));
-        o.x = (const float*)d_x + b * pl->N;
-        o.xs = (cpx<float>*)(ws + L.os_xs);
-        o.tw1024 = (const cpx<float>*)pl->d_tw1024;
-        o.q = q;
-        o.dbg_Wx = d_dbg_Wx ? (cpx<float>*)d_dbg_Wx + b * plane : nullptr;
-        o.dbg_dWx = d_dbg_dWx ? (cpx<float>*)d_dbg_dWx + b * plane : nullptr;
-        o.n_signal = pl->N;
-        o.padtype = pl->padtype;
-        if (pl->os_s0 > pl->os_a0) {
-          if (int rc = analytic_signal<T>(pl, p, ws, st)) return rc;
-          o.xa = (const cpx<float>*)(ws + L.xa);
-          o.xa_off = pl->n1;
-          o.H = (const float*)pl->d_osHa;
-          o.s_begin = pl->os_a0;
-          o.s_end = pl->os_s0;
-          o.xi_step = (float)((2.0 * M_PI / 4096.0) / pl->dt);
-          o.inv_F = (float)(1.0 / 4096.0);
-          SSQ_HIP(launch_cwt_os_analytic(o, st));
-        }
-        for (int rows = 4; rows <= 8; rows += 4) {               // ascending scales: the short tiles first
-          const double F = 1024.0 * rows;
-          o.H = (const float*)(rows == 4 ? pl->d_osH4 : pl->d_osH);
-          o.s_begin = rows == 4 ? pl->os_s0 : pl->os_mid;
-          o.s_end = rows == 4 ? pl->os_mid : pl->os_s1;
-          o.xi_step = (float)((2.0 * M_PI / F) / pl->dt);
-          o.inv_F = (float)(1.0 / F);
-          SSQ_HIP(launch_cwt_os(o, rows, 0, st));
-        }
-        if (pl->os_d1 > pl->os_s1) {
-          const double S = (double)kOsF * (double)(1 << kOsLogDec);
-          o.H = (const float*)pl->d_osHd;
-          o.s_begin = pl->os_s1;
-          o.s_end = pl->os_d1;
-          o.xi_step = (float)((2.0 * M_PI / S) / pl->dt);
-          o.inv_F = (float)(1.0 / S);
-          SSQ_HIP(launch_cwt_os(o, 8, kOsLogDec, st));
-        }
-        if (pl->os_z1 > pl->os_z0) {                             // band-limited scales: full-circle phase blocks
-          o.H = (const float*)pl->d_osHz;
-          o.xh = p.xh;
-          o.log_dec = pl->logP - 12;
-          o.full_n0 = pl->P / 4 - pl->n1;                        // <= 0: the emitted window covers [n1, n1 + N)
-          o.s_begin = pl->os_z0;
-          o.s_end = pl->os_z1;
-          o.xi_step = (float)((2.0 * M_PI / (double)pl->P) / pl->dt);
-          o.inv_F = (float)(1.0 / (double)pl->P);
-          SSQ_HIP(launch_cwt_os_full(o, st));
-        }
-        // ... and the rest added by the column-ordered reassignment (read-modify-write), run by run
-        for (int s0 = lead_sweep ? lead : 0; s0 < n;) {
-          if (pl->os_mask[(size_t)s0]) {
-            ++s0;
-            continue;
-          }
-          int s1 = s0;
-          while (s1 < n && !pl->os_mask[(size_t)s1]) ++s1;
-          q.s_begin = s0;
-          q.s_end = s1;
-          SSQ_HIP(launch_cwt_reassign<T>(q, st, false, ups && pl->ups_rows ? &rows : nullptr));
-          s0 = s1;
-        }
-      }
-      continue;
-    } else {
-      if (int rc = run_inverse<T>(pl, p, W, dW, true, false, st)) return rc;
+    if (int rc = run_forward<T>(pl, p, x, st)) return rc;
+    if (!os) {
+      if (int rc = run_inverse<T>(pl, p, W, dW, true, false, st)) return rc;   // always L1 (:405)
       if (side_clear) SSQ_HIP(hipStreamWaitEvent(st, pl->ev_join, 0));
       q.s_begin = 0;
       q.s_end = n;
       if (sweep) SSQ_HIP(launch_cwt_reassign_sweep<T>(q, st, self_zero));
-      else SSQ_HIP(launch_cwt_reassign<T>(q, st, !side_clear, ups && pl->ups_rows ? &rows : nullptr));
+      else SSQ_HIP(launch_cwt_reassign<T>(q, st, !side_clear, by_rows));
+      if (int rc = copy_dbg()) return rc;
+      continue;
     }
-    if (d_dbg_Wx)
-      SSQ_HIP(hipMemcpyAsync((cpx<T>*)d_dbg_Wx + b * plane, W, (size_t)plane * sizeof(cpx<T>),
-                             hipMemcpyDeviceToDevice, st));
-    if (d_dbg_dWx)
-      SSQ_HIP(hipMemcpyAsync((cpx<T>*)d_dbg_dWx + b * plane, dW, (size_t)plane * sizeof(cpx<T>),
-                             hipMemcpyDeviceToDevice, st));
+    // every scale outside the time tiles through the transforms into the workspaces ...
+    if (!pl->all_tiled) {
+      if (int rc = run_inverse<T>(pl, p, W, dW, true, false, st, pl->os_mask.data())) return rc;
+      if (int rc = copy_dbg()) return rc;
+    }
+    SSQ_HIP(hipStreamWaitEvent(st, pl->ev_join, 0));           // Tx is clear from here on
+    // the scales in FRONT of the tiled ones first, while Tx is still empty: with the written-rows bitmap their runs
+    // are plain stores (behind the tile kernels each would be a dependent read-modify-write chain per column)
+    int lead = 0;
+    while (lead < n && !pl->os_mask[(size_t)lead]) ++lead;
+    const bool lead_sweep = lead > 0 && lead < n && cwt_reassign_can_sweep<T>(n);
+    if (lead_sweep) {
+      q.s_begin = 0;
+      q.s_end = lead;
+      SSQ_HIP(launch_cwt_reassign_sweep<T>(q, st, false));
+    }
+    // ... the short-wavelet scales tile by tile straight into Tx (their Wx / dWx exist only on chip) ...
+    if (int rc = launch_time_tiles<T>(pl, p, x, q, dbgW, dbgdW, true, nullptr, 1.0, ws, st)) return rc;
+    // ... and the rest added by the column-ordered reassignment (read-modify-write), run by run
+    for (int s0 = lead_sweep ? lead : 0; s0 < n;) {
+      if (pl->os_mask[(size_t)s0]) {
+        ++s0;
+        continue;
+      }
+      int s1 = s0;
+      while (s1 < n && !pl->os_mask[(size_t)s1]) ++s1;
+      q.s_begin = s0;
+      q.s_end = s1;
+      SSQ_HIP(launch_cwt_reassign<T>(q, st, false, by_rows));
+      s0 = s1;
+    }
   }
   return 0;
 }
 
-}  // namespace
-
-// arguments of the higher-order GMW entry points: n_groups polynomials of n_coeffs (1 .. kGmwMaxOrder + 1) finite
-// coefficients each, upstream numerics, at most 32767 rows in all
-static int check_gmwk_args(const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
-                           int variant) {
-  if (!(variant & SSQ_VARIANT_UPSTREAM)) SSQ_FAIL("higher-order GMW: variant must include SSQ_VARIANT_UPSTREAM");
-  if (!coeffs) SSQ_FAIL("higher-order GMW: coeffs is NULL");
-  if (n_coeffs < 1 || n_coeffs > kGmwMaxOrder + 1)
-    SSQ_FAIL("higher-order GMW: n_coeffs must be 1 .. " + std::to_string(kGmwMaxOrder + 1) + " (order <= " +
-             std::to_string(kGmwMaxOrder) + ")");
-  if (n_groups < 1) SSQ_FAIL("higher-order GMW: n_groups must be >= 1");
-  if (na < 1 || !scales) SSQ_FAIL("higher-order GMW: bad scales");
-  if (na * n_groups > 32767) SSQ_FAIL("higher-order GMW: na * n_groups above 32767 rows");
-  for (int64_t i = 0; i < n_coeffs * n_groups; ++i)
-    if (!std::isfinite(coeffs[i])) SSQ_FAIL("higher-order GMW: coefficients must be finite");
-  return 0;
-}
-
-// plan creation; gmwk != nullptr: the upstream GMW of higher order (n_groups polynomials of gmwk_n coefficients, the
-// scales repeated once per group), else the table codes 0-3
-static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wavelet, double p0, double p1,
-                           const double* scales, int64_t na, double dt, int padtype, int variant, const double* gmwk,
-                           int gmwk_n, int gmwk_groups) {
-  if (!plan) SSQ_FAIL("plan is NULL");
-  *plan = nullptr;
-  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
-  if (n_signal <= 0) SSQ_FAIL("empty input signal");
-  if (na < 0 || (na > 0 && !scales)) SSQ_FAIL("bad scales");
-  if (na > 32767) SSQ_FAIL("too many scales (max 32767)");
-  ssq_cwt_plan* pl = new ssq_cwt_plan();
-  if (gmwk) {
-    pl->gmwk.assign(gmwk, gmwk + (size_t)gmwk_n * gmwk_groups);
-    pl->gmwk_n = gmwk_n;
-    pl->gmwk_groups = gmwk_groups;
+// The four TEST hooks of plan creation, read from the environment here and nowhere else: plan_routes decides from
+// them, and they are part of the host path's plan-cache key (tests flip them between calls).
+struct CwtHooks {
+  bool noprune;     // SSQ_CWT_NOPRUNE=1: every scale through the plain two-step transform, no band-limit shortcuts
+  bool force_big;   // SSQ_CWT_FORCE_BIG=1: the P > 2^24 path at a small size
+  bool reg_off;     // SSQ_CWT_REG=0 keeps the tile kernels for the two-step scales (A/B and tests)
+  bool os_off;      // SSQ_CWT_OS=0 switches the time-tile family off
+  CwtHooks() {
+    auto is_one = [](const char* e) { return e && e[0] == '1'; };
+    auto is_zero = [](const char* e) { return e && std::atoi(e) == 0; };
+    noprune = is_one(std::getenv("SSQ_CWT_NOPRUNE"));
+    force_big = is_one(std::getenv("SSQ_CWT_FORCE_BIG"));
+    reg_off = is_zero(std::getenv("SSQ_CWT_REG"));
+    os_off = is_zero(std::getenv("SSQ_CWT_OS"));
   }
-  pl->dtype = dtype;
-  pl->N = n_signal;
-  pl->P = host::next_power_of_2(n_signal + n_signal / 2);        // cwt.rs:87
-  pl->n1 = (pl->P - pl->N) / 2;                                  // cwt.rs:98
-  const bool ups = (variant & SSQ_VARIANT_UPSTREAM) != 0;
-  if (ups) {
-    int64_t up = 0, n1 = 0, n2 = 0;
-    host::p2up(n_signal, &up, &n1, &n2);                         // old/ssqueezepy/utils/common.py:32-51
-    pl->P = up;
-    pl->n1 = n1;
-    pl->variant = variant;
-    pl->table_code = wavelet == SSQ_WAVELET_MORLET ? 3 : 2;
-    pl->wp0 = p0;
-    pl->wp1 = p1;
-    if (wavelet == SSQ_WAVELET_MORLET && !(p0 > 0.0)) {
-      delete pl;
-      SSQ_FAIL("upstream morlet needs mu > 0");
-    }
-    if (wavelet != SSQ_WAVELET_MORLET && !(p0 > 0.0 && p1 > 0.0)) {
-      delete pl;
-      SSQ_FAIL("upstream gmw needs gamma > 0 and beta > 0");
-    }
+  bool operator==(const CwtHooks& o) const {
+    return noprune == o.noprune && force_big == o.force_big && reg_off == o.reg_off && os_off == o.os_off;
   }
-  pl->wavelet = wavelet;
-  // reference variant: reflect, and every other code pads with zeros; upstream plans hand the code to the loaders as it
-  // is (pad_index.h: 0-4).  The time-tile, register-core and full-circle families below are reference-variant only, so
-  // they meet codes 0 and 1 alone
-  pl->padtype = ups ? padtype : (padtype != SSQ_PAD_REFLECT ? SSQ_PAD_ZERO : SSQ_PAD_REFLECT);
-  pl->na = (int)na;
-  pl->dt = dt;
-  pl->scales.assign(scales, scales + na);
+};
+
+// Which kernels compute which scale: the transform lengths, the band limits and single-pass lengths, the register core
+// and the segments of the time-tile families.  A function of the plan's N, P, dtype, wavelet (and its parameters),
+// variant and scales, which the caller has set, and of the hooks; it touches no device.
+int plan_routes(ssq_cwt_plan* pl, const CwtHooks& hooks) {
+  const int dtype = pl->dtype, wavelet = pl->wavelet;
+  const bool ups = (pl->variant & SSQ_VARIANT_UPSTREAM) != 0;
+  const int64_t na = pl->na, n_signal = pl->N;
+  const double* scales = pl->scales.data();
+  const double p0 = pl->wp0, p1 = pl->wp1;
   int lp = 0;
   while ((1LL << lp) < pl->P) ++lp;
   pl->logP = lp;
-  const char* force_big = std::getenv("SSQ_CWT_FORCE_BIG");     // tests: the P > 2^24 path at a small size
-  if (lp > 24 || (force_big && force_big[0] == '1' && lp >= 4)) {
-    if (lp > 30) {
-      delete pl;
-      SSQ_FAIL("signal too long: padded length above 2^30");
-    }
+  if (lp > 24 || (hooks.force_big && lp >= 4)) {
+    if (lp > 30) SSQ_FAIL("signal too long: padded length above 2^30");
     pl->big = true;                                              // cwt.rs:87 takes any N
     pl->log_p1 = 4;                                              // (tile-kernel fields: unused on this path)
     pl->log_p2 = 0;
@@ -929,12 +839,10 @@ static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int
     if (dtype == SSQ_F64) pl->log_p2 = (lp + 1) / 2;
     pl->log_p1 = lp - pl->log_p2;
   }
-  // SSQ_CWT_REG=0 keeps the tile kernels for the two-step scales (A/B and tests)
-  {
-    const char* e = std::getenv("SSQ_CWT_REG");
-    pl->reg = !ups && dtype == SSQ_F32 && pl->two_step && (lp == 20 || lp == 21) && !(e && std::atoi(e) == 0);
-    pl->reg_D = pl->reg ? (int)(pl->P >> 20) : 0;
-  }
+  // the families of reference-variant fp32 two-step plans: the register core, the time tiles, the full-circle blocks
+  const bool fp32_two_step = !ups && dtype == SSQ_F32 && pl->two_step;
+  pl->reg = fp32_two_step && (lp == 20 || lp == 21) && !hooks.reg_off;
+  pl->reg_D = pl->reg ? (int)(pl->P >> 20) : 0;
   const long long csz = dtype == SSQ_F32 ? 8 : 16;
   long long chunk_mb = 128;                                      // ybuf of a chunk stays inside the 256 MB Infinity Cache
   long long ch = (chunk_mb << 20) / (2 * pl->P * csz);
@@ -943,10 +851,7 @@ static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int
   pl->chunk = (int)ch;
   pl->zoom_logq.assign((size_t)na, 0);
   pl->band.assign((size_t)na, (int)(pl->P / 2 + 1));
-  // SSQ_CWT_NOPRUNE=1 (tests): every scale through the plain two-step transform, no band-limit shortcuts
-  const char* noprune = std::getenv("SSQ_CWT_NOPRUNE");
-  const char* os_env = std::getenv("SSQ_CWT_OS");               // tests: 0 switches the time-tile family off
-  if ((pl->two_step || pl->big) && !(noprune && noprune[0] == '1')) {
+  if ((pl->two_step || pl->big) && !hooks.noprune) {
     const double h = 2.0 * M_PI / (double)pl->P;                     // base.rs:20
     std::vector<double> wmax_g((size_t)pl->gmwk_groups);              // per polynomial group (one without gmwk)
     for (int g = 0; g < pl->gmwk_groups; ++g)
@@ -970,14 +875,13 @@ static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int
   // time-tiled ssq path: the longest run of ascending scales whose wavelet fits the tile halo in time (6 sigma_t <= halo,
   // sigma_t = a for the Morlet wavelet, 4.943 a for the GMW: 1 / the spectral width at the peak) and is negligible at the
   // Nyquist frequency (so that the spectrum's cut leaves no slow tail); SSQ_CWT_OS=0 switches it off
+  bool ascending = true;
+  for (int64_t i = 1; i < na; ++i) ascending = ascending && scales[i] >= scales[i - 1];
   {
-    const char* e = os_env;
-    if (!ups && dtype == SSQ_F32 && pl->two_step && !(e && std::atoi(e) == 0)) {
+    if (fp32_two_step && !hooks.os_off) {
       const double sig = wavelet == SSQ_WAVELET_MORLET ? 1.0 : 4.943;
       const double a_hi = (double)kOsHalo / (6.0 * sig);
       const double a_lo = wavelet == SSQ_WAVELET_MORLET ? 4.0 : 1.3;
-      bool ascending = true;
-      for (int64_t i = 1; i < na; ++i) ascending = ascending && scales[i] >= scales[i - 1];
       int best0 = 0, best1 = 0, run0 = -1;
       for (int64_t i = 0; ascending && i <= na; ++i) {
         const bool ok = i < na && scales[i] >= a_lo && scales[i] <= a_hi && pl->zoom_logq[(size_t)i] == 0;
@@ -1028,11 +932,7 @@ static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int
   // full-circle phase blocks for the band-limited scales: 2 N <= P (the kept samples lie inside the middle half of the
   // padded length, which is what the tile kernel emits), spectrum below 2048 bins (profiles/r02_ab_cwt_os_full.txt)
   {
-    const char* e = os_env;
-    if (!ups && dtype == SSQ_F32 && pl->two_step && !(e && std::atoi(e) == 0) && 2 * pl->N <= pl->P &&
-        n_signal >= 64LL * kOsL) {
-      bool ascending = true;
-      for (int64_t i = 1; i < na; ++i) ascending = ascending && scales[i] >= scales[i - 1];
+    if (fp32_two_step && !hooks.os_off && 2 * pl->N <= pl->P && n_signal >= 64LL * kOsL) {
       int z0 = pl->os_d1;
       while (ascending && z0 < (int)na && !(pl->zoom_logq[(size_t)z0] > 0 && pl->band[(size_t)z0] <= 2048)) ++z0;
       int z1 = z0;
@@ -1048,8 +948,74 @@ static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int
     pl->all_tiled = na > 0;
     for (int64_t i = 0; i < na; ++i) pl->all_tiled = pl->all_tiled && pl->os_mask[(size_t)i];
   }
-  int rc = dtype == SSQ_F32 ? build_tables<float>(pl) : build_tables<double>(pl);
-  if (rc) {
+  return 0;
+}
+
+}  // namespace
+
+// arguments of the higher-order GMW entry points: n_groups polynomials of n_coeffs (1 .. kGmwMaxOrder + 1) finite
+// coefficients each, upstream numerics, at most 32767 rows in all
+static int check_gmwk_args(const double* coeffs, int64_t n_coeffs, int64_t n_groups, const double* scales, int64_t na,
+                           int variant) {
+  if (!(variant & SSQ_VARIANT_UPSTREAM)) SSQ_FAIL("higher-order GMW: variant must include SSQ_VARIANT_UPSTREAM");
+  if (!coeffs) SSQ_FAIL("higher-order GMW: coeffs is NULL");
+  if (n_coeffs < 1 || n_coeffs > kGmwMaxOrder + 1)
+    SSQ_FAIL("higher-order GMW: n_coeffs must be 1 .. " + std::to_string(kGmwMaxOrder + 1) + " (order <= " +
+             std::to_string(kGmwMaxOrder) + ")");
+  if (n_groups < 1) SSQ_FAIL("higher-order GMW: n_groups must be >= 1");
+  if (na < 1 || !scales) SSQ_FAIL("higher-order GMW: bad scales");
+  if (na * n_groups > 32767) SSQ_FAIL("higher-order GMW: na * n_groups above 32767 rows");
+  for (int64_t i = 0; i < n_coeffs * n_groups; ++i)
+    if (!std::isfinite(coeffs[i])) SSQ_FAIL("higher-order GMW: coefficients must be finite");
+  return 0;
+}
+
+// plan creation; gmwk != nullptr: the upstream GMW of higher order (n_groups polynomials of gmwk_n coefficients, the
+// scales repeated once per group), else the table codes 0-3
+static int cwt_plan_create(ssq_cwt_plan** plan, int dtype, int64_t n_signal, int wavelet, double p0, double p1,
+                           const double* scales, int64_t na, double dt, int padtype, int variant, const double* gmwk,
+                           int gmwk_n, int gmwk_groups) {
+  if (!plan) SSQ_FAIL("plan is NULL");
+  *plan = nullptr;
+  if (dtype != SSQ_F32 && dtype != SSQ_F64) SSQ_FAIL("dtype must be SSQ_F32 or SSQ_F64");
+  if (n_signal <= 0) SSQ_FAIL("empty input signal");
+  if (na < 0 || (na > 0 && !scales)) SSQ_FAIL("bad scales");
+  if (na > 32767) SSQ_FAIL("too many scales (max 32767)");
+  const bool ups = (variant & SSQ_VARIANT_UPSTREAM) != 0;
+  if (ups && wavelet == SSQ_WAVELET_MORLET && !(p0 > 0.0)) SSQ_FAIL("upstream morlet needs mu > 0");
+  if (ups && wavelet != SSQ_WAVELET_MORLET && !(p0 > 0.0 && p1 > 0.0))
+    SSQ_FAIL("upstream gmw needs gamma > 0 and beta > 0");
+  ssq_cwt_plan* pl = new ssq_cwt_plan();
+  if (gmwk) {
+    pl->gmwk.assign(gmwk, gmwk + (size_t)gmwk_n * gmwk_groups);
+    pl->gmwk_n = gmwk_n;
+    pl->gmwk_groups = gmwk_groups;
+  }
+  pl->dtype = dtype;
+  pl->N = n_signal;
+  pl->P = host::next_power_of_2(n_signal + n_signal / 2);        // cwt.rs:87
+  pl->n1 = (pl->P - pl->N) / 2;                                  // cwt.rs:98
+  if (ups) {
+    int64_t up = 0, n1 = 0, n2 = 0;
+    host::p2up(n_signal, &up, &n1, &n2);                         // old/ssqueezepy/utils/common.py:32-51
+    pl->P = up;
+    pl->n1 = n1;
+    pl->variant = variant;
+    pl->table_code = wavelet == SSQ_WAVELET_MORLET ? 3 : 2;
+    pl->wp0 = p0;
+    pl->wp1 = p1;
+  }
+  pl->wavelet = wavelet;
+  // reference variant: reflect, and every other code pads with zeros; upstream plans hand the code to the loaders as it
+  // is (pad_index.h: 0-4).  The time-tile, register-core and full-circle families below are reference-variant only, so
+  // they meet codes 0 and 1 alone
+  pl->padtype = ups ? padtype : (padtype != SSQ_PAD_REFLECT ? SSQ_PAD_ZERO : SSQ_PAD_REFLECT);
+  pl->na = (int)na;
+  pl->dt = dt;
+  pl->scales.assign(scales, scales + na);
+  int rc = plan_routes(pl, CwtHooks());
+  if (!rc) rc = dtype == SSQ_F32 ? build_tables<float>(pl) : build_tables<double>(pl);
+  if (rc) {                                                      // (the plan frees what it allocated so far)
     ssq_cwt_plan_destroy(pl);
     return rc;
   }
@@ -1083,38 +1049,10 @@ int ssq_cwt_plan_create_gmwk(ssq_cwt_plan** plan, int dtype, int64_t n_signal, d
 
 int ssq_cwt_plan_destroy(ssq_cwt_plan* pl) {
   if (!pl) return 0;
-  hipFree(pl->d_psih);
-  hipFree(pl->d_psi_off);
-  hipFree(pl->d_tw1);
-  hipFree(pl->d_tw2);
-  hipFree(pl->d_twz);
-  hipFree(pl->d_f2a);
-  for (void* q : pl->d_f2z) hipFree(q);
-  hipFree(pl->d_band);
-  hipFree(pl->d_twhi);
-  hipFree(pl->d_twlo);
-  hipFree(pl->d_scale_l1);
-  hipFree(pl->d_scale_l2);
-  hipFree(pl->d_scales);
-  hipFree(pl->d_psiT);
-  hipFree(pl->d_psiT_off);
-  hipFree(pl->d_psiT_A);
-  hipFree(pl->d_tw1024);
-  hipFree(pl->d_tw20);
-  hipFree(pl->d_osH);
-  hipFree(pl->d_osH4);
-  hipFree(pl->d_osHd);
-  hipFree(pl->d_osHz);
-  hipFree(pl->d_osHa);
-  hipFree(pl->d_xa_psiT);
-  hipFree(pl->d_xa_off);
-  hipFree(pl->d_xa_int);
-  hipFree(pl->d_xa_scale);
-  hipFree(pl->d_ups_const);
   if (pl->ev_fork) (void)hipEventDestroy(pl->ev_fork);
   if (pl->ev_join) (void)hipEventDestroy(pl->ev_join);
   if (pl->side) (void)hipStreamDestroy(pl->side);
-  delete pl;
+  delete pl;                   // (pl->mem frees the tables)
   return 0;
 }
 
@@ -1128,7 +1066,7 @@ int ssq_cwt_plan_tiled_rows(const ssq_cwt_plan* pl) {
 int ssq_cwt_plan_tile_segments(const ssq_cwt_plan* pl, int32_t out[8]) {
   if (!pl) SSQ_FAIL("plan is NULL");
   if (!out) SSQ_FAIL("out is NULL");
-  // the fields exec_ssq_typed launches from, in its launch order
+  // the fields launch_time_tiles launches from, in its launch order
   out[0] = pl->os_a0;
   out[1] = pl->os_s0;
   out[2] = pl->os_mid;
@@ -1159,9 +1097,10 @@ int ssq_cwt_plan_exec_cwt(ssq_cwt_plan* pl, const void* d_x, int64_t batch, int 
                                 (hipStream_t)stream);
 }
 
-int ssq_cwt_plan_exec_ssq(ssq_cwt_plan* pl, const void* d_x, int64_t batch, int freq_dist, int maprange,
-                          int squeezing, int flipud, double gamma, void* d_Tx, void* d_dbg_Wx, void* d_dbg_dWx,
-                          void* d_dbg_wk, void* d_workspace, int64_t workspace_bytes, void* stream) {
+// the ssq exec with what an upstream-variant plan bins with (the host path's; nullptr: none)
+static int exec_ssq(ssq_cwt_plan* pl, const void* d_x, int64_t batch, int freq_dist, int maprange, int squeezing,
+                    int flipud, double gamma, void* d_Tx, void* d_dbg_Wx, void* d_dbg_dWx, void* d_dbg_wk,
+                    void* d_workspace, int64_t workspace_bytes, void* stream, const SsqBins* bins) {
   if (!pl) SSQ_FAIL("plan is NULL");
   if (pl->na == 0) SSQ_FAIL("index out of bounds: scales is empty (ssq_cwt.rs:459)");
   if (batch <= 0) return 0;
@@ -1170,9 +1109,16 @@ int ssq_cwt_plan_exec_ssq(ssq_cwt_plan* pl, const void* d_x, int64_t batch, int 
   if (!d_workspace || workspace_bytes < ws_layout(pl).total) SSQ_FAIL("workspace too small");
   if (pl->dtype == SSQ_F32)
     return exec_ssq_typed<float>(pl, d_x, batch, freq_dist, maprange, squeezing, flipud, gamma, d_Tx, d_dbg_Wx,
-                                 d_dbg_dWx, d_dbg_wk, (char*)d_workspace, (hipStream_t)stream);
+                                 d_dbg_dWx, d_dbg_wk, (char*)d_workspace, (hipStream_t)stream, bins);
   return exec_ssq_typed<double>(pl, d_x, batch, freq_dist, maprange, squeezing, flipud, gamma, d_Tx, d_dbg_Wx,
-                                d_dbg_dWx, d_dbg_wk, (char*)d_workspace, (hipStream_t)stream);
+                                d_dbg_dWx, d_dbg_wk, (char*)d_workspace, (hipStream_t)stream, bins);
+}
+
+int ssq_cwt_plan_exec_ssq(ssq_cwt_plan* pl, const void* d_x, int64_t batch, int freq_dist, int maprange,
+                          int squeezing, int flipud, double gamma, void* d_Tx, void* d_dbg_Wx, void* d_dbg_dWx,
+                          void* d_dbg_wk, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return exec_ssq(pl, d_x, batch, freq_dist, maprange, squeezing, flipud, gamma, d_Tx, d_dbg_Wx, d_dbg_dWx, d_dbg_wk,
+                  d_workspace, workspace_bytes, stream, nullptr);
 }
 
 }  // extern "C"
@@ -1181,16 +1127,6 @@ int ssq_cwt_plan_exec_ssq(ssq_cwt_plan* pl, const void* d_x, int64_t batch, int 
 // ---- D2H of signal b on a second stream while signal b+1 computes -----------------------------------------------
 namespace {
 
-// the four TEST hooks plan creation reads from the environment are part of the key (tests flip them between calls)
-std::string plan_env() {
-  std::string k;
-  for (const char* v : {"SSQ_CWT_NOPRUNE", "SSQ_CWT_FORCE_BIG", "SSQ_CWT_REG", "SSQ_CWT_OS"}) {
-    const char* e = std::getenv(v);
-    k += e ? e : "";
-    k += '|';
-  }
-  return k;
-}
 struct CwtKey {
   int dtype, wavelet, padtype;
   int64_t n_signal;
@@ -1198,7 +1134,7 @@ struct CwtKey {
   std::vector<double> scales;
   int variant = 0;
   double p0 = 0.0, p1 = 0.0;
-  std::string env = plan_env();
+  CwtHooks env = {};               // (tests flip the hooks between calls)
   std::vector<double> gmwk = {};   // higher-order GMW polynomials (empty: table codes 0-3) ...
   int gmwk_groups = 1;             // ... and their count (the rows are scales x groups)
   bool operator==(const CwtKey& o) const {
@@ -1259,6 +1195,48 @@ struct EventPair {
   }
 };
 
+// one output plane of a host call: where it goes on the host (nullptr: not asked for) and the scratch slot it passes through
+struct HostPlane {
+  void* host;
+  hostpath::Slot slot;
+};
+
+// The pipeline of the host entry points: all samples up on stream 0, then signal by signal `exec(d_x of the signal,
+// d_planes, ws, ws_bytes, stream 0)` into half b & 1 of every requested plane's slot (d_planes[i]: nullptr for a plane
+// not asked for) and the download of those halves, out1 bytes each, on stream 1 while the next signal computes.
+template <typename Exec>
+int cwt_host_pipeline(const ssq_cwt_plan* pl, const void* x, int64_t batch, long long in1, long long out1,
+                      const std::vector<HostPlane>& planes, Exec&& exec) {
+  void *dx = nullptr, *ws = nullptr;
+  std::vector<void*> slot(planes.size(), nullptr), cur(planes.size(), nullptr);
+  if (int rc = hostpath::scratch(hostpath::SLOT_X, batch * in1, &dx)) return rc;
+  for (size_t i = 0; i < planes.size(); ++i)
+    if (planes[i].host)
+      if (int rc = hostpath::scratch(planes[i].slot, 2 * out1, &slot[i])) return rc;
+  const long long wsb = ssq_cwt_plan_workspace_bytes(pl, 1);
+  if (int rc = hostpath::scratch(hostpath::SLOT_WS0, wsb, &ws)) return rc;
+  hipStream_t s0 = hostpath::stream(0), s1 = hostpath::stream(1);
+  EventPair done, freed;
+  // the asynchronous copies write into the caller's (pinned) arrays: from here on EVERY return synchronises both streams
+  hostpath::SyncedStreams synced(s0, s1);
+  if (int rc = done.init()) return rc;
+  if (int rc = freed.init()) return rc;
+  SSQ_HIP(hipMemcpyAsync(dx, x, (size_t)(batch * in1), hipMemcpyHostToDevice, s0));
+  for (int64_t b = 0; b < batch; ++b) {
+    const int k = (int)(b & 1);
+    for (size_t i = 0; i < planes.size(); ++i) cur[i] = slot[i] ? (char*)slot[i] + (long long)k * out1 : nullptr;
+    if (b >= 2) SSQ_HIP(hipStreamWaitEvent(s0, freed.ev[k], 0));          // half k was downloaded
+    if (int rc = exec((char*)dx + b * in1, cur.data(), ws, wsb, s0)) return rc;
+    SSQ_HIP(hipEventRecord(done.ev[k], s0));
+    SSQ_HIP(hipStreamWaitEvent(s1, done.ev[k], 0));
+    for (size_t i = 0; i < planes.size(); ++i)
+      if (cur[i])
+        SSQ_HIP(hipMemcpyAsync((char*)planes[i].host + b * out1, cur[i], (size_t)out1, hipMemcpyDeviceToHost, s1));
+    SSQ_HIP(hipEventRecord(freed.ev[k], s1));
+  }
+  return synced.finish();
+}
+
 }  // namespace
 
 namespace ssq {
@@ -1290,41 +1268,11 @@ static int cwt_host_impl(int dtype, const void* x, int64_t batch, int64_t n_sign
   if (int rc = cached_cwt_plan(key, &pl)) return rc;
   const long long esz = dtype == SSQ_F32 ? 4 : 8;
   const long long cols = rpadded ? pl->P : n_signal;
-  const long long out1 = (long long)pl->na * cols * 2 * esz, in1 = n_signal * esz;
-  void *dx = nullptr, *dW = nullptr, *ddW = nullptr, *ws = nullptr;
-  if (int rc = hostpath::scratch(hostpath::SLOT_X, batch * in1, &dx)) return rc;
-  if (int rc = hostpath::scratch(hostpath::SLOT_OUT, 2 * out1, &dW)) return rc;
-  if (dWx)
-    if (int rc = hostpath::scratch(hostpath::SLOT_A, 2 * out1, &ddW)) return rc;
-  const long long wsb = ssq_cwt_plan_workspace_bytes(pl, 1);
-  if (int rc = hostpath::scratch(hostpath::SLOT_WS0, wsb, &ws)) return rc;
-  hipStream_t s0 = hostpath::stream(0), s1 = hostpath::stream(1);
-  EventPair done, freed;
-  if (int rc = done.init()) return rc;
-  if (int rc = freed.init()) return rc;
-  SSQ_HIP(hipMemcpyAsync(dx, x, (size_t)(batch * in1), hipMemcpyHostToDevice, s0));
-  int rc = 0;
-  // one signal: any failure is recorded and the loop left -- both streams are ALWAYS synchronised before returning, the
-  // asynchronous copies write into the caller's (pinned) arrays
-  auto one = [&](int64_t b) -> int {
-    const int k = (int)(b & 1);
-    char* oW = (char*)dW + (long long)k * out1;
-    char* odW = dWx ? (char*)ddW + (long long)k * out1 : nullptr;
-    if (b >= 2) SSQ_HIP(hipStreamWaitEvent(s0, freed.ev[k], 0));          // slot k was downloaded
-    if (int r = ssq_cwt_plan_exec_cwt(pl, (char*)dx + b * in1, 1, l1_norm, rpadded, oW, odW, ws, wsb, s0)) return r;
-    SSQ_HIP(hipEventRecord(done.ev[k], s0));
-    SSQ_HIP(hipStreamWaitEvent(s1, done.ev[k], 0));
-    SSQ_HIP(hipMemcpyAsync((char*)Wx + b * out1, oW, (size_t)out1, hipMemcpyDeviceToHost, s1));
-    if (dWx) SSQ_HIP(hipMemcpyAsync((char*)dWx + b * out1, odW, (size_t)out1, hipMemcpyDeviceToHost, s1));
-    SSQ_HIP(hipEventRecord(freed.ev[k], s1));
-    return 0;
-  };
-  for (int64_t b = 0; b < batch && rc == 0; ++b) rc = one(b);
-  const hipError_t e0 = hipStreamSynchronize(s0), e1 = hipStreamSynchronize(s1);
-  if (rc) return rc;
-  SSQ_HIP(e0);
-  SSQ_HIP(e1);
-  return 0;
+  return cwt_host_pipeline(pl, x, batch, n_signal * esz, (long long)pl->na * cols * 2 * esz,
+                           {{Wx, hostpath::SLOT_OUT}, {dWx, hostpath::SLOT_A}},
+                           [&](const void* d_x, void* const* d, void* ws, long long wsb, hipStream_t st) {
+                             return ssq_cwt_plan_exec_cwt(pl, d_x, 1, l1_norm, rpadded, d[0], d[1], ws, wsb, st);
+                           });
 }
 
 extern "C" {
@@ -1367,21 +1315,20 @@ static int ssq_cwt_host_impl(int dtype, const void* x, int64_t batch, int64_t n_
   CwtKey key{dtype, wavelet, padtype, n_signal, dt, std::vector<double>(scales, scales + na), variant, p0, p1};
   if (gmwk) key.gmwk.assign(gmwk, gmwk + n_coeffs);
   if (int rc = cached_cwt_plan(key, &pl)) return rc;
-  if (variant & SSQ_VARIANT_UPSTREAM) {
+  const bool ups = (variant & SSQ_VARIANT_UPSTREAM) != 0;
+  SsqBins bins{ups_freqs, ups_const, (int)ups_idx, false, nullptr};
+  if (ups) {
     if (!ups_freqs) SSQ_FAIL("ssq_freqs_asc is NULL");
     if (!ups_const) SSQ_FAIL("row_const is NULL");
     for (int64_t i = 0; i < na; ++i)
       if (!std::isfinite(ups_const[i])) SSQ_FAIL("row_const must be finite");
-    pl->ups_freqs.assign(ups_freqs, ups_freqs + na);
-    pl->ups_const.assign(ups_const, ups_const + na);
     if (freq_dist == SSQ_FREQS_LOG_PIECEWISE && (ups_idx < 2 || ups_idx > na - 1))
       SSQ_FAIL("freq_transition must be 2 .. na-1 for SSQ_FREQS_LOG_PIECEWISE");
-    pl->ups_idx = (int)ups_idx;
     // one weight for every row on a log / linear frequency grid: the scalar-constant kernel (the exponential scales)
-    pl->ups_rows = freq_dist == SSQ_FREQS_LOG_PIECEWISE ||
-                   std::any_of(ups_const, ups_const + na, [&](double c) { return c != ups_const[0]; });
-    if (pl->ups_rows) {
-      if (!pl->d_ups_const) SSQ_HIP(hipMalloc(&pl->d_ups_const, (size_t)na * sizeof(double)));
+    bins.rows = freq_dist == SSQ_FREQS_LOG_PIECEWISE ||
+                std::any_of(ups_const, ups_const + na, [&](double c) { return c != ups_const[0]; });
+    if (bins.rows) {                                           // the weights in the input's dtype, in the plan's buffer
+      if (!pl->d_ups_const) SSQ_HIP(pl->mem.alloc(&pl->d_ups_const, (size_t)na * sizeof(double)));
       if (dtype == SSQ_F32) {
         const std::vector<float> c32(ups_const, ups_const + na);
         SSQ_HIP(hipMemcpy(pl->d_ups_const, c32.data(), (size_t)na * sizeof(float), hipMemcpyHostToDevice));
@@ -1389,49 +1336,18 @@ static int ssq_cwt_host_impl(int dtype, const void* x, int64_t batch, int64_t n_
         SSQ_HIP(hipMemcpy(pl->d_ups_const, ups_const, (size_t)na * sizeof(double), hipMemcpyHostToDevice));
       }
     }
+    bins.d_row_const = pl->d_ups_const;
   }
   const long long esz = dtype == SSQ_F32 ? 4 : 8;
-  const long long out1 = na * n_signal * 2 * esz, in1 = n_signal * esz;
-  void *dx = nullptr, *dT = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr, *ws = nullptr;
-  if (int rc = hostpath::scratch(hostpath::SLOT_X, batch * in1, &dx)) return rc;
-  if (int rc = hostpath::scratch(hostpath::SLOT_OUT, 2 * out1, &dT)) return rc;
-  if (dbg_Wx)
-    if (int rc = hostpath::scratch(hostpath::SLOT_A, 2 * out1, &d1)) return rc;
-  if (dbg_dWx)
-    if (int rc = hostpath::scratch(hostpath::SLOT_B, 2 * out1, &d2)) return rc;
-  if (dbg_wk)
-    if (int rc = hostpath::scratch(hostpath::SLOT_C, 2 * out1, &d3)) return rc;
-  const long long wsb = ssq_cwt_plan_workspace_bytes(pl, 1);
-  if (int rc = hostpath::scratch(hostpath::SLOT_WS0, wsb, &ws)) return rc;
-  hipStream_t s0 = hostpath::stream(0), s1 = hostpath::stream(1);
-  EventPair done, freed;
-  if (int rc = done.init()) return rc;
-  if (int rc = freed.init()) return rc;
-  SSQ_HIP(hipMemcpyAsync(dx, x, (size_t)(batch * in1), hipMemcpyHostToDevice, s0));
-  int rc = 0;
-  auto one = [&](int64_t b) -> int {             // (errors leave the loop; the streams are synchronised below either way)
-    const int k = (int)(b & 1);
-    const long long so = (long long)k * out1;
-    if (b >= 2) SSQ_HIP(hipStreamWaitEvent(s0, freed.ev[k], 0));
-    if (int r = ssq_cwt_plan_exec_ssq(pl, (char*)dx + b * in1, 1, freq_dist, maprange, squeezing, flipud, gamma,
-                                      (char*)dT + so, dbg_Wx ? (char*)d1 + so : nullptr,
-                                      dbg_dWx ? (char*)d2 + so : nullptr, dbg_wk ? (char*)d3 + so : nullptr, ws, wsb, s0))
-      return r;
-    SSQ_HIP(hipEventRecord(done.ev[k], s0));
-    SSQ_HIP(hipStreamWaitEvent(s1, done.ev[k], 0));
-    SSQ_HIP(hipMemcpyAsync((char*)Tx + b * out1, (char*)dT + so, (size_t)out1, hipMemcpyDeviceToHost, s1));
-    if (dbg_Wx) SSQ_HIP(hipMemcpyAsync((char*)dbg_Wx + b * out1, (char*)d1 + so, (size_t)out1, hipMemcpyDeviceToHost, s1));
-    if (dbg_dWx) SSQ_HIP(hipMemcpyAsync((char*)dbg_dWx + b * out1, (char*)d2 + so, (size_t)out1, hipMemcpyDeviceToHost, s1));
-    if (dbg_wk) SSQ_HIP(hipMemcpyAsync((char*)dbg_wk + b * out1, (char*)d3 + so, (size_t)out1, hipMemcpyDeviceToHost, s1));
-    SSQ_HIP(hipEventRecord(freed.ev[k], s1));
-    return 0;
-  };
-  for (int64_t b = 0; b < batch && rc == 0; ++b) rc = one(b);
-  const hipError_t e0 = hipStreamSynchronize(s0), e1 = hipStreamSynchronize(s1);
-  if (rc) return rc;
-  SSQ_HIP(e0);
-  SSQ_HIP(e1);
-  if (ssq_freqs && !(variant & SSQ_VARIANT_UPSTREAM))
+  if (int rc = cwt_host_pipeline(
+          pl, x, batch, n_signal * esz, na * n_signal * 2 * esz,
+          {{Tx, hostpath::SLOT_OUT}, {dbg_Wx, hostpath::SLOT_A}, {dbg_dWx, hostpath::SLOT_B}, {dbg_wk, hostpath::SLOT_C}},
+          [&](const void* d_x, void* const* d, void* ws, long long wsb, hipStream_t st) {
+            return exec_ssq(pl, d_x, 1, freq_dist, maprange, squeezing, flipud, gamma, d[0], d[1], d[2], d[3], ws, wsb,
+                            st, ups ? &bins : nullptr);
+          }))
+    return rc;
+  if (ssq_freqs && !ups)
     if (int rc2 = ssq_cwt_ssq_freqs(scales, na, n_signal, dt, maprange, freq_dist, ssq_freqs)) return rc2;
   return 0;
 }

@@ -209,7 +209,7 @@ int ssq_icwt_host(int dtype, const void* Wx, int64_t na, int64_t n_times, int wa
     else fac[i] = l1_norm ? 1.0 / scales[i] : 1.0 / (std::sqrt(scales[i]) * std::sqrt(scales[i]));   // :679-683
   }
   const size_t nsc = (size_t)(na > 0 ? na : 0), nx = (size_t)x_len;          // no scales: the holder's minimum size
-  HostCallBufs d;
+  DeviceBufs d;
   void *dW, *dfac, *dsc, *dx;
   SSQ_HIP(d.upload(&dW, Wx, nsc * (size_t)n_times * esz));
   SSQ_HIP(d.upload(&dfac, fac.data(), nsc * 8));

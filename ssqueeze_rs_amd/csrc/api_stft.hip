@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <mutex>
 
+#include "dev_buffers.h"
 #include "fft_generic.h"
 #include "host_cache.h"
 #include "host_math.h"
@@ -40,6 +41,7 @@ struct ssq_stft_plan {
   std::vector<double> ssq_freqs;   // ssq_stft.rs:42-54
   double sfs_step = 0, dw = 0;
   double alpha = 1.0;              // power of two: scales the derivative channel of the packed FFT
+  DeviceBufs mem;                  // owns every device table below (the fields are views)
   // device tables (typed by dtype)
   void* d_tw = nullptr;
   void* d_win2 = nullptr;
@@ -147,27 +149,18 @@ int upload_tables(ssq_stft_plan* pl, const std::vector<double>& g, const std::ve
     std::vector<cpx<T>> bh((size_t)m), post((size_t)n);
     for (int i = 0; i < m; ++i) bh[i] = {(T)(B[i].real() / (double)m), (T)(B[i].imag() / (double)m)};
     for (int i = 0; i < n; ++i) post[i] = {(T)chirp[i].real(), (T)chirp[i].imag()};
-    SSQ_HIP(hipMalloc(&pl->d_blue_b, sizeof(cpx<T>) * m));
-    SSQ_HIP(hipMalloc(&pl->d_blue_post, sizeof(cpx<T>) * n));
-    SSQ_HIP(hipMemcpy(pl->d_blue_b, bh.data(), sizeof(cpx<T>) * m, hipMemcpyHostToDevice));
-    SSQ_HIP(hipMemcpy(pl->d_blue_post, post.data(), sizeof(cpx<T>) * n, hipMemcpyHostToDevice));
+    SSQ_HIP(pl->mem.upload(&pl->d_blue_b, bh));
+    SSQ_HIP(pl->mem.upload(&pl->d_blue_post, post));
   }
   std::vector<T> fr((size_t)pl->n_freqs);
   for (int i = 0; i < pl->n_freqs; ++i) fr[i] = (T)pl->ssq_freqs[i];
-  SSQ_HIP(hipMalloc(&pl->d_tw, sizeof(cpx<T>) * tw.size()));
-  SSQ_HIP(hipMalloc(&pl->d_win2, sizeof(cpx<T>) * m));
-  SSQ_HIP(hipMalloc(&pl->d_ssq_freqs, sizeof(T) * pl->n_freqs));
-  SSQ_HIP(hipMemcpy(pl->d_tw, tw.data(), sizeof(cpx<T>) * tw.size(), hipMemcpyHostToDevice));
-  SSQ_HIP(hipMemcpy(pl->d_win2, win2.data(), sizeof(cpx<T>) * m, hipMemcpyHostToDevice));
-  SSQ_HIP(hipMemcpy(pl->d_ssq_freqs, fr.data(), sizeof(T) * pl->n_freqs, hipMemcpyHostToDevice));
-  SSQ_HIP(hipMalloc((void**)&pl->d_g, sizeof(double) * n));
-  SSQ_HIP(hipMalloc((void**)&pl->d_gd, sizeof(double) * n));
-  SSQ_HIP(hipMalloc((void**)&pl->d_twre, sizeof(double) * n));
-  SSQ_HIP(hipMalloc((void**)&pl->d_twim, sizeof(double) * n));
-  SSQ_HIP(hipMemcpy(pl->d_g, g.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-  SSQ_HIP(hipMemcpy(pl->d_gd, gdfs.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-  SSQ_HIP(hipMemcpy(pl->d_twre, twre.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-  SSQ_HIP(hipMemcpy(pl->d_twim, twim.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+  SSQ_HIP(pl->mem.upload(&pl->d_tw, tw));
+  SSQ_HIP(pl->mem.upload(&pl->d_win2, win2));
+  SSQ_HIP(pl->mem.upload(&pl->d_ssq_freqs, fr));
+  SSQ_HIP(pl->mem.upload(&pl->d_g, g));
+  SSQ_HIP(pl->mem.upload(&pl->d_gd, gdfs));
+  SSQ_HIP(pl->mem.upload(&pl->d_twre, twre));
+  SSQ_HIP(pl->mem.upload(&pl->d_twim, twim));
   return 0;
 }
 
@@ -400,17 +393,7 @@ int ssq_stft_plan_create_v(ssq_stft_plan** plan, int dtype, int64_t n_signal, co
 }
 
 int ssq_stft_plan_destroy(ssq_stft_plan* pl) {
-  if (!pl) return 0;
-  hipFree(pl->d_tw);
-  hipFree(pl->d_win2);
-  hipFree(pl->d_ssq_freqs);
-  hipFree(pl->d_blue_b);
-  hipFree(pl->d_blue_post);
-  hipFree(pl->d_g);
-  hipFree(pl->d_gd);
-  hipFree(pl->d_twre);
-  hipFree(pl->d_twim);
-  delete pl;
+  delete pl;                       // (pl->mem frees the tables)
   return 0;
 }
 
@@ -621,26 +604,21 @@ static int run_host(int dtype, const void* x, int64_t batch, int64_t n_signal, c
   }
   hipStream_t st[2] = {hostpath::stream(0), hostpath::stream(1)};
   if (!st[0] || !st[1]) SSQ_FAIL("hipStreamCreate failed");
-  int rc = 0;
+  hostpath::SyncedStreams synced(st[0], st[1]);              // from here on every return synchronises both streams
   int64_t g = 0;
-  for (int64_t b0 = 0; b0 < batch && rc == 0; b0 += grp, ++g) {
+  for (int64_t b0 = 0; b0 < batch; b0 += grp, ++g) {
     const int64_t nb = std::min<int64_t>(grp, batch - b0);
     const int s = (int)(g & 1);
     char* dxg = (char*)d_x + b0 * in1;
     char* dog = (char*)d_out + (int64_t)s * grp * out1;
     SSQ_HIP(hipMemcpyAsync(dxg, (const char*)x + b0 * in1, (size_t)(nb * in1), hipMemcpyHostToDevice, st[s]));
-    for (int i = 0; i < n_out && rc == 0; ++i) {
+    for (int i = 0; i < n_out; ++i) {
       if (!outs[i]) continue;
-      rc = ssq_stft_plan_exec(pl, kinds[i], dxg, nb, dog, d_ws[s], ws1, st[s]);
-      if (rc) break;
+      if (int rc = ssq_stft_plan_exec(pl, kinds[i], dxg, nb, dog, d_ws[s], ws1, st[s])) return rc;
       SSQ_HIP(hipMemcpyAsync((char*)outs[i] + b0 * out1, dog, (size_t)(nb * out1), hipMemcpyDeviceToHost, st[s]));
     }
   }
-  const hipError_t e0 = hipStreamSynchronize(st[0]), e1 = hipStreamSynchronize(st[1]);
-  if (rc) return rc;
-  SSQ_HIP(e0);
-  SSQ_HIP(e1);
-  return 0;
+  return synced.finish();
 }
 
 extern "C" {

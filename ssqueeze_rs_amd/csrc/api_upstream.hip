@@ -97,7 +97,7 @@ int istft_typed(const void* Sx, int64_t n_frames, const std::vector<double>& wpo
                 int64_t n, int64_t hop, int64_t N, int modulated, void* x_out) {
   const int64_t nf = n / 2 + 1;
   const long long we = fft_work_elems(n, n_frames);
-  HostCallBufs d;
+  DeviceBufs d;
   void *d_S, *d_Z, *d_work, *d_wp, *d_wn, *d_x;
   SSQ_HIP(d.upload(&d_S, Sx, sizeof(cpx<T>) * nf * n_frames));
   SSQ_HIP(d.alloc(&d_Z, sizeof(cpx<T>) * n * n_frames));
@@ -139,7 +139,7 @@ int istft_batch_fused(const IstftPlan& pl, const void* Sx, int64_t batch, const 
                                         istft_fused_bytes<T>(pl, 0, N, true), 65535);
   const std::vector<cpx<T>> tw = istft_twiddles<T>(n);
   const size_t sx_sig = sizeof(cpx<T>) * (size_t)nf * (size_t)n_frames;
-  HostCallBufs d;
+  DeviceBufs d;
   void *d_S, *d_x, *d_tw, *d_wp, *d_wn;
   SSQ_HIP(d.alloc(&d_S, sx_sig * slice));
   SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)N * slice));
@@ -161,7 +161,7 @@ int issq_batch_typed(const void* Tx, int64_t batch, int64_t rows, int64_t cols, 
                      void* x_out) {
   const size_t map_b = sizeof(cpx<T>) * (size_t)rows * (size_t)cols;
   const long long slice = slice_signals(batch, (double)map_b + (double)sizeof(T) * (double)cols, 8.0 * (double)rows, 65535);
-  HostCallBufs d;
+  DeviceBufs d;
   void *d_T, *d_x, *d_r = nullptr;
   SSQ_HIP(d.alloc(&d_T, map_b * slice));
   SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)cols * slice));
@@ -186,7 +186,7 @@ int istft_batch_exec_typed(const void* d_Sx, int64_t batch, int64_t n_frames, co
   const int64_t nf = n / 2 + 1;
   const cpx<T>* d_S = (const cpx<T>*)d_Sx;
   T* d_x = (T*)d_x_out;
-  HostCallBufs d;
+  DeviceBufs d;
   void *d_wp, *d_wn, *d_tw = nullptr, *d_Z = nullptr, *d_work = nullptr;
   SSQ_HIP(d.upload(&d_wp, wpow.data(), sizeof(double) * n));
   SSQ_HIP(d.upload(&d_wn, wnorm.data(), sizeof(double) * n));

@@ -40,7 +40,7 @@ __device__ __forceinline__ int bin_of(const BinRule<T>& r, T w) {
 }
 
 // algos.py:341-370 (`_get_params_find_closest_log`, `_ensure_nonzero_nonnegative`) and :84-90 in fp64, as
-// exec_ssq_typed (api_cwt.hip) sets up the fused kernels (sets the error and returns non-zero)
+// ssq_bin_params (api_cwt.hip) sets up the fused kernels (sets the error and returns non-zero)
 template <typename T>
 int bin_rule(const double* f, int64_t rows, int kind, int64_t idx, int flipud, BinRule<T>& r) {
   if (!f) SSQ_FAIL("ssq_freqs_asc is NULL");

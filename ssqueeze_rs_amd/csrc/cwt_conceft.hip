@@ -255,7 +255,7 @@ int conceft_run(const ConceftCall& c, const ConceftShape& s, const void* d_x, vo
                                         c.dt, c.padtype, SSQ_VARIANT_UPSTREAM))
     return rc;
   const int64_t plan_bytes = ssq_cwt_plan_workspace_bytes(ph.pl, 1);
-  HostCallBufs d;
+  DeviceBufs d;
   TimingEvents t;
   void *d_plan = nullptr, *d_vec = nullptr, *d_rc = nullptr;
   SSQ_HIP(d.alloc(&d_plan, (size_t)plan_bytes));
@@ -333,7 +333,7 @@ int conceft_run(const ConceftCall& c, const ConceftShape& s, const void* d_x, vo
 template <typename T>
 int conceft_host_typed(const ConceftCall& c, const ConceftShape& s, const void* x, int64_t work_bytes, void* Tx, void* Wx,
                        void* w) {
-  HostCallBufs d;
+  DeviceBufs d;
   const size_t n = (size_t)c.batch * (size_t)s.plane;
   void *d_x, *d_Tx, *d_work, *d_Wx = nullptr, *d_w = nullptr;
   SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.batch * (size_t)c.N));

@@ -141,7 +141,7 @@ template <typename T>
 int mcwt_run(const Cwt2Call& c, const CwtMapsShape& s, int order, int n_iter, const int32_t* row_of_bin, const void* d_x,
              void* d_Tx, void* d_Wx, void* d_w, int* d_rows, int* d_bins, void* d_wn, void* d_work, int64_t work_bytes,
              hipStream_t st, float* kernel_ms) {
-  HostCallBufs d;
+  DeviceBufs d;
   TimingEvents t;
   void *d_scales = nullptr, *d_rc = nullptr, *d_rho = nullptr;
   if (int rc = cwt2_tables<T>(d, c, &d_scales, &d_rc)) return rc;
@@ -177,7 +177,7 @@ int mcwt_run(const Cwt2Call& c, const CwtMapsShape& s, int order, int n_iter, co
 template <typename T>
 int mcwt_host_typed(const Cwt2Call& c, const CwtMapsShape& s, int order, int n_iter, const int32_t* row_of_bin, const void* x,
                     int64_t work_bytes, void* Tx, void* Wx, void* w, int32_t* rows, int32_t* bins) {
-  HostCallBufs d;
+  DeviceBufs d;
   const size_t n = (size_t)s.rows * (size_t)c.m.N;
   void *d_x, *d_Tx, *d_Wx, *d_w, *d_wn = nullptr, *d_rows = nullptr, *d_bins = nullptr, *d_work;
   SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));
@@ -202,7 +202,7 @@ int mcwt_host_typed(const Cwt2Call& c, const CwtMapsShape& s, int order, int n_i
 template <typename T>
 int mcwt_walk_typed(const void* w, int64_t batch, int64_t na, int64_t n, const double* f_asc, int freq_kind,
                     int64_t freq_transition, const int32_t* row_of_bin, int n_iter, int32_t* rows, int32_t* bins, void* w_n) {
-  HostCallBufs d;
+  DeviceBufs d;
   CwtWalkDev<T> wk{};
   if (int rc = bin_rule<T>(f_asc, na, freq_kind, freq_transition, 0, wk.rule)) return rc;
   const size_t sig = (size_t)na * (size_t)n;

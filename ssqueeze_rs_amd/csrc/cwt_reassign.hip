@@ -194,7 +194,7 @@ template <typename T>
 int cwtr_run(const CwtRCall& c, const CwtMapsShape& s, const void* d_x, void* d_Rx, void* d_Wx, void* d_w, void* d_tau,
              void* d_kk, void* d_mm, void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
   const int64_t batch = c.m.batch, N = c.m.N, na = c.m.na;
-  HostCallBufs d;
+  DeviceBufs d;
   TimingEvents t;
   void* d_scales = nullptr;
   SSQ_HIP(d.upload(&d_scales, c.m.scales, sizeof(double) * (size_t)na));
@@ -267,7 +267,7 @@ int cwtr_run(const CwtRCall& c, const CwtMapsShape& s, const void* d_x, void* d_
 template <typename T>
 int cwtr_host_typed(const CwtRCall& c, const CwtMapsShape& s, const void* x, int64_t work_bytes, void* Rx, void* Wx,
                     void* w, void* tau, void* kk, void* mm) {
-  HostCallBufs d;
+  DeviceBufs d;
   const size_t n = (size_t)s.rows * (size_t)c.m.N;
   void *d_x, *d_Rx, *d_Wx, *d_work, *d_w = nullptr, *d_tau = nullptr;
   SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));

@@ -24,7 +24,7 @@ int cwt2_check(const CwtMapsKind& k, const char* own_fail, const Cwt2Call& c, Cw
 
 // the call's tables on the device (held by `d`): the scales in fp64 and the row weights in the call's dtype
 template <typename T>
-int cwt2_tables(HostCallBufs& d, const Cwt2Call& c, void** d_scales, void** d_rc);
+int cwt2_tables(DeviceBufs& d, const Cwt2Call& c, void** d_scales, void** d_rc);
 
 // The operator half on device buffers: Wx and the one-step frequency, [batch][na][N] in the call's dtype.  `work_bytes`
 // >= s.min_bytes sets the rows per chunk.  gamma_sq: the second-order estimate is used where |D| > gamma_sq (ssq_cwt2:

@@ -74,7 +74,7 @@ int cwt2_check(const CwtMapsKind& k, const char* own_fail, const Cwt2Call& c, Cw
 }
 
 template <typename T>
-int cwt2_tables(HostCallBufs& d, const Cwt2Call& c, void** d_scales, void** d_rc) {
+int cwt2_tables(DeviceBufs& d, const Cwt2Call& c, void** d_scales, void** d_rc) {
   SSQ_HIP(d.upload(d_scales, c.m.scales, sizeof(double) * (size_t)c.m.na));
   const std::vector<T> rc(c.row_const, c.row_const + c.m.na);
   SSQ_HIP(d.upload(d_rc, rc.data(), sizeof(T) * (size_t)c.m.na));
@@ -110,8 +110,8 @@ int cwt2_squeeze_run(const Cwt2Call& c, const void* d_Wx, const void* d_w, const
                              c.squeezing, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, d_Tx, st);
 }
 
-template int cwt2_tables<float>(HostCallBufs&, const Cwt2Call&, void**, void**);
-template int cwt2_tables<double>(HostCallBufs&, const Cwt2Call&, void**, void**);
+template int cwt2_tables<float>(DeviceBufs&, const Cwt2Call&, void**, void**);
+template int cwt2_tables<double>(DeviceBufs&, const Cwt2Call&, void**, void**);
 template int cwt2_operator_run<float>(const Cwt2Call&, const CwtMapsShape&, double, const void*, const void*, void*, void*,
                                       void*, int64_t, hipStream_t);
 template int cwt2_operator_run<double>(const Cwt2Call&, const CwtMapsShape&, double, const void*, const void*, void*, void*,
@@ -129,7 +129,7 @@ constexpr CwtMapsKind kCwt2Kind = {"ssq_cwt2", "ssq_ssq_cwt2_workspace_bytes", 1
 template <typename T>
 int cwt2_run(const Cwt2Call& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_w2, void* d_work,
              int64_t work_bytes, hipStream_t st, float* kernel_ms) {
-  HostCallBufs d;
+  DeviceBufs d;
   TimingEvents t;
   void *d_scales = nullptr, *d_rc = nullptr;
   if (int rc = cwt2_tables<T>(d, c, &d_scales, &d_rc)) return rc;
@@ -148,7 +148,7 @@ int cwt2_run(const Cwt2Call& c, const CwtMapsShape& s, const void* d_x, void* d_
 template <typename T>
 int cwt2_host_typed(const Cwt2Call& c, const CwtMapsShape& s, const void* x, int64_t work_bytes, void* Tx, void* Wx,
                     void* w2) {
-  HostCallBufs d;
+  DeviceBufs d;
   const size_t n = (size_t)s.rows * (size_t)c.m.N;
   void *d_x, *d_Tx, *d_Wx, *d_w2, *d_work;
   SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));

@@ -248,7 +248,7 @@ template <typename T, int ORDER>
 int cwtt_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm,
              void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
   const int64_t batch = c.m.batch, N = c.m.N, na = c.m.na;
-  HostCallBufs d;
+  DeviceBufs d;
   TimingEvents t;
   void *d_scales = nullptr, *d_nu = nullptr;
   SSQ_HIP(d.upload(&d_scales, c.m.scales, sizeof(double) * (size_t)na));
@@ -327,7 +327,7 @@ int cwtt_run_order(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, vo
 template <typename T>
 int cwtt_host_typed(const CwtTCall& c, const CwtMapsShape& s, const void* x, int64_t work_bytes, void* Tx, void* Wx,
                     void* tau, void* mm) {
-  HostCallBufs d;
+  DeviceBufs d;
   const size_t n = (size_t)s.rows * (size_t)c.m.N;
   void *d_x, *d_Tx, *d_Wx, *d_work, *d_tau = nullptr;
   SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));

@@ -14,15 +14,16 @@ inline int require_device() {
   return 0;
 }
 
-// Device buffers of one synchronous host call: hipMalloc per buffer, all freed when the holder goes out of scope, so
-// an entry point may return through SSQ_HIP at any point.  A request of 0 bytes still allocates (16 bytes): a kernel
+// Device buffers with one owner -- a synchronous host call, or a plan (its tables): hipMalloc per buffer, all freed
+// when the holder is destroyed, so an entry point or a plan's creation may return through SSQ_HIP at any point and
+// nobody lists the buffers a second time to free them.  A request of 0 bytes still allocates (16 bytes): a kernel
 // never receives nullptr for a buffer that was asked for, only for an optional one the caller left out.
-struct HostCallBufs {
+struct DeviceBufs {
   std::vector<void*> ptrs;
-  HostCallBufs() = default;
-  HostCallBufs(const HostCallBufs&) = delete;
-  HostCallBufs& operator=(const HostCallBufs&) = delete;
-  ~HostCallBufs() {
+  DeviceBufs() = default;
+  DeviceBufs(const DeviceBufs&) = delete;
+  DeviceBufs& operator=(const DeviceBufs&) = delete;
+  ~DeviceBufs() {
     for (void* p : ptrs) (void)hipFree(p);
   }
   hipError_t alloc(void** out, size_t bytes) {
@@ -37,6 +38,11 @@ struct HostCallBufs {
     hipError_t e = alloc(out, bytes);
     if (e == hipSuccess && bytes) e = hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice);
     return e;
+  }
+  // upload of a host vector into a pointer of any element type
+  template <typename P, typename V>
+  hipError_t upload(P** out, const std::vector<V>& h) {
+    return upload((void**)out, h.data(), sizeof(V) * h.size());
   }
 };
 

@@ -274,7 +274,7 @@ int ssq_issq_components_host(int dtype, const void* Tx, int64_t batch, int64_t r
   if (int rc = require_device()) return rc;
   const size_t tx_bytes = (size_t)(batch * rows * cols) * (dtype == SSQ_F64 ? 16 : 8);
   const size_t x_bytes = (size_t)(batch * (n_comp + 1) * cols) * sizeof(double);
-  HostCallBufs d;
+  DeviceBufs d;
   void *dT, *dcc, *dcw = nullptr, *dx;
   SSQ_HIP(d.upload(&dT, Tx, tx_bytes));
   SSQ_HIP(d.upload(&dcc, cc, nb * sizeof(int64_t)));

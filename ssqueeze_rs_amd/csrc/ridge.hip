@@ -474,7 +474,7 @@ int ssq_extract_ridges_host(int dtype, int param_dtype, int is_complex, const vo
   if (int rc = require_device()) return rc;
   const size_t es = dtype == SSQ_F64 ? 8 : 4, ps = param_dtype == SSQ_F64 ? 8 : 4;
   const size_t n = (size_t)(batch * n_freqs * n_time), outs = (size_t)(batch * n_time * n_ridges);
-  HostCallBufs d;
+  DeviceBufs d;
   void *dT, *dm, *ds = nullptr, *di, *df = nullptr, *de = nullptr, *dc = nullptr, *dw;
   const int64_t wsb = (int64_t)ws_bytes(dtype, batch, n_freqs, n_time);
   SSQ_HIP(d.upload(&dT, Tf, n * es * (is_complex ? 2 : 1)));
@@ -503,7 +503,7 @@ int ssq_ridge_track_host(int dtype, int param_dtype, const void* cost, int64_t b
   const size_t es = dtype == SSQ_F64 ? 8 : 4, ps = param_dtype == SSQ_F64 ? 8 : 4;
   const int64_t F = n_freqs, N = n_time;
   const size_t n = (size_t)(batch * F * N);
-  HostCallBufs d;
+  DeviceBufs d;
   void *dsrc, *dct, *dpen, *dm, *dr;
   SSQ_HIP(d.upload(&dsrc, cost, n * es));
   SSQ_HIP(d.alloc(&dct, n * es));

@@ -229,7 +229,7 @@ int squeeze_dwx_typed(const void* Wx, const void* dWx, const void* Sfs, int64_t 
   return 0;
 }
 
-int upload_row_const(HostCallBufs& d, int dtype, const double* row_const, int64_t rows, void** out) {
+int upload_row_const(DeviceBufs& d, int dtype, const double* row_const, int64_t rows, void** out) {
   if (!row_const) SSQ_FAIL("row_const is NULL");
   for (int64_t i = 0; i < rows; ++i)
     if (!std::isfinite(row_const[i])) SSQ_FAIL("row_const must be finite");
@@ -261,7 +261,7 @@ int ssq_phase_host(int dtype, const void* Wx, const void* dWx, const void* Sfs, 
   if (!Wx || !dWx || !w) SSQ_FAIL("NULL argument");
   if (int rc = require_device()) return rc;
   const size_t esz = dtype == SSQ_F64 ? 8 : 4, n = (size_t)(batch * rows * cols);
-  HostCallBufs d;
+  DeviceBufs d;
   void *dW = nullptr, *ddW = nullptr, *dS = nullptr, *dw = nullptr;
   SSQ_HIP(d.upload(&dW, Wx, n * 2 * esz));
   SSQ_HIP(d.upload(&ddW, dWx, n * 2 * esz));
@@ -295,7 +295,7 @@ int ssq_ssqueeze_w_host(int dtype, const void* Wx, const void* w, int64_t batch,
   if (int rc = require_device()) return rc;
   const size_t esz = dtype == SSQ_F64 ? 8 : 4, n = (size_t)(batch * rows * cols);
   const size_t tx_bytes = n * (squeezing == SSQ_SQUEEZE_ABS ? esz : 2 * esz);
-  HostCallBufs d;
+  DeviceBufs d;
   void *dW = nullptr, *dw = nullptr, *dc = nullptr, *dT = nullptr;
   if (squeezing != SSQ_SQUEEZE_LEBESGUE) SSQ_HIP(d.upload(&dW, Wx, n * 2 * esz));
   SSQ_HIP(d.upload(&dw, w, n * esz));
@@ -336,7 +336,7 @@ int ssq_ssqueeze_dwx_host(int dtype, const void* Wx, const void* dWx, const void
     if (s0 != f0) SSQ_FAIL("STFT from dSx: ssq_freqs_asc[0] must equal Sfs[0]");
   }
   if (int rc = require_device()) return rc;
-  HostCallBufs d;
+  DeviceBufs d;
   void *dW = nullptr, *ddW = nullptr, *dS = nullptr, *dc = nullptr, *dT = nullptr;
   SSQ_HIP(d.upload(&dW, Wx, n * 2 * esz));
   SSQ_HIP(d.upload(&ddW, dWx, n * 2 * esz));

@@ -365,7 +365,7 @@ template <typename T>
 int cf_stft_run(const CfStftCall& c, const CfStftShape& s, const void* d_x, void* d_Tx, void* d_Sx, void* d_dSx, void* d_w,
                 void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
   const int64_t batch = c.batch, N = c.N, n = c.n_fft, J = c.J, M = c.M, F = s.n_freqs, nfr = s.n_frames;
-  HostCallBufs d;
+  DeviceBufs d;
   TimingEvents t;
   std::vector<double> wa((size_t)(2 * J * n)), h1((size_t)J);
   for (int64_t j = 0; j < J; ++j) {
@@ -469,7 +469,7 @@ int cf_stft_run(const CfStftCall& c, const CfStftShape& s, const void* d_x, void
 template <typename T>
 int cf_stft_host_typed(const CfStftCall& c, const CfStftShape& s, const void* x, int64_t work_bytes, void* Tx, void* Sx,
                        void* dSx, void* w) {
-  HostCallBufs d;
+  DeviceBufs d;
   const size_t n = (size_t)c.batch * (size_t)s.n_freqs * (size_t)s.n_frames;
   void *d_x, *d_Tx, *d_work, *d_Sx = nullptr, *d_dSx = nullptr, *d_w = nullptr;
   SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.batch * (size_t)c.N));

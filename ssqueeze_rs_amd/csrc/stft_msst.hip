@@ -101,7 +101,7 @@ const char* msst_own_fail(int order, int n_iter) {
 
 // the operator runs unflipped (the walk indexes rows by bin); the flip is applied when the final bin is written
 template <typename T>
-int msst_tables(HostCallBufs& d, const Sst2Shape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
+int msst_tables(DeviceBufs& d, const Sst2Shape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
                 int padtype, int variant, int order, Sst2Dev<T>* p) {
   if (int rc = sst2_tables<T>(d, s, window, n, n_signal, hop, padtype, variant & ~SSQ_VARIANT_FLIPUD, p)) return rc;
   if (order == 1) p->gamma_sq = INFINITY;                    // |D| > gamma_sq nowhere: the operator reports fs |Re w1|
@@ -129,7 +129,7 @@ template <typename T>
 int msst_host_typed(const Sst2Shape& s, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
                     int64_t hop, int padtype, int squeezing, int variant, int order, int n_iter, void* Tx, void* Sx, void* w,
                     int32_t* bins) {
-  HostCallBufs d;
+  DeviceBufs d;
   Sst2Dev<T> p;
   if (int rc = msst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, order, &p)) return rc;
   const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
@@ -161,7 +161,7 @@ template <typename T>
 int msst_exec_typed(const Sst2Shape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
                     int64_t hop, int padtype, int squeezing, int variant, int order, int n_iter, void* d_Tx, void* d_Sx,
                     void* d_w, int32_t* d_bins, void* d_work, float* kernel_ms) {
-  HostCallBufs d;
+  DeviceBufs d;
   Sst2Dev<T> p;
   if (int rc = msst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, order, &p)) return rc;
   // the workspace of ssq_ssq_stft2_exec: the map, then (float32 calls) the widened signals
@@ -244,7 +244,7 @@ int ssq_msst_walk_host(const int32_t* bins_in, int64_t batch, int64_t n_rows, in
     if (bins_in[i] < -1 || bins_in[i] >= n_rows) SSQ_FAIL("msst_walk: a target lies outside -1 .. n_rows - 1");
   if (int rc = require_device()) return rc;
   // the kernel's format is the packed map of a float32 call, (w, bin): packing to and from it is host plumbing
-  HostCallBufs d;
+  DeviceBufs d;
   const int64_t slice = slice_signals(batch, (double)map_sig * (sizeof(cpx<float>) + sizeof(int32_t)), 0.0, batch);
   void *d_map, *d_bins;
   SSQ_HIP(d.alloc(&d_map, sizeof(cpx<float>) * map_sig * slice));

@@ -330,7 +330,7 @@ int reassign_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, in
 
 // the call's tables on the device (held by `d`) and the two parameter blocks without their signal / output pointers
 template <typename T>
-int reassign_tables(HostCallBufs& d, const ReassignShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
+int reassign_tables(DeviceBufs& d, const ReassignShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
                     int padtype, int variant, ReassignDev<T>* p, ReassignScat<T>* sc) {
   const host::SstTables t = host::sst_level_tables(window, n, host::kSstFirst);
   const std::vector<double> tw = host::pass_twiddles(s.logn);
@@ -360,7 +360,7 @@ int reassign_tables(HostCallBufs& d, const ReassignShape& s, const double* windo
 
 // the operator kernel's output block (ReassignOut) on the device, held by `d`
 template <typename T>
-int reassign_out_block(HostCallBufs& d, const ReassignShape& s, int64_t hop, void* d_Sx, void* d_w, void* d_tau, void* d_tgt,
+int reassign_out_block(DeviceBufs& d, const ReassignShape& s, int64_t hop, void* d_Sx, void* d_w, void* d_tau, void* d_tgt,
                        void* d_emax, ReassignDev<T>* p) {
   ReassignOut<T> o{};
   o.Sx = (cpx<T>*)d_Sx;
@@ -420,7 +420,7 @@ hipError_t reassign_run(ReassignDev<T> p, ReassignScat<T> sc, const ReassignShap
 template <typename T>
 int reassign_host_typed(const ReassignShape& s, const void* x, int64_t batch, int64_t n_signal, const double* window,
                         int64_t n, int64_t hop, int padtype, int variant, void* Rx, void* Sx, void* w, void* tau) {
-  HostCallBufs d;
+  DeviceBufs d;
   ReassignDev<T> p;
   ReassignScat<T> sc;
   if (int rc = reassign_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
@@ -461,7 +461,7 @@ template <typename T>
 int reassign_exec_typed(const ReassignShape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window,
                         int64_t n, int64_t hop, int padtype, int variant, void* d_Rx, void* d_Sx, void* d_w, void* d_tau,
                         void* d_work, float* kernel_ms) {
-  HostCallBufs d;
+  DeviceBufs d;
   ReassignDev<T> p;
   ReassignScat<T> sc;
   if (int rc = reassign_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;

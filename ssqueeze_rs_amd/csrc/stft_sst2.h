@@ -43,7 +43,7 @@ int sst2_shape(const char* name, const char* own_fail, int dtype, int64_t batch,
 
 // the call's tables on the device (held by `d`) and the parameter block without its signal / output pointers
 template <typename T>
-int sst2_tables(HostCallBufs& d, const Sst2Shape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
+int sst2_tables(DeviceBufs& d, const Sst2Shape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
                 int padtype, int variant, Sst2Dev<T>* p);
 
 // the operator kernel of `nb` signals on device buffers: Sx and the packed map (d_xd: float32 calls, [nb][n_signal])

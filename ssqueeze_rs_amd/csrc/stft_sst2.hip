@@ -224,7 +224,7 @@ int sst2_shape(const char* name, const char* own_fail, int dtype, int64_t batch,
 
 // the call's tables on the device (held by `d`) and the parameter block without its signal / output pointers
 template <typename T>
-int sst2_tables(HostCallBufs& d, const Sst2Shape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
+int sst2_tables(DeviceBufs& d, const Sst2Shape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
                 int padtype, int variant, Sst2Dev<T>* p) {
   const host::SstTables t = host::sst_level_tables(window, n, host::kSstSecond);   // fp64 for either dtype of the call
   const std::vector<double> tw = host::pass_twiddles(s.logn);
@@ -299,7 +299,7 @@ hipError_t sst2_scatter_run(const Sst2Shape& s, int squeezing, T dw, int64_t nb,
 }
 
 #define SSQ_SST2_INSTANTIATE(T)                                                                                          \
-  template int sst2_tables<T>(HostCallBufs&, const Sst2Shape&, const double*, int64_t, int64_t, int64_t, int, int,        \
+  template int sst2_tables<T>(DeviceBufs&, const Sst2Shape&, const double*, int64_t, int64_t, int64_t, int, int,        \
                               Sst2Dev<T>*);                                                                              \
   template hipError_t sst2_operator_run<T>(Sst2Dev<T>, const Sst2Shape&, const T*, int64_t, cpx<T>*, cpx<T>*, double*);   \
   template hipError_t sst2_scatter_run<T>(const Sst2Shape&, int, T, int64_t, const cpx<T>*, const cpx<T>*, cpx<T>*, T*);
@@ -324,7 +324,7 @@ hipError_t sst2_run(Sst2Dev<T> p, const Sst2Shape& s, int squeezing, const T* d_
 template <typename T>
 int sst2_host_typed(const Sst2Shape& s, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
                     int64_t hop, int padtype, int squeezing, int variant, void* Tx, void* Sx, void* w2) {
-  HostCallBufs d;
+  DeviceBufs d;
   Sst2Dev<T> p;
   if (int rc = sst2_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p)) return rc;
   const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
@@ -352,7 +352,7 @@ template <typename T>
 int sst2_exec_typed(const Sst2Shape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
                     int64_t hop, int padtype, int squeezing, int variant, void* d_Tx, void* d_Sx, void* d_w2, void* d_work,
                     float* kernel_ms) {
-  HostCallBufs d;
+  DeviceBufs d;
   Sst2Dev<T> p;
   if (int rc = sst2_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p)) return rc;
   // the workspace: the map, then (float32 calls) the widened signals

@@ -365,7 +365,7 @@ int tsst_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_
 
 // the call's tables on the device (held by `d`) and the two parameter blocks without their signal / output pointers
 template <typename T>
-int tsst_tables(HostCallBufs& d, const TsstShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
+int tsst_tables(DeviceBufs& d, const TsstShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
                 int padtype, int variant, TsstDev<T>* p, TsstScat<T>* sc) {
   const host::SstTables t = host::sst_level_tables(window, n, s.order == 1 ? host::kSstTimeFirst : host::kSstSecond);
   const std::vector<double> tw = host::pass_twiddles(s.logn);
@@ -409,7 +409,7 @@ int tsst_tables(HostCallBufs& d, const TsstShape& s, const double* window, int64
 
 // the operator kernel's output block (TsstOut) on the device, held by `d`
 template <typename T>
-int tsst_out_block(HostCallBufs& d, const TsstShape& s, int64_t hop, void* d_Sx, void* d_tau, void* d_rel, TsstDev<T>* p) {
+int tsst_out_block(DeviceBufs& d, const TsstShape& s, int64_t hop, void* d_Sx, void* d_tau, void* d_rel, TsstDev<T>* p) {
   TsstOut<T> o{};
   o.Sx = (cpx<T>*)d_Sx;
   o.tau = (T*)d_tau;
@@ -458,7 +458,7 @@ hipError_t tsst_run(TsstDev<T> p, TsstScat<T> sc, const TsstShape& s, const T* d
 template <typename T>
 int tsst_host_typed(const TsstShape& s, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
                     int64_t hop, int padtype, int variant, void* Tx, void* Sx, void* tau) {
-  HostCallBufs d;
+  DeviceBufs d;
   TsstDev<T> p;
   TsstScat<T> sc;
   if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
@@ -489,7 +489,7 @@ template <typename T>
 int tsst_exec_typed(const TsstShape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
                     int64_t hop, int padtype, int variant, void* d_Tx, void* d_Sx, void* d_tau, void* d_work,
                     float* kernel_ms) {
-  HostCallBufs d;
+  DeviceBufs d;
   TsstDev<T> p;
   TsstScat<T> sc;
   if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;

@@ -1,4 +1,4 @@
-"""The time-tile kernel families of the fp32 `ssq_cwt` (csrc/cwt_os.hip, launched by `exec_ssq_typed` in
+"""The time-tile kernel families of the fp32 `ssq_cwt` (csrc/cwt_os.hip, launched by `launch_time_tiles` in
 csrc/api_cwt.hip), each at the smallest shape at which it exists, cell by cell: Tx against the re-accumulation of the
 kernel's own (Wx, k), k against the kernel's own w, w against the kernel's own (Wx, dWx), and Wx / dWx of EVERY row
 against the fp64 oracle (tests/helpers/cwt_scatter_check.py: the bounds and where they come from).
