@@ -258,6 +258,44 @@ int64_t ssq_tssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal
 int ssq_tssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
                        int64_t hop, double fs, int padtype, int order, double gamma, int variant, void* d_Tx, void* d_Sx,
                        void* d_tau, void* d_workspace, int64_t workspace_bytes, float* kernel_ms);
+/* Time-reassigned multisynchrosqueezed STFT, `upstream.tmssq_stft` (csrc/stft_tmsst.hip; Yu, Lin, Ma and He
+ * 2020; upstream has no such transform): ssq_tssq_stft_host whose time map is asked again at the frame a coefficient
+ * landed on, n_iter steps in all.  Arguments, conventions and the n_fft range of ssq_tssq_stft_host; order 1 or 2, n_iter
+ * 1 .. 64, and n_iter H <= 16384 with H = ceil(n_fft / (2 hop)) (the final relative target is an int16 and a tile of
+ * targets with both halos is staged in LDS).  Per row, with t[m] = m' of ssq_tssq_stft_host for a kept bin, none where
+ * |V| <= gamma:
+ *   c1[m] = t[m];   c(i+1)[m] = t[ci[m]] if t[ci[m]] is kept, else ci[m]                  (i = 1 .. n_iter - 1)
+ *   Tx[k][c_n[m]] += Sx[k][m] exp(-2 pi i ((k (m - c_n[m]) hop) mod n_fft) / n_fft) for every kept m, every cell in
+ *   ascending source frame (a compensated fp64 sum, no atomics: the result does not depend on `batch` or on the tiling).
+ * A chain stops on a frame whose bin of that row is not kept and on a fixed point; a cycle turns until n_iter runs out.
+ * n_iter = 1 is ssq_tssq_stft_host bit for bit.  Tx, Sx as there; tau (may be NULL): the ONE-step map, REAL of `dtype`,
+ * +inf where a bin is not kept; targets (may be NULL): [batch][n_freqs][n_frames] int32, the frame of Tx each
+ * coefficient went to, -1 where it was not kept.  Synchronous, sliced like ssq_tssq_stft_host. */
+int ssq_tmssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                        int64_t hop, double fs, int padtype, int order, double gamma, int variant, int n_iter, void* Tx,
+                        void* Sx, void* tau, int32_t* targets);
+/* Device bytes of the workspace ssq_tmssq_stft_exec needs (ssq_tssq_stft_workspace_bytes' and one more int16 per bin,
+ * the walked targets), computed on the host; -1 on a shape ssq_tmssq_stft_host refuses (n_iter enters through
+ * n_iter H <= 16384). */
+int64_t ssq_tmssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop, int n_iter);
+/* The same transform on device buffers: d_x [batch][N], d_Tx, d_Sx, d_tau and d_targets (each may be NULL) as above,
+ * d_workspace of at least ssq_tmssq_stft_workspace_bytes bytes; `window` on the host.  Synchronous.  kernel_ms (may be
+ * NULL): THREE floats, the time of the operator kernel (with the widening of a float32 call), of the walk kernel (0 work
+ * at n_iter = 1 without d_targets: no launch), and of the time scatter, from HIP events around the launches with the
+ * tables set up before them. */
+int ssq_tmssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                        int64_t hop, double fs, int padtype, int order, double gamma, int variant, int n_iter, void* d_Tx,
+                        void* d_Sx, void* d_tau, int32_t* d_targets, void* d_workspace, int64_t workspace_bytes,
+                        float* kernel_ms);
+/* The walk of ssq_tmssq_stft_host alone, on maps the caller holds (the same kernel): targets_in, targets_out
+ * [batch][n_rows][n_frames] int32 on the host, a target indexes the frame axis itself, -1: none.  n_iter 1 .. 64,
+ * reach >= 1, n_iter reach <= 16384; a target outside -1 .. n_frames - 1 or farther than `reach` from its own frame is
+ * refused on the host.  Synchronous. */
+int ssq_tmsst_walk_host(const int32_t* targets_in, int64_t batch, int64_t n_rows, int64_t n_frames, int n_iter, int64_t reach,
+                        int32_t* targets_out);
+/* Target frames of the tile one workgroup of the walk kernel (and of the scatter) owns for one-step targets within `reach`
+ * frames walked n_iter steps (1024 .. 4096; host only), -1 where ssq_tmsst_walk_host refuses the pair. */
+int ssq_tmsst_tile_frames(int64_t reach, int n_iter);
 /* Reassigned spectrogram, `upstream.reassign_stft` (csrc/stft_reassign.hip; Kodera et al. 1978; Auger and
  * Flandrin 1995; upstream has no such transform): every bin's energy |Sx|^2 moves along frequency AND time at once, to
  * its instantaneous frequency and its group delay (first order only).  window [n_fft] already sized, padtype SSQ_PAD_*,

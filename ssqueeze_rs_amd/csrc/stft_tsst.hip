@@ -23,6 +23,8 @@
 //                          The owner adds them with a compensated (Neumaier) fp64 sum.  Every cell is therefore the sum of
 //                          its contributions in ascending source frame whatever the tiling or the batch, no atomics,
 //                          and every cell of Tx is written exactly once (no clear of Tx).
+// The two halves (tsst_operator_run, tsst_scatter_run) are lent to stft_tmsst.hip through stft_tsst.h, which
+// runs the scatter's other instantiations: a reach of several windows, trimmed to what a workgroup's map really moves.
 #include <cmath>
 #include <vector>
 
@@ -30,42 +32,11 @@
 #include "dev_buffers.h"
 #include "sst_tables.h"
 #include "stft_frames64.h"
+#include "stft_tsst.h"
 
 namespace ssq {
 
-constexpr int kTsstThreads = 256;          // the scatter kernel's workgroup
-constexpr int kTsstNone = -32768;          // the relative target of a bin that is not kept
-constexpr int kTsstMaxReach = 2048;        // H at n_fft = 4096, hop 1
-constexpr int kTsstMaxTile = 4096;         // target frames of one scatter workgroup
-constexpr int kTsstStage = kTsstMaxTile + 2 * kTsstMaxReach;
-
-// O: the dtype of the call (float or double: x in, Sx / tau / Tx out).  The transforms and the operator always run in
-// fp64, on the widened signal, as in stft_sst2.hip.
-// What the operator kernel needs only when it stores a tile.  It lives in device memory and is read there, behind an
-// opaque offset: as kernel arguments these would sit in scalar registers across the transforms, which are at the limit.
-template <typename O>
-struct TsstOut {
-  cpx<O>* Sx;              // [batch][F][n_frames]
-  O* tau;                  // [batch][F][n_frames], or nullptr
-  short* rel;              // [batch][F][n_frames]  m' - m, or kTsstNone
-  double fs;
-  O step;                  // hop / fs in the call's dtype: the target rule runs on the tau the call reports
-};
-
-template <typename O>
-struct TsstDev {
-  const double* x;         // [batch][n_signal], widened (widen_f64) for a float32 call
-  const cpx<double>* tw;   // the passes' twiddle tables, passes 1, 2, .. back to back
-  const cpx<double>* wa;   // order 2: (g, g1 a1); order 1: (g, tg at)      a*: powers of two that level the channels
-  const double* wb;        // order 2: tg at
-  const cpx<double>* wc;   // order 2: (tg1 at1, g2 a2)
-  const TsstOut<O>* out;
-  long long n_signal, n_frames;
-  int hop, padtype, rot, tile_frames, b0;   // b0: the signal of blockIdx.y = 0
-  double gamma, gamma_sq;
-  double h1, it, ht1, h2;  // 0.5 / a1, 1 / at (order 1: 0.5 / at), 0.5 / at1, 0.5 / a2
-};
-
+// (the constants and the parameter blocks TsstOut, TsstDev, TsstScat: stft_tsst.h, shared with stft_tmsst.hip)
 // first order: the group-delay offset Re(Vt / V) in samples, or +inf where the bin is not kept
 template <typename O>
 __device__ __forceinline__ double tsst_operator1(const TsstDev<O>& p, double half, cpx<double> V, cpx<double> Vt) {
@@ -237,16 +208,6 @@ __global__ __launch_bounds__(kFrameThreads) void tsst_operator_kernel(const Tsst
   }
 }
 
-template <typename O>
-struct TsstScat {
-  const cpx<O>* Sx;        // [batch][F][n_frames]
-  const short* rel;        // [batch][F][n_frames]
-  const cpx<double>* rot;  // [n]  exp(-2 pi i j / n)
-  cpx<O>* Tx;              // [batch][F][n_frames]
-  long long n_frames;
-  int n_freqs, n, hop, reach, tile;    // reach = H <= kTsstMaxReach; tile <= kTsstMaxTile, a multiple of 256
-};
-
 __device__ __forceinline__ void tsst_neumaier(double& s, double& c, double x) {
   const double t = s + x;
   c += fabs(s) >= fabs(x) ? (s - t) + x : (x - t) + s;
@@ -258,9 +219,14 @@ __device__ __forceinline__ double tsst_readlane(double v, int j) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
 }
 
-template <typename O>
+// STAGE: the int16 targets a workgroup stages, tile + 2 reach at the most (kTsstStage: tssq_stft's one-window reach;
+// kTsstWideStage: a walked map's, stft_tmsst.hip).  TRIM: the workgroup walks only the sources within the largest
+// |target| it staged -- a source farther from a cell than that cannot hit it, and the hits of a cell still arrive in
+// ascending source frame, so every cell is the same sum; what a map that moves little saves is the walk over a reach of
+// several windows.  tssq_stft runs <kTsstStage, false>, the kernel as it was.
+template <typename O, int STAGE, bool TRIM>
 __global__ __launch_bounds__(kTsstThreads) void tsst_scatter_kernel(const TsstScat<O> p) {
-  __shared__ short rel_s[kTsstStage];
+  __shared__ short rel_s[STAGE];
   __shared__ int slot_s[kTsstThreads];
   const long long nfr = p.n_frames;
   const int k = blockIdx.y;
@@ -270,13 +236,33 @@ __global__ __launch_bounds__(kTsstThreads) void tsst_scatter_kernel(const TsstSc
   const long long s0 = t0 - p.reach > 0 ? t0 - p.reach : 0;              // the sources [s0, s1) can reach them
   const long long s1 = t1 + p.reach < nfr ? t1 + p.reach : nfr;
   const int tid = threadIdx.x;
-  for (int i = tid; i < (int)(s1 - s0); i += kTsstThreads) rel_s[i] = p.rel[base + s0 + i];
-  __syncthreads();
+  int far = 0;                                                             // TRIM: the largest |target| staged
+  for (int i = tid; i < (int)(s1 - s0); i += kTsstThreads) {
+    const short r = p.rel[base + s0 + i];
+    rel_s[i] = r;
+    if constexpr (TRIM) {
+      const int a = r < 0 ? -(int)r : (int)r;
+      if (r != kTsstNone && a > far) far = a;
+    }
+  }
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  int reach = p.reach;
+  if constexpr (TRIM) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      const int o = __shfl_xor(far, d);
+      far = o > far ? o : far;
+    }
+    if (lane == 0) slot_s[wave] = far;
+    __syncthreads();
+    for (int w = 0; w < kTsstThreads / 64; ++w) far = slot_s[w] > far ? slot_s[w] : far;
+    reach = __builtin_amdgcn_readfirstlane(far < reach ? far : reach);
+  }
+  __syncthreads();                                                         // (TRIM: slot_s is the waves' own from here on)
   volatile int* slot = slot_s + 64 * wave;                                // the wave's own 64 slots: no workgroup barrier
   for (long long g0 = t0 + 64 * wave; g0 < t1; g0 += kTsstThreads) {     // the wave's 64 cells, one per lane
     double sr = 0, si = 0, cr = 0, ci = 0;
-    for (long long c0 = g0 - p.reach; c0 <= g0 + 63 + p.reach; c0 += 64) {   // 64 sources a step, ascending
+    for (long long c0 = g0 - reach; c0 <= g0 + 63 + reach; c0 += 64) {   // 64 sources a step, ascending
       const long long m = c0 + lane;
       int r = kTsstNone;
       if (m >= s0 && m < s1) r = rel_s[m - s0];
@@ -342,24 +328,12 @@ static hipError_t tsst_launch(TsstDev<T> p, int logn, int order, long long batch
   });
 }
 
-}  // namespace ssq
-
-using namespace ssq;
-
-namespace {
-
-struct TsstShape : FrameShape {
-  int order = 2, tile = 1024;
-};
-
-// The argument checks of the three entry points, and the shape they work on (sets the error and returns non-zero)
-int tsst_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop, double fs, int padtype, int order,
-               double gamma, TsstShape* s) {
-  if (int rc = frame_shape("tssq_stft", true, order == 1 || order == 2 ? nullptr : "order must be 1 or 2", dtype, batch,
-                           n_signal, n_fft, hop, fs, padtype, gamma, s))
-    return rc;
+// The argument checks of the entry points, and the shape they work on (sets the error and returns non-zero)
+int tsst_shape(const char* name, const char* own_fail, int dtype, int64_t batch, int64_t n_signal, int64_t n_fft,
+               int64_t hop, double fs, int padtype, int order, double gamma, TsstShape* s) {
+  if (int rc = frame_shape(name, true, own_fail, dtype, batch, n_signal, n_fft, hop, fs, padtype, gamma, s)) return rc;
   s->order = order;
-  s->tile = 2 * s->reach < 1024 ? 1024 : (2 * s->reach + 255) / 256 * 256;   // halo re-read (tile + 2 H) / tile <= 2
+  s->tile = tsst_tile(s->reach);                             // halo re-read (tile + 2 H) / tile <= 2
   return 0;
 }
 
@@ -422,11 +396,9 @@ int tsst_out_block(DeviceBufs& d, const TsstShape& s, int64_t hop, void* d_Sx, v
   return 0;
 }
 
-// both kernels of `nb` signals on device buffers; ev (may be nullptr): an event recorded between the two
 template <typename T>
-hipError_t tsst_run(TsstDev<T> p, TsstScat<T> sc, const TsstShape& s, const T* d_x, int64_t nb, cpx<T>* d_Tx, cpx<T>* d_Sx,
-                    short* d_rel, double* d_xd /* float32 calls: [nb][n_signal] */, hipEvent_t ev) {
-  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
+hipError_t tsst_operator_run(TsstDev<T> p, const TsstShape& s, const T* d_x, int64_t nb,
+                             double* d_xd /* float32 calls: [nb][n_signal] */) {
   hipError_t e;
   const double* xd;
   if constexpr (sizeof(T) == 4) {
@@ -441,18 +413,62 @@ hipError_t tsst_run(TsstDev<T> p, TsstScat<T> sc, const TsstShape& s, const T* d
     p.b0 = (int)b0;
     if ((e = tsst_launch<T>(p, s.logn, s.order, n1, nullptr)) != hipSuccess) return e;
   }
-  if (ev && (e = hipEventRecord(ev, nullptr)) != hipSuccess) return e;
-  const long long tiles = (s.n_frames + s.tile - 1) / s.tile;
+  return hipSuccess;
+}
+
+template <typename T>
+hipError_t tsst_scatter_run(TsstScat<T> sc, const TsstShape& s, int64_t nb, const cpx<T>* d_Sx, const short* d_rel,
+                            cpx<T>* d_Tx, bool trim) {
+  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
+  const long long tiles = (s.n_frames + sc.tile - 1) / sc.tile;
+  const long long stage = (long long)sc.tile + 2LL * sc.reach;
+  if (sc.reach < 1 || sc.tile < 256 || sc.tile % 256 || sc.tile > kTsstMaxTile || stage > kTsstWideStage ||
+      (!trim && stage > kTsstStage))
+    return hipErrorInvalidValue;
   for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
     const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
     sc.Sx = d_Sx + map_sig * b0;
     sc.rel = d_rel + map_sig * b0;
     sc.Tx = d_Tx + map_sig * b0;
-    hipLaunchKernelGGL(tsst_scatter_kernel<T>, dim3((unsigned)tiles, (unsigned)s.n_freqs, (unsigned)n1), dim3(kTsstThreads), 0,
-                       nullptr, sc);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const dim3 grid((unsigned)tiles, (unsigned)s.n_freqs, (unsigned)n1);
+    if (!trim)
+      hipLaunchKernelGGL((tsst_scatter_kernel<T, kTsstStage, false>), grid, dim3(kTsstThreads), 0, nullptr, sc);
+    else if (stage <= kTsstStage)
+      hipLaunchKernelGGL((tsst_scatter_kernel<T, kTsstStage, true>), grid, dim3(kTsstThreads), 0, nullptr, sc);
+    else
+      hipLaunchKernelGGL((tsst_scatter_kernel<T, kTsstWideStage, true>), grid, dim3(kTsstThreads), 0, nullptr, sc);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+#define SSQ_TSST_INSTANTIATE(T)                                                                                          \
+  template int tsst_tables<T>(DeviceBufs&, const TsstShape&, const double*, int64_t, int64_t, int64_t, int, int,        \
+                              TsstDev<T>*, TsstScat<T>*);                                                                \
+  template int tsst_out_block<T>(DeviceBufs&, const TsstShape&, int64_t, void*, void*, void*, TsstDev<T>*);             \
+  template hipError_t tsst_operator_run<T>(TsstDev<T>, const TsstShape&, const T*, int64_t, double*);                    \
+  template hipError_t tsst_scatter_run<T>(TsstScat<T>, const TsstShape&, int64_t, const cpx<T>*, const short*, cpx<T>*,  \
+                                          bool);
+SSQ_TSST_INSTANTIATE(float)
+SSQ_TSST_INSTANTIATE(double)
+#undef SSQ_TSST_INSTANTIATE
+
+}  // namespace ssq
+
+using namespace ssq;
+
+namespace {
+
+const char* tsst_own_fail(int order) { return order == 1 || order == 2 ? nullptr : "order must be 1 or 2"; }
+
+// both kernels of `nb` signals on device buffers; ev (may be nullptr): an event recorded between the two
+template <typename T>
+hipError_t tsst_run(TsstDev<T> p, TsstScat<T> sc, const TsstShape& s, const T* d_x, int64_t nb, cpx<T>* d_Tx, cpx<T>* d_Sx,
+                    short* d_rel, double* d_xd /* float32 calls: [nb][n_signal] */, hipEvent_t ev) {
+  hipError_t e = tsst_operator_run<T>(p, s, d_x, nb, d_xd);
+  if (e != hipSuccess) return e;
+  if (ev && (e = hipEventRecord(ev, nullptr)) != hipSuccess) return e;
+  return tsst_scatter_run<T>(sc, s, nb, d_Sx, d_rel, d_Tx, false);
 }
 
 template <typename T>
@@ -512,7 +528,9 @@ int ssq_tssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal
                        void* tau) {
   if (!x || !window || !Tx || !Sx) SSQ_FAIL("NULL argument");
   TsstShape s;
-  if (int rc = tsst_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, order, gamma, &s)) return rc;
+  if (int rc = tsst_shape("tssq_stft", tsst_own_fail(order), dtype, batch, n_signal, n_fft, hop, fs, padtype, order, gamma,
+                          &s))
+    return rc;
   if (int rc = require_device()) return rc;
   return dtype == SSQ_F32 ? tsst_host_typed<float>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, Tx, Sx, tau)
                           : tsst_host_typed<double>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, Tx, Sx, tau);
@@ -520,7 +538,7 @@ int ssq_tssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal
 
 int64_t ssq_tssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop) {
   TsstShape s;
-  if (tsst_shape(dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, 2, -1.0, &s)) return -1;
+  if (tsst_shape("tssq_stft", nullptr, dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, 2, -1.0, &s)) return -1;
   return (dtype == SSQ_F32 ? 8 * batch * n_signal : 0) + 2 * batch * s.n_freqs * s.n_frames;
 }
 
@@ -529,7 +547,9 @@ int ssq_tssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_sign
                        void* d_tau, void* d_workspace, int64_t workspace_bytes, float* kernel_ms) {
   if (!d_x || !window || !d_Tx || !d_Sx || !d_workspace) SSQ_FAIL("NULL argument");
   TsstShape s;
-  if (int rc = tsst_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, order, gamma, &s)) return rc;
+  if (int rc = tsst_shape("tssq_stft", tsst_own_fail(order), dtype, batch, n_signal, n_fft, hop, fs, padtype, order, gamma,
+                          &s))
+    return rc;
   if (workspace_bytes < ssq_tssq_stft_workspace_bytes(dtype, batch, n_signal, n_fft, hop))
     SSQ_FAIL("tssq_stft: workspace smaller than ssq_tssq_stft_workspace_bytes");
   if (int rc = require_device()) return rc;

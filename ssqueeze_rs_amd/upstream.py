@@ -49,6 +49,11 @@ Supported subset (anything else raises ValueError naming the option):
     concentrates impulses and fast chirps; the conventions of `ssq_stft2` (ndarray window, the five padtypes,
     `modulated`, batches, a power-of-two `n_fft` from 16 to 4096); no inverse (its row sums give the spectrum at n_fft
     points only);
+  * `tmssq_stft`: the time-reassigned multisynchrosqueezed STFT (Yu, Lin, Ma and He 2020; orders 1 and 2), which upstream
+    does not have (the definition is this project's: DESIGN 4.21, csrc/stft_tmsst.hip): `tssq_stft`'s time map asked
+    again at the frame a coefficient landed on, `n_iter` steps in all (1 .. 64, with n_iter ceil(n_fft / (2 hop_len)) <=
+    16384), which narrows the ridge of an impulsive or dispersive signal whose group delay is not linear inside the
+    window; the conventions of `tssq_stft`; no inverse; `tmsst_walk` runs the walk alone on an int32 map the caller holds;
   * `reassign_stft`: the reassigned spectrogram (Kodera et al.; Auger and Flandrin 1995), which upstream does not have
     (the definition is this project's: DESIGN 4.14, csrc/stft_reassign.hip): every bin's energy |Sx|^2 moves along
     frequency and time at once, to its instantaneous frequency and group delay (first order); the conventions of
@@ -614,6 +619,102 @@ def tssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=No
     _call(lib.ssq_tssq_stft_host(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs, pad, order,
                                  _gamma_arg(gamma), _variant(modulated), _ptr(Tx), _ptr(Sx), _ptr(tau)))
     return (*_unbatch(f.batched, Tx, Sx), _times(f, hop_len), _Sfs(f), *_unbatch(f.batched, tau))
+
+
+TMSST_MAX_REACH = 16384                 # csrc/stft_tsst.h: kTsstWideReach, the farthest a walked coefficient may land
+
+
+def _tmsst_reach(n_iter, reach, what):
+    if n_iter * reach > TMSST_MAX_REACH:
+        raise ValueError(f"{what}: n_iter * reach = {n_iter} * {reach} exceeds {TMSST_MAX_REACH} (the final relative "
+                         "target is an int16, and a tile of targets with both halos is staged in LDS)")
+
+
+def tmssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
+               order=2, gamma=None, n_iter=4, get_tau=False, get_targets=False):
+    """Time-reassigned multisynchrosqueezed STFT -> (Tx, Sx, times, Sfs[, tau][, targets]); not in upstream (Yu, Lin, Ma
+    and He 2020), conventions of `tssq_stft`.  Where `tssq_stft` applies its time map once, this asks the map again at the
+    frame a coefficient landed on, `n_iter` steps in all: on an impulsive or dispersive signal whose group delay is not
+    linear inside the window the one-step estimate taken off the ridge is biased, and the estimate taken where it points
+    is closer.  It is the dual of `mssq_stft`.
+
+    Everything up to the one-step target is `tssq_stft`'s: the five windows, d1, d2 and the fallback, the clamp to
+    +- n_fft / 2, `tau` in the call's dtype (+inf where |V| <= gamma), r = rint(tau / (hop_len / fs)), and for a kept bin
+    t[k, m] = clip(m + r, 0, n_frames - 1).  Then, per row k, with H = ceil(n_fft / (2 hop_len)):
+        c1[m] = t[m]
+        c(i+1)[m] = t[ci[m]]  if bin (k, ci[m]) is kept,  else ci[m]                    (i = 1 .. n_iter - 1)
+        Tx[k, c_n[m]] += Sx[k, m] exp(-2 pi i ((k (m - c_n[m]) hop_len) mod n_fft) / n_fft)     kept m, ascending source frame
+    A chain stops on a frame whose bin in that row is not kept and on a fixed point; a cycle keeps turning until `n_iter`
+    runs out.  The rotation takes the total displacement, so the per-row marginal identity of `tssq_stft` holds as it
+    does there.  Every cell is the compensated fp64 sum of its contributions in ascending source frame, rounded once: no
+    atomics, bitwise independent of the batch and of the tiling.  `n_iter=1` is `tssq_stft` bit for bit.  There is no
+    inverse.
+
+    `Sx` equals `stft(x, ...)`; `tau` (get_tau=True) is the ONE-step map, +inf where a bin is not kept; `targets`
+    (get_targets=True) is int32: the frame of `Tx` each coefficient went to, -1 where it was not kept.  `tmsst_walk` runs
+    the walk alone on a map the caller holds.
+
+    `n_fft` must be a power of two from 16 to 4096, `order` 1 or 2, `n_iter` an int from 1 to 64, and n_iter H <= 16384
+    (|c_n[m] - m| <= n_iter H: the final relative target is an int16, and a tile of targets with both halos is staged in
+    LDS; n_fft 4096 at hop 1 allows n_iter <= 8); ValueError otherwise, before any GPU work.  The walk and both scatter
+    stages are built without register spills or scratch (profiles/tmsst_resources.txt)."""
+    lib = _lib.load()
+    order = _order12(order, "tmssq_stft builds orders 1 and 2")
+    n_iter = _n_iter(n_iter)
+    f = _stft_front(x, window, n_fft, win_len, hop_len, fs, t, "tmssq_stft")
+    if gamma is not None and math.isnan(float(gamma)):
+        raise ValueError("gamma is NaN")
+    pad = _pad_code(padtype)
+    if isinstance(hop_len, (int, np.integer)) and hop_len >= 1:
+        _tmsst_reach(n_iter, (f.n_fft // 2 - 1) // int(hop_len) + 1, "tmssq_stft")
+    _lib.require_gpu()
+    shape = _stft_shape(f, hop_len)
+    Tx, Sx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    tau = _lib.pinned_empty(shape, f.rdt) if get_tau else None
+    targets = _lib.pinned_empty(shape, np.int32) if get_targets else None
+    _call(lib.ssq_tmssq_stft_host(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs, pad, order,
+                                  _gamma_arg(gamma), _variant(modulated), n_iter, _ptr(Tx), _ptr(Sx), _ptr(tau),
+                                  _ptr(targets)))
+    return (*_unbatch(f.batched, Tx, Sx), _times(f, hop_len), _Sfs(f), *_unbatch(f.batched, tau, targets))
+
+
+def tmsst_walk(targets, n_iter, reach):
+    """The walk of `tmssq_stft` alone, on a map the caller holds -> int32, same shape.  `targets`: int32 [F, n] or
+    [B, F, n], a target indexes the frame axis itself and -1 means none; per row
+        c1[m] = targets[m];   c(i+1)[m] = targets[ci[m]] if targets[ci[m]] >= 0, else ci[m]        (i = 1 .. n_iter - 1)
+    and the result is c_n (-1 where targets[m] is).  `reach`: how far a target may lie from its own frame (the H of
+    `tmssq_stft`).  Runs the kernel of `tmssq_stft` (csrc/stft_tmsst.hip); a non-int32 array, a kept target outside
+    0 .. n - 1 or farther than `reach` from its frame, `reach < 1`, n_iter * reach > 16384 and an `n_iter` that is not an
+    int from 1 to 64 raise ValueError before any GPU work."""
+    lib = _lib.load()
+    n_iter = _n_iter(n_iter)
+    if not isinstance(reach, (int, np.integer)) or isinstance(reach, (bool, np.bool_)) or reach < 1:
+        raise ValueError(f"reach {reach!r}: an int >= 1")
+    _tmsst_reach(n_iter, int(reach), "tmsst_walk")
+    if not isinstance(targets, np.ndarray) or targets.dtype != np.int32 or targets.ndim not in (2, 3):
+        raise ValueError("`targets` must be an int32 ndarray [F, n] or [B, F, n]")
+    t3 = np.ascontiguousarray(targets if targets.ndim == 3 else targets[None])
+    B, F, n = t3.shape
+    if B < 1 or F < 1 or n < 1:
+        raise ValueError(f"`targets` of shape {targets.shape}: no empty axis")
+    if t3.min() < -1 or t3.max() >= n:
+        raise ValueError(f"`targets` holds targets outside -1 .. n - 1 = {n - 1}")
+    if (np.abs(t3.astype(np.int64) - np.arange(n)) > reach)[t3 >= 0].any():
+        raise ValueError(f"`targets` holds a target farther than reach = {reach} from its own frame")
+    _lib.require_gpu()
+    out = np.empty_like(t3)
+    _call(lib.ssq_tmsst_walk_host(_ptr(t3), B, F, n, n_iter, int(reach), _ptr(out)))
+    return _unbatch(targets.ndim == 3, out)[0]
+
+
+def tmsst_tile_frames(reach, n_iter):
+    """Target frames of the tile one workgroup of the walk kernel owns for one-step targets within `reach` frames walked
+    `n_iter` steps (no GPU needed)."""
+    c = _lib.load().ssq_tmsst_tile_frames(int(reach), int(n_iter))
+    if c < 0:
+        raise ValueError(f"reach {reach!r}, n_iter {n_iter!r}: reach >= 1, n_iter 1 .. {MSST_MAX_ITER}, "
+                         f"n_iter * reach <= {TMSST_MAX_REACH}")
+    return int(c)
 
 
 # csrc/stft_reassign.hip: kReassignQuantumLog2.  `reassign_stft` accumulates |Sx|^2 in 64-bit fixed point with the quantum
