@@ -57,10 +57,28 @@ __device__ __forceinline__ void rows_transpose4(float& r0, float& r1, float& r2,
   r3 = __uint_as_float(d[1]);
 }
 
+// window multiply of a frame's prefetched samples (lane t holds x[t + 64 q]) and pass 0 of its FFT.  The multiply is the
+// first use of xn[], so the vmcnt waits for the prefetch sit here; and it stays in ONE basic block with pass 0's first
+// butterflies, because the compiler contracts the two (fma(x[q], w[q], x[q + 8] w[q + 8])): apart, the bits change.
+__device__ __forceinline__ void tx1024_window_pass0(const cpx<float>* win_lds, int t, const float (&xn)[16],
+                                                    const cpx<float> (&twr_unused)[3][16], cpx<float> (&v)[16]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    cpx<float> w0, w1;
+    lds_pair(win_lds + tx1024::win_row(t, j), w0, w1);
+    v[2 * j] = {xn[2 * j] * w0.x, xn[2 * j] * w0.y};
+    v[2 * j + 1] = {xn[2 * j + 1] * w1.x, xn[2 * j + 1] * w1.y};
+  }
+  fft_compute<float, 10, 0, false, false>(v, twr_unused, nullptr, t);
+}
+
 // (Measured and removed in round 2: replacing the two tile barriers by arrival counters in LDS, with the read-out of
 // tile i-1 placed inside tile i's FFT or at the loop top, ran 10-14 % SLOWER -- profiles/r02_ab_freerun.txt.)
-template <bool EDGE, bool LEB, bool WKDBG = false>
+// PAIRED picks the tile read-out at COMPILE time (see read_out): the host passes it for the interior Tx launch with
+// even n_frames (launch_one).
+template <bool EDGE, bool LEB, bool WKDBG = false, bool PAIRED = false>
 __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) {
+  static_assert(!PAIRED || (!EDGE && !WKDBG), "the paired read-out has no frame guard and no (w, k) form");
   using H = Hi1024;
   constexpr int THREADS = H::THREADS;
   using T = float;
@@ -122,44 +140,51 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
   load_frame(sig, tile_frame0(jt), xn);
   const cpx<T> twr_unused[3][16] = {};
 
-  // ---- tile read-out: thread -> (frame f, rows k0 + 64 j); re-zeroes what it reads ----
+  // ---- tile read-out: re-zeroes what it reads ----
+  // EXACTLY ONE store sequence per instantiation, chosen by PAIRED and never by a run-time test of n_frames.  With both
+  // sequences behind a test the loop body has a path from one tile barrier to the next that passes through neither, and
+  // the compiler's wait counts must assume the fewest operations behind the prefetched samples: no store at all.  The
+  // window multiply at the loop top then waits vmcnt(7..0) for xn[] -- loads and stores share that one in-order counter
+  // -- and with it for every Tx store of the tile just read out, once per tile, all 16 waves at the same point.  With
+  // one unguarded sequence (and the waits behind it, see PASS0_AT_END) they read vmcnt(>= number of stores) and the
+  // stores stay in flight under the next tile's window multiply, pass 0 and exchange 1
+  // (tests/test_tx1024_isa_waits.py holds this).  Do not fold the test of n_frames back in.
   auto read_out = [&](long long rsig, int rframe0) {
-    if constexpr (!EDGE && !WKDBG) {
+    if constexpr (PAIRED) {
       // thread -> (frame pair fp, rows k0 + 128 j): two adjacent cells per thread, ONE 16-byte store per row
       // (half as many store instructions; T21 of the programming guide).  Needs even n_frames for the alignment.
-      if ((p.n_frames & 1) == 0) {
-        constexpr int RS2 = THREADS / (F / 2);              // 128 rows per sweep
-        const int fp = tid % (F / 2);
-        const int k0 = tid / (F / 2);
-        float4* __restrict__ og4 = reinterpret_cast<float4*>(p.out + rsig * (long long)NF * p.n_frames + rframe0 + 2 * fp +
-                                                             (long long)k0 * p.n_frames);
-        const long long gstep4 = (long long)RS2 * p.n_frames / 2;     // in float4 units
-        // (round 3: a wave-uniform base + 32-bit per-thread offset does not make the compiler take the SGPR-base store form --
-        //  loop strength reduction rebuilds the 64-bit vector address chain either way.  A raw buffer store through a
-        //  per-signal descriptor does take it -- 10 vector instructions per sweep, no address arithmetic -- and so does a
-        //  64-bit LDS exchange in place of the read + CELL0 store (one ds_wrxchg_rtn_b64 per cell); on top of the short
-        //  Nyquist pass neither pays: +0.4 ... +0.7 % and +-0, profiles/readout_ab_parts.txt)
-        const T sc0 = col_scale[2 * fp], sc1 = col_scale[2 * fp + 1];
-        long long* tc = reinterpret_cast<long long*>(tile_re) + k0 * PITCH + 2 * fp;
-        auto sweep2 = [&](int j) {
-          const long long c0 = tc[j * RS2 * PITCH], c1 = tc[j * RS2 * PITCH + 1];
-          tc[j * RS2 * PITCH] = CELL0;
-          tc[j * RS2 * PITCH + 1] = CELL0;
-          const int r0 = (int)c0 ^ (int)0x80000000, r1 = (int)c1 ^ (int)0x80000000;
-          const int i0 = (int)(c0 >> 32), i1 = (int)(c1 >> 32);
-          const float4 val = make_float4((T)r0 * sc0, (T)i0 * sc0, (T)r1 * sc1, (T)i1 * sc1);
-          // nontemporal: Tx is written once, never read back here (-0.7 % on the bench shape, profiles/r02_ab_nt.txt)
-          typedef float vf4 __attribute__((ext_vector_type(4)));
-          const vf4 nv = {val.x, val.y, val.z, val.w};
-          __builtin_nontemporal_store(nv, reinterpret_cast<vf4*>(&og4[j * gstep4]));
-        };
-        constexpr int NFULL2 = NF / RS2;                      // 4 full sweeps
+      constexpr int RS2 = THREADS / (F / 2);              // 128 rows per sweep
+      const int fp = tid % (F / 2);
+      const int k0 = tid / (F / 2);
+      float4* __restrict__ og4 = reinterpret_cast<float4*>(p.out + rsig * (long long)NF * p.n_frames + rframe0 + 2 * fp +
+                                                           (long long)k0 * p.n_frames);
+      const long long gstep4 = (long long)RS2 * p.n_frames / 2;     // in float4 units
+      // (round 3: a wave-uniform base + 32-bit per-thread offset does not make the compiler take the SGPR-base store form --
+      //  loop strength reduction rebuilds the 64-bit vector address chain either way.  A raw buffer store through a
+      //  per-signal descriptor does take it -- 10 vector instructions per sweep, no address arithmetic -- and so does a
+      //  64-bit LDS exchange in place of the read + CELL0 store (one ds_wrxchg_rtn_b64 per cell); on top of the short
+      //  Nyquist pass neither pays: +0.4 ... +0.7 % and +-0, profiles/readout_ab_parts.txt)
+      const T sc0 = col_scale[2 * fp], sc1 = col_scale[2 * fp + 1];
+      long long* tc = reinterpret_cast<long long*>(tile_re) + k0 * PITCH + 2 * fp;
+      auto sweep2 = [&](int j) {
+        const long long c0 = tc[j * RS2 * PITCH], c1 = tc[j * RS2 * PITCH + 1];
+        tc[j * RS2 * PITCH] = CELL0;
+        tc[j * RS2 * PITCH + 1] = CELL0;
+        const int r0 = (int)c0 ^ (int)0x80000000, r1 = (int)c1 ^ (int)0x80000000;
+        const int i0 = (int)(c0 >> 32), i1 = (int)(c1 >> 32);
+        const float4 val = make_float4((T)r0 * sc0, (T)i0 * sc0, (T)r1 * sc1, (T)i1 * sc1);
+        // nontemporal: Tx is written once, never read back here (-0.7 % on the bench shape, profiles/r02_ab_nt.txt)
+        typedef float vf4 __attribute__((ext_vector_type(4)));
+        const vf4 nv = {val.x, val.y, val.z, val.w};
+        __builtin_nontemporal_store(nv, reinterpret_cast<vf4*>(&og4[j * gstep4]));
+      };
+      constexpr int NFULL2 = NF / RS2;                      // 4 full sweeps
 #pragma unroll
-        for (int j = 0; j < NFULL2; ++j) sweep2(j);
-        if (k0 + NFULL2 * RS2 < NF) sweep2(NFULL2);
-        return;
-      }
+      for (int j = 0; j < NFULL2; ++j) sweep2(j);
+      if (k0 + NFULL2 * RS2 < NF) sweep2(NFULL2);
+      return;
     }
+    // thread -> (frame f, rows k0 + 64 j)
     constexpr int RSTEP = THREADS / F;                    // 64 rows per sweep
     const int f = tid % F;
     const int k0 = tid / F;
@@ -186,6 +211,15 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
   };
 
   const int grid_n = (int)gridDim.x;          // (read once: inside the loop it is a scalar load + wait per tile)
+  // The interior instantiations take the window multiply and pass 0 of the block's FIRST tile ahead of the loop and
+  // those of every later tile at the loop's end, behind the read-out -- the same instruction order tile after tile.
+  // At the loop top the waits for xn[] would also be reached from the block's first sample load, which has no store
+  // behind it, and the wait counts take the fewest: vmcnt(7..0) again, the drain read_out's comment speaks of.  At the
+  // loop's end the only way in is through the read-out's stores.
+  // (The edge kernel's stores are guarded per frame and make their own store-free path; it keeps the plain loop.)
+  constexpr bool PASS0_AT_END = !EDGE && !WKDBG;
+  cpx<T> vw[16];                              // (dead in the plain loop)
+  if constexpr (PASS0_AT_END) tx1024_window_pass0(win_lds, t, xn, twr_unused, vw);
 #pragma unroll 1
   while (true) {
     const int frame0 = tile_frame0(jt);
@@ -199,16 +233,22 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
     }
     const bool has_next = nsig < n_sig;
     cpx<T> v[16];
+    if constexpr (PASS0_AT_END) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      cpx<T> w0, w1;
-      lds_pair(win_lds + X::win_row(t, j), w0, w1);
-      v[2 * j] = {xn[2 * j] * w0.x, xn[2 * j] * w0.y};
-      v[2 * j + 1] = {xn[2 * j + 1] * w1.x, xn[2 * j + 1] * w1.y};
+      for (int q = 0; q < 16; ++q) v[q] = vw[q];
+    } else {
+      // (tx1024_window_pass0 written out: through the call the compiler schedules the edge kernel's sample loads
+      //  differently, and this change leaves that kernel's code as it was)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        cpx<T> w0, w1;
+        lds_pair(win_lds + X::win_row(t, j), w0, w1);
+        v[2 * j] = {xn[2 * j] * w0.x, xn[2 * j] * w0.y};
+        v[2 * j + 1] = {xn[2 * j + 1] * w1.x, xn[2 * j + 1] * w1.y};
+      }
+      // ---- pass 0: radix 16 over elements t + 64q ----
+      fft_compute<T, 10, 0, false, false>(v, twr_unused, nullptr, t);
     }
-
-    // ---- pass 0: radix 16 over elements t + 64q ----
-    fft_compute<T, 10, 0, false, false>(v, twr_unused, nullptr, t);
     // ---- exchange 1 by REGISTER halves: in phase ph EVERY lane writes its values u = 8 ph .. 8 ph + 7 (elements
     //      16 t + u) -- full-width stores -- and the lanes whose element residue (t & 15) lies in that half read all 16
     //      of their elements t + 64 q = 16 ((t >> 4) + 4 q) + (t & 15).
@@ -416,6 +456,7 @@ __global__ __launch_bounds__(1024, 1) void stft_tx1024_kernel(StftDev<float> p) 
     if (!has_next) break;
     sig = nsig;
     jt = njt;
+    if constexpr (PASS0_AT_END) tx1024_window_pass0(win_lds, t, xn, twr_unused, vw);
   }
 }
 
@@ -504,14 +545,18 @@ static hipError_t launch_one(const StftDev<T>& p0, int cu_count, long long batch
     if constexpr (sizeof(T) == 4 && LOGN == 10) {
       if (tx1024) {
         const dim3 gh((unsigned)l.blocks), bh(Hi1024::THREADS);
+        // the 16-byte paired read-out needs even n_frames (alignment); the edge and (w, k) kernels stay per-frame
+        const bool paired = !edge && p.out_kind == 0 && (p.n_frames & 1) == 0;
         if (p.out_kind == 3) {
           if (edge) hipLaunchKernelGGL((stft_tx1024_kernel<true, false, true>), gh, bh, 0, stream, p);
           else hipLaunchKernelGGL((stft_tx1024_kernel<false, false, true>), gh, bh, 0, stream, p);
         } else if (p.squeezing == 1) {
           if (edge) hipLaunchKernelGGL((stft_tx1024_kernel<true, true>), gh, bh, 0, stream, p);
+          else if (paired) hipLaunchKernelGGL((stft_tx1024_kernel<false, true, false, true>), gh, bh, 0, stream, p);
           else hipLaunchKernelGGL((stft_tx1024_kernel<false, true>), gh, bh, 0, stream, p);
         } else {
           if (edge) hipLaunchKernelGGL((stft_tx1024_kernel<true, false>), gh, bh, 0, stream, p);
+          else if (paired) hipLaunchKernelGGL((stft_tx1024_kernel<false, false, false, true>), gh, bh, 0, stream, p);
           else hipLaunchKernelGGL((stft_tx1024_kernel<false, false>), gh, bh, 0, stream, p);
         }
         const hipError_t eh = hipGetLastError();
