@@ -529,6 +529,42 @@ int ssq_tssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
                       const double* scales, const double* row_freqs, int64_t na, double dt, int padtype, int order,
                       double gamma, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm, void* d_workspace,
                       int64_t workspace_bytes, void* stream, float* kernel_ms);
+/* Time-reassigned multisynchrosqueezed CWT, `upstream.tmssq_cwt` (csrc/cwt_tmsst.hip; the iteration of Yu,
+ * Lin, Ma and He 2020 on ssq_tssq_cwt_host's time map; upstream has no such transform): the map is asked again at the
+ * column a coefficient landed on, n_iter steps in all.  Arguments, conventions and limits of ssq_tssq_cwt_host; order 1
+ * or 2, n_iter 1 .. 64.  Per row, with t[j] = m' of ssq_tssq_cwt_host for a kept bin, none where |W| < gamma:
+ *   c1[j] = t[j];   c(k+1)[j] = t[ck[j]] if t[ck[j]] is kept, else ck[j]                  (k = 1 .. n_iter - 1)
+ *   Tx[i][c_n[j]] += Wx[i][j] exp(-2 pi i frac(nu_i (j - c_n[j]))) for every kept j, accumulated as there (the same
+ *   quantum: a cell still takes at most n_signal contributions), so Tx is bitwise independent of the order of the adds,
+ *   of the chunking and of `batch`.
+ * A chain stops on a column that is not kept and on a fixed point; a cycle turns until n_iter runs out.  A target may lie
+ * anywhere in its row (the offset is clamped to +- n_signal, not to a window), so the walk reads the steps that leave
+ * its staged tile from device memory.  n_iter = 1 is ssq_tssq_cwt_host bit for bit (no walk is launched).  Tx, Wx as
+ * there; tau (may be NULL): the ONE-step map; mm (may be NULL): int32, the column of Tx each coefficient went to, -1
+ * where it was not kept.  Workspace: ssq_tssq_cwt_host's with 24 bytes a cell in the head where that has 20 (the walked
+ * plane).  The walk runs after all chunks. */
+int ssq_tmssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                       const double* scales, const double* row_freqs, int64_t na, double dt, int padtype, int order,
+                       double gamma, int n_iter, int64_t work_limit_bytes, void* Tx, void* Wx, void* tau, void* mm);
+/* Device bytes of the workspace, as ssq_tssq_cwt_workspace_bytes reports them: the preferred size returned, the least
+ * one in *min_bytes (may be NULL); computed on the host; -1 on a bad shape. */
+int64_t ssq_tmssq_cwt_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int order, int64_t* min_bytes);
+/* The same transform on device buffers, as ssq_tssq_cwt_exec.  Synchronous on `stream`.  kernel_ms (may be NULL): FOUR
+ * floats, the time of all the kernels, of the operator part (everything before the walk), of the walk kernel (no launch
+ * at n_iter = 1) and of the scatter kernel, from HIP events around the launches. */
+int ssq_tmssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                       const double* scales, const double* row_freqs, int64_t na, double dt, int padtype, int order,
+                       double gamma, int n_iter, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm, void* d_workspace,
+                       int64_t workspace_bytes, void* stream, float* kernel_ms);
+/* The walk of ssq_tmssq_cwt_host alone, on maps the caller holds (the same kernel, launched at n_iter = 1 too):
+ * targets_in, targets_out [batch][n_rows][n_cols] int32 on the host, a target indexes the column axis itself, -1: none.
+ * n_cols 1 .. 2^30, n_iter 1 .. 64; a target outside -1 .. n_cols - 1 is refused on the host.  Synchronous, the batch
+ * sliced to the device's free memory. */
+int ssq_tmssq_cwt_walk_host(const int32_t* targets_in, int64_t batch, int64_t n_rows, int64_t n_cols, int n_iter,
+                            int32_t* targets_out);
+/* Columns of the tile one workgroup of the walk kernel owns; *halo (may be NULL): the columns it stages on either side of
+ * the tile.  Host only. */
+int ssq_tmssq_cwt_tile_cols(int* halo);
 /* ConceFT, the multitaper synchrosqueezed CWT, `upstream.conceft_cwt` (csrc/cwt_conceft.hip; Daubechies,
  * Wang and Wu 2016; upstream has no such transform).  The wavelets are the GMWs (gmw_gamma, gmw_beta; bandpass norm) of
  * n_orders distinct orders, coeffs [n_orders][n_coeffs] their polynomials as for ssq_cwt_host_gmwk (1 <= n_orders <= 8,

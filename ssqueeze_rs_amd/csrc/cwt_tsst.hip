@@ -28,34 +28,15 @@
 //                              cell takes at most N of them (one row), so |cell| < 2^61.
 //   cwt_tsst_readout_kernel<O> : converts every cell once to fp64, scales it by q, rounds to the call's dtype and writes
 //                              every cell of Tx exactly once.
-// The rotation's angle is formed in turns: t = nu r with the product's rounding error recovered by an fma, then
-// t - rint(t) (exact) plus that remainder, and sinpi / cospi: its error does not grow with |r| <= N.
+// The rotation's angle is formed in turns: one fma of the exact product nu r against rint(nu r), rounded once, then sinpi
+// / cospi: its error does not grow with |r| <= N.
 // The head of the workspace: the signals' maxima [batch] (to a multiple of 16 bytes), the accumulators [batch][na][N][2]
 // and the int32 target map [batch][na][N] (to a multiple of 16 bytes).
 #include <cmath>
 
-#include "cwt_maps64.h"
+#include "cwt_tsst.h"
 
 namespace ssq {
-
-constexpr int kCwtTQuantumBitsMax = 38;                       // upstream.TSSQ_CWT_QUANTUM_LOG2_MAX
-
-constexpr unsigned cwt_tsst_map_set(int order) { return order == 2 ? kMapsAll : kMapW | kMapWt; }
-constexpr int cwt_tsst_maps(int order) { return cwt_map_count(cwt_tsst_map_set(order)); }
-
-template <typename O>
-struct CwtTOpDev {
-  const cpx<double>* maps;   // [rows][maps][P]: the unnormalised inverse transforms
-  const double* nu;          // [na]: the rows' frequencies, cycles/sample
-  cpx<O>* Wx;                // [batch * na][N], these three at the chunk's first row
-  O* tau;                    // or nullptr
-  int* mm;
-  unsigned long long* emax;  // [batch]: bit pattern of max |Wx|^2, zeroed before the first chunk
-  long long P, N, n1, r0, rows;
-  int na;
-  double inv_P, gamma, gamma_sq, dt;
-  O dt_o;                    // dt in the call's dtype: the time rule runs on the tau the call reports
-};
 
 // grid (ceil(N / 256), min(rows, 65535)): thread = column j of row rl.  No thread leaves early (cwt_flush_max).
 template <typename O, int ORDER>
@@ -126,18 +107,6 @@ __device__ __forceinline__ void cwt_tsst_quantum(unsigned long long bits, int qb
   }
 }
 
-template <typename O>
-struct CwtTScatDev {
-  const cpx<O>* Wx;                  // [batch][na][N]
-  const int* mm;                     // [batch][na][N]: target column, -1 where the bin is not kept
-  const double* nu;                  // [na]
-  const unsigned long long* emax;    // [batch]
-  unsigned long long* acc;           // [batch][na][N][2]: the fixed-point cells, zeroed before the scatter
-  cpx<O>* Tx;                        // [batch][na][N]
-  long long batch, plane, N;         // plane = na N <= 2^40
-  int qbits;
-};
-
 // grid (min(ceil(plane / 256), 2^31 - 1), min(batch, 65535)): 64-bit flat index i over a signal's na x N bins, lanes
 // along time, the x blocks stride over the plane and the y blocks over the signals
 template <typename O>
@@ -162,8 +131,10 @@ __global__ __launch_bounds__(kCwtThreads) void cwt_tsst_scatter_kernel(const Cwt
           const long long row = i / p.N;
           const double nu = p.nu[row];
           const double r = (double)((i - row * p.N) - (long long)mm);     // j - m', |r| < N <= 2^26: exact
-          const double t = nu * r;
-          const double f = (t - rint(t)) + fma(nu, r, -t);                // frac(nu r) in turns, |f| <= 1/2 (+ 1 ulp)
+          // frac(nu r) in turns, |f| <= 1/2 (+ 1 ulp): ONE fma on the exact product.  (Written as (t - rint(t)) +
+          // fma(nu, r, -t) the compiler contracts the first term to this very fma and the remainder is counted twice:
+          // an angle error of up to half an ulp of nu r turns, which grows with |r|.  DESIGN 4.22.)
+          const double f = fma(nu, r, -rint(nu * r));
           const double sn = sinpi(-2.0 * f), cs = cospi(-2.0 * f);
           const double re = a * cs - c * sn, im = a * sn + c * cs;
           fr = to_fixed_f64(fmax(fmin(re * inv_q, cap), -cap));           // |.| <= 2^qbits quanta
@@ -212,57 +183,39 @@ __global__ __launch_bounds__(kCwtThreads) void cwt_tsst_readout_kernel(const Cwt
   }
 }
 
-}  // namespace ssq
+// ---------------------------------------------------------------- host side ----
+// the two halves of the pipeline (cwt_tsst.h), which cwt_tmsst.hip runs with its walk between them
 
-using namespace ssq;
-
-namespace {
-
-// the head: 16 bytes of accumulator and one int32 target per cell
-constexpr CwtMapsKind kCwtTKind = {"tssq_cwt", "ssq_tssq_cwt_workspace_bytes", 20.0, 4.0e18, 20};
-
-struct CwtTCall {
-  CwtMapsCall m;
-  int order;
-  const double* nu;
-};
-
-const char* cwtt_order_fail(int order) { return order != 1 && order != 2 ? "order must be 1 or 2" : nullptr; }
-
-int cwtt_check(const CwtTCall& c, CwtMapsShape* s) {
+int cwtt_check(const CwtMapsKind& k, const char* own_fail, const CwtTCall& c, CwtMapsShape* s) {
+  const std::string pre = std::string(k.name) + ": ";
   const auto rows = [&]() -> int {
     if (!c.m.scales || !c.nu) SSQ_FAIL("NULL argument");
     for (int64_t i = 0; i < c.m.na; ++i) {
-      if (!(c.m.scales[i] > 0) || !std::isfinite(c.m.scales[i])) SSQ_FAIL("tssq_cwt: scales must be positive and finite");
-      if (!(c.nu[i] > 0) || !std::isfinite(c.nu[i])) SSQ_FAIL("tssq_cwt: row_freqs must be positive and finite");
+      if (!(c.m.scales[i] > 0) || !std::isfinite(c.m.scales[i])) SSQ_FAIL(pre + "scales must be positive and finite");
+      if (!(c.nu[i] > 0) || !std::isfinite(c.nu[i])) SSQ_FAIL(pre + "row_freqs must be positive and finite");
     }
     return 0;
   };
-  return cwt_maps_check(kCwtTKind, cwt_tsst_maps(c.order), cwtt_order_fail(c.order), c.m, rows, nullptr, 0, nullptr, s);
+  return cwt_maps_check(k, cwt_tsst_maps(c.order), own_fail, c.m, rows, nullptr, 0, nullptr, s);
 }
 
-// The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the rows per chunk.  d_tau, d_mm may be nullptr
-// (the targets then live in the workspace alone).  Synchronous.  kernel_ms: three floats, all kernels, the scatter kernel
-// alone, and everything before the scatter.
+int cwtt_tables(DeviceBufs& d, const CwtTCall& c, void** d_scales, void** d_nu) {
+  SSQ_HIP(d.upload(d_scales, c.m.scales, sizeof(double) * (size_t)c.m.na));
+  SSQ_HIP(d.upload(d_nu, c.nu, sizeof(double) * (size_t)c.m.na));
+  return 0;
+}
+
+namespace {
+
 template <typename T, int ORDER>
-int cwtt_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm,
-             void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
+int cwtt_operator_order(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, const void* d_scales, const void* d_nu,
+                        void* d_Wx, void* d_tau, int* mm, void* d_work, int64_t work_bytes, hipStream_t st) {
   const int64_t batch = c.m.batch, N = c.m.N, na = c.m.na;
-  DeviceBufs d;
-  TimingEvents t;
-  void *d_scales = nullptr, *d_nu = nullptr;
-  SSQ_HIP(d.upload(&d_scales, c.m.scales, sizeof(double) * (size_t)na));
-  SSQ_HIP(d.upload(&d_nu, c.nu, sizeof(double) * (size_t)na));
-  if (kernel_ms) SSQ_HIP(t.start(4, st));
   const int64_t cells = batch * s.plane;
-  char* head = static_cast<char*>(d_work);
-  unsigned long long* emax = reinterpret_cast<unsigned long long*>(head);                                  // [batch]
-  unsigned long long* acc = reinterpret_cast<unsigned long long*>(head + cwt_emax_bytes(batch));          // [cells][2]
-  int* mm = d_mm ? static_cast<int*>(d_mm) : reinterpret_cast<int*>(acc + 2 * cells);
-  SSQ_HIP(hipMemsetAsync(head, 0, (size_t)(cwt_emax_bytes(batch) + 16 * cells), st));
+  SSQ_HIP(hipMemsetAsync(d_work, 0, (size_t)(cwt_emax_bytes(batch) + 16 * cells), st));
   CwtTOpDev<T> op{};
   op.nu = static_cast<const double*>(d_nu);
-  op.emax = emax;
+  op.emax = static_cast<unsigned long long*>(d_work);                                                    // [batch]
   op.P = s.P;
   op.N = N;
   op.n1 = s.n1;
@@ -283,16 +236,30 @@ int cwtt_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_
     SSQ_HIP(hipGetLastError());
     return 0;
   };
-  if (int rc = cwt_maps_chunks<T, cwt_tsst_map_set(ORDER)>(c.m, s, d_x, d_scales, d_work, work_bytes, st, launch_op))
-    return rc;
+  return cwt_maps_chunks<T, cwt_tsst_map_set(ORDER)>(c.m, s, d_x, d_scales, d_work, work_bytes, st, launch_op);
+}
+
+}  // namespace
+
+template <typename T>
+int cwtt_operator_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, const void* d_scales, const void* d_nu,
+                      void* d_Wx, void* d_tau, int* mm, void* d_work, int64_t work_bytes, hipStream_t st) {
+  return c.order == 2 ? cwtt_operator_order<T, 2>(c, s, d_x, d_scales, d_nu, d_Wx, d_tau, mm, d_work, work_bytes, st)
+                      : cwtt_operator_order<T, 1>(c, s, d_x, d_scales, d_nu, d_Wx, d_tau, mm, d_work, work_bytes, st);
+}
+
+template <typename T>
+int cwtt_scatter_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_nu, const void* d_Wx, const int* mm,
+                     void* d_work, void* d_Tx, hipStream_t st, hipEvent_t mid) {
+  const int64_t batch = c.m.batch, N = c.m.N;
   int L = 0;
   while (((int64_t)1 << L) < N) ++L;                          // ceil(log2 N) <= 26
   CwtTScatDev<T> sc{};
   sc.Wx = static_cast<const cpx<T>*>(d_Wx);
   sc.mm = mm;
   sc.nu = static_cast<const double*>(d_nu);
-  sc.emax = emax;
-  sc.acc = acc;
+  sc.emax = static_cast<const unsigned long long*>(d_work);
+  sc.acc = cwtt_head_acc(d_work, batch);
   sc.Tx = static_cast<cpx<T>*>(d_Tx);
   sc.batch = batch;
   sc.plane = s.plane;
@@ -300,12 +267,48 @@ int cwtt_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_
   sc.qbits = std::min(kCwtTQuantumBitsMax, 61 - L);
   const dim3 grid((unsigned)std::min<int64_t>((s.plane + kCwtThreads - 1) / kCwtThreads, 0x7fffffffLL),
                   (unsigned)std::min<int64_t>(batch, 65535));
-  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
   hipLaunchKernelGGL((cwt_tsst_scatter_kernel<T>), grid, dim3(kCwtThreads), 0, st, sc);
   SSQ_HIP(hipGetLastError());
-  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[2], st));
+  if (mid) SSQ_HIP(hipEventRecord(mid, st));
   hipLaunchKernelGGL((cwt_tsst_readout_kernel<T>), grid, dim3(kCwtThreads), 0, st, sc);
   SSQ_HIP(hipGetLastError());
+  return 0;
+}
+
+template int cwtt_operator_run<float>(const CwtTCall&, const CwtMapsShape&, const void*, const void*, const void*, void*,
+                                      void*, int*, void*, int64_t, hipStream_t);
+template int cwtt_operator_run<double>(const CwtTCall&, const CwtMapsShape&, const void*, const void*, const void*, void*,
+                                       void*, int*, void*, int64_t, hipStream_t);
+template int cwtt_scatter_run<float>(const CwtTCall&, const CwtMapsShape&, const void*, const void*, const int*, void*,
+                                     void*, hipStream_t, hipEvent_t);
+template int cwtt_scatter_run<double>(const CwtTCall&, const CwtMapsShape&, const void*, const void*, const int*, void*,
+                                      void*, hipStream_t, hipEvent_t);
+
+}  // namespace ssq
+
+using namespace ssq;
+
+namespace {
+
+// the head: 16 bytes of accumulator and one int32 target per cell
+constexpr CwtMapsKind kCwtTKind = {"tssq_cwt", "ssq_tssq_cwt_workspace_bytes", 20.0, 4.0e18, 20};
+
+// The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the rows per chunk.  d_tau, d_mm may be nullptr
+// (the targets then live in the workspace alone).  Synchronous.  kernel_ms: three floats, all kernels, the scatter kernel
+// alone, and everything before the scatter.
+template <typename T>
+int cwtt_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm,
+             void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
+  DeviceBufs d;
+  TimingEvents t;
+  void *d_scales = nullptr, *d_nu = nullptr;
+  if (int rc = cwtt_tables(d, c, &d_scales, &d_nu)) return rc;
+  if (kernel_ms) SSQ_HIP(t.start(4, st));
+  int* mm = d_mm ? static_cast<int*>(d_mm) : cwtt_head_plane(d_work, c.m.batch, c.m.batch * s.plane, 0);
+  if (int rc = cwtt_operator_run<T>(c, s, d_x, d_scales, d_nu, d_Wx, d_tau, mm, d_work, work_bytes, st)) return rc;
+  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
+  if (int rc = cwtt_scatter_run<T>(c, s, d_nu, d_Wx, mm, d_work, d_Tx, st, kernel_ms ? t.ev[2] : (hipEvent_t) nullptr))
+    return rc;
   if (kernel_ms) {
     SSQ_HIP(hipEventRecord(t.ev[3], st));
     SSQ_HIP(hipEventSynchronize(t.ev[3]));
@@ -315,13 +318,6 @@ int cwtt_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_
   }
   SSQ_HIP(hipStreamSynchronize(st));                           // (the tables above are freed on return)
   return 0;
-}
-
-template <typename T>
-int cwtt_run_order(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau,
-                   void* d_mm, void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
-  return c.order == 2 ? cwtt_run<T, 2>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_work, work_bytes, st, kernel_ms)
-                      : cwtt_run<T, 1>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_work, work_bytes, st, kernel_ms);
 }
 
 template <typename T>
@@ -335,14 +331,12 @@ int cwtt_host_typed(const CwtTCall& c, const CwtMapsShape& s, const void* x, int
   SSQ_HIP(d.alloc(&d_Wx, sizeof(cpx<T>) * n));
   if (tau) SSQ_HIP(d.alloc(&d_tau, sizeof(T) * n));
   SSQ_HIP(d.alloc(&d_work, (size_t)work_bytes));
-  if (int rc = cwtt_run_order<T>(c, s, d_x, d_Tx, d_Wx, d_tau, nullptr, d_work, work_bytes, nullptr, nullptr)) return rc;
+  if (int rc = cwtt_run<T>(c, s, d_x, d_Tx, d_Wx, d_tau, nullptr, d_work, work_bytes, nullptr, nullptr)) return rc;
   SSQ_HIP(hipMemcpy(Tx, d_Tx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
   SSQ_HIP(hipMemcpy(Wx, d_Wx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
   if (tau) SSQ_HIP(hipMemcpy(tau, d_tau, sizeof(T) * n, hipMemcpyDeviceToHost));
   // the targets of the workspace: behind the maxima and the accumulators at its head
-  if (mm)
-    SSQ_HIP(hipMemcpy(mm, static_cast<const char*>(d_work) + cwt_emax_bytes(c.m.batch) + 16 * n, sizeof(int) * n,
-                      hipMemcpyDeviceToHost));
+  if (mm) SSQ_HIP(hipMemcpy(mm, cwtt_head_plane(d_work, c.m.batch, (int64_t)n, 0), sizeof(int) * n, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -364,13 +358,12 @@ int ssq_tssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
   if (!d_x || !d_Tx || !d_Wx || !d_workspace) SSQ_FAIL("NULL argument");
   const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales}, order, row_freqs};
   CwtMapsShape s;
-  if (int rc = cwtt_check(c, &s)) return rc;
+  if (int rc = cwtt_check(kCwtTKind, cwtt_order_fail(order), c, &s)) return rc;
   if (int rc = cwt_exec_bytes(kCwtTKind, s, workspace_bytes)) return rc;
   if (int rc = require_device()) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == SSQ_F32
-             ? cwtt_run_order<float>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_workspace, workspace_bytes, st, kernel_ms)
-             : cwtt_run_order<double>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_workspace, workspace_bytes, st, kernel_ms);
+  return dtype == SSQ_F32 ? cwtt_run<float>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_workspace, workspace_bytes, st, kernel_ms)
+                          : cwtt_run<double>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_workspace, workspace_bytes, st, kernel_ms);
 }
 
 int ssq_tssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
@@ -380,7 +373,7 @@ int ssq_tssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal,
   const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales}, order, row_freqs};
   CwtMapsShape s;
   int64_t work = 0;
-  if (int rc = cwtt_check(c, &s)) return rc;
+  if (int rc = cwtt_check(kCwtTKind, cwtt_order_fail(order), c, &s)) return rc;
   if (int rc = cwt_host_bytes(kCwtTKind, s, batch, work_limit_bytes, &work)) return rc;
   if (int rc = require_device()) return rc;
   return dtype == SSQ_F32 ? cwtt_host_typed<float>(c, s, x, work, Tx, Wx, tau, mm)

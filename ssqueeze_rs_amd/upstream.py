@@ -78,6 +78,12 @@ Supported subset (anything else raises ValueError naming the option):
     to its group delay, rotated to keep its phase reference, so clicks and fast sweeps concentrate and add coherently;
     the conventions of `ssq_cwt2` without `ssq_freqs`, `maprange`, `squeezing`, `flipud` and row weights; accumulated by
     64-bit integer atomic adds in fixed point (`tssq_cwt_quantum_log2`); no inverse (a per-row marginal identity);
+  * `tmssq_cwt`: the time-reassigned multisynchrosqueezed CWT (orders 1 and 2), the CWT counterpart of `tmssq_stft`,
+    which upstream does not have (the definition is this project's: DESIGN 4.22, csrc/cwt_tmsst.hip): `tssq_cwt`'s time
+    map asked again at the column a coefficient landed on, `n_iter` steps in all (1 .. 64), which narrows the ridge of a
+    dispersive signal; a target may lie anywhere in its row, so the walk kernel stages a tile in LDS and reads the far
+    steps from device memory; the conventions, the accumulation and the quantum of `tssq_cwt`; no inverse;
+    `tmssq_cwt_walk` runs the walk alone on an int32 map the caller holds;
   * `conceft_cwt`: ConceFT, the multitaper synchrosqueezed CWT (Daubechies, Wang and Wu 2016), which upstream does not
     have (the definition is this project's: DESIGN 4.18, csrc/cwt_conceft.hip): `ssq_cwt` under M random unit
     combinations of the GMWs of J orders (`conceft_vectors`, gauged by the orders' admittances `gmw_adm_ssq`), averaged,
@@ -1246,6 +1252,27 @@ def tssq_cwt_row_freqs(wavelet, scales):
     return np.ascontiguousarray(wc / (2 * np.pi * s))
 
 
+def _tssq_cwt_args(bytes_fn, x, wavelet, scales, nv, fs, t, padtype, order, gamma, work_limit_bytes):
+    """The checks `tssq_cwt` and `tmssq_cwt` share, before any GPU work -> (order, the front end, scales, nu, the
+    work_limit_bytes argument).  bytes_fn: the transform's *_workspace_bytes."""
+    order = _order12(order, "1 and 2 are built")
+    f = _cwt_front(x, wavelet, scales, fs, t, gamma, padtype)
+    if not (math.isfinite(f.p0) and math.isfinite(f.p1)):                   # (the front end: positive; here finite too)
+        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
+    s, scaletype, _nv, _ = _scales(scales)
+    if scaletype == "log" and nv is not None and nv != _nv:                  # (a ValueError here, `_cwt_freq_grid`: Exception)
+        raise ValueError("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))
+    nu = tssq_cwt_row_freqs(wavelet, s)
+    if not (np.isfinite(nu).all() and (nu > 0).all()):
+        raise ValueError("`scales` give row frequencies that are not positive and finite")
+    mn = C.c_int64(0)
+    _shape_checked(_lib.load(), bytes_fn(f.code, f.batch, f.N, len(s), order, C.byref(mn)))
+    limit = 0 if work_limit_bytes is None else int(work_limit_bytes)
+    if work_limit_bytes is not None and limit < mn.value:
+        raise ValueError(f"`work_limit_bytes` must be at least {mn.value} for this shape")
+    return order, f, s, nu, limit
+
+
 def tssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, padtype="reflect", order=2, gamma=None,
              get_tau=False, get_targets=False, work_limit_bytes=None):
     """Time-reassigned synchrosqueezed CWT -> (Tx, Wx, scales, row_freqs[, tau][, mm]); not in upstream, conventions of
@@ -1282,21 +1309,8 @@ def tssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None,
     padtypes; orders 1 and 2; 1-D or batched 2-D `x`; N <= 2^26 and na N <= 2^40.  Anything else raises ValueError before
     any GPU work."""
     lib = _lib.load()
-    order = _order12(order, "1 and 2 are built")
-    f = _cwt_front(x, wavelet, scales, fs, t, gamma, padtype)
-    if not (math.isfinite(f.p0) and math.isfinite(f.p1)):                   # (the front end: positive; here finite too)
-        raise ValueError(f"wavelet {wavelet!r}: the parameters must be positive")
-    s, scaletype, _nv, _ = _scales(scales)
-    if scaletype == "log" and nv is not None and nv != _nv:                  # (a ValueError here, `_cwt_freq_grid`: Exception)
-        raise ValueError("`nv` used in `scales` differs from `nv` passed (%s != %s)" % (_nv, nv))
-    nu = tssq_cwt_row_freqs(wavelet, s)
-    if not (np.isfinite(nu).all() and (nu > 0).all()):
-        raise ValueError("`scales` give row frequencies that are not positive and finite")
-    mn = C.c_int64(0)
-    _shape_checked(lib, lib.ssq_tssq_cwt_workspace_bytes(f.code, f.batch, f.N, len(s), order, C.byref(mn)))
-    limit = 0 if work_limit_bytes is None else int(work_limit_bytes)
-    if work_limit_bytes is not None and limit < mn.value:
-        raise ValueError(f"`work_limit_bytes` must be at least {mn.value} for this shape")
+    order, f, s, nu, limit = _tssq_cwt_args(lib.ssq_tssq_cwt_workspace_bytes, x, wavelet, scales, nv, fs, t, padtype, order,
+                                            gamma, work_limit_bytes)
     _lib.require_gpu()
     shape = (f.batch, len(s), f.N)
     Tx, Wx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
@@ -1305,6 +1319,86 @@ def tssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None,
     _call(lib.ssq_tssq_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), _ptr(nu), len(s), f.dt,
                                 f.pad, order, f.gamma, limit, _ptr(Tx), _ptr(Wx), _ptr(tau), _ptr(mm)))
     return (*_unbatch(f.batched, Tx, Wx), s.astype(f.rdt), (nu / f.dt).astype(f.rdt), *_unbatch(f.batched, tau, mm))
+
+
+def tmssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, padtype="reflect", order=2, n_iter=4,
+              gamma=None, get_tau=False, get_targets=False, work_limit_bytes=None):
+    """Time-reassigned multisynchrosqueezed CWT -> (Tx, Wx, scales, row_freqs[, tau][, mm]); not in upstream (the
+    iteration of Yu, Lin, Ma and He 2020 on `tssq_cwt`'s time map), conventions of `tssq_cwt`.  Where `tssq_cwt` applies
+    its time map once, this asks the map again at the column a coefficient landed on, `n_iter` steps in all: on a
+    dispersive signal whose group delay is not linear across a row's wavelet the one-step estimate taken off the ridge is
+    biased, and the estimate taken where it points is closer.  It is the CWT counterpart of `tmssq_stft` and the dual of
+    `mssq_cwt`.
+
+    Everything up to the one-step target is `tssq_cwt`'s: the maps, d1, d2 and the fallback, the clamp to +- N, `tau` in
+    the call's dtype (+inf where |W| < gamma) and t[i, j] = clip(j + rint(tau / dt), 0, N - 1) in the call's dtype on
+    the reported tau.  Then, per row i:
+        c1[j] = t[j]
+        c(k+1)[j] = t[ck[j]]  if bin (i, ck[j]) is kept,  else ck[j]                    (k = 1 .. n_iter - 1)
+        Tx[i, c_n[j]] += Wx[i, j] exp(-2 pi i frac(nu_i (j - c_n[j])))                  kept j
+    A chain stops on a column whose bin in that row is not kept and on a fixed point; a cycle keeps turning until
+    `n_iter` runs out.  The rotation takes the total displacement, so the per-row marginal identity of `tssq_cwt` holds
+    as it does there.  Rows do not mix.  `Tx` is accumulated as `tssq_cwt`'s, by 64-bit integer atomic adds in fixed
+    point with the same quantum (`tssq_cwt_quantum_log2`: a cell still takes at most N contributions), so it is bitwise
+    independent of the order of the adds, of the chunking (`work_limit_bytes`) and of the batch.  `n_iter=1` is
+    `tssq_cwt` bit for bit.  There is no inverse.
+
+    `Wx` equals `tssq_cwt`'s; `tau` (get_tau=True) is the ONE-step map, +inf where a bin is not kept; `mm`
+    (get_targets=True) is int32: the column of `Tx` each coefficient went to, -1 where it was not kept.
+    `tmssq_cwt_walk` runs the walk alone on a map the caller holds.
+
+    A one-step target may lie anywhere in its row (the offset is clamped to +- N, not to a window), so the walk kernel
+    stages a tile of targets with a halo in LDS (`tmssq_cwt_tile_cols`) and reads the steps that leave it from device
+    memory; it is built without register spills or scratch (profiles/tmssq_cwt_resources.txt).  `order` 1 or 2, `n_iter`
+    an int from 1 to 64, and the limits of `tssq_cwt`; ValueError otherwise, before any GPU work."""
+    lib = _lib.load()
+    n_iter = _n_iter(n_iter)
+    order, f, s, nu, limit = _tssq_cwt_args(lib.ssq_tmssq_cwt_workspace_bytes, x, wavelet, scales, nv, fs, t, padtype, order,
+                                            gamma, work_limit_bytes)
+    _lib.require_gpu()
+    shape = (f.batch, len(s), f.N)
+    Tx, Wx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    tau = _lib.pinned_empty(shape, f.rdt) if get_tau else None
+    mm = _lib.pinned_empty(shape, np.int32) if get_targets else None
+    _call(lib.ssq_tmssq_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), _ptr(nu), len(s), f.dt,
+                                 f.pad, order, f.gamma, n_iter, limit, _ptr(Tx), _ptr(Wx), _ptr(tau), _ptr(mm)))
+    return (*_unbatch(f.batched, Tx, Wx), s.astype(f.rdt), (nu / f.dt).astype(f.rdt), *_unbatch(f.batched, tau, mm))
+
+
+TMSSQ_CWT_WALK_MAX_N = 1 << 30          # csrc/cwt_tmsst.hip: columns of a map handed to `tmssq_cwt_walk`
+
+
+def tmssq_cwt_walk(targets, n_iter):
+    """The walk of `tmssq_cwt` alone, on a map the caller holds -> int32, same shape.  `targets`: int32 [rows, n] or
+    [B, rows, n], a target indexes the column axis itself (anywhere in 0 .. n - 1) and -1 means none; per row
+        c1[j] = targets[j];   c(k+1)[j] = targets[ck[j]] if targets[ck[j]] >= 0, else ck[j]        (k = 1 .. n_iter - 1)
+    and the result is c_n (-1 where targets[j] is).  Runs the kernel of `tmssq_cwt` (csrc/cwt_tmsst.hip); a non-int32
+    array, an empty axis, n > 2^30, a target outside -1 .. n - 1 and an `n_iter` that is not an int from 1 to 64 raise
+    ValueError before any GPU work."""
+    lib = _lib.load()
+    n_iter = _n_iter(n_iter)
+    if not isinstance(targets, np.ndarray) or targets.dtype != np.int32 or targets.ndim not in (2, 3):
+        raise ValueError("`targets` must be an int32 ndarray [rows, n] or [B, rows, n]")
+    t3 = np.ascontiguousarray(targets if targets.ndim == 3 else targets[None])
+    B, R, n = t3.shape
+    if B < 1 or R < 1 or n < 1:
+        raise ValueError(f"`targets` of shape {targets.shape}: no empty axis")
+    if n > TMSSQ_CWT_WALK_MAX_N:
+        raise ValueError(f"`targets` of {n} columns: at most 2^30")
+    if t3.min() < -1 or t3.max() >= n:
+        raise ValueError(f"`targets` holds targets outside -1 .. n - 1 = {n - 1}")
+    _lib.require_gpu()
+    out = np.empty_like(t3)
+    _call(lib.ssq_tmssq_cwt_walk_host(_ptr(t3), B, R, n, n_iter, _ptr(out)))
+    return _unbatch(targets.ndim == 3, out)[0]
+
+
+def tmssq_cwt_tile_cols():
+    """(T, halo): the columns of the tile one workgroup of `tmssq_cwt`'s walk kernel owns, and the columns it stages in
+    LDS on either side of it; a step of a chain that lands outside them is read from device memory (no GPU needed)."""
+    halo = C.c_int(0)
+    T = _lib.load().ssq_tmssq_cwt_tile_cols(C.byref(halo))
+    return int(T), int(halo.value)
 
 
 def mssq_cwt_row_of_bin(wavelet, scales, ssq_freqs_asc, fs=None):
