@@ -849,6 +849,10 @@ int ssq_pinned_alloc(void** ptr, int64_t bytes);         /* pooled hipHostMalloc
 int ssq_pinned_free(void* ptr);                          /* back to the pool */
 int ssq_host_cache_limit(int64_t idle_pinned_bytes);     /* idle pinned memory the pool may keep (default 8 GiB) */
 int ssq_host_cache_stats(int64_t* live_pinned_bytes, int64_t* idle_pinned_bytes);
+/* An aid for testing the host slices: at most `signals` signals per slice in every synchronous *_host entry point that
+ * slices a batch to fit device memory (0, the default: no cap; negative: an error).  Process-wide; results do not
+ * depend on it. */
+int ssq_host_slice_cap(int64_t signals);
 int ssq_host_cache_clear(void);                          /* drop cached plans, device scratch, idle pinned blocks */
 
 /* ---- device memory / stream / event plumbing for FFI callers --------------- */

@@ -222,6 +222,7 @@ _SIGNATURES = {
     "ssq_pinned_alloc": (C.c_int, [C.POINTER(vp), i64]),
     "ssq_pinned_free": (C.c_int, [vp]),
     "ssq_host_cache_limit": (C.c_int, [i64]),
+    "ssq_host_slice_cap": (C.c_int, [i64]),
     "ssq_host_cache_stats": (C.c_int, [C.POINTER(i64), C.POINTER(i64)]),
     "ssq_host_cache_clear": (C.c_int, []),
     "ssq_dev_malloc": (C.c_int, [C.POINTER(vp), i64]),

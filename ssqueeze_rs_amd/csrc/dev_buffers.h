@@ -1,7 +1,10 @@
 // dev_buffers.h -- the plumbing of the synchronous host entry points (host pointers in, device buffers for the
 // length of one call, host pointers out): the device check, the holder of the call's device allocations, the sizing of
-// a slice of signals, and the timing events of the device entry points.
+// a slice of signals (and the cap on it that lets a test reach the slices after the first), the sliced host call itself
+// (host_sliced: H2D, run, D2H per slice), the timing events of the device entry points (run_timed: up to three parts),
+// and the two doors of a pipeline that is written once for both (pipe_host, pipe_exec).
 #pragma once
+#include <atomic>
 #include <vector>
 
 #include "ssq_common.h"
@@ -46,16 +49,60 @@ struct DeviceBufs {
   }
 };
 
-// signals of `per_signal` device bytes each that fit beside `fixed` bytes: most of the free memory, at most `cap`
-// (a signal's result does not depend on the slice it is in)
+// the process-wide cap on a slice of the host entry points (ssq_host_slice_cap; 0: none)
+inline std::atomic<long long>& host_slice_cap() {
+  static std::atomic<long long> cap{0};
+  return cap;
+}
+
+// signals of `per_signal` device bytes each that fit beside `fixed` bytes: most of the free memory, at most `cap` and
+// at most host_slice_cap() (a signal's result does not depend on the slice it is in)
 inline long long slice_signals(long long batch, double per_signal, double fixed, long long cap) {
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)1 << 30;
   double room = 0.8 * (double)free_b - fixed;
   long long s = room > per_signal ? (long long)(room / per_signal) : 1;      // one signal is always tried: hipMalloc reports the rest
   if (s > cap) s = cap;
+  if (const long long hc = host_slice_cap().load(); hc > 0 && s > hc) s = hc;
   if (s > batch) s = batch;
   return s < 1 ? 1 : s;
+}
+
+// an output of a sliced host call: `bytes` per signal; host == nullptr: not asked for (no device buffer, nullptr to bind)
+struct HostOut {
+  void* host;
+  size_t bytes;
+};
+
+// A synchronous host entry over a batch: x ([batch] x `x_bytes`) in, the outputs that were asked for out, `work_bytes` of
+// workspace per signal.  The slice is slice_signals' of everything a signal needs on the device; the buffers are
+// allocated once.  bind(cap, d_outs, d_work) is called once with the slice's capacity in signals (where the pipeline
+// carves its workspace and fixes its device pointers), then per slice: H2D of x, run(nb, d_x), D2H of each output.
+// bind and run return the entry point's status (0, or non-zero with the error set).
+template <size_t N, typename Bind, typename Run>
+int host_sliced(int64_t batch, const void* x, size_t x_bytes, const HostOut (&outs)[N], size_t work_bytes, Bind&& bind,
+                Run&& run) {
+  double per = (double)x_bytes + (double)work_bytes;
+  for (const HostOut& o : outs)
+    if (o.host) per += (double)o.bytes;
+  const int64_t slice = slice_signals(batch, per, 0.0, batch);
+  DeviceBufs d;
+  void *d_x, *d_work, *d_outs[N] = {};
+  SSQ_HIP(d.alloc(&d_x, x_bytes * (size_t)slice));
+  SSQ_HIP(d.alloc(&d_work, work_bytes * (size_t)slice));
+  for (size_t i = 0; i < N; ++i)
+    if (outs[i].host) SSQ_HIP(d.alloc(&d_outs[i], outs[i].bytes * (size_t)slice));
+  if (int rc = bind(slice, d_outs, d_work)) return rc;
+  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
+    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
+    SSQ_HIP(hipMemcpy(d_x, (const char*)x + x_bytes * (size_t)b0, x_bytes * (size_t)nb, hipMemcpyHostToDevice));
+    if (int rc = run(nb, (const void*)d_x)) return rc;
+    for (size_t i = 0; i < N; ++i)
+      if (outs[i].host)
+        SSQ_HIP(hipMemcpy((char*)outs[i].host + outs[i].bytes * (size_t)b0, d_outs[i], outs[i].bytes * (size_t)nb,
+                          hipMemcpyDeviceToHost));
+  }
+  return 0;
 }
 
 // the timing events of one call, released on every path
@@ -77,27 +124,48 @@ struct TimingEvents {
 };
 
 // The launches of a device entry point on the null stream, synchronous.  `run(mid)` issues them and returns the entry
-// point's status (0, or non-zero with the error set); kernel_ms (may be nullptr) receives their time: one float, or with `split` two, the launches before and
-// after the point where `run` records the event `mid` it is handed (nullptr when no time is asked for).
+// point's status (0, or non-zero with the error set).  kernel_ms (may be nullptr) receives their time in n_mid + 1 parts
+// (n_mid: 0, 1 or 2): `run` records the event mid[i], i < n_mid, where part i ends.  Without kernel_ms every mid[i] is
+// nullptr and `run` records nothing.
 template <typename Run>
-int run_timed(float* kernel_ms, bool split, Run&& run) {
+int run_timed(float* kernel_ms, int n_mid, Run&& run) {
+  TimingEvents t;
   if (!kernel_ms) {
-    if (int rc = run((hipEvent_t) nullptr)) return rc;
+    if (int rc = run((const hipEvent_t*)t.ev)) return rc;
     SSQ_HIP(hipDeviceSynchronize());
     return 0;
   }
-  TimingEvents t;
-  SSQ_HIP(t.start(3, nullptr));
-  if (int rc = run(split ? t.ev[1] : (hipEvent_t) nullptr)) return rc;
-  SSQ_HIP(hipEventRecord(t.ev[2], nullptr));
-  SSQ_HIP(hipEventSynchronize(t.ev[2]));
-  if (split) {
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[0], t.ev[0], t.ev[1]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[1], t.ev[1], t.ev[2]));
-  } else {
-    SSQ_HIP(hipEventElapsedTime(kernel_ms, t.ev[0], t.ev[2]));
-  }
+  SSQ_HIP(t.start(n_mid + 2, nullptr));
+  if (int rc = run((const hipEvent_t*)t.ev + 1)) return rc;
+  SSQ_HIP(hipEventRecord(t.ev[n_mid + 1], nullptr));
+  SSQ_HIP(hipEventSynchronize(t.ev[n_mid + 1]));
+  for (int i = 0; i <= n_mid; ++i) SSQ_HIP(hipEventElapsedTime(&kernel_ms[i], t.ev[i], t.ev[i + 1]));
   return 0;
+}
+
+// The two doors of a pipeline on device buffers.  Pipe{c, s} holds the call and its shape by reference and has
+//   tables()                  the call's tables on the device, once per call
+//   bind(cap, outs, work)     outs: the device outputs in the entry point's order (nullptr: not asked for); work: the
+//                             pipeline's workspace of `cap` signals, carved here by its one layout function
+//   run(nb, d_x, mid)         the launches of nb <= cap signals; mid: run_timed's events (Pipe::kMid of them)
+// each returning the entry point's status.  pipe_host: host pointers, in slices; pipe_exec: the caller's device buffers
+// and workspace at cap = batch, timed.
+template <typename Pipe, typename Call, typename Shape, size_t N>
+int pipe_host(const Call& c, const Shape& s, const void* x, size_t x_bytes, const HostOut (&outs)[N], size_t work_bytes) {
+  Pipe pl{c, s};
+  if (int rc = pl.tables()) return rc;
+  const hipEvent_t none[2] = {nullptr, nullptr};
+  return host_sliced(
+      c.batch, x, x_bytes, outs, work_bytes, [&](int64_t cap, void* const* o, void* work) { return pl.bind(cap, o, work); },
+      [&](int64_t nb, const void* d_x) { return pl.run(nb, d_x, none); });
+}
+
+template <typename Pipe, typename Call, typename Shape>
+int pipe_exec(const Call& c, const Shape& s, const void* d_x, void* const* d_outs, void* d_work, float* kernel_ms) {
+  Pipe pl{c, s};
+  if (int rc = pl.tables()) return rc;
+  if (int rc = pl.bind(c.batch, d_outs, d_work)) return rc;
+  return run_timed(kernel_ms, Pipe::kMid, [&](const hipEvent_t* mid) { return pl.run(c.batch, d_x, mid); });
 }
 
 }  // namespace ssq

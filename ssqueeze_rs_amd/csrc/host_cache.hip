@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/ssq_hip.h"
+#include "dev_buffers.h"
 
 namespace ssq {
 namespace hostpath {
@@ -153,6 +154,12 @@ int ssq_host_cache_clear(void) {
 int ssq_host_cache_limit(int64_t idle_pinned_bytes) {
   std::lock_guard<std::mutex> lk(g_pin_mu);
   g_free_limit = idle_pinned_bytes < 0 ? 0 : idle_pinned_bytes;
+  return 0;
+}
+
+int ssq_host_slice_cap(int64_t signals) {
+  if (signals < 0) SSQ_FAIL("ssq_host_slice_cap: signals must be >= 0 (0: no cap)");
+  host_slice_cap().store(signals);
   return 0;
 }
 

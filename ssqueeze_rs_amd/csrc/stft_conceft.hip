@@ -527,8 +527,7 @@ int ssq_conceft_stft_host(int dtype, const void* x, int64_t batch, int64_t n_sig
   if (work_limit_bytes < 0 || (work_limit_bytes > 0 && work_limit_bytes < s.min_bytes))
     SSQ_FAIL("conceft_stft: work_limit_bytes must be 0 or at least " + std::to_string(s.min_bytes) + " bytes");
   const int64_t work = work_limit_bytes ? std::min(work_limit_bytes, s.pref_bytes) : s.pref_bytes;
-  if (ssq_freqs)
-    for (int64_t i = 0; i < s.n_freqs; ++i) ssq_freqs[i] = (variant & SSQ_VARIANT_FLIPUD) ? s.sfs[s.n_freqs - 1 - i] : s.sfs[i];
+  fill_ssq_freqs(ssq_freqs, s.sfs, variant);
   if (int rc = require_device()) return rc;
   return dtype == SSQ_F32 ? cf_stft_host_typed<float>(c, s, x, work, Tx, Sx, dSx, w)
                           : cf_stft_host_typed<double>(c, s, x, work, Tx, Sx, dSx, w);

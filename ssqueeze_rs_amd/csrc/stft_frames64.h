@@ -2,13 +2,14 @@
 // stft_reassign.hip share: a workgroup of 256 lanes owns a tile of consecutive frames of one signal, a
 // frame is held by n/16 lanes, 256/(n/16) frames side by side (fft_core.h; frames of 2048 points and more span several
 // waves).  Here: the per-length configuration, the sample loader, the split of a packed pair of real-input spectra, the
-// float32 -> fp64 widening of the signals, the dispatch on the transform length, and the argument checks and shape the
-// three entry points have in common.  The kernels' own bodies (their transforms in order, operators and read-outs) stay
+// float32 -> fp64 widening of the signals, the dispatch on the transform length, and the call struct, argument checks and
+// shape the entry points have in common.  The kernels' own bodies (their transforms in order, operators and read-outs) stay
 // in their files: what is here compiles to the same machine code in each of them.
 #pragma once
 #include <cmath>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/ssq_hip.h"
 #include "fft_core.h"
@@ -146,6 +147,39 @@ inline int frame_shape(const char* name, bool strict, const char* own_fail, int 
   s->fs = fs;
   s->gamma = gamma < 0 ? 10.0 * (dtype == SSQ_F64 ? 2.2204460492503131e-16 : 1.1920928955078125e-07) : gamma;
   return 0;
+}
+
+// The arguments of an entry point of the family as it received them (ssq_stft2, tssq_stft, reassign_stft, mssq_stft,
+// tmssq_stft); a field the transform does not have keeps its default.
+struct FrameCall {
+  int dtype;
+  int64_t batch, n_signal;
+  const double* window;
+  int64_t n_fft, hop;
+  double fs;
+  int padtype;
+  double gamma;
+  int variant;
+  int squeezing = SSQ_SQUEEZE_SUM, order = 2, n_iter = 1;
+};
+
+// the call ssq_*_workspace_bytes checks its sizes with
+inline FrameCall frame_sizes_call(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop) {
+  return FrameCall{dtype, batch, n_signal, nullptr, n_fft, hop, 1.0, SSQ_PAD_REFLECT, -1.0, 0};
+}
+
+inline int frame_shape(const char* name, bool strict, const char* own_fail, const FrameCall& c, FrameShape* s) {
+  return frame_shape(name, strict, own_fail, c.dtype, c.batch, c.n_signal, c.n_fft, c.hop, c.fs, c.padtype, c.gamma, s);
+}
+
+// bytes of the fp64 copy of `cap` signals that a float32 call widens into (a float64 call has none)
+inline int64_t widened_bytes(int dtype, int64_t cap, int64_t n_signal) { return dtype == SSQ_F32 ? 8 * cap * n_signal : 0; }
+
+// ssq_freqs (may be nullptr) of the linear grid `sfs`, reversed under SSQ_VARIANT_FLIPUD
+inline void fill_ssq_freqs(double* ssq_freqs, const std::vector<double>& sfs, int variant) {
+  if (!ssq_freqs) return;
+  const size_t n = sfs.size();
+  for (size_t i = 0; i < n; ++i) ssq_freqs[i] = (variant & SSQ_VARIANT_FLIPUD) ? sfs[n - 1 - i] : sfs[i];
 }
 
 }  // namespace ssq

@@ -99,86 +99,48 @@ const char* msst_own_fail(int order, int n_iter) {
   return nullptr;
 }
 
-// the operator runs unflipped (the walk indexes rows by bin); the flip is applied when the final bin is written
+// mssq_stft on device buffers (pipe_host, pipe_exec), in ssq_stft2's workspace (sst2_work): the operator, the walk, the
+// scatter.  kernel_ms: three parts, the events recorded after the operator and after the walk.
 template <typename T>
-int msst_tables(DeviceBufs& d, const Sst2Shape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
-                int padtype, int variant, int order, Sst2Dev<T>* p) {
-  if (int rc = sst2_tables<T>(d, s, window, n, n_signal, hop, padtype, variant & ~SSQ_VARIANT_FLIPUD, p)) return rc;
-  if (order == 1) p->gamma_sq = INFINITY;                    // |D| > gamma_sq nowhere: the operator reports fs |Re w1|
-  return 0;
-}
-
-// the three kernels of `nb` signals on device buffers; ev (may be nullptr): two events, recorded after the operator and
-// after the walk
-template <typename T>
-hipError_t msst_run(const Sst2Dev<T>& p, const Sst2Shape& s, int squeezing, int variant, int n_iter, const T* d_x, int64_t nb,
-                    cpx<T>* d_Tx, cpx<T>* d_Sx, T* d_w, int* d_bins, cpx<T>* d_map, double* d_xd, hipEvent_t* ev) {
-  hipError_t e = sst2_operator_run<T>(p, s, d_x, nb, d_Sx, d_map, d_xd);
-  if (e != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[0], nullptr)) != hipSuccess) return e;
-  const int flip = (variant & SSQ_VARIANT_FLIPUD) ? 1 : 0;
-  if (n_iter > 1 || flip || d_bins) {                        // (one step, unflipped, no bins asked for: the map is final)
-    e = msst_walk_run<T>(d_map, d_bins, nb, (int)s.n_freqs, (long long)s.n_frames, n_iter, flip);
-    if (e != hipSuccess) return e;
-  }
-  if (ev && (e = hipEventRecord(ev[1], nullptr)) != hipSuccess) return e;
-  return sst2_scatter_run<T>(s, squeezing, p.dw, nb, d_Sx, d_map, d_Tx, d_w);
-}
-
-template <typename T>
-int msst_host_typed(const Sst2Shape& s, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
-                    int64_t hop, int padtype, int squeezing, int variant, int order, int n_iter, void* Tx, void* Sx, void* w,
-                    int32_t* bins) {
+struct MsstPipe {
+  static constexpr int kMid = 2;
+  const FrameCall& c;
+  const Sst2Shape& s;
   DeviceBufs d;
   Sst2Dev<T> p;
-  if (int rc = msst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, order, &p)) return rc;
-  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  const double per = (double)(sizeof(T) == 4 ? 12 : 8) * (double)n_signal +
-                     (double)map_sig * (3.0 * sizeof(cpx<T>) + (w ? sizeof(T) : 0) + (bins ? sizeof(int32_t) : 0));
-  const int64_t slice = slice_signals(batch, per, 0.0, batch);
-  void *d_x, *d_Tx, *d_Sx, *d_map, *d_w = nullptr, *d_bins = nullptr, *d_xd = nullptr;
-  SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)n_signal * slice));
-  if (sizeof(T) == 4) SSQ_HIP(d.alloc(&d_xd, sizeof(double) * (size_t)n_signal * slice));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_Sx, sizeof(cpx<T>) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_map, sizeof(cpx<T>) * map_sig * slice));
-  if (w) SSQ_HIP(d.alloc(&d_w, sizeof(T) * map_sig * slice));
-  if (bins) SSQ_HIP(d.alloc(&d_bins, sizeof(int32_t) * map_sig * slice));
-  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
-    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
-    SSQ_HIP(hipMemcpy(d_x, (const T*)x + (size_t)n_signal * b0, sizeof(T) * (size_t)n_signal * nb, hipMemcpyHostToDevice));
-    SSQ_HIP(msst_run<T>(p, s, squeezing, variant, n_iter, (const T*)d_x, nb, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, (T*)d_w, (int*)d_bins,
-                        (cpx<T>*)d_map, (double*)d_xd, nullptr));
-    SSQ_HIP(hipMemcpy((cpx<T>*)Tx + map_sig * b0, d_Tx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
-    SSQ_HIP(hipMemcpy((cpx<T>*)Sx + map_sig * b0, d_Sx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
-    if (w) SSQ_HIP(hipMemcpy((T*)w + map_sig * b0, d_w, sizeof(T) * map_sig * nb, hipMemcpyDeviceToHost));
-    if (bins) SSQ_HIP(hipMemcpy(bins + map_sig * b0, d_bins, sizeof(int32_t) * map_sig * nb, hipMemcpyDeviceToHost));
-  }
-  return 0;
-}
-
-template <typename T>
-int msst_exec_typed(const Sst2Shape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
-                    int64_t hop, int padtype, int squeezing, int variant, int order, int n_iter, void* d_Tx, void* d_Sx,
-                    void* d_w, int32_t* d_bins, void* d_work, float* kernel_ms) {
-  DeviceBufs d;
-  Sst2Dev<T> p;
-  if (int rc = msst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, order, &p)) return rc;
-  // the workspace of ssq_ssq_stft2_exec: the map, then (float32 calls) the widened signals
-  double* d_xd = (double*)((char*)d_work + sizeof(cpx<T>) * (size_t)batch * (size_t)s.n_freqs * (size_t)s.n_frames);
-  TimingEvents t;
-  if (kernel_ms) SSQ_HIP(t.start(4, nullptr));
-  SSQ_HIP(msst_run<T>(p, s, squeezing, variant, n_iter, (const T*)d_x, batch, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, (T*)d_w, (int*)d_bins,
-                      (cpx<T>*)d_work, d_xd, kernel_ms ? &t.ev[1] : nullptr));
-  if (!kernel_ms) {
-    SSQ_HIP(hipDeviceSynchronize());
+  cpx<T>*Tx, *Sx, *map;
+  T* w;
+  int* bins;
+  double* xd;
+  // the operator runs unflipped (the walk indexes rows by bin); the flip is applied when the final bin is written
+  int tables() {
+    FrameCall u = c;
+    u.variant &= ~SSQ_VARIANT_FLIPUD;
+    if (int rc = sst2_tables<T>(d, s, u, &p)) return rc;
+    if (c.order == 1) p.gamma_sq = INFINITY;                 // |D| > gamma_sq nowhere: the operator reports fs |Re w1|
     return 0;
   }
-  SSQ_HIP(hipEventRecord(t.ev[3], nullptr));
-  SSQ_HIP(hipEventSynchronize(t.ev[3]));
-  for (int i = 0; i < 3; ++i) SSQ_HIP(hipEventElapsedTime(&kernel_ms[i], t.ev[i], t.ev[i + 1]));
-  return 0;
-}
+  int bind(int64_t cap, void* const* outs /* Tx, Sx, w, bins */, void* work) {
+    const Sst2Work k = sst2_work(c.dtype, cap, c.n_signal, s);
+    Tx = (cpx<T>*)outs[0];
+    Sx = (cpx<T>*)outs[1];
+    w = (T*)outs[2];
+    bins = (int*)outs[3];
+    map = (cpx<T>*)((char*)work + k.map);
+    xd = (double*)((char*)work + k.xd);
+    return 0;
+  }
+  int run(int64_t nb, const void* d_x, const hipEvent_t* mid) {
+    SSQ_HIP(sst2_operator_run<T>(p, s, (const T*)d_x, nb, Sx, map, xd));
+    if (mid[0]) SSQ_HIP(hipEventRecord(mid[0], nullptr));
+    const int flip = (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0;
+    if (c.n_iter > 1 || flip || bins)                        // (one step, unflipped, no bins asked for: the map is final)
+      SSQ_HIP(msst_walk_run<T>(map, bins, nb, (int)s.n_freqs, (long long)s.n_frames, c.n_iter, flip));
+    if (mid[1]) SSQ_HIP(hipEventRecord(mid[1], nullptr));
+    SSQ_HIP(sst2_scatter_run<T>(s, c.squeezing, p.dw, nb, Sx, map, Tx, w));
+    return 0;
+  }
+};
 
 }  // namespace
 
@@ -188,23 +150,22 @@ int ssq_mssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal
                        int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, int order, int n_iter,
                        void* Tx, double* ssq_freqs, void* Sx, void* w, int32_t* bins) {
   if (!x || !window || !Tx || !Sx) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant, squeezing, order, n_iter};
   Sst2Shape s;
-  if (int rc = sst2_shape("mssq_stft", msst_own_fail(order, n_iter), dtype, batch, n_signal, n_fft, hop, fs, padtype, squeezing,
-                          gamma, &s))
-    return rc;
-  if (ssq_freqs)
-    for (int64_t i = 0; i < s.n_freqs; ++i) ssq_freqs[i] = (variant & SSQ_VARIANT_FLIPUD) ? s.sfs[s.n_freqs - 1 - i] : s.sfs[i];
+  if (int rc = sst2_shape("mssq_stft", msst_own_fail(order, n_iter), c, &s)) return rc;
+  fill_ssq_freqs(ssq_freqs, s.sfs, variant);
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? msst_host_typed<float>(s, x, batch, n_signal, window, n_fft, hop, padtype, squeezing, variant, order,
-                                                   n_iter, Tx, Sx, w, bins)
-                          : msst_host_typed<double>(s, x, batch, n_signal, window, n_fft, hop, padtype, squeezing, variant, order,
-                                                    n_iter, Tx, Sx, w, bins);
+  const size_t el = dtype == SSQ_F32 ? 4 : 8, map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
+  const HostOut outs[] = {{Tx, 2 * el * map_sig}, {Sx, 2 * el * map_sig}, {w, el * map_sig}, {bins, sizeof(int32_t) * map_sig}};
+  const size_t work = (size_t)sst2_work(dtype, 1, n_signal, s).bytes;
+  return dtype == SSQ_F32 ? pipe_host<MsstPipe<float>>(c, s, x, el * (size_t)n_signal, outs, work)
+                          : pipe_host<MsstPipe<double>>(c, s, x, el * (size_t)n_signal, outs, work);
 }
 
 int64_t ssq_mssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop) {
   Sst2Shape s;
-  if (sst2_shape("mssq_stft", nullptr, dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, SSQ_SQUEEZE_SUM, -1.0, &s)) return -1;
-  return (int64_t)(dtype == SSQ_F32 ? 8 : 16) * batch * s.n_freqs * s.n_frames + (dtype == SSQ_F32 ? 8 * batch * n_signal : 0);
+  if (sst2_shape("mssq_stft", nullptr, frame_sizes_call(dtype, batch, n_signal, n_fft, hop), &s)) return -1;
+  return sst2_work(dtype, batch, n_signal, s).bytes;
 }
 
 int ssq_mssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
@@ -212,17 +173,15 @@ int ssq_mssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_sign
                        void* d_Tx, void* d_Sx, void* d_w, int32_t* d_bins, void* d_workspace, int64_t workspace_bytes,
                        float* kernel_ms) {
   if (!d_x || !window || !d_Tx || !d_Sx || !d_workspace) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant, squeezing, order, n_iter};
   Sst2Shape s;
-  if (int rc = sst2_shape("mssq_stft", msst_own_fail(order, n_iter), dtype, batch, n_signal, n_fft, hop, fs, padtype, squeezing,
-                          gamma, &s))
-    return rc;
-  if (workspace_bytes < ssq_mssq_stft_workspace_bytes(dtype, batch, n_signal, n_fft, hop))
+  if (int rc = sst2_shape("mssq_stft", msst_own_fail(order, n_iter), c, &s)) return rc;
+  if (workspace_bytes < sst2_work(dtype, batch, n_signal, s).bytes)
     SSQ_FAIL("mssq_stft: workspace smaller than ssq_mssq_stft_workspace_bytes");
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? msst_exec_typed<float>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, squeezing, variant, order,
-                                                   n_iter, d_Tx, d_Sx, d_w, d_bins, d_workspace, kernel_ms)
-                          : msst_exec_typed<double>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, squeezing, variant,
-                                                    order, n_iter, d_Tx, d_Sx, d_w, d_bins, d_workspace, kernel_ms);
+  void* const outs[] = {d_Tx, d_Sx, d_w, d_bins};
+  return dtype == SSQ_F32 ? pipe_exec<MsstPipe<float>>(c, s, d_x, outs, d_workspace, kernel_ms)
+                          : pipe_exec<MsstPipe<double>>(c, s, d_x, outs, d_workspace, kernel_ms);
 }
 
 int ssq_msst_tile_cols(int64_t n_rows) {

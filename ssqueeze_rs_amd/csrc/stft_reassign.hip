@@ -314,25 +314,33 @@ struct ReassignShape : FrameShape {
 };
 
 // The argument checks of the three entry points, and the shape they work on (sets the error and returns non-zero)
-int reassign_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop, double fs, int padtype,
-                   double gamma, ReassignShape* s) {
-  if (int rc = frame_shape("reassign_stft", true, nullptr, dtype, batch, n_signal, n_fft, hop, fs, padtype, gamma, s))
-    return rc;
+int reassign_shape(const FrameCall& c, ReassignShape* s) {
+  if (int rc = frame_shape("reassign_stft", true, nullptr, c, s)) return rc;
   // target frames of a scatter workgroup: what kReassignCells accumulators hold of all F rows (1024 ... 7)
   int64_t tile = kReassignCells / s->n_freqs;
   if (tile > kReassignMaxTile) tile = kReassignMaxTile;
   if (tile > s->n_frames) tile = s->n_frames;
   s->tile = (int)tile;
-  const std::vector<double> sfs = host::np_linspace(0.0, 0.5 * fs, s->n_freqs);
+  const std::vector<double> sfs = host::np_linspace(0.0, 0.5 * c.fs, s->n_freqs);
   s->dw = sfs[1] - sfs[0];
   return 0;
 }
 
+// The workspace of `cap` signals, as byte offsets: (float32 calls) the widened signals, the signals' maxima, the packed
+// targets.  The only place that knows the layout: the workspace_bytes, exec and host doors all go through it.
+struct ReassignWork {
+  int64_t xd, emax, tgt, bytes;
+};
+ReassignWork reassign_work(int dtype, int64_t cap, int64_t n_signal, const FrameShape& s) {
+  const int64_t xd_b = widened_bytes(dtype, cap, n_signal);
+  return {0, xd_b, xd_b + 8 * cap, xd_b + 8 * cap + 4 * cap * s.n_freqs * s.n_frames};
+}
+
 // the call's tables on the device (held by `d`) and the two parameter blocks without their signal / output pointers
 template <typename T>
-int reassign_tables(DeviceBufs& d, const ReassignShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
-                    int padtype, int variant, ReassignDev<T>* p, ReassignScat<T>* sc) {
-  const host::SstTables t = host::sst_level_tables(window, n, host::kSstFirst);
+int reassign_tables(DeviceBufs& d, const ReassignShape& s, const FrameCall& c, ReassignDev<T>* p, ReassignScat<T>* sc) {
+  const int64_t n = c.n_fft;
+  const host::SstTables t = host::sst_level_tables(c.window, n, host::kSstFirst);
   const std::vector<double> tw = host::pass_twiddles(s.logn);
   void *d_tw, *d_wa, *d_wb;
   SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(double) * tw.size()));
@@ -342,11 +350,11 @@ int reassign_tables(DeviceBufs& d, const ReassignShape& s, const double* window,
   p->tw = (const cpx<double>*)d_tw;
   p->wa = (const cpx<double>*)d_wa;
   p->wb = (const double*)d_wb;
-  p->n_signal = n_signal;
+  p->n_signal = c.n_signal;
   p->n_frames = s.n_frames;
-  p->hop = (int)hop;
-  p->padtype = padtype;
-  p->rot = (variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
+  p->hop = (int)c.hop;
+  p->padtype = c.padtype;
+  p->rot = (c.variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
   p->gamma = s.gamma;
   p->h1 = t.h1;
   p->it = t.it;
@@ -417,64 +425,36 @@ hipError_t reassign_run(ReassignDev<T> p, ReassignScat<T> sc, const ReassignShap
   return hipSuccess;
 }
 
+// reassign_stft on device buffers (pipe_host, pipe_exec).  kernel_ms: two parts, the event recorded between the operator
+// and the scatter.
 template <typename T>
-int reassign_host_typed(const ReassignShape& s, const void* x, int64_t batch, int64_t n_signal, const double* window,
-                        int64_t n, int64_t hop, int padtype, int variant, void* Rx, void* Sx, void* w, void* tau) {
+struct ReassignPipe {
+  static constexpr int kMid = 1;
+  const FrameCall& c;
+  const ReassignShape& s;
   DeviceBufs d;
   ReassignDev<T> p;
   ReassignScat<T> sc;
-  if (int rc = reassign_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
-  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  const double per = (double)(sizeof(T) == 4 ? 12 : 8) * (double)n_signal + 8.0 +
-                     (double)map_sig * (sizeof(cpx<T>) + sizeof(T) + sizeof(unsigned) + (w ? sizeof(T) : 0) +
-                                        (tau ? sizeof(T) : 0));
-  const int64_t slice = slice_signals(batch, per, 0.0, batch);
-  void *d_x, *d_Rx, *d_Sx, *d_tgt, *d_emax, *d_w = nullptr, *d_tau = nullptr, *d_xd = nullptr;
-  SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)n_signal * slice));
-  if (sizeof(T) == 4) SSQ_HIP(d.alloc(&d_xd, sizeof(double) * (size_t)n_signal * slice));
-  SSQ_HIP(d.alloc(&d_Rx, sizeof(T) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_Sx, sizeof(cpx<T>) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_tgt, sizeof(unsigned) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_emax, sizeof(unsigned long long) * (size_t)slice));
-  if (w) SSQ_HIP(d.alloc(&d_w, sizeof(T) * map_sig * slice));
-  if (tau) SSQ_HIP(d.alloc(&d_tau, sizeof(T) * map_sig * slice));
-  if (int rc = reassign_out_block<T>(d, s, hop, d_Sx, d_w, d_tau, d_tgt, d_emax, &p)) return rc;
-  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
-    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
-    SSQ_HIP(hipMemcpy(d_x, (const T*)x + (size_t)n_signal * b0, sizeof(T) * (size_t)n_signal * nb, hipMemcpyHostToDevice));
-    SSQ_HIP(reassign_run<T>(p, sc, s, (const T*)d_x, nb, (T*)d_Rx, (cpx<T>*)d_Sx, (unsigned*)d_tgt,
-                            (unsigned long long*)d_emax, (double*)d_xd, nullptr));
-    SSQ_HIP(hipMemcpy((T*)Rx + map_sig * b0, d_Rx, sizeof(T) * map_sig * nb, hipMemcpyDeviceToHost));
-    SSQ_HIP(hipMemcpy((cpx<T>*)Sx + map_sig * b0, d_Sx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
-    if (w) SSQ_HIP(hipMemcpy((T*)w + map_sig * b0, d_w, sizeof(T) * map_sig * nb, hipMemcpyDeviceToHost));
-    if (tau) SSQ_HIP(hipMemcpy((T*)tau + map_sig * b0, d_tau, sizeof(T) * map_sig * nb, hipMemcpyDeviceToHost));
+  T* Rx;
+  cpx<T>* Sx;
+  unsigned* tgt;
+  unsigned long long* emax;
+  double* xd;
+  int tables() { return reassign_tables<T>(d, s, c, &p, &sc); }
+  int bind(int64_t cap, void* const* outs /* Rx, Sx, w, tau */, void* work) {
+    const ReassignWork k = reassign_work(c.dtype, cap, c.n_signal, s);
+    Rx = (T*)outs[0];
+    Sx = (cpx<T>*)outs[1];
+    xd = (double*)((char*)work + k.xd);
+    emax = (unsigned long long*)((char*)work + k.emax);
+    tgt = (unsigned*)((char*)work + k.tgt);
+    return reassign_out_block<T>(d, s, c.hop, Sx, outs[2], outs[3], tgt, emax, &p);
   }
-  return 0;
-}
-
-// the workspace of the device entry point: (float32 calls) the widened signals, the signals' maxima, the packed targets
-int64_t reassign_workspace_xd(int dtype, int64_t batch, int64_t n_signal) {
-  return dtype == SSQ_F32 ? 8 * batch * n_signal : 0;
-}
-
-template <typename T>
-int reassign_exec_typed(const ReassignShape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window,
-                        int64_t n, int64_t hop, int padtype, int variant, void* d_Rx, void* d_Sx, void* d_w, void* d_tau,
-                        void* d_work, float* kernel_ms) {
-  DeviceBufs d;
-  ReassignDev<T> p;
-  ReassignScat<T> sc;
-  if (int rc = reassign_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
-  double* d_xd = (double*)d_work;
-  char* after = (char*)d_work + reassign_workspace_xd(sizeof(T) == 4 ? SSQ_F32 : SSQ_F64, batch, n_signal);
-  unsigned long long* d_emax = (unsigned long long*)after;
-  unsigned* d_tgt = (unsigned*)(after + 8 * batch);
-  if (int rc = reassign_out_block<T>(d, s, hop, d_Sx, d_w, d_tau, d_tgt, d_emax, &p)) return rc;
-  return run_timed(kernel_ms, true, [&](hipEvent_t mid) -> int {
-    SSQ_HIP(reassign_run<T>(p, sc, s, (const T*)d_x, batch, (T*)d_Rx, (cpx<T>*)d_Sx, d_tgt, d_emax, d_xd, mid));
+  int run(int64_t nb, const void* d_x, const hipEvent_t* mid) {
+    SSQ_HIP(reassign_run<T>(p, sc, s, (const T*)d_x, nb, Rx, Sx, tgt, emax, xd, mid[0]));
     return 0;
-  });
-}
+  }
+};
 
 }  // namespace
 
@@ -484,33 +464,36 @@ int ssq_reassign_stft_host(int dtype, const void* x, int64_t batch, int64_t n_si
                            int64_t hop, double fs, int padtype, double gamma, int variant, void* Rx, void* Sx, void* w,
                            void* tau) {
   if (!x || !window || !Rx || !Sx) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant};
   ReassignShape s;
-  if (int rc = reassign_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, gamma, &s)) return rc;
+  if (int rc = reassign_shape(c, &s)) return rc;
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32
-             ? reassign_host_typed<float>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, Rx, Sx, w, tau)
-             : reassign_host_typed<double>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, Rx, Sx, w, tau);
+  const size_t el = dtype == SSQ_F32 ? 4 : 8, map_el = (size_t)s.n_freqs * (size_t)s.n_frames * el;
+  const HostOut outs[] = {{Rx, map_el}, {Sx, 2 * map_el}, {w, map_el}, {tau, map_el}};
+  const size_t work = (size_t)reassign_work(dtype, 1, n_signal, s).bytes;
+  return dtype == SSQ_F32 ? pipe_host<ReassignPipe<float>>(c, s, x, el * (size_t)n_signal, outs, work)
+                          : pipe_host<ReassignPipe<double>>(c, s, x, el * (size_t)n_signal, outs, work);
 }
 
 int64_t ssq_reassign_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop) {
   ReassignShape s;
-  if (reassign_shape(dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, -1.0, &s)) return -1;
-  return reassign_workspace_xd(dtype, batch, n_signal) + 8 * batch + 4 * batch * s.n_freqs * s.n_frames;
+  if (reassign_shape(frame_sizes_call(dtype, batch, n_signal, n_fft, hop), &s)) return -1;
+  return reassign_work(dtype, batch, n_signal, s).bytes;
 }
 
 int ssq_reassign_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
                            int64_t hop, double fs, int padtype, double gamma, int variant, void* d_Rx, void* d_Sx,
                            void* d_w, void* d_tau, void* d_workspace, int64_t workspace_bytes, float* kernel_ms) {
   if (!d_x || !window || !d_Rx || !d_Sx || !d_workspace) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant};
   ReassignShape s;
-  if (int rc = reassign_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, gamma, &s)) return rc;
-  if (workspace_bytes < ssq_reassign_stft_workspace_bytes(dtype, batch, n_signal, n_fft, hop))
+  if (int rc = reassign_shape(c, &s)) return rc;
+  if (workspace_bytes < reassign_work(dtype, batch, n_signal, s).bytes)
     SSQ_FAIL("reassign_stft: workspace smaller than ssq_reassign_stft_workspace_bytes");
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? reassign_exec_typed<float>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, variant, d_Rx,
-                                                       d_Sx, d_w, d_tau, d_workspace, kernel_ms)
-                          : reassign_exec_typed<double>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, variant, d_Rx,
-                                                        d_Sx, d_w, d_tau, d_workspace, kernel_ms);
+  void* const outs[] = {d_Rx, d_Sx, d_w, d_tau};
+  return dtype == SSQ_F32 ? pipe_exec<ReassignPipe<float>>(c, s, d_x, outs, d_workspace, kernel_ms)
+                          : pipe_exec<ReassignPipe<double>>(c, s, d_x, outs, d_workspace, kernel_ms);
 }
 
 }  // extern "C"

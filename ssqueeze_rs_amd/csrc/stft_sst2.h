@@ -1,5 +1,5 @@
 // stft_sst2.h -- what stft_sst2.hip lends to stft_msst.hip: the parameter block of sst2_operator_kernel,
-// the argument checks and the shape, the call's tables on the device, and the two halves of the pipeline (operator,
+// the argument checks and the shape, the workspace layout, the call's tables on the device, and the two halves of the pipeline (operator,
 // rows-ascending scatter) on device buffers.  The kernels and the host code are compiled once, in stft_sst2.hip, for
 // float and double; this header only declares them.
 #pragma once
@@ -38,13 +38,21 @@ struct Sst2Shape : FrameShape {
 
 // The argument checks of the entry points, and the shape they work on (sets the error and returns non-zero).  name: the
 // entry point's prefix of the messages; own_fail: the message of its own argument check that failed, or nullptr.
-int sst2_shape(const char* name, const char* own_fail, int dtype, int64_t batch, int64_t n_signal, int64_t n_fft,
-               int64_t hop, double fs, int padtype, int squeezing, double gamma, Sst2Shape* s);
+int sst2_shape(const char* name, const char* own_fail, const FrameCall& c, Sst2Shape* s);
+
+// The workspace of `cap` signals of ssq_stft2 and mssq_stft, as byte offsets: the packed map, then (float32 calls) the
+// widened signals.  The only place that knows the layout: the workspace_bytes, exec and host doors all go through it.
+struct Sst2Work {
+  int64_t map, xd, bytes;
+};
+inline Sst2Work sst2_work(int dtype, int64_t cap, int64_t n_signal, const FrameShape& s) {
+  const int64_t map_b = (int64_t)(dtype == SSQ_F32 ? 8 : 16) * cap * s.n_freqs * s.n_frames;
+  return {0, map_b, map_b + widened_bytes(dtype, cap, n_signal)};
+}
 
 // the call's tables on the device (held by `d`) and the parameter block without its signal / output pointers
 template <typename T>
-int sst2_tables(DeviceBufs& d, const Sst2Shape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
-                int padtype, int variant, Sst2Dev<T>* p);
+int sst2_tables(DeviceBufs& d, const Sst2Shape& s, const FrameCall& c, Sst2Dev<T>* p);
 
 // the operator kernel of `nb` signals on device buffers: Sx and the packed map (d_xd: float32 calls, [nb][n_signal])
 template <typename T>

@@ -212,21 +212,20 @@ static hipError_t sst2_launch(Sst2Dev<T> p, int logn, long long batch, hipStream
 }
 
 // The argument checks of the entry points, and the shape they work on (sets the error and returns non-zero)
-int sst2_shape(const char* name, const char* own_fail, int dtype, int64_t batch, int64_t n_signal, int64_t n_fft,
-               int64_t hop, double fs, int padtype, int squeezing, double gamma, Sst2Shape* s) {
-  const bool sq_ok = squeezing == SSQ_SQUEEZE_SUM || squeezing == SSQ_SQUEEZE_LEBESGUE;
+int sst2_shape(const char* name, const char* own_fail, const FrameCall& c, Sst2Shape* s) {
+  const bool sq_ok = c.squeezing == SSQ_SQUEEZE_SUM || c.squeezing == SSQ_SQUEEZE_LEBESGUE;
   if (!own_fail && !sq_ok) own_fail = "squeezing must be 'sum' or 'lebesgue'";
-  if (int rc = frame_shape(name, false, own_fail, dtype, batch, n_signal, n_fft, hop, fs, padtype, gamma, s)) return rc;
-  s->sfs = host::np_linspace(0.0, 0.5 * fs, s->n_freqs);
+  if (int rc = frame_shape(name, false, own_fail, c, s)) return rc;
+  s->sfs = host::np_linspace(0.0, 0.5 * c.fs, s->n_freqs);
   s->dw = s->sfs[1] - s->sfs[0];
   return 0;
 }
 
 // the call's tables on the device (held by `d`) and the parameter block without its signal / output pointers
 template <typename T>
-int sst2_tables(DeviceBufs& d, const Sst2Shape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
-                int padtype, int variant, Sst2Dev<T>* p) {
-  const host::SstTables t = host::sst_level_tables(window, n, host::kSstSecond);   // fp64 for either dtype of the call
+int sst2_tables(DeviceBufs& d, const Sst2Shape& s, const FrameCall& c, Sst2Dev<T>* p) {
+  const int64_t n = c.n_fft;
+  const host::SstTables t = host::sst_level_tables(c.window, n, host::kSstSecond);   // fp64 for either dtype of the call
   const std::vector<double> tw = host::pass_twiddles(s.logn);
   void *d_tw, *d_wa, *d_wb, *d_wc;
   SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(double) * tw.size()));
@@ -238,13 +237,13 @@ int sst2_tables(DeviceBufs& d, const Sst2Shape& s, const double* window, int64_t
   p->wa = (const cpx<double>*)d_wa;
   p->wb = (const double*)d_wb;
   p->wc = (const cpx<double>*)d_wc;
-  p->n_signal = n_signal;
+  p->n_signal = c.n_signal;
   p->n_frames = s.n_frames;
-  p->hop = (int)hop;
+  p->hop = (int)c.hop;
   p->pad_left = (int)(n / 2);                                // the larger half of the n - 1 pad samples on the left
-  p->padtype = padtype;
-  p->rot = (variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
-  p->flip = (variant & SSQ_VARIANT_FLIPUD) ? 1 : 0;
+  p->padtype = c.padtype;
+  p->rot = (c.variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
+  p->flip = (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0;
   p->gamma = s.gamma;
   p->gamma_sq = s.gamma * s.gamma;
   p->dw = (T)s.dw;
@@ -299,8 +298,7 @@ hipError_t sst2_scatter_run(const Sst2Shape& s, int squeezing, T dw, int64_t nb,
 }
 
 #define SSQ_SST2_INSTANTIATE(T)                                                                                          \
-  template int sst2_tables<T>(DeviceBufs&, const Sst2Shape&, const double*, int64_t, int64_t, int64_t, int, int,        \
-                              Sst2Dev<T>*);                                                                              \
+  template int sst2_tables<T>(DeviceBufs&, const Sst2Shape&, const FrameCall&, Sst2Dev<T>*);                            \
   template hipError_t sst2_operator_run<T>(Sst2Dev<T>, const Sst2Shape&, const T*, int64_t, cpx<T>*, cpx<T>*, double*);   \
   template hipError_t sst2_scatter_run<T>(const Sst2Shape&, int, T, int64_t, const cpx<T>*, const cpx<T>*, cpx<T>*, T*);
 SSQ_SST2_INSTANTIATE(float)
@@ -313,55 +311,33 @@ using namespace ssq;
 
 namespace {
 
-// both kernels of `nb` signals on device buffers (Tx is zeroed here)
+// ssq_stft2 on device buffers (pipe_host, pipe_exec): the operator, then the scatter (Tx is zeroed there)
 template <typename T>
-hipError_t sst2_run(Sst2Dev<T> p, const Sst2Shape& s, int squeezing, const T* d_x, int64_t nb, cpx<T>* d_Tx, cpx<T>* d_Sx,
-                    T* d_w, cpx<T>* d_map, double* d_xd /* float32 calls: [nb][n_signal] */) {
-  if (hipError_t e = sst2_operator_run<T>(p, s, d_x, nb, d_Sx, d_map, d_xd); e != hipSuccess) return e;
-  return sst2_scatter_run<T>(s, squeezing, p.dw, nb, d_Sx, d_map, d_Tx, d_w);
-}
-
-template <typename T>
-int sst2_host_typed(const Sst2Shape& s, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
-                    int64_t hop, int padtype, int squeezing, int variant, void* Tx, void* Sx, void* w2) {
+struct Sst2Pipe {
+  static constexpr int kMid = 0;
+  const FrameCall& c;
+  const Sst2Shape& s;
   DeviceBufs d;
   Sst2Dev<T> p;
-  if (int rc = sst2_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p)) return rc;
-  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  const double per = (double)(sizeof(T) == 4 ? 12 : 8) * (double)n_signal + (double)map_sig * (3.0 * sizeof(cpx<T>) + (w2 ? sizeof(T) : 0));
-  const int64_t slice = slice_signals(batch, per, 0.0, batch);
-  void *d_x, *d_Tx, *d_Sx, *d_map, *d_w = nullptr, *d_xd = nullptr;
-  SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)n_signal * slice));
-  if (sizeof(T) == 4) SSQ_HIP(d.alloc(&d_xd, sizeof(double) * (size_t)n_signal * slice));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_Sx, sizeof(cpx<T>) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_map, sizeof(cpx<T>) * map_sig * slice));
-  if (w2) SSQ_HIP(d.alloc(&d_w, sizeof(T) * map_sig * slice));
-  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
-    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
-    SSQ_HIP(hipMemcpy(d_x, (const T*)x + (size_t)n_signal * b0, sizeof(T) * (size_t)n_signal * nb, hipMemcpyHostToDevice));
-    SSQ_HIP(sst2_run<T>(p, s, squeezing, (const T*)d_x, nb, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, (T*)d_w, (cpx<T>*)d_map, (double*)d_xd));
-    SSQ_HIP(hipMemcpy((cpx<T>*)Tx + map_sig * b0, d_Tx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
-    SSQ_HIP(hipMemcpy((cpx<T>*)Sx + map_sig * b0, d_Sx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
-    if (w2) SSQ_HIP(hipMemcpy((T*)w2 + map_sig * b0, d_w, sizeof(T) * map_sig * nb, hipMemcpyDeviceToHost));
-  }
-  return 0;
-}
-
-template <typename T>
-int sst2_exec_typed(const Sst2Shape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
-                    int64_t hop, int padtype, int squeezing, int variant, void* d_Tx, void* d_Sx, void* d_w2, void* d_work,
-                    float* kernel_ms) {
-  DeviceBufs d;
-  Sst2Dev<T> p;
-  if (int rc = sst2_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p)) return rc;
-  // the workspace: the map, then (float32 calls) the widened signals
-  double* d_xd = (double*)((char*)d_work + sizeof(cpx<T>) * (size_t)batch * (size_t)s.n_freqs * (size_t)s.n_frames);
-  return run_timed(kernel_ms, false, [&](hipEvent_t) -> int {
-    SSQ_HIP(sst2_run<T>(p, s, squeezing, (const T*)d_x, batch, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, (T*)d_w2, (cpx<T>*)d_work, d_xd));
+  cpx<T>*Tx, *Sx, *map;
+  T* w;
+  double* xd;
+  int tables() { return sst2_tables<T>(d, s, c, &p); }
+  int bind(int64_t cap, void* const* outs /* Tx, Sx, w2 */, void* work) {
+    const Sst2Work k = sst2_work(c.dtype, cap, c.n_signal, s);
+    Tx = (cpx<T>*)outs[0];
+    Sx = (cpx<T>*)outs[1];
+    w = (T*)outs[2];
+    map = (cpx<T>*)((char*)work + k.map);
+    xd = (double*)((char*)work + k.xd);
     return 0;
-  });
-}
+  }
+  int run(int64_t nb, const void* d_x, const hipEvent_t*) {
+    SSQ_HIP(sst2_operator_run<T>(p, s, (const T*)d_x, nb, Sx, map, xd));
+    SSQ_HIP(sst2_scatter_run<T>(s, c.squeezing, p.dw, nb, Sx, map, Tx, w));
+    return 0;
+  }
+};
 
 }  // namespace
 
@@ -371,14 +347,16 @@ int ssq_ssq_stft2_host(int dtype, const void* x, int64_t batch, int64_t n_signal
                        int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, void* Tx,
                        double* ssq_freqs, void* Sx, void* w2) {
   if (!x || !window || !Tx || !Sx) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant, squeezing};
   Sst2Shape s;
-  if (int rc = sst2_shape("ssq_stft2", nullptr, dtype, batch, n_signal, n_fft, hop, fs, padtype, squeezing, gamma, &s)) return rc;
-  if (ssq_freqs)
-    for (int64_t i = 0; i < s.n_freqs; ++i) ssq_freqs[i] = (variant & SSQ_VARIANT_FLIPUD) ? s.sfs[s.n_freqs - 1 - i] : s.sfs[i];
+  if (int rc = sst2_shape("ssq_stft2", nullptr, c, &s)) return rc;
+  fill_ssq_freqs(ssq_freqs, s.sfs, variant);
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32
-             ? sst2_host_typed<float>(s, x, batch, n_signal, window, n_fft, hop, padtype, squeezing, variant, Tx, Sx, w2)
-             : sst2_host_typed<double>(s, x, batch, n_signal, window, n_fft, hop, padtype, squeezing, variant, Tx, Sx, w2);
+  const size_t el = dtype == SSQ_F32 ? 4 : 8, map_el = (size_t)s.n_freqs * (size_t)s.n_frames * el;
+  const HostOut outs[] = {{Tx, 2 * map_el}, {Sx, 2 * map_el}, {w2, map_el}};
+  const size_t work = (size_t)sst2_work(dtype, 1, n_signal, s).bytes;
+  return dtype == SSQ_F32 ? pipe_host<Sst2Pipe<float>>(c, s, x, el * (size_t)n_signal, outs, work)
+                          : pipe_host<Sst2Pipe<double>>(c, s, x, el * (size_t)n_signal, outs, work);
 }
 
 int ssq_ssq_stft2_window_tables(const double* window, int64_t n_fft, double* g1, double* g2, double* tg, double* tg1) {
@@ -397,23 +375,23 @@ int ssq_ssq_stft2_window_tables(const double* window, int64_t n_fft, double* g1,
 
 int64_t ssq_ssq_stft2_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop) {
   Sst2Shape s;
-  if (sst2_shape("ssq_stft2", nullptr, dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, SSQ_SQUEEZE_SUM, -1.0, &s)) return -1;
-  return (int64_t)(dtype == SSQ_F32 ? 8 : 16) * batch * s.n_freqs * s.n_frames + (dtype == SSQ_F32 ? 8 * batch * n_signal : 0);
+  if (sst2_shape("ssq_stft2", nullptr, frame_sizes_call(dtype, batch, n_signal, n_fft, hop), &s)) return -1;
+  return sst2_work(dtype, batch, n_signal, s).bytes;
 }
 
 int ssq_ssq_stft2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
                        int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, void* d_Tx, void* d_Sx,
                        void* d_w2, void* d_workspace, int64_t workspace_bytes, float* kernel_ms) {
   if (!d_x || !window || !d_Tx || !d_Sx || !d_workspace) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant, squeezing};
   Sst2Shape s;
-  if (int rc = sst2_shape("ssq_stft2", nullptr, dtype, batch, n_signal, n_fft, hop, fs, padtype, squeezing, gamma, &s)) return rc;
-  if (workspace_bytes < ssq_ssq_stft2_workspace_bytes(dtype, batch, n_signal, n_fft, hop))
+  if (int rc = sst2_shape("ssq_stft2", nullptr, c, &s)) return rc;
+  if (workspace_bytes < sst2_work(dtype, batch, n_signal, s).bytes)
     SSQ_FAIL("ssq_stft2: workspace smaller than ssq_ssq_stft2_workspace_bytes");
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? sst2_exec_typed<float>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, squeezing, variant, d_Tx,
-                                                   d_Sx, d_w2, d_workspace, kernel_ms)
-                          : sst2_exec_typed<double>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, squeezing, variant,
-                                                    d_Tx, d_Sx, d_w2, d_workspace, kernel_ms);
+  void* const outs[] = {d_Tx, d_Sx, d_w2};
+  return dtype == SSQ_F32 ? pipe_exec<Sst2Pipe<float>>(c, s, d_x, outs, d_workspace, kernel_ms)
+                          : pipe_exec<Sst2Pipe<double>>(c, s, d_x, outs, d_workspace, kernel_ms);
 }
 
 }  // extern "C"

@@ -98,100 +98,54 @@ const char* tmsst_own_fail(int order, int n_iter) {
 }
 
 // tssq_stft's checks and shape, then the reach of the walked map: s->reach stays H, s->tile becomes the tile of n_iter H
-int tmsst_shape(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop, double fs, int padtype, int order,
-                int n_iter, double gamma, TsstShape* s) {
-  if (int rc = tsst_shape("tmssq_stft", tmsst_own_fail(order, n_iter), dtype, batch, n_signal, n_fft, hop, fs, padtype, order,
-                          gamma, s))
-    return rc;
-  if ((long long)n_iter * s->reach > kTsstWideReach)
+int tmsst_shape(const FrameCall& c, TsstShape* s) {
+  if (int rc = tsst_shape("tmssq_stft", tmsst_own_fail(c.order, c.n_iter), c, s)) return rc;
+  if ((long long)c.n_iter * s->reach > kTsstWideReach)
     SSQ_FAIL("tmssq_stft: n_iter * ceil(n_fft / (2 hop)) must not exceed 16384");
-  s->tile = tsst_tile((long long)n_iter * s->reach);
+  s->tile = tsst_tile((long long)c.n_iter * s->reach);
   return 0;
 }
 
-// the three parts of `nb` signals on device buffers; ev (may be nullptr): two events, recorded after the operator and
-// after the walk.  d_rel: the one-step plane the operator writes (p.out names it), d_rel2: the walked plane.
+// tmssq_stft on device buffers (pipe_host, pipe_exec), in tssq_stft's workspace with the walked plane (tsst_work): the
+// operator, the walk, the time scatter.  kernel_ms: three parts, the events recorded after the operator and after the
+// walk.  rel: the one-step plane the operator writes (p.out names it), rel2: the walked plane.
 template <typename T>
-hipError_t tmsst_run(const TsstDev<T>& p, TsstScat<T> sc, const TsstShape& s, int n_iter, const T* d_x, int64_t nb,
-                     cpx<T>* d_Tx, cpx<T>* d_Sx, short* d_rel, short* d_rel2, int* d_tgt, double* d_xd, hipEvent_t* ev) {
-  hipError_t e = tsst_operator_run<T>(p, s, d_x, nb, d_xd);
-  if (e != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[0], nullptr)) != hipSuccess) return e;
-  const short* final_rel = d_rel;
-  if (n_iter > 1 || d_tgt) {                                  // (one step, no targets asked for: the map is final)
-    e = tmsst_walk_run(d_rel, d_rel2, d_tgt, (long long)nb * s.n_freqs, (long long)s.n_frames, s.tile, (n_iter - 1) * s.reach,
-                       n_iter);
-    if (e != hipSuccess) return e;
-    final_rel = d_rel2;
-  }
-  if (ev && (e = hipEventRecord(ev[1], nullptr)) != hipSuccess) return e;
-  sc.reach = n_iter * s.reach;
-  sc.tile = s.tile;
-  return tsst_scatter_run<T>(sc, s, nb, d_Sx, final_rel, d_Tx, true);
-}
-
-template <typename T>
-int tmsst_host_typed(const TsstShape& s, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
-                     int64_t hop, int padtype, int variant, int n_iter, void* Tx, void* Sx, void* tau, int32_t* targets) {
+struct TmsstPipe {
+  static constexpr int kMid = 2;
+  const FrameCall& c;
+  const TsstShape& s;
   DeviceBufs d;
   TsstDev<T> p;
   TsstScat<T> sc;
-  if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
-  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  const double per = (double)(sizeof(T) == 4 ? 12 : 8) * (double)n_signal +
-                     (double)map_sig * (2.0 * sizeof(cpx<T>) + 2 * sizeof(short) + (tau ? sizeof(T) : 0) +
-                                        (targets ? sizeof(int32_t) : 0));
-  const int64_t slice = slice_signals(batch, per, 0.0, batch);
-  void *d_x, *d_Tx, *d_Sx, *d_rel, *d_rel2, *d_tau = nullptr, *d_tgt = nullptr, *d_xd = nullptr;
-  SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)n_signal * slice));
-  if (sizeof(T) == 4) SSQ_HIP(d.alloc(&d_xd, sizeof(double) * (size_t)n_signal * slice));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_Sx, sizeof(cpx<T>) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_rel, sizeof(short) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_rel2, sizeof(short) * map_sig * slice));
-  if (tau) SSQ_HIP(d.alloc(&d_tau, sizeof(T) * map_sig * slice));
-  if (targets) SSQ_HIP(d.alloc(&d_tgt, sizeof(int32_t) * map_sig * slice));
-  if (int rc = tsst_out_block<T>(d, s, hop, d_Sx, d_tau, d_rel, &p)) return rc;
-  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
-    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
-    SSQ_HIP(hipMemcpy(d_x, (const T*)x + (size_t)n_signal * b0, sizeof(T) * (size_t)n_signal * nb, hipMemcpyHostToDevice));
-    SSQ_HIP(tmsst_run<T>(p, sc, s, n_iter, (const T*)d_x, nb, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, (short*)d_rel, (short*)d_rel2,
-                         (int*)d_tgt, (double*)d_xd, nullptr));
-    SSQ_HIP(hipMemcpy((cpx<T>*)Tx + map_sig * b0, d_Tx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
-    SSQ_HIP(hipMemcpy((cpx<T>*)Sx + map_sig * b0, d_Sx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
-    if (tau) SSQ_HIP(hipMemcpy((T*)tau + map_sig * b0, d_tau, sizeof(T) * map_sig * nb, hipMemcpyDeviceToHost));
-    if (targets) SSQ_HIP(hipMemcpy(targets + map_sig * b0, d_tgt, sizeof(int32_t) * map_sig * nb, hipMemcpyDeviceToHost));
+  cpx<T>*Tx, *Sx;
+  int* tgt;
+  short *rel, *rel2;
+  double* xd;
+  int tables() { return tsst_tables<T>(d, s, c, &p, &sc); }
+  int bind(int64_t cap, void* const* outs /* Tx, Sx, tau, targets */, void* work) {
+    const TsstWork k = tsst_work(c.dtype, cap, c.n_signal, s, true);
+    Tx = (cpx<T>*)outs[0];
+    Sx = (cpx<T>*)outs[1];
+    tgt = (int*)outs[3];
+    xd = (double*)((char*)work + k.xd);
+    rel = (short*)((char*)work + k.rel);
+    rel2 = (short*)((char*)work + k.rel2);
+    sc.reach = c.n_iter * s.reach;
+    sc.tile = s.tile;
+    return tsst_out_block<T>(d, s, c.hop, Sx, outs[2], rel, &p);
   }
-  return 0;
-}
-
-template <typename T>
-int tmsst_exec_typed(const TsstShape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
-                     int64_t hop, int padtype, int variant, int n_iter, void* d_Tx, void* d_Sx, void* d_tau, int32_t* d_tgt,
-                     void* d_work, float* kernel_ms) {
-  DeviceBufs d;
-  TsstDev<T> p;
-  TsstScat<T> sc;
-  if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
-  // the workspace: ssq_tssq_stft_exec's ((float32 calls) the widened signals, then the one-step targets), then the walked targets
-  const size_t map_all = (size_t)batch * (size_t)s.n_freqs * (size_t)s.n_frames;
-  double* d_xd = (double*)d_work;
-  short* d_rel = (short*)((char*)d_work + (sizeof(T) == 4 ? sizeof(double) * (size_t)batch * (size_t)n_signal : 0));
-  short* d_rel2 = d_rel + map_all;
-  if (int rc = tsst_out_block<T>(d, s, hop, d_Sx, d_tau, d_rel, &p)) return rc;
-  TimingEvents t;
-  if (kernel_ms) SSQ_HIP(t.start(4, nullptr));
-  SSQ_HIP(tmsst_run<T>(p, sc, s, n_iter, (const T*)d_x, batch, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, d_rel, d_rel2, (int*)d_tgt, d_xd,
-                       kernel_ms ? &t.ev[1] : nullptr));
-  if (!kernel_ms) {
-    SSQ_HIP(hipDeviceSynchronize());
+  int run(int64_t nb, const void* d_x, const hipEvent_t* mid) {
+    SSQ_HIP(tsst_operator_run<T>(p, s, (const T*)d_x, nb, xd));
+    if (mid[0]) SSQ_HIP(hipEventRecord(mid[0], nullptr));
+    const bool walk = c.n_iter > 1 || tgt;                   // (one step, no targets asked for: the map is final)
+    if (walk)
+      SSQ_HIP(tmsst_walk_run(rel, rel2, tgt, (long long)nb * s.n_freqs, (long long)s.n_frames, s.tile,
+                             (c.n_iter - 1) * s.reach, c.n_iter));
+    if (mid[1]) SSQ_HIP(hipEventRecord(mid[1], nullptr));
+    SSQ_HIP(tsst_scatter_run<T>(sc, s, nb, Sx, walk ? rel2 : rel, Tx, true));
     return 0;
   }
-  SSQ_HIP(hipEventRecord(t.ev[3], nullptr));
-  SSQ_HIP(hipEventSynchronize(t.ev[3]));
-  for (int i = 0; i < 3; ++i) SSQ_HIP(hipEventElapsedTime(&kernel_ms[i], t.ev[i], t.ev[i + 1]));
-  return 0;
-}
+};
 
 // the checks ssq_tmsst_walk_host and ssq_tmsst_tile_frames share (sets the error and returns non-zero)
 int tmsst_reach_ok(int64_t reach, int n_iter) {
@@ -210,19 +164,23 @@ int ssq_tmssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signa
                         int64_t hop, double fs, int padtype, int order, double gamma, int variant, int n_iter, void* Tx,
                         void* Sx, void* tau, int32_t* targets) {
   if (!x || !window || !Tx || !Sx) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant, SSQ_SQUEEZE_SUM, order, n_iter};
   TsstShape s;
-  if (int rc = tmsst_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, order, n_iter, gamma, &s)) return rc;
+  if (int rc = tmsst_shape(c, &s)) return rc;
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? tmsst_host_typed<float>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, n_iter, Tx, Sx,
-                                                    tau, targets)
-                          : tmsst_host_typed<double>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, n_iter, Tx, Sx,
-                                                     tau, targets);
+  const size_t el = dtype == SSQ_F32 ? 4 : 8, map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
+  const HostOut outs[] = {{Tx, 2 * el * map_sig}, {Sx, 2 * el * map_sig}, {tau, el * map_sig}, {targets, sizeof(int32_t) * map_sig}};
+  const size_t work = (size_t)tsst_work(dtype, 1, n_signal, s, true).bytes;
+  return dtype == SSQ_F32 ? pipe_host<TmsstPipe<float>>(c, s, x, el * (size_t)n_signal, outs, work)
+                          : pipe_host<TmsstPipe<double>>(c, s, x, el * (size_t)n_signal, outs, work);
 }
 
 int64_t ssq_tmssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop, int n_iter) {
+  FrameCall c = frame_sizes_call(dtype, batch, n_signal, n_fft, hop);
+  c.n_iter = n_iter;
   TsstShape s;
-  if (tmsst_shape(dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, 2, n_iter, -1.0, &s)) return -1;
-  return (dtype == SSQ_F32 ? 8 * batch * n_signal : 0) + 4 * batch * s.n_freqs * s.n_frames;
+  if (tmsst_shape(c, &s)) return -1;
+  return tsst_work(dtype, batch, n_signal, s, true).bytes;
 }
 
 int ssq_tmssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
@@ -230,15 +188,15 @@ int ssq_tmssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_sig
                         void* d_Sx, void* d_tau, int32_t* d_targets, void* d_workspace, int64_t workspace_bytes,
                         float* kernel_ms) {
   if (!d_x || !window || !d_Tx || !d_Sx || !d_workspace) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant, SSQ_SQUEEZE_SUM, order, n_iter};
   TsstShape s;
-  if (int rc = tmsst_shape(dtype, batch, n_signal, n_fft, hop, fs, padtype, order, n_iter, gamma, &s)) return rc;
-  if (workspace_bytes < ssq_tmssq_stft_workspace_bytes(dtype, batch, n_signal, n_fft, hop, n_iter))
+  if (int rc = tmsst_shape(c, &s)) return rc;
+  if (workspace_bytes < tsst_work(dtype, batch, n_signal, s, true).bytes)
     SSQ_FAIL("tmssq_stft: workspace smaller than ssq_tmssq_stft_workspace_bytes");
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? tmsst_exec_typed<float>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, variant, n_iter, d_Tx,
-                                                    d_Sx, d_tau, d_targets, d_workspace, kernel_ms)
-                          : tmsst_exec_typed<double>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, variant, n_iter, d_Tx,
-                                                     d_Sx, d_tau, d_targets, d_workspace, kernel_ms);
+  void* const outs[] = {d_Tx, d_Sx, d_tau, d_targets};
+  return dtype == SSQ_F32 ? pipe_exec<TmsstPipe<float>>(c, s, d_x, outs, d_workspace, kernel_ms)
+                          : pipe_exec<TmsstPipe<double>>(c, s, d_x, outs, d_workspace, kernel_ms);
 }
 
 int ssq_tmsst_tile_frames(int64_t reach, int n_iter) {

@@ -1,5 +1,5 @@
 // stft_tsst.h -- what stft_tsst.hip lends to stft_tmsst.hip: the parameter blocks of its two kernels, the
-// argument checks and the shape, the call's tables on the device, and the two halves of the pipeline (operator, time
+// argument checks and the shape, the workspace layout, the call's tables on the device, and the two halves of the pipeline (operator, time
 // scatter) on device buffers.  The kernels and the host code are compiled once, in stft_tsst.hip, for float and double;
 // this header only declares them.
 #pragma once
@@ -68,13 +68,22 @@ inline int tsst_tile(long long reach) {
 
 // The argument checks of the entry points, and the shape they work on (sets the error and returns non-zero).  name: the
 // entry point's prefix of the messages; own_fail: the message of its own argument check that failed, or nullptr.
-int tsst_shape(const char* name, const char* own_fail, int dtype, int64_t batch, int64_t n_signal, int64_t n_fft,
-               int64_t hop, double fs, int padtype, int order, double gamma, TsstShape* s);
+int tsst_shape(const char* name, const char* own_fail, const FrameCall& c, TsstShape* s);
+
+// The workspace of `cap` signals of tssq_stft and (walked) tmssq_stft, as byte offsets: (float32 calls) the widened
+// signals, the one-step int16 targets, then tmssq_stft's walked ones.  The only place that knows the layout: the
+// workspace_bytes, exec and host doors all go through it.
+struct TsstWork {
+  int64_t xd, rel, rel2, bytes;
+};
+inline TsstWork tsst_work(int dtype, int64_t cap, int64_t n_signal, const FrameShape& s, bool walked) {
+  const int64_t xd_b = widened_bytes(dtype, cap, n_signal), rel_b = 2 * cap * s.n_freqs * s.n_frames;
+  return {0, xd_b, xd_b + rel_b, xd_b + (walked ? 2 : 1) * rel_b};
+}
 
 // the call's tables on the device (held by `d`) and the two parameter blocks without their signal / output pointers
 template <typename T>
-int tsst_tables(DeviceBufs& d, const TsstShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
-                int padtype, int variant, TsstDev<T>* p, TsstScat<T>* sc);
+int tsst_tables(DeviceBufs& d, const TsstShape& s, const FrameCall& c, TsstDev<T>* p, TsstScat<T>* sc);
 
 // the operator kernel's output block (TsstOut) on the device, held by `d`
 template <typename T>

@@ -329,19 +329,18 @@ static hipError_t tsst_launch(TsstDev<T> p, int logn, int order, long long batch
 }
 
 // The argument checks of the entry points, and the shape they work on (sets the error and returns non-zero)
-int tsst_shape(const char* name, const char* own_fail, int dtype, int64_t batch, int64_t n_signal, int64_t n_fft,
-               int64_t hop, double fs, int padtype, int order, double gamma, TsstShape* s) {
-  if (int rc = frame_shape(name, true, own_fail, dtype, batch, n_signal, n_fft, hop, fs, padtype, gamma, s)) return rc;
-  s->order = order;
+int tsst_shape(const char* name, const char* own_fail, const FrameCall& c, TsstShape* s) {
+  if (int rc = frame_shape(name, true, own_fail, c, s)) return rc;
+  s->order = c.order;
   s->tile = tsst_tile(s->reach);                             // halo re-read (tile + 2 H) / tile <= 2
   return 0;
 }
 
 // the call's tables on the device (held by `d`) and the two parameter blocks without their signal / output pointers
 template <typename T>
-int tsst_tables(DeviceBufs& d, const TsstShape& s, const double* window, int64_t n, int64_t n_signal, int64_t hop,
-                int padtype, int variant, TsstDev<T>* p, TsstScat<T>* sc) {
-  const host::SstTables t = host::sst_level_tables(window, n, s.order == 1 ? host::kSstTimeFirst : host::kSstSecond);
+int tsst_tables(DeviceBufs& d, const TsstShape& s, const FrameCall& c, TsstDev<T>* p, TsstScat<T>* sc) {
+  const int64_t n = c.n_fft;
+  const host::SstTables t = host::sst_level_tables(c.window, n, s.order == 1 ? host::kSstTimeFirst : host::kSstSecond);
   const std::vector<double> tw = host::pass_twiddles(s.logn);
   std::vector<cpx<double>> rot((size_t)n);
   for (int64_t j = 0; j < n; ++j) {
@@ -359,11 +358,11 @@ int tsst_tables(DeviceBufs& d, const TsstShape& s, const double* window, int64_t
   p->wa = (const cpx<double>*)d_wa;
   p->wb = (const double*)d_wb;
   p->wc = (const cpx<double>*)d_wc;
-  p->n_signal = n_signal;
+  p->n_signal = c.n_signal;
   p->n_frames = s.n_frames;
-  p->hop = (int)hop;
-  p->padtype = padtype;
-  p->rot = (variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
+  p->hop = (int)c.hop;
+  p->padtype = c.padtype;
+  p->rot = (c.variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
   p->gamma = s.gamma;
   p->gamma_sq = s.gamma * s.gamma;
   p->h1 = t.h1;
@@ -375,7 +374,7 @@ int tsst_tables(DeviceBufs& d, const TsstShape& s, const double* window, int64_t
   sc->n_frames = s.n_frames;
   sc->n_freqs = (int)s.n_freqs;
   sc->n = (int)n;
-  sc->hop = (int)hop;
+  sc->hop = (int)c.hop;
   sc->reach = s.reach;
   sc->tile = s.tile;
   return 0;
@@ -443,8 +442,7 @@ hipError_t tsst_scatter_run(TsstScat<T> sc, const TsstShape& s, int64_t nb, cons
 }
 
 #define SSQ_TSST_INSTANTIATE(T)                                                                                          \
-  template int tsst_tables<T>(DeviceBufs&, const TsstShape&, const double*, int64_t, int64_t, int64_t, int, int,        \
-                              TsstDev<T>*, TsstScat<T>*);                                                                \
+  template int tsst_tables<T>(DeviceBufs&, const TsstShape&, const FrameCall&, TsstDev<T>*, TsstScat<T>*);              \
   template int tsst_out_block<T>(DeviceBufs&, const TsstShape&, int64_t, void*, void*, void*, TsstDev<T>*);             \
   template hipError_t tsst_operator_run<T>(TsstDev<T>, const TsstShape&, const T*, int64_t, double*);                    \
   template hipError_t tsst_scatter_run<T>(TsstScat<T>, const TsstShape&, int64_t, const cpx<T>*, const short*, cpx<T>*,  \
@@ -461,63 +459,35 @@ namespace {
 
 const char* tsst_own_fail(int order) { return order == 1 || order == 2 ? nullptr : "order must be 1 or 2"; }
 
-// both kernels of `nb` signals on device buffers; ev (may be nullptr): an event recorded between the two
+// tssq_stft on device buffers (pipe_host, pipe_exec): the operator, then the time scatter.  kernel_ms: two parts, the
+// event recorded between the two.
 template <typename T>
-hipError_t tsst_run(TsstDev<T> p, TsstScat<T> sc, const TsstShape& s, const T* d_x, int64_t nb, cpx<T>* d_Tx, cpx<T>* d_Sx,
-                    short* d_rel, double* d_xd /* float32 calls: [nb][n_signal] */, hipEvent_t ev) {
-  hipError_t e = tsst_operator_run<T>(p, s, d_x, nb, d_xd);
-  if (e != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev, nullptr)) != hipSuccess) return e;
-  return tsst_scatter_run<T>(sc, s, nb, d_Sx, d_rel, d_Tx, false);
-}
-
-template <typename T>
-int tsst_host_typed(const TsstShape& s, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
-                    int64_t hop, int padtype, int variant, void* Tx, void* Sx, void* tau) {
+struct TsstPipe {
+  static constexpr int kMid = 1;
+  const FrameCall& c;
+  const TsstShape& s;
   DeviceBufs d;
   TsstDev<T> p;
   TsstScat<T> sc;
-  if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
-  const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  const double per = (double)(sizeof(T) == 4 ? 12 : 8) * (double)n_signal +
-                     (double)map_sig * (2.0 * sizeof(cpx<T>) + sizeof(short) + (tau ? sizeof(T) : 0));
-  const int64_t slice = slice_signals(batch, per, 0.0, batch);
-  void *d_x, *d_Tx, *d_Sx, *d_rel, *d_tau = nullptr, *d_xd = nullptr;
-  SSQ_HIP(d.alloc(&d_x, sizeof(T) * (size_t)n_signal * slice));
-  if (sizeof(T) == 4) SSQ_HIP(d.alloc(&d_xd, sizeof(double) * (size_t)n_signal * slice));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_Sx, sizeof(cpx<T>) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_rel, sizeof(short) * map_sig * slice));
-  if (tau) SSQ_HIP(d.alloc(&d_tau, sizeof(T) * map_sig * slice));
-  if (int rc = tsst_out_block<T>(d, s, hop, d_Sx, d_tau, d_rel, &p)) return rc;
-  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
-    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
-    SSQ_HIP(hipMemcpy(d_x, (const T*)x + (size_t)n_signal * b0, sizeof(T) * (size_t)n_signal * nb, hipMemcpyHostToDevice));
-    SSQ_HIP(tsst_run<T>(p, sc, s, (const T*)d_x, nb, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, (short*)d_rel, (double*)d_xd, nullptr));
-    SSQ_HIP(hipMemcpy((cpx<T>*)Tx + map_sig * b0, d_Tx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
-    SSQ_HIP(hipMemcpy((cpx<T>*)Sx + map_sig * b0, d_Sx, sizeof(cpx<T>) * map_sig * nb, hipMemcpyDeviceToHost));
-    if (tau) SSQ_HIP(hipMemcpy((T*)tau + map_sig * b0, d_tau, sizeof(T) * map_sig * nb, hipMemcpyDeviceToHost));
+  cpx<T>*Tx, *Sx;
+  short* rel;
+  double* xd;
+  int tables() { return tsst_tables<T>(d, s, c, &p, &sc); }
+  int bind(int64_t cap, void* const* outs /* Tx, Sx, tau */, void* work) {
+    const TsstWork k = tsst_work(c.dtype, cap, c.n_signal, s, false);
+    Tx = (cpx<T>*)outs[0];
+    Sx = (cpx<T>*)outs[1];
+    xd = (double*)((char*)work + k.xd);
+    rel = (short*)((char*)work + k.rel);
+    return tsst_out_block<T>(d, s, c.hop, Sx, outs[2], rel, &p);
   }
-  return 0;
-}
-
-template <typename T>
-int tsst_exec_typed(const TsstShape& s, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n,
-                    int64_t hop, int padtype, int variant, void* d_Tx, void* d_Sx, void* d_tau, void* d_work,
-                    float* kernel_ms) {
-  DeviceBufs d;
-  TsstDev<T> p;
-  TsstScat<T> sc;
-  if (int rc = tsst_tables<T>(d, s, window, n, n_signal, hop, padtype, variant, &p, &sc)) return rc;
-  // the workspace: (float32 calls) the widened signals, then the relative targets
-  double* d_xd = (double*)d_work;
-  short* d_rel = (short*)((char*)d_work + (sizeof(T) == 4 ? sizeof(double) * (size_t)batch * (size_t)n_signal : 0));
-  if (int rc = tsst_out_block<T>(d, s, hop, d_Sx, d_tau, d_rel, &p)) return rc;
-  return run_timed(kernel_ms, true, [&](hipEvent_t mid) -> int {
-    SSQ_HIP(tsst_run<T>(p, sc, s, (const T*)d_x, batch, (cpx<T>*)d_Tx, (cpx<T>*)d_Sx, d_rel, d_xd, mid));
+  int run(int64_t nb, const void* d_x, const hipEvent_t* mid) {
+    SSQ_HIP(tsst_operator_run<T>(p, s, (const T*)d_x, nb, xd));
+    if (mid[0]) SSQ_HIP(hipEventRecord(mid[0], nullptr));
+    SSQ_HIP(tsst_scatter_run<T>(sc, s, nb, Sx, rel, Tx, false));
     return 0;
-  });
-}
+  }
+};
 
 }  // namespace
 
@@ -527,36 +497,36 @@ int ssq_tssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal
                        int64_t hop, double fs, int padtype, int order, double gamma, int variant, void* Tx, void* Sx,
                        void* tau) {
   if (!x || !window || !Tx || !Sx) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant, SSQ_SQUEEZE_SUM, order};
   TsstShape s;
-  if (int rc = tsst_shape("tssq_stft", tsst_own_fail(order), dtype, batch, n_signal, n_fft, hop, fs, padtype, order, gamma,
-                          &s))
-    return rc;
+  if (int rc = tsst_shape("tssq_stft", tsst_own_fail(order), c, &s)) return rc;
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? tsst_host_typed<float>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, Tx, Sx, tau)
-                          : tsst_host_typed<double>(s, x, batch, n_signal, window, n_fft, hop, padtype, variant, Tx, Sx, tau);
+  const size_t el = dtype == SSQ_F32 ? 4 : 8, map_el = (size_t)s.n_freqs * (size_t)s.n_frames * el;
+  const HostOut outs[] = {{Tx, 2 * map_el}, {Sx, 2 * map_el}, {tau, map_el}};
+  const size_t work = (size_t)tsst_work(dtype, 1, n_signal, s, false).bytes;
+  return dtype == SSQ_F32 ? pipe_host<TsstPipe<float>>(c, s, x, el * (size_t)n_signal, outs, work)
+                          : pipe_host<TsstPipe<double>>(c, s, x, el * (size_t)n_signal, outs, work);
 }
 
 int64_t ssq_tssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop) {
   TsstShape s;
-  if (tsst_shape("tssq_stft", nullptr, dtype, batch, n_signal, n_fft, hop, 1.0, SSQ_PAD_REFLECT, 2, -1.0, &s)) return -1;
-  return (dtype == SSQ_F32 ? 8 * batch * n_signal : 0) + 2 * batch * s.n_freqs * s.n_frames;
+  if (tsst_shape("tssq_stft", nullptr, frame_sizes_call(dtype, batch, n_signal, n_fft, hop), &s)) return -1;
+  return tsst_work(dtype, batch, n_signal, s, false).bytes;
 }
 
 int ssq_tssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
                        int64_t hop, double fs, int padtype, int order, double gamma, int variant, void* d_Tx, void* d_Sx,
                        void* d_tau, void* d_workspace, int64_t workspace_bytes, float* kernel_ms) {
   if (!d_x || !window || !d_Tx || !d_Sx || !d_workspace) SSQ_FAIL("NULL argument");
+  const FrameCall c{dtype, batch, n_signal, window, n_fft, hop, fs, padtype, gamma, variant, SSQ_SQUEEZE_SUM, order};
   TsstShape s;
-  if (int rc = tsst_shape("tssq_stft", tsst_own_fail(order), dtype, batch, n_signal, n_fft, hop, fs, padtype, order, gamma,
-                          &s))
-    return rc;
-  if (workspace_bytes < ssq_tssq_stft_workspace_bytes(dtype, batch, n_signal, n_fft, hop))
+  if (int rc = tsst_shape("tssq_stft", tsst_own_fail(order), c, &s)) return rc;
+  if (workspace_bytes < tsst_work(dtype, batch, n_signal, s, false).bytes)
     SSQ_FAIL("tssq_stft: workspace smaller than ssq_tssq_stft_workspace_bytes");
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? tsst_exec_typed<float>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, variant, d_Tx, d_Sx,
-                                                   d_tau, d_workspace, kernel_ms)
-                          : tsst_exec_typed<double>(s, d_x, batch, n_signal, window, n_fft, hop, padtype, variant, d_Tx, d_Sx,
-                                                    d_tau, d_workspace, kernel_ms);
+  void* const outs[] = {d_Tx, d_Sx, d_tau};
+  return dtype == SSQ_F32 ? pipe_exec<TsstPipe<float>>(c, s, d_x, outs, d_workspace, kernel_ms)
+                          : pipe_exec<TsstPipe<double>>(c, s, d_x, outs, d_workspace, kernel_ms);
 }
 
 }  // extern "C"

@@ -1,0 +1,117 @@
+"""The slices of the synchronous host entry points after the first (csrc/dev_buffers.h: `slice_signals`, `host_sliced`).
+
+A host entry point keeps as many signals on the device as fit, and every test shape of the suite fits whole: without a cap
+the loop over slices runs once and `b0 > 0` never happens.  `ssq_host_slice_cap` (include/ssq_hip.h) caps the slice for
+the whole process, so here every caller of `slice_signals` runs 5 signals in slices of 2, 2, 1 and of 1, and every array
+it returns must equal the uncapped call's bit for bit (`np.array_equal`): the H2D offset of a slice, the D2H offset of
+every output, the optional outputs, and a workspace carved for fewer signals than the batch.
+
+The STFT family runs its smallest shape (5 signals of 32 samples, n_fft 16, hop 8: tests/test_gpu_grid_limits.py's);
+the signals differ and each carries an impulse, which moves time targets."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from ssqueeze_rs_amd import _lib
+from ssqueeze_rs_amd import upstream as up
+from tests.test_gpu_grid_limits import FS, HOP, N_ST, NFFT, STFT_IDS, STFT_RUNS, base_signals, gwin, stft_host
+
+pytestmark = pytest.mark.gpu
+
+B = 5
+CAPS = (2, 1)
+DTYPES = pytest.mark.parametrize("rdt", [np.float64, np.float32], ids=["f64", "f32"])
+
+
+def signals(rdt):
+    """[5, 32]: five different base signals of the grid-limits module and on each, at another sample, an impulse six times
+    its largest sample, 5 samples from the centre of a frame (hop 8: more than half a hop, so the frame's bins move)."""
+    X = base_signals(N_ST)[:B].copy()
+    for b, at in enumerate((5, 11, 13, 19, 29)):
+        X[b, at] += 6.0 * np.abs(X[b]).max()
+    return X.astype(rdt)
+
+
+def capped(call):
+    """-> [the arrays of call() without a cap, with slices of 2, with slices of 1]; the cap is 0 again afterwards."""
+    lib = _lib.load()
+    try:
+        runs = []
+        for cap in (0,) + CAPS:
+            _lib.check(lib.ssq_host_slice_cap(cap))
+            runs.append([np.array(a, copy=True) for a in call()])
+    finally:
+        _lib.check(lib.ssq_host_slice_cap(0))
+    return runs
+
+
+def assert_slices_change_nothing(call, what):
+    whole, *sliced = capped(call)
+    assert len(whole) > 0
+    for cap, got in zip(CAPS, sliced):
+        assert len(got) == len(whole)
+        for k, (a, w) in enumerate(zip(got, whole)):
+            assert a.dtype == w.dtype and a.shape == w.shape and w.shape[0] == B, (what, cap, k)
+            assert np.array_equal(a, w, equal_nan=a.dtype.kind in "fc"), "%s: plane %d differs at a cap of %d" % (what, k, cap)
+
+
+def test_signals_differ_and_move_targets():
+    X = signals(np.float64)
+    assert all(not np.array_equal(X[a], X[b]) for a in range(B) for b in range(a))
+    targets = up.tmssq_stft(X, gwin(), n_fft=NFFT, hop_len=HOP, fs=FS, n_iter=1, get_targets=True)[4]
+    frames = np.arange(targets.shape[-1])
+    assert all(((targets[b] >= 0) & (targets[b] != frames)).any() for b in range(B))
+
+
+@DTYPES
+@pytest.mark.parametrize("name,order", STFT_RUNS, ids=STFT_IDS)
+def test_stft_family(name, order, rdt):
+    """ssq_stft2; mssq_stft orders 1 and 2, n_iter 3; tssq_stft orders 1 and 2; reassign_stft: every optional output."""
+    X = signals(rdt)
+    assert_slices_change_nothing(lambda: stft_host(name, order, X, "reflect"), name)
+
+
+@DTYPES
+def test_tmssq_stft(rdt):
+    X = signals(rdt)
+
+    def call():
+        out = up.tmssq_stft(X, gwin(), n_fft=NFFT, hop_len=HOP, fs=FS, order=2, n_iter=2, get_tau=True, get_targets=True)
+        return [out[0], out[1], out[4], out[5]]
+    assert_slices_change_nothing(call, "tmssq_stft")
+
+
+@pytest.mark.parametrize("cdt", [np.complex128, np.complex64], ids=["c128", "c64"])
+def test_batched_inverses(cdt, monkeypatch):
+    """`istft` on the fused kernel (its host path slices; the switch holds this small shape on it), and the row sums of
+    `issq_stft` and `issq_cwt`."""
+    rng = np.random.default_rng(11)
+    nfr = (N_ST - 1) // HOP + 1
+    monkeypatch.setenv("SSQ_ISTFT_FUSED", "1")
+    fused = C.c_int(-1)
+    _lib.load().ssq_istft_batch_workspace_bytes(_lib.SSQ_F64, B, nfr, NFFT, HOP, N_ST, C.byref(fused))
+    assert fused.value == 1
+    S = (rng.standard_normal((B, NFFT // 2 + 1, nfr)) + 1j * rng.standard_normal((B, NFFT // 2 + 1, nfr))).astype(cdt)
+    T = (rng.standard_normal((B, NFFT // 2 + 1, N_ST)) + 1j * rng.standard_normal((B, NFFT // 2 + 1, N_ST))).astype(cdt)
+    win = gwin()
+    assert_slices_change_nothing(lambda: [up.istft(S, win, n_fft=NFFT, hop_len=HOP, N=N_ST)], "istft")
+    assert_slices_change_nothing(lambda: [up.issq_stft(T, win, n_fft=NFFT)], "issq_stft")
+    assert_slices_change_nothing(lambda: [up.issq_cwt(T, "gmw")], "issq_cwt")
+
+
+def test_walk_hosts():
+    """msst_walk, tmsst_walk, mssq_cwt_walk and tmssq_cwt_walk, which repack every slice on the host: [5, 9, 4] maps."""
+    rng = np.random.default_rng(12)
+    R, n = NFFT // 2 + 1, (N_ST - 1) // HOP + 1
+    bins = rng.integers(-1, R, size=(B, R, n)).astype(np.int32)
+    assert_slices_change_nothing(lambda: [up.msst_walk(bins, 3)], "msst_walk")
+    step = rng.integers(-1, 2, size=(B, R, n))
+    targets = np.where(rng.random((B, R, n)) < 0.25, -1, np.clip(np.arange(n) + step, 0, n - 1)).astype(np.int32)
+    assert_slices_change_nothing(lambda: [up.tmsst_walk(targets, 3, 1)], "tmsst_walk")
+    anywhere = rng.integers(-1, n, size=(B, R, n)).astype(np.int32)
+    assert_slices_change_nothing(lambda: [up.tmssq_cwt_walk(anywhere, 3)], "tmssq_cwt_walk")
+    f = 0.5 * 2.0 ** ((np.arange(R) - (R - 1)) / 16)                       # an ascending log grid
+    w = np.where(bins >= 0, f[np.maximum(bins, 0)], np.inf)
+    rho = rng.permutation(R)
+    assert_slices_change_nothing(lambda: list(up.mssq_cwt_walk(w, f, rho, 3)), "mssq_cwt_walk")

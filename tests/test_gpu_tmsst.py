@@ -241,3 +241,41 @@ def test_walk_of_random_maps(reach, n_iter):
         far = np.abs(want - np.arange(n))[want >= 0].max(initial=0)
         print("n %d, batch %s, tile %d: largest displacement %d of %d" % (n, B, T, far, reach * n_iter))
         assert np.array_equal(got, want), (n, B)
+
+
+# ------------------------------------------------------------------------------------------------ the device door ----
+@DTYPES
+def test_device_door_equals_the_host_call(rdt):
+    """`ssq_tmssq_stft_exec` on buffers from `ssq_dev_malloc`, a workspace of exactly `ssq_tmssq_stft_workspace_bytes` and
+    guards behind every buffer (tests/test_gpu_grid_limits.py's Door): Tx, Sx, tau and targets equal `tmssq_stft`'s bit
+    for bit.  The family's smallest shape, 5 different signals with an impulse each (tests/test_gpu_host_slices.py)."""
+    import ctypes as C
+
+    from ssqueeze_rs_amd import _lib
+    from tests.test_gpu_grid_limits import FS as FS_ST
+    from tests.test_gpu_grid_limits import HOP, NFFT, Door, assert_same, gwin
+    from tests.test_gpu_host_slices import signals
+    lib = _lib.load()
+    X = signals(rdt)
+    B, N = X.shape
+    code = _lib.SSQ_F32 if rdt == np.float32 else _lib.SSQ_F64
+    cdt = np.complex64 if rdt == np.float32 else np.complex128
+    win = gwin()
+    shape = (B, NFFT // 2 + 1, (N - 1) // HOP + 1)
+    cells = int(np.prod(shape))
+    for order, n_iter in ((2, 2), (1, 3)):
+        out = up.tmssq_stft(X, win, n_fft=NFFT, hop_len=HOP, fs=FS_ST, order=order, n_iter=n_iter, get_tau=True,
+                            get_targets=True)
+        host = [out[0], out[1], out[4], out[5]]
+        ws = int(lib.ssq_tmssq_stft_workspace_bytes(code, B, N, NFFT, HOP, n_iter))
+        assert ws > 0
+        with Door() as d:
+            dx, dws = d.buf(X.nbytes, X), d.buf(ws)
+            dT, dS = d.buf(cells * np.dtype(cdt).itemsize), d.buf(cells * np.dtype(cdt).itemsize)
+            dtau, dtg = d.buf(cells * np.dtype(rdt).itemsize), d.buf(cells * 4)
+            _lib.check(lib.ssq_tmssq_stft_exec(code, dx.p, B, N, win.ctypes.data_as(C.c_void_p), NFFT, HOP, FS_ST,
+                                               up.PAD_MODES["reflect"], order, -1.0, 3, n_iter, dT.p, dS.p, dtau.p, dtg.p,
+                                               dws.p, ws, None))
+            dev = [dT.get(shape, cdt), dS.get(shape, cdt), dtau.get(shape, rdt), dtg.get(shape, np.int32)]
+        for name, a, h in zip(("Tx", "Sx", "tau", "targets"), dev, host):
+            assert_same(a, np.ascontiguousarray(h), "order %d: device %s against the host call's" % (order, name))

@@ -249,3 +249,16 @@ def test_c_entry_points_refuse_on_the_host():
         m[1, 8, 4] = v
         assert lib.ssq_tmsst_walk_host(_vp(m), 2, 9, 5, 2, 3, _vp(o)) != 0
         assert word in lib.ssq_last_error().decode()
+
+
+def test_host_slice_cap_is_exported_bound_and_refuses_a_negative_cap():
+    """`ssq_host_slice_cap` (include/ssq_hip.h: an aid for testing the host slices; tests/test_gpu_host_slices.py uses it)."""
+    lib = _lib.load()
+    assert "ssq_host_slice_cap" in _lib.header_symbols()
+    assert _lib._SIGNATURES["ssq_host_slice_cap"] == (C.c_int, [i64])
+    try:
+        assert lib.ssq_host_slice_cap(-1) != 0
+        assert lib.ssq_last_error().decode() == "ssq_host_slice_cap: signals must be >= 0 (0: no cap)"
+        assert lib.ssq_host_slice_cap(3) == 0
+    finally:
+        assert lib.ssq_host_slice_cap(0) == 0
