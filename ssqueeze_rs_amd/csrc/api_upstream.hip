@@ -198,7 +198,7 @@ int istft_batch_exec_typed(const void* d_Sx, int64_t batch, int64_t n_frames, co
     SSQ_HIP(d.alloc(&d_Z, sizeof(cpx<T>) * n * n_frames));
     SSQ_HIP(d.alloc(&d_work, sizeof(cpx<T>) * (we > 0 ? we : 1)));
   }
-  return run_timed(kernel_ms, 0, [&](const hipEvent_t*) -> int {
+  return run_timed(kernel_ms, 0, nullptr, [&](const hipEvent_t*) -> int {
     if (fused) {
       for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
         const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;

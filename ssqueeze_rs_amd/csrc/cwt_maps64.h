@@ -1,6 +1,7 @@
 // cwt_maps64.h -- the fp64 map pipeline that cwt_sst2.hip (ssq_cwt2), cwt_reassign.hip (reassign_cwt) and cwt_tsst.hip
-// (tssq_cwt) share.  A self-contained pipeline beside the tuned CWT plan (api_cwt.hip and its kernels are
-// not involved).  Per-sample units.  With P, n1, n2 = p2up(N), xh the forward DFT of the padded signal, xi_k = 2 pi k / P
+// (tssq_cwt) share, and through the halves those lend, cwt_msst.hip (mssq_cwt) and cwt_tmsst.hip
+// (tmssq_cwt).  A self-contained pipeline beside the tuned CWT plan (api_cwt.hip and its kernels are not involved).
+// Per-sample units.  With P, n1, n2 = p2up(N), xh the forward DFT of the padded signal, xi_k = 2 pi k / P
 // (k <= P/2, analytic tables: zero above) and, for scale a, T0(k) = psih(a xi_k), T1(k) = a psih'(a xi_k)
 // (cwt_sst2_wavelets.h; both halved at 2k == P), a row (signal, scale) has up to five maps:
 //   W = F^-1[xh T0]   W1 = F^-1[xh i xi T0]   W2 = F^-1[xh (-xi^2) T0]   Wt = F^-1[xh (-i) T1]   Wt1 = F^-1[xh xi T1]
@@ -16,9 +17,11 @@
 // (the decision of DESIGN 4.11, taken over).  A row is transformed on its own by every kernel, so its result depends
 // neither on the chunk it is in nor on the batch.  Here too: what the operator, scatter and read-out kernels of the two
 // scatter transforms share (the maximum's reduction, the time rule, the power of two of a quantum), and the shape,
-// workspace arithmetic and argument checks of the entry points.  The workspace is a fixed head of the transform's own
-// (the signals' maxima, its accumulators and targets; none for ssq_cwt2), then xh [batch][P] and a chunk area of R rows:
-// [R][M][P] spectra and as much again for the transforms' ping-pong.
+// workspace layout and argument checks of the entry points.  The workspace is a fixed head of the transform's own
+// (cwt_head: mssq_cwt's w_n plane, or the signals' maxima, the accumulators and the int32 target planes; none for
+// ssq_cwt2), then xh [batch][P] and a chunk area of R rows: [R][M][P] spectra and as much again for the transforms'
+// ping-pong.  Each transform is one pipe struct (tables, bind, run) behind the two doors of dev_buffers.h; the doors
+// take the batch whole (cwt_pipe_host), because the workspace is not linear in the signals.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -151,23 +154,35 @@ struct CwtMapsKind {
   const char* name;            // the prefix of its messages
   const char* bytes_fn;        // its *_workspace_bytes function, named by the workspace messages
   double big_bytes, big_limit; // batch na N big_bytes > big_limit: "transform too large"
-  int cell_bytes;              // its accumulators and targets per (signal, row, column) in the head; 0: no head, and no
-                               // na N <= 2^40 limit (ssq_cwt2 scatters without accumulators)
+  // its head, per (signal, row, column): planes of the call's real dtype in front (mssq_cwt's w_n), bytes of accumulator
+  // (0: no maxima either, and no na N <= 2^40 limit: ssq_cwt2 and mssq_cwt scatter without accumulators), int32 planes
+  int real_planes, acc_bytes, int_planes;
 };
 
-// what the entry points of the three transforms take in common
+// what the entry points of the transforms take in common; st: the stream of a device entry point (the host doors run
+// on the null stream).  A transform's own call struct derives from it.
 struct CwtMapsCall {
   int dtype, wavelet, padtype;
   int64_t batch, N, na;
   double p0, p1, dt, gamma;
   const double* scales;
+  hipStream_t st;
+};
+
+// The head of a workspace, the one layout of every kind (byte offsets): the real planes [cells] each, the signals'
+// maxima [batch] (to a multiple of 16 bytes), the accumulators [cells] and the int32 planes [cells] each; `bytes` to a
+// multiple of 16.  The maxima and the accumulators (emax .. planes) are what a call zeroes.
+struct CwtHead {
+  int64_t emax = 0, acc = 0, planes = 0, bytes = 0;
 };
 
 struct CwtMapsShape {
-  int64_t P = 0, n1 = 0, n2 = 0, rows = 0, plane = 0;
+  int64_t P = 0, n1 = 0, n2 = 0, rows = 0, plane = 0, cells = 0;
   int maps = 0;
   double gamma = 0.0;
-  int64_t head_bytes = 0, min_bytes = 0, pref_bytes = 0;
+  CwtHead head;
+  int64_t min_bytes = 0, pref_bytes = 0;
+  int64_t work_bytes = 0;      // of the workspace the call runs in (cwt_exec_bytes, cwt_host_bytes): sets the rows per chunk
 };
 
 // xh and the chunk area of R rows; the signals' maxima [batch] to a multiple of 16 bytes; rows per chunk in `bytes`
@@ -175,6 +190,18 @@ inline int64_t cwt_chunk_bytes(int64_t batch, int64_t P, int64_t R, int maps) { 
 inline int64_t cwt_emax_bytes(int64_t batch) { return (8 * batch + 15) / 16 * 16; }
 inline int64_t cwt_chunk_rows(int64_t bytes, int64_t batch, int64_t P, int maps) {
   return (bytes - 16 * P * batch) / (16 * P * 2 * maps);
+}
+inline CwtHead cwt_head(const CwtMapsKind& k, int dtype, int64_t batch, int64_t cells) {
+  CwtHead h;
+  h.emax = (k.real_planes * (dtype == SSQ_F32 ? 4 : 8) * cells + 15) / 16 * 16;
+  h.acc = h.emax + (k.acc_bytes ? cwt_emax_bytes(batch) : 0);
+  h.planes = h.acc + k.acc_bytes * cells;
+  h.bytes = (h.planes + 4 * k.int_planes * cells + 15) / 16 * 16;
+  return h;
+}
+template <typename P>
+P* cwt_head_at(void* d_work, int64_t offset) {
+  return reinterpret_cast<P*>(static_cast<char*>(d_work) + offset);
 }
 
 // The limits of the three transforms and the shape they work on (sets the error and returns non-zero).  own_fail: the
@@ -187,18 +214,19 @@ inline int cwt_maps_shape(const CwtMapsKind& k, int maps, const char* own_fail, 
   if (own_fail) SSQ_FAIL(pre + own_fail);
   if (N < 2 || N > ((int64_t)1 << 26)) SSQ_FAIL(pre + "n_signal must be in [2, 2^26]");
   if (na < 2 || na > 32767) SSQ_FAIL(pre + "na must be in [2, 32767]");
-  if (k.cell_bytes && na * N > ((int64_t)1 << 40)) SSQ_FAIL(pre + "na * n_signal must be <= 2^40");
+  if (k.acc_bytes && na * N > ((int64_t)1 << 40)) SSQ_FAIL(pre + "na * n_signal must be <= 2^40");
   host::p2up(N, &s->P, &s->n1, &s->n2);
   if (s->P < N || (s->P & (s->P - 1)) != 0) SSQ_FAIL(pre + "bad padded length");
   if ((double)batch * (double)na * (double)N * k.big_bytes > k.big_limit || (double)batch * (double)s->P * 16.0 > 4.0e18)
     SSQ_FAIL(pre + "transform too large");
   s->rows = batch * na;
   s->plane = na * N;
+  s->cells = batch * s->plane;
   s->maps = maps;
-  s->head_bytes = k.cell_bytes ? cwt_emax_bytes(batch) + (k.cell_bytes * batch * s->plane + 15) / 16 * 16 : 0;
-  s->min_bytes = cwt_chunk_bytes(batch, s->P, 1, maps) + s->head_bytes;
+  s->head = cwt_head(k, dtype, batch, s->cells);
+  s->min_bytes = cwt_chunk_bytes(batch, s->P, 1, maps) + s->head.bytes;
   const int64_t R = std::max<int64_t>(1, std::min(cwt_chunk_rows(kCwtDefaultWorkBytes, batch, s->P, maps), s->rows));
-  s->pref_bytes = cwt_chunk_bytes(batch, s->P, R, maps) + s->head_bytes;
+  s->pref_bytes = cwt_chunk_bytes(batch, s->P, R, maps) + s->head.bytes;
   return 0;
 }
 
@@ -236,34 +264,45 @@ int cwt_maps_check(const CwtMapsKind& k, int maps, const char* own_fail, const C
 }
 
 // the workspace of a device entry point: at least min_bytes
-inline int cwt_exec_bytes(const CwtMapsKind& k, const CwtMapsShape& s, int64_t workspace_bytes) {
-  if (workspace_bytes < s.min_bytes)
+inline int cwt_exec_bytes(const CwtMapsKind& k, CwtMapsShape* s, int64_t workspace_bytes) {
+  if (workspace_bytes < s->min_bytes)
     SSQ_FAIL(std::string(k.name) + ": workspace smaller than the min_bytes of " + k.bytes_fn);
+  s->work_bytes = workspace_bytes;
   return 0;
 }
 
 // the workspace a host entry point allocates: pref_bytes, or with a limit what the limit allows, all rows in one chunk
-// at the most
-inline int cwt_host_bytes(const CwtMapsKind& k, const CwtMapsShape& s, int64_t batch, int64_t work_limit_bytes,
-                          int64_t* work) {
-  if (work_limit_bytes < 0 || (work_limit_bytes > 0 && work_limit_bytes < s.min_bytes))
+// at the most.  The limit counts what lies behind the real planes in front (mssq_cwt: ssq_cwt2's workspace, as that
+// entry point's limit does); they are added to it.
+inline int cwt_host_bytes(const CwtMapsKind& k, CwtMapsShape* s, int64_t batch, int64_t work_limit_bytes) {
+  const int64_t front = s->head.emax;
+  if (work_limit_bytes < 0 || (work_limit_bytes > 0 && work_limit_bytes < s->min_bytes - front))
     SSQ_FAIL(std::string(k.name) + ": work_limit_bytes below the min_bytes of " + k.bytes_fn);
-  *work = work_limit_bytes > 0 ? std::min(work_limit_bytes, cwt_chunk_bytes(batch, s.P, s.rows, s.maps) + s.head_bytes)
-                               : s.pref_bytes;
+  s->work_bytes = work_limit_bytes > 0
+                      ? front + std::min(work_limit_bytes, cwt_chunk_bytes(batch, s->P, s->rows, s->maps) + s->head.bytes - front)
+                      : s->pref_bytes;
   return 0;
 }
 
-// The pipeline up to the operator on device buffers: carves `d_work` (work_bytes >= s.min_bytes sets the rows per
-// chunk) behind the head, pads, runs the forward transforms and walks the chunks; per chunk the spectra kernel, the
-// inverse transforms, then op(maps, r0, nr) launches the transform's operator on rows r0 .. r0 + nr - 1, whose maps are
-// [nr][M][P] at `maps` (non-zero with the error set ends the walk).  d_scales: c.scales on the device.
+// the host door of a transform's pipe: the batch in one slice on the workspace cwt_host_bytes chose
+template <typename Pipe, typename Call, size_t N>
+int cwt_pipe_host(const Call& c, const CwtMapsShape& s, const void* x, const HostOut (&outs)[N]) {
+  return pipe_host<Pipe>(c, s, x, (size_t)(c.dtype == SSQ_F32 ? 4 : 8) * (size_t)c.N, outs,
+                         HostSlice{c.batch, (size_t)s.work_bytes});
+}
+
+// The pipeline up to the operator on device buffers, asynchronous on c.st: carves `d_work` (s.work_bytes >= s.min_bytes
+// sets the rows per chunk) behind the head, pads, runs the forward transforms and walks the chunks; per chunk the
+// spectra kernel, the inverse transforms, then op(maps, r0, nr) launches the transform's operator on rows r0 .. r0 + nr
+// - 1, whose maps are [nr][M][P] at `maps` (non-zero with the error set ends the walk).  d_scales: c.scales on the device.
 template <typename T, unsigned MAPS, typename Op>
 int cwt_maps_chunks(const CwtMapsCall& c, const CwtMapsShape& s, const void* d_x, const void* d_scales, void* d_work,
-                    int64_t work_bytes, hipStream_t st, Op&& op) {
+                    Op&& op) {
   constexpr int M = cwt_map_count(MAPS);
   const int64_t P = s.P;
-  const int64_t R = std::min(cwt_chunk_rows(work_bytes - s.head_bytes, c.batch, P, M), s.rows);
-  cpx<double>* xh = reinterpret_cast<cpx<double>*>(static_cast<char*>(d_work) + s.head_bytes);
+  const hipStream_t st = c.st;
+  const int64_t R = std::min(cwt_chunk_rows(s.work_bytes - s.head.bytes, c.batch, P, M), s.rows);
+  cpx<double>* xh = cwt_head_at<cpx<double>>(d_work, s.head.bytes);
   cpx<double>* spec = xh + c.batch * P;                        // [R][M][P]
   cpx<double>* pong = spec + R * M * P;                        // [R][M][P]
   hipLaunchKernelGGL((cwt_pad_kernel<T>), cwt_rows_grid(P, c.batch), dim3(kCwtThreads), 0, st, static_cast<const T*>(d_x), xh,

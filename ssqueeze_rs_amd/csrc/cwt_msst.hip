@@ -19,6 +19,8 @@
 //                         asked, r_n and the one-step bins it computed.
 //   cwt2 squeeze half     ssq_ssqueeze_w_exec, unchanged, on w_n: it bins w_n by the rule the walk kernel ran, so a
 //                         coefficient lands on b[r_n[k]]; the flip is applied there and nowhere else.
+// The head of the workspace is the plane of w_n (at every n_iter; n_iter = 1 leaves it unused); McwtPipe runs the three
+// stages behind both doors.
 #include <cmath>
 #include <vector>
 
@@ -115,7 +117,13 @@ using namespace ssq;
 
 namespace {
 
-constexpr CwtMapsKind kMcwtKind = {"mssq_cwt", "ssq_mssq_cwt_workspace_bytes", 16.0, 9.0e18, 0};   // no head
+// the head: the plane of w_n in front of the workspace of ssq_cwt2
+constexpr CwtMapsKind kMcwtKind = {"mssq_cwt", "ssq_mssq_cwt_workspace_bytes", 16.0, 9.0e18, 1, 0, 0};
+
+struct McwtCall : Cwt2Call {
+  int order, n_iter;
+  const int32_t* row_of_bin;
+};
 
 const char* mcwt_own_fail(int order, int n_iter, int64_t na) {
   if (order != 1 && order != 2) return "order must be 1 or 2";
@@ -131,105 +139,79 @@ int rho_check(const char* pre, const int32_t* row_of_bin, int64_t na) {
   return 0;
 }
 
-// the plane of w_n in front of the workspace of ssq_cwt2, to a multiple of 16 bytes
-int64_t wn_bytes(int dtype, int64_t batch, int64_t na, int64_t N) {
-  return ((dtype == SSQ_F32 ? 4 : 8) * batch * na * N + 15) / 16 * 16;
+int mcwt_check(const McwtCall& c, CwtMapsShape* s) {
+  if (int rc = cwt2_check(kMcwtKind, mcwt_own_fail(c.order, c.n_iter, c.na), c, s)) return rc;
+  return rho_check("mssq_cwt", c.row_of_bin, c.na);
 }
 
-// The three stages on device buffers.  Synchronous.  kernel_ms (may be nullptr): pipeline + operator, walk, scatter.
+// mssq_cwt on device buffers (cwt_pipe_host, pipe_exec): the operator half, the walk, the squeeze half.  kernel_ms: three
+// parts, the events after the operator half and after the walk.
 template <typename T>
-int mcwt_run(const Cwt2Call& c, const CwtMapsShape& s, int order, int n_iter, const int32_t* row_of_bin, const void* d_x,
-             void* d_Tx, void* d_Wx, void* d_w, int* d_rows, int* d_bins, void* d_wn, void* d_work, int64_t work_bytes,
-             hipStream_t st, float* kernel_ms) {
+struct McwtPipe {
+  static constexpr int kMid = 2;
+  const McwtCall& c;
+  const CwtMapsShape& s;
   DeviceBufs d;
-  TimingEvents t;
-  void *d_scales = nullptr, *d_rc = nullptr, *d_rho = nullptr;
-  if (int rc = cwt2_tables<T>(d, c, &d_scales, &d_rc)) return rc;
-  SSQ_HIP(d.upload(&d_rho, row_of_bin, sizeof(int32_t) * (size_t)c.m.na));
-  CwtWalkDev<T> wk{};
-  if (int rc = bin_rule<T>(c.f_asc, c.m.na, c.freq_kind, c.freq_transition, 0, wk.rule)) return rc;
-  if (kernel_ms) SSQ_HIP(t.start(4, st));
-  const double gamma_sq = order == 1 ? (double)INFINITY : s.gamma * s.gamma;   // |D| > gamma_sq nowhere: |Im om1| / (2 pi dt)
-  if (int rc = cwt2_operator_run<T>(c, s, gamma_sq, d_x, d_scales, d_Wx, d_w, d_work, work_bytes, st)) return rc;
-  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
-  if (n_iter > 1 || d_rows || d_bins) {                        // (one step, nothing else asked for: w is final)
-    wk.w = static_cast<const T*>(d_w);
-    wk.w_n = n_iter > 1 ? static_cast<T*>(d_wn) : nullptr;
-    wk.rows = d_rows;
-    wk.bins = d_bins;
-    wk.row_of_bin = static_cast<const int*>(d_rho);
-    wk.n_cols = c.m.N;
-    wk.na = (int)c.m.na;
-    wk.n_iter = n_iter;
-    SSQ_HIP(cwt_walk_run<T>(wk, c.m.batch, st));
+  void *scales, *rc, *rho, *Tx, *Wx, *w, *work;
+  CwtWalkDev<T> wk;
+  int tables() {
+    if (int r = cwt2_tables<T>(d, c, &scales, &rc)) return r;
+    SSQ_HIP(d.upload(&rho, c.row_of_bin, sizeof(int32_t) * (size_t)c.na));
+    return bin_rule<T>(c.f_asc, c.na, c.freq_kind, c.freq_transition, 0, wk.rule);
   }
-  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[2], st));
-  if (int rc = cwt2_squeeze_run(c, d_Wx, n_iter > 1 ? d_wn : d_w, d_rc, d_Tx, st)) return rc;
-  if (kernel_ms) {
-    SSQ_HIP(hipEventRecord(t.ev[3], st));
-    SSQ_HIP(hipEventSynchronize(t.ev[3]));
-    for (int i = 0; i < 3; ++i) SSQ_HIP(hipEventElapsedTime(&kernel_ms[i], t.ev[i], t.ev[i + 1]));
+  int bind(int64_t, void* const* outs /* Tx, Wx, w, rows, bins */, void* wkspace) {
+    Tx = outs[0];
+    Wx = outs[1];
+    work = wkspace;
+    if (!(w = outs[2])) SSQ_HIP(d.alloc(&w, sizeof(T) * (size_t)s.cells));     // (the host door without w: the walk reads it)
+    wk.w = static_cast<const T*>(w);
+    wk.w_n = c.n_iter > 1 ? cwt_head_at<T>(work, 0) : nullptr;                 // one step: w itself is final
+    wk.rows = static_cast<int*>(outs[3]);
+    wk.bins = static_cast<int*>(outs[4]);
+    wk.row_of_bin = static_cast<const int*>(rho);
+    wk.n_cols = c.N;
+    wk.na = (int)c.na;
+    wk.n_iter = c.n_iter;
+    return 0;
   }
-  SSQ_HIP(hipStreamSynchronize(st));                           // (the tables above are freed on return)
-  return 0;
-}
+  int run(int64_t, const void* d_x, const hipEvent_t* mid) {
+    const double gamma_sq = c.order == 1 ? (double)INFINITY : s.gamma * s.gamma;   // |D| > gamma_sq nowhere: |Im om1| / (2 pi dt)
+    if (int r = cwt2_operator_run<T>(c, s, gamma_sq, d_x, scales, Wx, w, work)) return r;
+    if (mid[0]) SSQ_HIP(hipEventRecord(mid[0], c.st));
+    if (wk.w_n || wk.rows || wk.bins) SSQ_HIP(cwt_walk_run<T>(wk, c.batch, c.st));   // (else nothing asks for the walk)
+    if (mid[1]) SSQ_HIP(hipEventRecord(mid[1], c.st));
+    return cwt2_squeeze_run(c, Wx, wk.w_n ? (const void*)wk.w_n : w, rc, Tx);
+  }
+};
 
-template <typename T>
-int mcwt_host_typed(const Cwt2Call& c, const CwtMapsShape& s, int order, int n_iter, const int32_t* row_of_bin, const void* x,
-                    int64_t work_bytes, void* Tx, void* Wx, void* w, int32_t* rows, int32_t* bins) {
-  DeviceBufs d;
-  const size_t n = (size_t)s.rows * (size_t)c.m.N;
-  void *d_x, *d_Tx, *d_Wx, *d_w, *d_wn = nullptr, *d_rows = nullptr, *d_bins = nullptr, *d_work;
-  SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * n));
-  SSQ_HIP(d.alloc(&d_Wx, sizeof(cpx<T>) * n));
-  SSQ_HIP(d.alloc(&d_w, sizeof(T) * n));
-  if (n_iter > 1) SSQ_HIP(d.alloc(&d_wn, sizeof(T) * n));
-  if (rows) SSQ_HIP(d.alloc(&d_rows, sizeof(int32_t) * n));
-  if (bins) SSQ_HIP(d.alloc(&d_bins, sizeof(int32_t) * n));
-  SSQ_HIP(d.alloc(&d_work, (size_t)work_bytes));
-  if (int rc = mcwt_run<T>(c, s, order, n_iter, row_of_bin, d_x, d_Tx, d_Wx, d_w, (int*)d_rows, (int*)d_bins, d_wn, d_work,
-                           work_bytes, nullptr, nullptr))
-    return rc;
-  SSQ_HIP(hipMemcpy(Tx, d_Tx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  SSQ_HIP(hipMemcpy(Wx, d_Wx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  if (w) SSQ_HIP(hipMemcpy(w, d_w, sizeof(T) * n, hipMemcpyDeviceToHost));
-  if (rows) SSQ_HIP(hipMemcpy(rows, d_rows, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  if (bins) SSQ_HIP(hipMemcpy(bins, d_bins, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  return 0;
-}
-
+// the walk alone on the host's maps: host_sliced with no workspace, w in, rows, bins and w_n out
 template <typename T>
 int mcwt_walk_typed(const void* w, int64_t batch, int64_t na, int64_t n, const double* f_asc, int freq_kind,
                     int64_t freq_transition, const int32_t* row_of_bin, int n_iter, int32_t* rows, int32_t* bins, void* w_n) {
   DeviceBufs d;
   CwtWalkDev<T> wk{};
   if (int rc = bin_rule<T>(f_asc, na, freq_kind, freq_transition, 0, wk.rule)) return rc;
-  const size_t sig = (size_t)na * (size_t)n;
-  const int64_t slice = slice_signals(batch, (double)sig * (2.0 * sizeof(T) + 2.0 * sizeof(int32_t)), 0.0, batch);
-  void *d_w, *d_wn, *d_rows, *d_bins, *d_rho;
+  void* d_rho;
   SSQ_HIP(d.upload(&d_rho, row_of_bin, sizeof(int32_t) * (size_t)na));
-  SSQ_HIP(d.alloc(&d_w, sizeof(T) * sig * slice));
-  SSQ_HIP(d.alloc(&d_wn, sizeof(T) * sig * slice));
-  SSQ_HIP(d.alloc(&d_rows, sizeof(int32_t) * sig * slice));
-  SSQ_HIP(d.alloc(&d_bins, sizeof(int32_t) * sig * slice));
-  wk.w = static_cast<const T*>(d_w);
-  wk.w_n = static_cast<T*>(d_wn);
-  wk.rows = static_cast<int*>(d_rows);
-  wk.bins = static_cast<int*>(d_bins);
   wk.row_of_bin = static_cast<const int*>(d_rho);
   wk.n_cols = n;
   wk.na = (int)na;
   wk.n_iter = n_iter;
-  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
-    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
-    SSQ_HIP(hipMemcpy(d_w, (const T*)w + sig * b0, sizeof(T) * sig * nb, hipMemcpyHostToDevice));
-    SSQ_HIP(cwt_walk_run<T>(wk, nb, nullptr));
-    SSQ_HIP(hipMemcpy(rows + sig * b0, d_rows, sizeof(int32_t) * sig * nb, hipMemcpyDeviceToHost));
-    SSQ_HIP(hipMemcpy(bins + sig * b0, d_bins, sizeof(int32_t) * sig * nb, hipMemcpyDeviceToHost));
-    SSQ_HIP(hipMemcpy((T*)w_n + sig * b0, d_wn, sizeof(T) * sig * nb, hipMemcpyDeviceToHost));
-  }
-  return 0;
+  const size_t sig = (size_t)na * (size_t)n;
+  const HostOut outs[] = {{rows, sizeof(int32_t) * sig}, {bins, sizeof(int32_t) * sig}, {w_n, sizeof(T) * sig}};
+  return host_sliced(
+      batch, host_slice(batch, sizeof(T) * sig, outs, 0), w, sizeof(T) * sig, outs,
+      [&](int64_t, void* const* o, void*) {
+        wk.rows = static_cast<int*>(o[0]);
+        wk.bins = static_cast<int*>(o[1]);
+        wk.w_n = static_cast<T*>(o[2]);
+        return 0;
+      },
+      [&](int64_t nb, const void* d_w) -> int {
+        wk.w = static_cast<const T*>(d_w);
+        SSQ_HIP(cwt_walk_run<T>(wk, nb, nullptr));
+        return 0;
+      });
 }
 
 }  // namespace
@@ -239,9 +221,8 @@ extern "C" {
 int64_t ssq_mssq_cwt_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int64_t* min_bytes) {
   CwtMapsShape s;
   if (cwt_maps_shape(kMcwtKind, kCwt2Maps, mcwt_own_fail(2, 1, na), dtype, batch, n_signal, na, &s)) return -1;
-  const int64_t head = wn_bytes(dtype, batch, na, n_signal);
-  if (min_bytes) *min_bytes = s.min_bytes + head;
-  return s.pref_bytes + head;
+  if (min_bytes) *min_bytes = s.min_bytes;
+  return s.pref_bytes;
 }
 
 int ssq_mssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
@@ -250,20 +231,16 @@ int ssq_mssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
                       int n_iter, const int32_t* row_of_bin, void* d_Tx, void* d_Wx, void* d_w, int32_t* d_rows,
                       int32_t* d_bins, void* d_workspace, int64_t workspace_bytes, void* stream, float* kernel_ms) {
   if (!d_x || !d_Tx || !d_Wx || !d_w || !d_workspace) SSQ_FAIL("NULL argument");
-  const Cwt2Call c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales},
-                   freq_kind, squeezing, variant, freq_transition, row_const, ssq_freqs_asc};
+  const McwtCall c{{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, (hipStream_t)stream},
+                    freq_kind, squeezing, variant, freq_transition, row_const, ssq_freqs_asc},
+                   order, n_iter, row_of_bin};
   CwtMapsShape s;
-  if (int rc = cwt2_check(kMcwtKind, mcwt_own_fail(order, n_iter, na), c, &s)) return rc;
-  if (int rc = rho_check("mssq_cwt", row_of_bin, na)) return rc;
-  const int64_t head = wn_bytes(dtype, batch, na, n_signal);
-  if (int rc = cwt_exec_bytes(kMcwtKind, s, workspace_bytes - head)) return rc;
+  if (int rc = mcwt_check(c, &s)) return rc;
+  if (int rc = cwt_exec_bytes(kMcwtKind, &s, workspace_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  void* d_rest = static_cast<char*>(d_workspace) + head;       // w_n first, then the workspace of ssq_cwt2
-  return dtype == SSQ_F32 ? mcwt_run<float>(c, s, order, n_iter, row_of_bin, d_x, d_Tx, d_Wx, d_w, d_rows, d_bins, d_workspace,
-                                            d_rest, workspace_bytes - head, st, kernel_ms)
-                          : mcwt_run<double>(c, s, order, n_iter, row_of_bin, d_x, d_Tx, d_Wx, d_w, d_rows, d_bins, d_workspace,
-                                             d_rest, workspace_bytes - head, st, kernel_ms);
+  void* const outs[] = {d_Tx, d_Wx, d_w, d_rows, d_bins};
+  return dtype == SSQ_F32 ? pipe_exec<McwtPipe<float>>(c, s, d_x, outs, d_workspace, kernel_ms, &c.st)
+                          : pipe_exec<McwtPipe<double>>(c, s, d_x, outs, d_workspace, kernel_ms, &c.st);
 }
 
 int ssq_mssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
@@ -272,16 +249,16 @@ int ssq_mssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal,
                       int64_t work_limit_bytes, int order, int n_iter, const int32_t* row_of_bin, void* Tx, void* Wx, void* w,
                       int32_t* rows, int32_t* bins) {
   if (!x || !Tx || !Wx) SSQ_FAIL("NULL argument");
-  const Cwt2Call c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales},
-                   freq_kind, squeezing, variant, freq_transition, row_const, ssq_freqs_asc};
+  const McwtCall c{{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, nullptr},
+                    freq_kind, squeezing, variant, freq_transition, row_const, ssq_freqs_asc},
+                   order, n_iter, row_of_bin};
   CwtMapsShape s;
-  int64_t work = 0;
-  if (int rc = cwt2_check(kMcwtKind, mcwt_own_fail(order, n_iter, na), c, &s)) return rc;
-  if (int rc = rho_check("mssq_cwt", row_of_bin, na)) return rc;
-  if (int rc = cwt_host_bytes(kMcwtKind, s, batch, work_limit_bytes, &work)) return rc;
+  if (int rc = mcwt_check(c, &s)) return rc;
+  if (int rc = cwt_host_bytes(kMcwtKind, &s, batch, work_limit_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? mcwt_host_typed<float>(c, s, order, n_iter, row_of_bin, x, work, Tx, Wx, w, rows, bins)
-                          : mcwt_host_typed<double>(c, s, order, n_iter, row_of_bin, x, work, Tx, Wx, w, rows, bins);
+  const size_t el = (dtype == SSQ_F32 ? 4 : 8) * (size_t)s.plane, i32 = sizeof(int32_t) * (size_t)s.plane;
+  const HostOut outs[] = {{Tx, 2 * el}, {Wx, 2 * el}, {w, el}, {rows, i32}, {bins, i32}};
+  return dtype == SSQ_F32 ? cwt_pipe_host<McwtPipe<float>>(c, s, x, outs) : cwt_pipe_host<McwtPipe<double>>(c, s, x, outs);
 }
 
 int ssq_mssq_cwt_tile_cols(int64_t na) {

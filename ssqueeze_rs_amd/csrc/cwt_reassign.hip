@@ -24,8 +24,8 @@
 //                              contribution is at most 2^S quanta and a cell takes at most na N <= 2^(62 - S) of them.
 //   cwt_reassign_readout_kernel : converts every cell once to fp64, scales it by q, rounds to the call's dtype and writes
 //                              every cell of Rx exactly once.
-// The head of the workspace: the signals' maxima [batch] (to a multiple of 16 bytes), the accumulators [batch][na][N]
-// and the two int32 target maps [batch][na][N].
+// The head of the workspace (cwt_maps64.h's cwt_head): the signals' maxima [batch], the accumulators [batch][na][N] and
+// the two int32 target maps [batch][na][N], kk then mm.  CwtRPipe runs the launches behind both doors.
 #include <cmath>
 
 #include "bin_rule.h"
@@ -166,10 +166,9 @@ using namespace ssq;
 namespace {
 
 // the head: 8 bytes of accumulator and two int32 targets per cell
-constexpr CwtMapsKind kCwtRKind = {"reassign_cwt", "ssq_reassign_cwt_workspace_bytes", 16.0, 4.0e18, 16};
+constexpr CwtMapsKind kCwtRKind = {"reassign_cwt", "ssq_reassign_cwt_workspace_bytes", 16.0, 4.0e18, 0, 8, 2};
 
-struct CwtRCall {
-  CwtMapsCall m;
+struct CwtRCall : CwtMapsCall {
   int freq_kind, variant;
   int64_t freq_transition;
   const double* f_asc;
@@ -177,117 +176,95 @@ struct CwtRCall {
 
 int cwtr_check(const CwtRCall& c, CwtMapsShape* s) {
   const auto rows = [&]() -> int {
-    if (!c.m.scales || !c.f_asc) SSQ_FAIL("NULL argument");
-    for (int64_t i = 0; i < c.m.na; ++i) {
-      if (!(c.m.scales[i] > 0) || !std::isfinite(c.m.scales[i])) SSQ_FAIL("reassign_cwt: scales must be positive and finite");
+    if (!c.scales || !c.f_asc) SSQ_FAIL("NULL argument");
+    for (int64_t i = 0; i < c.na; ++i) {
+      if (!(c.scales[i] > 0) || !std::isfinite(c.scales[i])) SSQ_FAIL("reassign_cwt: scales must be positive and finite");
       if (!std::isfinite(c.f_asc[i])) SSQ_FAIL("reassign_cwt: ssq_freqs_asc must be finite");
     }
     return 0;
   };
-  return cwt_maps_check(kCwtRKind, kCwtRMaps, nullptr, c.m, rows, &c.freq_kind, c.freq_transition, nullptr, s);
+  return cwt_maps_check(kCwtRKind, kCwtRMaps, nullptr, c, rows, &c.freq_kind, c.freq_transition, nullptr, s);
 }
 
-// The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the rows per chunk.  d_w, d_tau, d_kk, d_mm may
-// be nullptr (the targets then live in the workspace alone).  Synchronous.  kernel_ms: two floats, all kernels and the
-// scatter kernel alone.
+// reassign_cwt on device buffers (cwt_pipe_host, pipe_exec): the chunks with the operator, the scatter, the read-out.
+// The targets go to the caller's planes where given, else to the head's.  kernel_ms: three parts, the events before and
+// after the scatter kernel.
 template <typename T>
-int cwtr_run(const CwtRCall& c, const CwtMapsShape& s, const void* d_x, void* d_Rx, void* d_Wx, void* d_w, void* d_tau,
-             void* d_kk, void* d_mm, void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
-  const int64_t batch = c.m.batch, N = c.m.N, na = c.m.na;
+struct CwtRPipe {
+  static constexpr int kMid = 2;
+  const CwtRCall& c;
+  const CwtMapsShape& s;
   DeviceBufs d;
-  TimingEvents t;
-  void* d_scales = nullptr;
-  SSQ_HIP(d.upload(&d_scales, c.m.scales, sizeof(double) * (size_t)na));
-  if (kernel_ms) SSQ_HIP(t.start(4, st));
-  char* head = static_cast<char*>(d_work);
-  unsigned long long* emax = reinterpret_cast<unsigned long long*>(head);                                  // [batch]
-  unsigned long long* acc = reinterpret_cast<unsigned long long*>(head + cwt_emax_bytes(batch));          // [batch][na][N]
-  int* kk = d_kk ? static_cast<int*>(d_kk) : reinterpret_cast<int*>(acc + batch * s.plane);
-  int* mm = d_mm ? static_cast<int*>(d_mm) : reinterpret_cast<int*>(acc + batch * s.plane) + batch * s.plane;
-  SSQ_HIP(hipMemsetAsync(head, 0, (size_t)(cwt_emax_bytes(batch) + 8 * batch * s.plane), st));
-  CwtROpDev<T> op{};
-  op.emax = emax;
-  op.P = s.P;
-  op.N = N;
-  op.n1 = s.n1;
-  op.na = (int)na;
-  op.inv_P = 1.0 / (double)s.P;
-  op.gamma = s.gamma;
-  op.inv_two_pi_dt = 1.0 / (6.283185307179586 * c.m.dt);
-  op.dt = c.m.dt;
-  op.dt_o = (T)c.m.dt;
-  if (int rc = bin_rule<T>(c.f_asc, na, c.freq_kind, c.freq_transition, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, op.rule))
-    return rc;                                                 // (cwtr_check has made each of its checks already)
-  const auto launch_op = [&](const cpx<double>* maps, int64_t r0, int64_t nr) -> int {
-    op.maps = maps;
-    op.Wx = static_cast<cpx<T>*>(d_Wx) + r0 * N;
-    op.w = d_w ? static_cast<T*>(d_w) + r0 * N : nullptr;
-    op.tau = d_tau ? static_cast<T*>(d_tau) + r0 * N : nullptr;
-    op.kk = kk + r0 * N;
-    op.mm = mm + r0 * N;
-    op.r0 = r0;
-    op.rows = nr;
-    hipLaunchKernelGGL((cwt_reassign_operator_kernel<T>), cwt_rows_grid(N, nr), dim3(kCwtThreads), 0, st, op);
+  void *scales, *work, *Wx, *w, *tau;
+  int *kk, *mm;
+  CwtROpDev<T> op;
+  CwtRScatDev<T> sc;
+  int tables() {
+    SSQ_HIP(d.upload(&scales, c.scales, sizeof(double) * (size_t)c.na));
+    // (cwtr_check has made each of the rule's checks already)
+    return bin_rule<T>(c.f_asc, c.na, c.freq_kind, c.freq_transition, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, op.rule);
+  }
+  int bind(int64_t, void* const* outs /* Rx, Wx, w, tau, kk, mm */, void* wk) {
+    work = wk;
+    Wx = outs[1];
+    w = outs[2];
+    tau = outs[3];
+    kk = outs[4] ? static_cast<int*>(outs[4]) : cwt_head_at<int>(work, s.head.planes);
+    mm = outs[5] ? static_cast<int*>(outs[5]) : cwt_head_at<int>(work, s.head.planes) + s.cells;
+    op.emax = cwt_head_at<unsigned long long>(work, s.head.emax);
+    op.P = s.P;
+    op.N = c.N;
+    op.n1 = s.n1;
+    op.na = (int)c.na;
+    op.inv_P = 1.0 / (double)s.P;
+    op.gamma = s.gamma;
+    op.inv_two_pi_dt = 1.0 / (6.283185307179586 * c.dt);
+    op.dt = c.dt;
+    op.dt_o = (T)c.dt;
+    int L = 0;
+    while (((int64_t)1 << L) < s.plane) ++L;                    // ceil(log2(na N)) <= 40
+    sc.Wx = static_cast<const cpx<T>*>(Wx);
+    sc.kk = kk;
+    sc.mm = mm;
+    sc.emax = op.emax;
+    sc.acc = cwt_head_at<unsigned long long>(work, s.head.acc);
+    sc.Rx = static_cast<T*>(outs[0]);
+    sc.batch = c.batch;
+    sc.plane = s.plane;
+    sc.N = c.N;
+    sc.na = (int)c.na;
+    sc.qbits = std::min(kCwtRQuantumBitsMax, 62 - L);
+    return 0;
+  }
+  int run(int64_t, const void* d_x, const hipEvent_t* mid) {
+    const int64_t N = c.N;
+    const hipStream_t st = c.st;
+    SSQ_HIP(hipMemsetAsync(op.emax, 0, (size_t)(s.head.planes - s.head.emax), st));   // the maxima and the accumulators
+    const auto launch_op = [&](const cpx<double>* maps, int64_t r0, int64_t nr) -> int {
+      op.maps = maps;
+      op.Wx = static_cast<cpx<T>*>(Wx) + r0 * N;
+      op.w = w ? static_cast<T*>(w) + r0 * N : nullptr;
+      op.tau = tau ? static_cast<T*>(tau) + r0 * N : nullptr;
+      op.kk = kk + r0 * N;
+      op.mm = mm + r0 * N;
+      op.r0 = r0;
+      op.rows = nr;
+      hipLaunchKernelGGL((cwt_reassign_operator_kernel<T>), cwt_rows_grid(N, nr), dim3(kCwtThreads), 0, st, op);
+      SSQ_HIP(hipGetLastError());
+      return 0;
+    };
+    if (int rc = cwt_maps_chunks<T, kCwtRMapSet>(c, s, d_x, scales, work, launch_op)) return rc;
+    const dim3 grid((unsigned)std::min<int64_t>((s.plane + kCwtThreads - 1) / kCwtThreads, 0x7fffffffLL),
+                    (unsigned)std::min<int64_t>(c.batch, 65535));
+    if (mid[0]) SSQ_HIP(hipEventRecord(mid[0], st));
+    hipLaunchKernelGGL((cwt_reassign_scatter_kernel<T>), grid, dim3(kCwtThreads), 0, st, sc);
+    SSQ_HIP(hipGetLastError());
+    if (mid[1]) SSQ_HIP(hipEventRecord(mid[1], st));
+    hipLaunchKernelGGL((cwt_reassign_readout_kernel<T>), grid, dim3(kCwtThreads), 0, st, sc);
     SSQ_HIP(hipGetLastError());
     return 0;
-  };
-  if (int rc = cwt_maps_chunks<T, kCwtRMapSet>(c.m, s, d_x, d_scales, d_work, work_bytes, st, launch_op)) return rc;
-  int L = 0;
-  while (((int64_t)1 << L) < s.plane) ++L;                    // ceil(log2(na N)) <= 40
-  CwtRScatDev<T> sc{};
-  sc.Wx = static_cast<const cpx<T>*>(d_Wx);
-  sc.kk = kk;
-  sc.mm = mm;
-  sc.emax = emax;
-  sc.acc = acc;
-  sc.Rx = static_cast<T*>(d_Rx);
-  sc.batch = batch;
-  sc.plane = s.plane;
-  sc.N = N;
-  sc.na = (int)na;
-  sc.qbits = std::min(kCwtRQuantumBitsMax, 62 - L);
-  const dim3 grid((unsigned)std::min<int64_t>((s.plane + kCwtThreads - 1) / kCwtThreads, 0x7fffffffLL),
-                  (unsigned)std::min<int64_t>(batch, 65535));
-  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
-  hipLaunchKernelGGL((cwt_reassign_scatter_kernel<T>), grid, dim3(kCwtThreads), 0, st, sc);
-  SSQ_HIP(hipGetLastError());
-  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[2], st));
-  hipLaunchKernelGGL((cwt_reassign_readout_kernel<T>), grid, dim3(kCwtThreads), 0, st, sc);
-  SSQ_HIP(hipGetLastError());
-  if (kernel_ms) {
-    SSQ_HIP(hipEventRecord(t.ev[3], st));
-    SSQ_HIP(hipEventSynchronize(t.ev[3]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[0], t.ev[0], t.ev[3]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[1], t.ev[1], t.ev[2]));
   }
-  SSQ_HIP(hipStreamSynchronize(st));                           // (the scales above are freed on return)
-  return 0;
-}
-
-template <typename T>
-int cwtr_host_typed(const CwtRCall& c, const CwtMapsShape& s, const void* x, int64_t work_bytes, void* Rx, void* Wx,
-                    void* w, void* tau, void* kk, void* mm) {
-  DeviceBufs d;
-  const size_t n = (size_t)s.rows * (size_t)c.m.N;
-  void *d_x, *d_Rx, *d_Wx, *d_work, *d_w = nullptr, *d_tau = nullptr;
-  SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));
-  SSQ_HIP(d.alloc(&d_Rx, sizeof(T) * n));
-  SSQ_HIP(d.alloc(&d_Wx, sizeof(cpx<T>) * n));
-  if (w) SSQ_HIP(d.alloc(&d_w, sizeof(T) * n));
-  if (tau) SSQ_HIP(d.alloc(&d_tau, sizeof(T) * n));
-  SSQ_HIP(d.alloc(&d_work, (size_t)work_bytes));
-  if (int rc = cwtr_run<T>(c, s, d_x, d_Rx, d_Wx, d_w, d_tau, nullptr, nullptr, d_work, work_bytes, nullptr, nullptr))
-    return rc;
-  SSQ_HIP(hipMemcpy(Rx, d_Rx, sizeof(T) * n, hipMemcpyDeviceToHost));
-  SSQ_HIP(hipMemcpy(Wx, d_Wx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  if (w) SSQ_HIP(hipMemcpy(w, d_w, sizeof(T) * n, hipMemcpyDeviceToHost));
-  if (tau) SSQ_HIP(hipMemcpy(tau, d_tau, sizeof(T) * n, hipMemcpyDeviceToHost));
-  // the targets of the workspace: behind the maxima and the accumulators at its head
-  const char* tgt = static_cast<const char*>(d_work) + cwt_emax_bytes(c.m.batch) + 8 * n;
-  if (kk) SSQ_HIP(hipMemcpy(kk, tgt, sizeof(int) * n, hipMemcpyDeviceToHost));
-  if (mm) SSQ_HIP(hipMemcpy(mm, tgt + sizeof(int) * n, sizeof(int) * n, hipMemcpyDeviceToHost));
-  return 0;
-}
+};
 
 }  // namespace
 
@@ -306,17 +283,21 @@ int ssq_reassign_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_s
                           void* d_w, void* d_tau, void* d_kk, void* d_mm, void* d_workspace, int64_t workspace_bytes,
                           void* stream, float* kernel_ms) {
   if (!d_x || !d_Rx || !d_Wx || !d_workspace) SSQ_FAIL("NULL argument");
-  const CwtRCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales},
+  const CwtRCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, (hipStream_t)stream},
                    freq_kind, variant, freq_transition, ssq_freqs_asc};
   CwtMapsShape s;
   if (int rc = cwtr_check(c, &s)) return rc;
-  if (int rc = cwt_exec_bytes(kCwtRKind, s, workspace_bytes)) return rc;
+  if (int rc = cwt_exec_bytes(kCwtRKind, &s, workspace_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == SSQ_F32 ? cwtr_run<float>(c, s, d_x, d_Rx, d_Wx, d_w, d_tau, d_kk, d_mm, d_workspace, workspace_bytes, st,
-                                            kernel_ms)
-                          : cwtr_run<double>(c, s, d_x, d_Rx, d_Wx, d_w, d_tau, d_kk, d_mm, d_workspace, workspace_bytes, st,
-                                             kernel_ms);
+  void* const outs[] = {d_Rx, d_Wx, d_w, d_tau, d_kk, d_mm};
+  float part[3], *ms = kernel_ms ? part : nullptr;
+  const int rc = dtype == SSQ_F32 ? pipe_exec<CwtRPipe<float>>(c, s, d_x, outs, d_workspace, ms, &c.st)
+                                  : pipe_exec<CwtRPipe<double>>(c, s, d_x, outs, d_workspace, ms, &c.st);
+  if (rc == 0 && kernel_ms) {
+    kernel_ms[0] = part[0] + part[1] + part[2];                // all the kernels
+    kernel_ms[1] = part[1];                                    // the scatter kernel alone
+  }
+  return rc;
 }
 
 int ssq_reassign_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
@@ -324,15 +305,15 @@ int ssq_reassign_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_sig
                           int64_t freq_transition, int padtype, double gamma, int variant, int64_t work_limit_bytes,
                           void* Rx, void* Wx, void* w, void* tau, void* kk, void* mm) {
   if (!x || !Rx || !Wx) SSQ_FAIL("NULL argument");
-  const CwtRCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales},
+  const CwtRCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, nullptr},
                    freq_kind, variant, freq_transition, ssq_freqs_asc};
   CwtMapsShape s;
-  int64_t work = 0;
   if (int rc = cwtr_check(c, &s)) return rc;
-  if (int rc = cwt_host_bytes(kCwtRKind, s, batch, work_limit_bytes, &work)) return rc;
+  if (int rc = cwt_host_bytes(kCwtRKind, &s, batch, work_limit_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? cwtr_host_typed<float>(c, s, x, work, Rx, Wx, w, tau, kk, mm)
-                          : cwtr_host_typed<double>(c, s, x, work, Rx, Wx, w, tau, kk, mm);
+  const size_t el = (dtype == SSQ_F32 ? 4 : 8) * (size_t)s.plane, i32 = sizeof(int32_t) * (size_t)s.plane;
+  const HostOut outs[] = {{Rx, el}, {Wx, 2 * el}, {w, el}, {tau, el}, {kk, i32}, {mm, i32}};
+  return dtype == SSQ_F32 ? cwt_pipe_host<CwtRPipe<float>>(c, s, x, outs) : cwt_pipe_host<CwtRPipe<double>>(c, s, x, outs);
 }
 
 }  // extern "C"

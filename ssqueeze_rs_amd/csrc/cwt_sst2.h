@@ -11,8 +11,7 @@ namespace ssq {
 
 constexpr int kCwt2Maps = cwt_map_count(kMapsAll);            // W, W1, W2, Wt, Wt1
 
-struct Cwt2Call {
-  CwtMapsCall m;
+struct Cwt2Call : CwtMapsCall {
   int freq_kind, squeezing, variant;
   int64_t freq_transition;
   const double *row_const, *f_asc;
@@ -26,15 +25,16 @@ int cwt2_check(const CwtMapsKind& k, const char* own_fail, const Cwt2Call& c, Cw
 template <typename T>
 int cwt2_tables(DeviceBufs& d, const Cwt2Call& c, void** d_scales, void** d_rc);
 
-// The operator half on device buffers: Wx and the one-step frequency, [batch][na][N] in the call's dtype.  `work_bytes`
-// >= s.min_bytes sets the rows per chunk.  gamma_sq: the second-order estimate is used where |D| > gamma_sq (ssq_cwt2:
-// gamma^2; +inf, mssq_cwt's order 1: nowhere, so every element reports |Im om1| / (2 pi dt)).  Asynchronous on `st`.
+// The operator half on device buffers: Wx and the one-step frequency, [batch][na][N] in the call's dtype, in the
+// workspace d_work of s.work_bytes behind its head.  gamma_sq: the second-order estimate is used where |D| > gamma_sq
+// (ssq_cwt2: gamma^2; +inf, mssq_cwt's order 1: nowhere, so every element reports |Im om1| / (2 pi dt)).  Asynchronous
+// on c.st.
 template <typename T>
 int cwt2_operator_run(const Cwt2Call& c, const CwtMapsShape& s, double gamma_sq, const void* d_x, const void* d_scales,
-                      void* d_Wx, void* d_w2, void* d_work, int64_t work_bytes, hipStream_t st);
+                      void* d_Wx, void* d_w2, void* d_work);
 
 // The squeeze half: Tx = ssqueeze(Wx, w) by ssq_ssqueeze_w_exec (Tx zeroed there; the flip is applied there).
-// Asynchronous on `st`.
-int cwt2_squeeze_run(const Cwt2Call& c, const void* d_Wx, const void* d_w, const void* d_rc, void* d_Tx, hipStream_t st);
+// Asynchronous on c.st.
+int cwt2_squeeze_run(const Cwt2Call& c, const void* d_Wx, const void* d_w, const void* d_rc, void* d_Tx);
 
 }  // namespace ssq

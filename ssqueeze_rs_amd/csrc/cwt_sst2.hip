@@ -11,7 +11,7 @@
 // Wx and w2 are rounded once on store, the scatter runs in the call's dtype on the rounded values, so Tx is the scatter
 // of what the call reports.  A first version with no time target (DESIGN 4.12 has the cost).  cwt_msst.hip (mssq_cwt)
 // runs both halves of this file, the operator half and the squeeze half, through cwt_sst2.h, with its walk kernel
-// between them; ssq_cwt2 calls the same two halves one after the other.
+// between them; ssq_cwt2's pipe (Cwt2Pipe, behind both of its doors) runs the same two halves one after the other.
 #include <cmath>
 #include <vector>
 
@@ -60,31 +60,31 @@ __global__ __launch_bounds__(kCwtThreads) void cwt2_operator_kernel(const Cwt2Op
 int cwt2_check(const CwtMapsKind& k, const char* own_fail, const Cwt2Call& c, CwtMapsShape* s) {
   const std::string pre = std::string(k.name) + ": ";
   const auto rows = [&]() -> int {
-    if (!c.m.scales || !c.row_const || !c.f_asc) SSQ_FAIL("NULL argument");
-    for (int64_t i = 0; i < c.m.na; ++i) {
-      if (!(c.m.scales[i] > 0) || !std::isfinite(c.m.scales[i])) SSQ_FAIL(pre + "scales must be positive and finite");
+    if (!c.scales || !c.row_const || !c.f_asc) SSQ_FAIL("NULL argument");
+    for (int64_t i = 0; i < c.na; ++i) {
+      if (!(c.scales[i] > 0) || !std::isfinite(c.scales[i])) SSQ_FAIL(pre + "scales must be positive and finite");
       if (!std::isfinite(c.row_const[i])) SSQ_FAIL(pre + "row_const must be finite");
       if (!std::isfinite(c.f_asc[i])) SSQ_FAIL(pre + "ssq_freqs_asc must be finite");
     }
     return 0;
   };
   const bool sq_ok = c.squeezing == SSQ_SQUEEZE_SUM || c.squeezing == SSQ_SQUEEZE_LEBESGUE;
-  return cwt_maps_check(k, kCwt2Maps, own_fail, c.m, rows, &c.freq_kind, c.freq_transition,
+  return cwt_maps_check(k, kCwt2Maps, own_fail, c, rows, &c.freq_kind, c.freq_transition,
                         sq_ok ? nullptr : "squeezing must be 'sum' or 'lebesgue'", s);
 }
 
 template <typename T>
 int cwt2_tables(DeviceBufs& d, const Cwt2Call& c, void** d_scales, void** d_rc) {
-  SSQ_HIP(d.upload(d_scales, c.m.scales, sizeof(double) * (size_t)c.m.na));
-  const std::vector<T> rc(c.row_const, c.row_const + c.m.na);
-  SSQ_HIP(d.upload(d_rc, rc.data(), sizeof(T) * (size_t)c.m.na));
+  SSQ_HIP(d.upload(d_scales, c.scales, sizeof(double) * (size_t)c.na));
+  const std::vector<T> rc(c.row_const, c.row_const + c.na);
+  SSQ_HIP(d.upload(d_rc, rc.data(), sizeof(T) * (size_t)c.na));
   return 0;
 }
 
 template <typename T>
 int cwt2_operator_run(const Cwt2Call& c, const CwtMapsShape& s, double gamma_sq, const void* d_x, const void* d_scales,
-                      void* d_Wx, void* d_w2, void* d_work, int64_t work_bytes, hipStream_t st) {
-  const int64_t N = c.m.N;
+                      void* d_Wx, void* d_w2, void* d_work) {
+  const int64_t N = c.N;
   Cwt2OpDev<T> op{};
   op.P = s.P;
   op.N = N;
@@ -92,30 +92,30 @@ int cwt2_operator_run(const Cwt2Call& c, const CwtMapsShape& s, double gamma_sq,
   op.inv_P = 1.0 / (double)s.P;
   op.gamma = s.gamma;
   op.gamma_sq = gamma_sq;
-  op.inv_two_pi_dt = 1.0 / (6.283185307179586 * c.m.dt);
+  op.inv_two_pi_dt = 1.0 / (6.283185307179586 * c.dt);
   const auto launch_op = [&](const cpx<double>* maps, int64_t r0, int64_t nr) -> int {
     op.maps = maps;
     op.Wx = static_cast<cpx<T>*>(d_Wx) + r0 * N;
     op.w2 = static_cast<T*>(d_w2) + r0 * N;
     op.rows = nr;
-    hipLaunchKernelGGL((cwt2_operator_kernel<T>), cwt_rows_grid(N, nr), dim3(kCwtThreads), 0, st, op);
+    hipLaunchKernelGGL((cwt2_operator_kernel<T>), cwt_rows_grid(N, nr), dim3(kCwtThreads), 0, c.st, op);
     SSQ_HIP(hipGetLastError());
     return 0;
   };
-  return cwt_maps_chunks<T, kMapsAll>(c.m, s, d_x, d_scales, d_work, work_bytes, st, launch_op);
+  return cwt_maps_chunks<T, kMapsAll>(c, s, d_x, d_scales, d_work, launch_op);
 }
 
-int cwt2_squeeze_run(const Cwt2Call& c, const void* d_Wx, const void* d_w, const void* d_rc, void* d_Tx, hipStream_t st) {
-  return ssq_ssqueeze_w_exec(c.m.dtype, d_Wx, d_w, c.m.batch, c.m.na, c.m.N, d_rc, c.f_asc, c.freq_kind, c.freq_transition,
-                             c.squeezing, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, d_Tx, st);
+int cwt2_squeeze_run(const Cwt2Call& c, const void* d_Wx, const void* d_w, const void* d_rc, void* d_Tx) {
+  return ssq_ssqueeze_w_exec(c.dtype, d_Wx, d_w, c.batch, c.na, c.N, d_rc, c.f_asc, c.freq_kind, c.freq_transition,
+                             c.squeezing, (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0, d_Tx, c.st);
 }
 
 template int cwt2_tables<float>(DeviceBufs&, const Cwt2Call&, void**, void**);
 template int cwt2_tables<double>(DeviceBufs&, const Cwt2Call&, void**, void**);
 template int cwt2_operator_run<float>(const Cwt2Call&, const CwtMapsShape&, double, const void*, const void*, void*, void*,
-                                      void*, int64_t, hipStream_t);
+                                      void*);
 template int cwt2_operator_run<double>(const Cwt2Call&, const CwtMapsShape&, double, const void*, const void*, void*, void*,
-                                       void*, int64_t, hipStream_t);
+                                       void*);
 
 }  // namespace ssq
 
@@ -123,45 +123,29 @@ using namespace ssq;
 
 namespace {
 
-constexpr CwtMapsKind kCwt2Kind = {"ssq_cwt2", "ssq_ssq_cwt2_workspace_bytes", 16.0, 9.0e18, 0};   // no head
+constexpr CwtMapsKind kCwt2Kind = {"ssq_cwt2", "ssq_ssq_cwt2_workspace_bytes", 16.0, 9.0e18, 0, 0, 0};   // no head
 
-// The whole transform on device buffers: the two halves, one after the other.  Synchronous.
+// ssq_cwt2 on device buffers (cwt_pipe_host, pipe_exec): the two halves, one after the other.  kernel_ms: one part.
 template <typename T>
-int cwt2_run(const Cwt2Call& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_w2, void* d_work,
-             int64_t work_bytes, hipStream_t st, float* kernel_ms) {
+struct Cwt2Pipe {
+  static constexpr int kMid = 0;
+  const Cwt2Call& c;
+  const CwtMapsShape& s;
   DeviceBufs d;
-  TimingEvents t;
-  void *d_scales = nullptr, *d_rc = nullptr;
-  if (int rc = cwt2_tables<T>(d, c, &d_scales, &d_rc)) return rc;
-  if (kernel_ms) SSQ_HIP(t.start(2, st));
-  if (int rc = cwt2_operator_run<T>(c, s, s.gamma * s.gamma, d_x, d_scales, d_Wx, d_w2, d_work, work_bytes, st)) return rc;
-  if (int rc = cwt2_squeeze_run(c, d_Wx, d_w2, d_rc, d_Tx, st)) return rc;
-  if (kernel_ms) {
-    SSQ_HIP(hipEventRecord(t.ev[1], st));
-    SSQ_HIP(hipEventSynchronize(t.ev[1]));
-    SSQ_HIP(hipEventElapsedTime(kernel_ms, t.ev[0], t.ev[1]));
+  void *scales, *rc, *Tx, *Wx, *w2, *work;
+  int tables() { return cwt2_tables<T>(d, c, &scales, &rc); }
+  int bind(int64_t, void* const* outs /* Tx, Wx, w2 */, void* wk) {
+    Tx = outs[0];
+    Wx = outs[1];
+    work = wk;
+    if (!(w2 = outs[2])) SSQ_HIP(d.alloc(&w2, sizeof(T) * (size_t)s.cells));   // (the host door without w2: the squeeze reads it)
+    return 0;
   }
-  SSQ_HIP(hipStreamSynchronize(st));                           // (the tables above are freed on return)
-  return 0;
-}
-
-template <typename T>
-int cwt2_host_typed(const Cwt2Call& c, const CwtMapsShape& s, const void* x, int64_t work_bytes, void* Tx, void* Wx,
-                    void* w2) {
-  DeviceBufs d;
-  const size_t n = (size_t)s.rows * (size_t)c.m.N;
-  void *d_x, *d_Tx, *d_Wx, *d_w2, *d_work;
-  SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * n));
-  SSQ_HIP(d.alloc(&d_Wx, sizeof(cpx<T>) * n));
-  SSQ_HIP(d.alloc(&d_w2, sizeof(T) * n));
-  SSQ_HIP(d.alloc(&d_work, (size_t)work_bytes));
-  if (int rc = cwt2_run<T>(c, s, d_x, d_Tx, d_Wx, d_w2, d_work, work_bytes, nullptr, nullptr)) return rc;
-  SSQ_HIP(hipMemcpy(Tx, d_Tx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  SSQ_HIP(hipMemcpy(Wx, d_Wx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  if (w2) SSQ_HIP(hipMemcpy(w2, d_w2, sizeof(T) * n, hipMemcpyDeviceToHost));
-  return 0;
-}
+  int run(int64_t, const void* d_x, const hipEvent_t*) {
+    if (int r = cwt2_operator_run<T>(c, s, s.gamma * s.gamma, d_x, scales, Wx, w2, work)) return r;
+    return cwt2_squeeze_run(c, Wx, w2, rc, Tx);
+  }
+};
 
 }  // namespace
 
@@ -195,15 +179,15 @@ int ssq_ssq_cwt2_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
                       void* d_Tx, void* d_Wx, void* d_w2, void* d_workspace, int64_t workspace_bytes, void* stream,
                       float* kernel_ms) {
   if (!d_x || !d_Tx || !d_Wx || !d_w2 || !d_workspace) SSQ_FAIL("NULL argument");
-  const Cwt2Call c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales},
+  const Cwt2Call c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, (hipStream_t)stream},
                    freq_kind, squeezing, variant, freq_transition, row_const, ssq_freqs_asc};
   CwtMapsShape s;
   if (int rc = cwt2_check(kCwt2Kind, nullptr, c, &s)) return rc;
-  if (int rc = cwt_exec_bytes(kCwt2Kind, s, workspace_bytes)) return rc;
+  if (int rc = cwt_exec_bytes(kCwt2Kind, &s, workspace_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == SSQ_F32 ? cwt2_run<float>(c, s, d_x, d_Tx, d_Wx, d_w2, d_workspace, workspace_bytes, st, kernel_ms)
-                          : cwt2_run<double>(c, s, d_x, d_Tx, d_Wx, d_w2, d_workspace, workspace_bytes, st, kernel_ms);
+  void* const outs[] = {d_Tx, d_Wx, d_w2};
+  return dtype == SSQ_F32 ? pipe_exec<Cwt2Pipe<float>>(c, s, d_x, outs, d_workspace, kernel_ms, &c.st)
+                          : pipe_exec<Cwt2Pipe<double>>(c, s, d_x, outs, d_workspace, kernel_ms, &c.st);
 }
 
 int ssq_ssq_cwt2_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
@@ -211,14 +195,15 @@ int ssq_ssq_cwt2_host(int dtype, const void* x, int64_t batch, int64_t n_signal,
                       int freq_kind, int64_t freq_transition, int padtype, int squeezing, double gamma, int variant,
                       int64_t work_limit_bytes, void* Tx, void* Wx, void* w2) {
   if (!x || !Tx || !Wx) SSQ_FAIL("NULL argument");
-  const Cwt2Call c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales},
+  const Cwt2Call c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, nullptr},
                    freq_kind, squeezing, variant, freq_transition, row_const, ssq_freqs_asc};
   CwtMapsShape s;
-  int64_t work = 0;
   if (int rc = cwt2_check(kCwt2Kind, nullptr, c, &s)) return rc;
-  if (int rc = cwt_host_bytes(kCwt2Kind, s, batch, work_limit_bytes, &work)) return rc;
+  if (int rc = cwt_host_bytes(kCwt2Kind, &s, batch, work_limit_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? cwt2_host_typed<float>(c, s, x, work, Tx, Wx, w2) : cwt2_host_typed<double>(c, s, x, work, Tx, Wx, w2);
+  const size_t el = (dtype == SSQ_F32 ? 4 : 8) * (size_t)s.plane;
+  const HostOut outs[] = {{Tx, 2 * el}, {Wx, 2 * el}, {w2, el}};
+  return dtype == SSQ_F32 ? cwt_pipe_host<Cwt2Pipe<float>>(c, s, x, outs) : cwt_pipe_host<Cwt2Pipe<double>>(c, s, x, outs);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 //                              other's entries, so the walk writes a SECOND int32 plane, never in place.
 //   cwt_tsst_scatter_kernel, cwt_tsst_readout_kernel : cwt_tsst.hip's, as they are (cwtt_scatter_run), on the walked plane.
 // The head of the workspace: tssq_cwt's (maxima, accumulators, the one-step plane) and the walked plane behind it.
+// CwtTmPipe runs the three stages behind both doors.
 #include <cmath>
 #include <vector>
 
@@ -82,68 +83,49 @@ using namespace ssq;
 namespace {
 
 // the head: 16 bytes of accumulator and two int32 planes (the one-step targets, the walked ones) per cell
-constexpr CwtMapsKind kCwtTmKind = {"tmssq_cwt", "ssq_tmssq_cwt_workspace_bytes", 24.0, 4.0e18, 24};
+constexpr CwtMapsKind kCwtTmKind = {"tmssq_cwt", "ssq_tmssq_cwt_workspace_bytes", 24.0, 4.0e18, 0, 16, 2};
+
+struct CwtTmCall : CwtTCall {
+  int n_iter;
+};
 
 const char* cwttm_own_fail(int order, int n_iter) {
   if (const char* f = cwtt_order_fail(order)) return f;
   return n_iter < 1 || n_iter > kCwtWalkMaxIter ? "n_iter must be from 1 to 64" : nullptr;
 }
 
-// The whole transform on device buffers.  d_tau, d_mm may be nullptr.  At n_iter 1 there is no walk and the operator's
-// plane is the final one; else the operator writes the workspace's first plane and the walk d_mm, or the workspace's
-// second plane.  *final_mm (may be nullptr): where the final plane lies.  Synchronous.  kernel_ms: four floats.
+// tmssq_cwt on device buffers (cwt_pipe_host, pipe_exec): the operator part, the walk, the scatter with its read-out.  At
+// n_iter 1 there is no walk and the operator's plane is the final one: the caller's if given, else the head's first.
+// Else the operator writes the head's first plane and the walk the caller's plane, or the head's second.  kernel_ms: four
+// parts, the events after the operator part, after the walk and after the scatter kernel.
 template <typename T>
-int cwttm_run(const CwtTCall& c, const CwtMapsShape& s, int n_iter, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau,
-              void* d_mm, void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms, const int** final_mm) {
+struct CwtTmPipe {
+  static constexpr int kMid = 3;
+  const CwtTmCall& c;
+  const CwtMapsShape& s;
   DeviceBufs d;
-  TimingEvents t, end;
-  void *d_scales = nullptr, *d_nu = nullptr;
-  if (int rc = cwtt_tables(d, c, &d_scales, &d_nu)) return rc;
-  if (kernel_ms) SSQ_HIP(t.start(4, st));
-  const int64_t cells = c.m.batch * s.plane;
-  int* one = n_iter == 1 && d_mm ? static_cast<int*>(d_mm) : cwtt_head_plane(d_work, c.m.batch, cells, 0);
-  const int* last = one;
-  if (int rc = cwtt_operator_run<T>(c, s, d_x, d_scales, d_nu, d_Wx, d_tau, one, d_work, work_bytes, st)) return rc;
-  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
-  if (n_iter > 1) {
-    int* walked = d_mm ? static_cast<int*>(d_mm) : cwtt_head_plane(d_work, c.m.batch, cells, 1);
-    SSQ_HIP(cwt_tmsst_walk_run(one, walked, (long long)s.rows, (long long)c.m.N, n_iter, st));
-    last = walked;
+  void *scales, *nu, *work, *Tx, *Wx, *tau;
+  int *one, *last;
+  int tables() { return cwtt_tables(d, c, &scales, &nu); }
+  int bind(int64_t, void* const* outs /* Tx, Wx, tau, mm */, void* wk) {
+    work = wk;
+    Tx = outs[0];
+    Wx = outs[1];
+    tau = outs[2];
+    int* given = static_cast<int*>(outs[3]);
+    int* head = cwt_head_at<int>(work, s.head.planes);
+    one = c.n_iter == 1 && given ? given : head;
+    last = c.n_iter == 1 ? one : (given ? given : head + s.cells);
+    return 0;
   }
-  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[2], st));
-  if (int rc = cwtt_scatter_run<T>(c, s, d_nu, d_Wx, last, d_work, d_Tx, st, kernel_ms ? t.ev[3] : (hipEvent_t) nullptr))
-    return rc;
-  if (kernel_ms) {
-    SSQ_HIP(end.start(1, st));
-    SSQ_HIP(hipEventSynchronize(end.ev[0]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[0], t.ev[0], end.ev[0]));
-    for (int i = 0; i < 3; ++i) SSQ_HIP(hipEventElapsedTime(&kernel_ms[1 + i], t.ev[i], t.ev[i + 1]));
+  int run(int64_t, const void* d_x, const hipEvent_t* mid) {
+    if (int rc = cwtt_operator_run<T>(c, s, d_x, scales, nu, Wx, tau, one, work)) return rc;
+    if (mid[0]) SSQ_HIP(hipEventRecord(mid[0], c.st));
+    if (c.n_iter > 1) SSQ_HIP(cwt_tmsst_walk_run(one, last, (long long)s.rows, (long long)c.N, c.n_iter, c.st));
+    if (mid[1]) SSQ_HIP(hipEventRecord(mid[1], c.st));
+    return cwtt_scatter_run<T>(c, s, nu, Wx, last, work, Tx, mid[2]);
   }
-  SSQ_HIP(hipStreamSynchronize(st));                           // (the tables above are freed on return)
-  if (final_mm) *final_mm = last;
-  return 0;
-}
-
-template <typename T>
-int cwttm_host_typed(const CwtTCall& c, const CwtMapsShape& s, int n_iter, const void* x, int64_t work_bytes, void* Tx,
-                     void* Wx, void* tau, void* mm) {
-  DeviceBufs d;
-  const size_t n = (size_t)s.rows * (size_t)c.m.N;
-  void *d_x, *d_Tx, *d_Wx, *d_work, *d_tau = nullptr;
-  SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * n));
-  SSQ_HIP(d.alloc(&d_Wx, sizeof(cpx<T>) * n));
-  if (tau) SSQ_HIP(d.alloc(&d_tau, sizeof(T) * n));
-  SSQ_HIP(d.alloc(&d_work, (size_t)work_bytes));
-  const int* last = nullptr;
-  if (int rc = cwttm_run<T>(c, s, n_iter, d_x, d_Tx, d_Wx, d_tau, nullptr, d_work, work_bytes, nullptr, nullptr, &last))
-    return rc;
-  SSQ_HIP(hipMemcpy(Tx, d_Tx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  SSQ_HIP(hipMemcpy(Wx, d_Wx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  if (tau) SSQ_HIP(hipMemcpy(tau, d_tau, sizeof(T) * n, hipMemcpyDeviceToHost));
-  if (mm) SSQ_HIP(hipMemcpy(mm, last, sizeof(int) * n, hipMemcpyDeviceToHost));
-  return 0;
-}
+};
 
 }  // namespace
 
@@ -161,30 +143,36 @@ int ssq_tmssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_sign
                        double gamma, int n_iter, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm, void* d_workspace,
                        int64_t workspace_bytes, void* stream, float* kernel_ms) {
   if (!d_x || !d_Tx || !d_Wx || !d_workspace) SSQ_FAIL("NULL argument");
-  const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales}, order, row_freqs};
+  const CwtTmCall c{{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, (hipStream_t)stream},
+                     order, row_freqs}, n_iter};
   CwtMapsShape s;
   if (int rc = cwtt_check(kCwtTmKind, cwttm_own_fail(order, n_iter), c, &s)) return rc;
-  if (int rc = cwt_exec_bytes(kCwtTmKind, s, workspace_bytes)) return rc;
+  if (int rc = cwt_exec_bytes(kCwtTmKind, &s, workspace_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == SSQ_F32 ? cwttm_run<float>(c, s, n_iter, d_x, d_Tx, d_Wx, d_tau, d_mm, d_workspace, workspace_bytes, st,
-                                             kernel_ms, nullptr)
-                          : cwttm_run<double>(c, s, n_iter, d_x, d_Tx, d_Wx, d_tau, d_mm, d_workspace, workspace_bytes, st,
-                                              kernel_ms, nullptr);
+  void* const outs[] = {d_Tx, d_Wx, d_tau, d_mm};
+  float part[4], *ms = kernel_ms ? part : nullptr;
+  const int rc = dtype == SSQ_F32 ? pipe_exec<CwtTmPipe<float>>(c, s, d_x, outs, d_workspace, ms, &c.st)
+                                  : pipe_exec<CwtTmPipe<double>>(c, s, d_x, outs, d_workspace, ms, &c.st);
+  if (rc == 0 && kernel_ms) {
+    kernel_ms[0] = part[0] + part[1] + part[2] + part[3];      // all the kernels
+    for (int i = 0; i < 3; ++i) kernel_ms[1 + i] = part[i];    // the operator part, the walk, the scatter kernel
+  }
+  return rc;
 }
 
 int ssq_tmssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
                        const double* scales, const double* row_freqs, int64_t na, double dt, int padtype, int order,
                        double gamma, int n_iter, int64_t work_limit_bytes, void* Tx, void* Wx, void* tau, void* mm) {
   if (!x || !Tx || !Wx) SSQ_FAIL("NULL argument");
-  const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales}, order, row_freqs};
+  const CwtTmCall c{{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, nullptr},
+                     order, row_freqs}, n_iter};
   CwtMapsShape s;
-  int64_t work = 0;
   if (int rc = cwtt_check(kCwtTmKind, cwttm_own_fail(order, n_iter), c, &s)) return rc;
-  if (int rc = cwt_host_bytes(kCwtTmKind, s, batch, work_limit_bytes, &work)) return rc;
+  if (int rc = cwt_host_bytes(kCwtTmKind, &s, batch, work_limit_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? cwttm_host_typed<float>(c, s, n_iter, x, work, Tx, Wx, tau, mm)
-                          : cwttm_host_typed<double>(c, s, n_iter, x, work, Tx, Wx, tau, mm);
+  const size_t el = (dtype == SSQ_F32 ? 4 : 8) * (size_t)s.plane;
+  const HostOut outs[] = {{Tx, 2 * el}, {Wx, 2 * el}, {tau, el}, {mm, sizeof(int32_t) * (size_t)s.plane}};
+  return dtype == SSQ_F32 ? cwt_pipe_host<CwtTmPipe<float>>(c, s, x, outs) : cwt_pipe_host<CwtTmPipe<double>>(c, s, x, outs);
 }
 
 int ssq_tmssq_cwt_tile_cols(int* halo) {
@@ -203,19 +191,20 @@ int ssq_tmssq_cwt_walk_host(const int32_t* targets_in, int64_t batch, int64_t n_
   for (size_t i = 0; i < map_sig * (size_t)batch; ++i)
     if (targets_in[i] < -1 || targets_in[i] >= n_cols) SSQ_FAIL("tmssq_cwt_walk: a target lies outside -1 .. n_cols - 1");
   if (int rc = require_device()) return rc;
-  DeviceBufs d;
-  const int64_t slice = slice_signals(batch, (double)map_sig * (2 * sizeof(int32_t)), 0.0, batch);
-  void *d_in, *d_out;
-  SSQ_HIP(d.alloc(&d_in, sizeof(int32_t) * map_sig * slice));
-  SSQ_HIP(d.alloc(&d_out, sizeof(int32_t) * map_sig * slice));
-  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
-    const int64_t nb = batch - b0 < slice ? batch - b0 : slice;
-    SSQ_HIP(hipMemcpy(d_in, targets_in + map_sig * b0, sizeof(int32_t) * map_sig * nb, hipMemcpyHostToDevice));
-    // (n_iter 1 too: the entry point runs the kernel, which then copies the map)
-    SSQ_HIP(cwt_tmsst_walk_run((const int*)d_in, (int*)d_out, (long long)nb * n_rows, (long long)n_cols, n_iter, nullptr));
-    SSQ_HIP(hipMemcpy(targets_out + map_sig * b0, d_out, sizeof(int32_t) * map_sig * nb, hipMemcpyDeviceToHost));
-  }
-  return 0;
+  const size_t map_bytes = sizeof(int32_t) * map_sig;
+  const HostOut outs[] = {{targets_out, map_bytes}};
+  int* d_out = nullptr;
+  return host_sliced(                                          // no workspace: the map in, the walked map out
+      batch, host_slice(batch, map_bytes, outs, 0), targets_in, map_bytes, outs,
+      [&](int64_t, void* const* o, void*) {
+        d_out = static_cast<int*>(o[0]);
+        return 0;
+      },
+      [&](int64_t nb, const void* d_in) -> int {
+        // (n_iter 1 too: the entry point runs the kernel, which then copies the map)
+        SSQ_HIP(cwt_tmsst_walk_run((const int*)d_in, d_out, (long long)nb * n_rows, (long long)n_cols, n_iter, nullptr));
+        return 0;
+      });
 }
 
 }  // extern "C"

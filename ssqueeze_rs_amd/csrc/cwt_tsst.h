@@ -40,8 +40,7 @@ struct CwtTScatDev {
   int qbits;
 };
 
-struct CwtTCall {
-  CwtMapsCall m;
+struct CwtTCall : CwtMapsCall {
   int order;
   const double* nu;
 };
@@ -52,29 +51,23 @@ inline const char* cwtt_order_fail(int order) { return order != 1 && order != 2 
 // nothing here touches the GPU).  own_fail: the message of the entry point's own checks (order, n_iter), or nullptr.
 int cwtt_check(const CwtMapsKind& k, const char* own_fail, const CwtTCall& c, CwtMapsShape* s);
 
-// The head of a workspace of either kind: the signals' maxima [batch] (to a multiple of 16 bytes), the accumulators
-// [cells][2] and behind them the int32 planes [cells] of the kind (tssq_cwt: one; tmssq_cwt: two).
-inline unsigned long long* cwtt_head_acc(void* d_work, int64_t batch) {
-  return reinterpret_cast<unsigned long long*>(static_cast<char*>(d_work) + cwt_emax_bytes(batch));
-}
-inline int* cwtt_head_plane(void* d_work, int64_t batch, int64_t cells, int which) {
-  return reinterpret_cast<int*>(cwtt_head_acc(d_work, batch) + 2 * cells) + which * cells;
-}
+// The head of a workspace of either kind is cwt_maps64.h's cwt_head: the signals' maxima, the accumulators [cells][2] and
+// behind them the int32 planes [cells] of the kind (tssq_cwt: one; tmssq_cwt: two).
 
-// c.m.scales and c.nu on the device, held by `d`
+// c.scales and c.nu on the device, held by `d`
 int cwtt_tables(DeviceBufs& d, const CwtTCall& c, void** d_scales, void** d_nu);
 
-// The operator part on device buffers, asynchronous on `st`: zeroes the maxima and the accumulators at the head of
-// d_work, then walks the chunks (`work_bytes` >= s.min_bytes sets the rows per chunk) with cwt_tsst_operator_kernel:
-// Wx, tau (d_tau may be nullptr) and the int32 one-step plane `mm`, -1 where a bin is not kept.
+// The operator part on device buffers, asynchronous on c.st: zeroes the maxima and the accumulators at the head of
+// d_work, then walks the chunks (s.work_bytes sets the rows per chunk) with cwt_tsst_operator_kernel: Wx, tau (d_tau may
+// be nullptr) and the int32 one-step plane `mm`, -1 where a bin is not kept.
 template <typename T>
 int cwtt_operator_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, const void* d_scales, const void* d_nu,
-                      void* d_Wx, void* d_tau, int* mm, void* d_work, int64_t work_bytes, hipStream_t st);
+                      void* d_Wx, void* d_tau, int* mm, void* d_work);
 
 // The scatter of Wx under the plane `mm` into the accumulators at the head of d_work, and the read-out into every cell of
-// Tx; asynchronous on `st`.  mid (may be nullptr): an event recorded between the two kernels.
+// Tx; asynchronous on c.st.  mid (may be nullptr): an event recorded between the two kernels.
 template <typename T>
 int cwtt_scatter_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_nu, const void* d_Wx, const int* mm,
-                     void* d_work, void* d_Tx, hipStream_t st, hipEvent_t mid);
+                     void* d_work, void* d_Tx, hipEvent_t mid);
 
 }  // namespace ssq

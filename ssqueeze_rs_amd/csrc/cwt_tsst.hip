@@ -30,8 +30,8 @@
 //                              every cell of Tx exactly once.
 // The rotation's angle is formed in turns: one fma of the exact product nu r against rint(nu r), rounded once, then sinpi
 // / cospi: its error does not grow with |r| <= N.
-// The head of the workspace: the signals' maxima [batch] (to a multiple of 16 bytes), the accumulators [batch][na][N][2]
-// and the int32 target map [batch][na][N] (to a multiple of 16 bytes).
+// The head of the workspace (cwt_maps64.h's cwt_head): the signals' maxima [batch], the accumulators [batch][na][N][2]
+// and the int32 target map [batch][na][N].  CwtTPipe runs the two halves behind both doors.
 #include <cmath>
 
 #include "cwt_tsst.h"
@@ -189,19 +189,19 @@ __global__ __launch_bounds__(kCwtThreads) void cwt_tsst_readout_kernel(const Cwt
 int cwtt_check(const CwtMapsKind& k, const char* own_fail, const CwtTCall& c, CwtMapsShape* s) {
   const std::string pre = std::string(k.name) + ": ";
   const auto rows = [&]() -> int {
-    if (!c.m.scales || !c.nu) SSQ_FAIL("NULL argument");
-    for (int64_t i = 0; i < c.m.na; ++i) {
-      if (!(c.m.scales[i] > 0) || !std::isfinite(c.m.scales[i])) SSQ_FAIL(pre + "scales must be positive and finite");
+    if (!c.scales || !c.nu) SSQ_FAIL("NULL argument");
+    for (int64_t i = 0; i < c.na; ++i) {
+      if (!(c.scales[i] > 0) || !std::isfinite(c.scales[i])) SSQ_FAIL(pre + "scales must be positive and finite");
       if (!(c.nu[i] > 0) || !std::isfinite(c.nu[i])) SSQ_FAIL(pre + "row_freqs must be positive and finite");
     }
     return 0;
   };
-  return cwt_maps_check(k, cwt_tsst_maps(c.order), own_fail, c.m, rows, nullptr, 0, nullptr, s);
+  return cwt_maps_check(k, cwt_tsst_maps(c.order), own_fail, c, rows, nullptr, 0, nullptr, s);
 }
 
 int cwtt_tables(DeviceBufs& d, const CwtTCall& c, void** d_scales, void** d_nu) {
-  SSQ_HIP(d.upload(d_scales, c.m.scales, sizeof(double) * (size_t)c.m.na));
-  SSQ_HIP(d.upload(d_nu, c.nu, sizeof(double) * (size_t)c.m.na));
+  SSQ_HIP(d.upload(d_scales, c.scales, sizeof(double) * (size_t)c.na));
+  SSQ_HIP(d.upload(d_nu, c.nu, sizeof(double) * (size_t)c.na));
   return 0;
 }
 
@@ -209,13 +209,13 @@ namespace {
 
 template <typename T, int ORDER>
 int cwtt_operator_order(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, const void* d_scales, const void* d_nu,
-                        void* d_Wx, void* d_tau, int* mm, void* d_work, int64_t work_bytes, hipStream_t st) {
-  const int64_t batch = c.m.batch, N = c.m.N, na = c.m.na;
-  const int64_t cells = batch * s.plane;
-  SSQ_HIP(hipMemsetAsync(d_work, 0, (size_t)(cwt_emax_bytes(batch) + 16 * cells), st));
+                        void* d_Wx, void* d_tau, int* mm, void* d_work) {
+  const int64_t N = c.N, na = c.na;
+  const hipStream_t st = c.st;
   CwtTOpDev<T> op{};
   op.nu = static_cast<const double*>(d_nu);
-  op.emax = static_cast<unsigned long long*>(d_work);                                                    // [batch]
+  op.emax = cwt_head_at<unsigned long long>(d_work, s.head.emax);                                        // [batch]
+  SSQ_HIP(hipMemsetAsync(op.emax, 0, (size_t)(s.head.planes - s.head.emax), st));   // the maxima and the accumulators
   op.P = s.P;
   op.N = N;
   op.n1 = s.n1;
@@ -223,8 +223,8 @@ int cwtt_operator_order(const CwtTCall& c, const CwtMapsShape& s, const void* d_
   op.inv_P = 1.0 / (double)s.P;
   op.gamma = s.gamma;
   op.gamma_sq = s.gamma * s.gamma;
-  op.dt = c.m.dt;
-  op.dt_o = (T)c.m.dt;
+  op.dt = c.dt;
+  op.dt_o = (T)c.dt;
   const auto launch_op = [&](const cpx<double>* maps, int64_t r0, int64_t nr) -> int {
     op.maps = maps;
     op.Wx = static_cast<cpx<T>*>(d_Wx) + r0 * N;
@@ -236,30 +236,31 @@ int cwtt_operator_order(const CwtTCall& c, const CwtMapsShape& s, const void* d_
     SSQ_HIP(hipGetLastError());
     return 0;
   };
-  return cwt_maps_chunks<T, cwt_tsst_map_set(ORDER)>(c.m, s, d_x, d_scales, d_work, work_bytes, st, launch_op);
+  return cwt_maps_chunks<T, cwt_tsst_map_set(ORDER)>(c, s, d_x, d_scales, d_work, launch_op);
 }
 
 }  // namespace
 
 template <typename T>
 int cwtt_operator_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, const void* d_scales, const void* d_nu,
-                      void* d_Wx, void* d_tau, int* mm, void* d_work, int64_t work_bytes, hipStream_t st) {
-  return c.order == 2 ? cwtt_operator_order<T, 2>(c, s, d_x, d_scales, d_nu, d_Wx, d_tau, mm, d_work, work_bytes, st)
-                      : cwtt_operator_order<T, 1>(c, s, d_x, d_scales, d_nu, d_Wx, d_tau, mm, d_work, work_bytes, st);
+                      void* d_Wx, void* d_tau, int* mm, void* d_work) {
+  return c.order == 2 ? cwtt_operator_order<T, 2>(c, s, d_x, d_scales, d_nu, d_Wx, d_tau, mm, d_work)
+                      : cwtt_operator_order<T, 1>(c, s, d_x, d_scales, d_nu, d_Wx, d_tau, mm, d_work);
 }
 
 template <typename T>
 int cwtt_scatter_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_nu, const void* d_Wx, const int* mm,
-                     void* d_work, void* d_Tx, hipStream_t st, hipEvent_t mid) {
-  const int64_t batch = c.m.batch, N = c.m.N;
+                     void* d_work, void* d_Tx, hipEvent_t mid) {
+  const int64_t batch = c.batch, N = c.N;
+  const hipStream_t st = c.st;
   int L = 0;
   while (((int64_t)1 << L) < N) ++L;                          // ceil(log2 N) <= 26
   CwtTScatDev<T> sc{};
   sc.Wx = static_cast<const cpx<T>*>(d_Wx);
   sc.mm = mm;
   sc.nu = static_cast<const double*>(d_nu);
-  sc.emax = static_cast<const unsigned long long*>(d_work);
-  sc.acc = cwtt_head_acc(d_work, batch);
+  sc.emax = cwt_head_at<unsigned long long>(d_work, s.head.emax);
+  sc.acc = cwt_head_at<unsigned long long>(d_work, s.head.acc);
   sc.Tx = static_cast<cpx<T>*>(d_Tx);
   sc.batch = batch;
   sc.plane = s.plane;
@@ -276,13 +277,13 @@ int cwtt_scatter_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_nu,
 }
 
 template int cwtt_operator_run<float>(const CwtTCall&, const CwtMapsShape&, const void*, const void*, const void*, void*,
-                                      void*, int*, void*, int64_t, hipStream_t);
+                                      void*, int*, void*);
 template int cwtt_operator_run<double>(const CwtTCall&, const CwtMapsShape&, const void*, const void*, const void*, void*,
-                                       void*, int*, void*, int64_t, hipStream_t);
+                                       void*, int*, void*);
 template int cwtt_scatter_run<float>(const CwtTCall&, const CwtMapsShape&, const void*, const void*, const int*, void*,
-                                     void*, hipStream_t, hipEvent_t);
+                                     void*, hipEvent_t);
 template int cwtt_scatter_run<double>(const CwtTCall&, const CwtMapsShape&, const void*, const void*, const int*, void*,
-                                      void*, hipStream_t, hipEvent_t);
+                                      void*, hipEvent_t);
 
 }  // namespace ssq
 
@@ -291,54 +292,34 @@ using namespace ssq;
 namespace {
 
 // the head: 16 bytes of accumulator and one int32 target per cell
-constexpr CwtMapsKind kCwtTKind = {"tssq_cwt", "ssq_tssq_cwt_workspace_bytes", 20.0, 4.0e18, 20};
+constexpr CwtMapsKind kCwtTKind = {"tssq_cwt", "ssq_tssq_cwt_workspace_bytes", 20.0, 4.0e18, 0, 16, 1};
 
-// The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the rows per chunk.  d_tau, d_mm may be nullptr
-// (the targets then live in the workspace alone).  Synchronous.  kernel_ms: three floats, all kernels, the scatter kernel
-// alone, and everything before the scatter.
+// tssq_cwt on device buffers (cwt_pipe_host, pipe_exec): the operator part, then the scatter with its read-out.  The
+// targets go to the caller's plane if given, else to the head's.  kernel_ms: three parts, the events before and after
+// the scatter kernel.
 template <typename T>
-int cwtt_run(const CwtTCall& c, const CwtMapsShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm,
-             void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
+struct CwtTPipe {
+  static constexpr int kMid = 2;
+  const CwtTCall& c;
+  const CwtMapsShape& s;
   DeviceBufs d;
-  TimingEvents t;
-  void *d_scales = nullptr, *d_nu = nullptr;
-  if (int rc = cwtt_tables(d, c, &d_scales, &d_nu)) return rc;
-  if (kernel_ms) SSQ_HIP(t.start(4, st));
-  int* mm = d_mm ? static_cast<int*>(d_mm) : cwtt_head_plane(d_work, c.m.batch, c.m.batch * s.plane, 0);
-  if (int rc = cwtt_operator_run<T>(c, s, d_x, d_scales, d_nu, d_Wx, d_tau, mm, d_work, work_bytes, st)) return rc;
-  if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
-  if (int rc = cwtt_scatter_run<T>(c, s, d_nu, d_Wx, mm, d_work, d_Tx, st, kernel_ms ? t.ev[2] : (hipEvent_t) nullptr))
-    return rc;
-  if (kernel_ms) {
-    SSQ_HIP(hipEventRecord(t.ev[3], st));
-    SSQ_HIP(hipEventSynchronize(t.ev[3]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[0], t.ev[0], t.ev[3]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[1], t.ev[1], t.ev[2]));
-    SSQ_HIP(hipEventElapsedTime(&kernel_ms[2], t.ev[0], t.ev[1]));
+  void *scales, *nu, *work, *Tx, *Wx, *tau;
+  int* mm;
+  int tables() { return cwtt_tables(d, c, &scales, &nu); }
+  int bind(int64_t, void* const* outs /* Tx, Wx, tau, mm */, void* wk) {
+    work = wk;
+    Tx = outs[0];
+    Wx = outs[1];
+    tau = outs[2];
+    mm = outs[3] ? static_cast<int*>(outs[3]) : cwt_head_at<int>(work, s.head.planes);
+    return 0;
   }
-  SSQ_HIP(hipStreamSynchronize(st));                           // (the tables above are freed on return)
-  return 0;
-}
-
-template <typename T>
-int cwtt_host_typed(const CwtTCall& c, const CwtMapsShape& s, const void* x, int64_t work_bytes, void* Tx, void* Wx,
-                    void* tau, void* mm) {
-  DeviceBufs d;
-  const size_t n = (size_t)s.rows * (size_t)c.m.N;
-  void *d_x, *d_Tx, *d_Wx, *d_work, *d_tau = nullptr;
-  SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.m.batch * (size_t)c.m.N));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * n));
-  SSQ_HIP(d.alloc(&d_Wx, sizeof(cpx<T>) * n));
-  if (tau) SSQ_HIP(d.alloc(&d_tau, sizeof(T) * n));
-  SSQ_HIP(d.alloc(&d_work, (size_t)work_bytes));
-  if (int rc = cwtt_run<T>(c, s, d_x, d_Tx, d_Wx, d_tau, nullptr, d_work, work_bytes, nullptr, nullptr)) return rc;
-  SSQ_HIP(hipMemcpy(Tx, d_Tx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  SSQ_HIP(hipMemcpy(Wx, d_Wx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  if (tau) SSQ_HIP(hipMemcpy(tau, d_tau, sizeof(T) * n, hipMemcpyDeviceToHost));
-  // the targets of the workspace: behind the maxima and the accumulators at its head
-  if (mm) SSQ_HIP(hipMemcpy(mm, cwtt_head_plane(d_work, c.m.batch, (int64_t)n, 0), sizeof(int) * n, hipMemcpyDeviceToHost));
-  return 0;
-}
+  int run(int64_t, const void* d_x, const hipEvent_t* mid) {
+    if (int rc = cwtt_operator_run<T>(c, s, d_x, scales, nu, Wx, tau, mm, work)) return rc;
+    if (mid[0]) SSQ_HIP(hipEventRecord(mid[0], c.st));
+    return cwtt_scatter_run<T>(c, s, nu, Wx, mm, work, Tx, mid[1]);
+  }
+};
 
 }  // namespace
 
@@ -356,28 +337,36 @@ int ssq_tssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signa
                       double gamma, void* d_Tx, void* d_Wx, void* d_tau, void* d_mm, void* d_workspace,
                       int64_t workspace_bytes, void* stream, float* kernel_ms) {
   if (!d_x || !d_Tx || !d_Wx || !d_workspace) SSQ_FAIL("NULL argument");
-  const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales}, order, row_freqs};
+  const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, (hipStream_t)stream},
+                   order, row_freqs};
   CwtMapsShape s;
   if (int rc = cwtt_check(kCwtTKind, cwtt_order_fail(order), c, &s)) return rc;
-  if (int rc = cwt_exec_bytes(kCwtTKind, s, workspace_bytes)) return rc;
+  if (int rc = cwt_exec_bytes(kCwtTKind, &s, workspace_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == SSQ_F32 ? cwtt_run<float>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_workspace, workspace_bytes, st, kernel_ms)
-                          : cwtt_run<double>(c, s, d_x, d_Tx, d_Wx, d_tau, d_mm, d_workspace, workspace_bytes, st, kernel_ms);
+  void* const outs[] = {d_Tx, d_Wx, d_tau, d_mm};
+  float part[3], *ms = kernel_ms ? part : nullptr;
+  const int rc = dtype == SSQ_F32 ? pipe_exec<CwtTPipe<float>>(c, s, d_x, outs, d_workspace, ms, &c.st)
+                                  : pipe_exec<CwtTPipe<double>>(c, s, d_x, outs, d_workspace, ms, &c.st);
+  if (rc == 0 && kernel_ms) {
+    kernel_ms[0] = part[0] + part[1] + part[2];                // all the kernels
+    kernel_ms[1] = part[1];                                    // the scatter kernel alone
+    kernel_ms[2] = part[0];                                    // everything before the scatter
+  }
+  return rc;
 }
 
 int ssq_tssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
                       const double* scales, const double* row_freqs, int64_t na, double dt, int padtype, int order,
                       double gamma, int64_t work_limit_bytes, void* Tx, void* Wx, void* tau, void* mm) {
   if (!x || !Tx || !Wx) SSQ_FAIL("NULL argument");
-  const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales}, order, row_freqs};
+  const CwtTCall c{{dtype, wavelet, padtype, batch, n_signal, na, p0, p1, dt, gamma, scales, nullptr}, order, row_freqs};
   CwtMapsShape s;
-  int64_t work = 0;
   if (int rc = cwtt_check(kCwtTKind, cwtt_order_fail(order), c, &s)) return rc;
-  if (int rc = cwt_host_bytes(kCwtTKind, s, batch, work_limit_bytes, &work)) return rc;
+  if (int rc = cwt_host_bytes(kCwtTKind, &s, batch, work_limit_bytes)) return rc;
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? cwtt_host_typed<float>(c, s, x, work, Tx, Wx, tau, mm)
-                          : cwtt_host_typed<double>(c, s, x, work, Tx, Wx, tau, mm);
+  const size_t el = (dtype == SSQ_F32 ? 4 : 8) * (size_t)s.plane;
+  const HostOut outs[] = {{Tx, 2 * el}, {Wx, 2 * el}, {tau, el}, {mm, sizeof(int32_t) * (size_t)s.plane}};
+  return dtype == SSQ_F32 ? cwt_pipe_host<CwtTPipe<float>>(c, s, x, outs) : cwt_pipe_host<CwtTPipe<double>>(c, s, x, outs);
 }
 
 }  // extern "C"

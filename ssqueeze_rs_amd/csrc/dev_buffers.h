@@ -1,8 +1,10 @@
 // dev_buffers.h -- the plumbing of the synchronous host entry points (host pointers in, device buffers for the
 // length of one call, host pointers out): the device check, the holder of the call's device allocations, the sizing of
 // a slice of signals (and the cap on it that lets a test reach the slices after the first), the sliced host call itself
-// (host_sliced: H2D, run, D2H per slice), the timing events of the device entry points (run_timed: up to three parts),
-// and the two doors of a pipeline that is written once for both (pipe_host, pipe_exec).
+// (host_slice sizes it, host_sliced runs it: H2D, run, D2H per slice), the timing events of the device entry points
+// (run_timed: up to four parts, on the null stream or a caller's), and the two doors of a pipeline that is written once
+// for both (pipe_host, pipe_exec).  The fp64 STFT pipelines (stft_frames64.h) and the fp64 CWT map pipelines
+// (cwt_maps64.h) go through the same doors.
 #pragma once
 #include <atomic>
 #include <vector>
@@ -74,22 +76,36 @@ struct HostOut {
   size_t bytes;
 };
 
-// A synchronous host entry over a batch: x ([batch] x `x_bytes`) in, the outputs that were asked for out, `work_bytes` of
-// workspace per signal.  The slice is slice_signals' of everything a signal needs on the device; the buffers are
-// allocated once.  bind(cap, d_outs, d_work) is called once with the slice's capacity in signals (where the pipeline
-// carves its workspace and fixes its device pointers), then per slice: H2D of x, run(nb, d_x), D2H of each output.
-// bind and run return the entry point's status (0, or non-zero with the error set).
-template <size_t N, typename Bind, typename Run>
-int host_sliced(int64_t batch, const void* x, size_t x_bytes, const HostOut (&outs)[N], size_t work_bytes, Bind&& bind,
-                Run&& run) {
+// how a host call cuts its batch: signals per slice, and the workspace bytes of one slice
+struct HostSlice {
+  int64_t signals;
+  size_t work_bytes;
+};
+
+// the slice of a workspace that is linear in the signals (`work_bytes` each): slice_signals' of everything a signal
+// needs on the device, x, the outputs that were asked for and its workspace
+template <size_t N>
+HostSlice host_slice(int64_t batch, size_t x_bytes, const HostOut (&outs)[N], size_t work_bytes) {
   double per = (double)x_bytes + (double)work_bytes;
   for (const HostOut& o : outs)
     if (o.host) per += (double)o.bytes;
   const int64_t slice = slice_signals(batch, per, 0.0, batch);
+  return {slice, work_bytes * (size_t)slice};
+}
+
+// A synchronous host entry over a batch: x ([batch] x `x_bytes`) in, the outputs that were asked for out, in slices of
+// sl.signals on a workspace of sl.work_bytes (host_slice's, or the caller's own: a workspace that is not linear in the
+// signals takes the batch whole).  The buffers are allocated once.  bind(cap, d_outs, d_work) is called once with the
+// slice's capacity in signals (where the pipeline carves its workspace and fixes its device pointers), then per slice:
+// H2D of x, run(nb, d_x), D2H of each output.  bind and run return the entry point's status (0, or non-zero with the
+// error set).
+template <size_t N, typename Bind, typename Run>
+int host_sliced(int64_t batch, HostSlice sl, const void* x, size_t x_bytes, const HostOut (&outs)[N], Bind&& bind, Run&& run) {
+  const int64_t slice = sl.signals;
   DeviceBufs d;
   void *d_x, *d_work, *d_outs[N] = {};
   SSQ_HIP(d.alloc(&d_x, x_bytes * (size_t)slice));
-  SSQ_HIP(d.alloc(&d_work, work_bytes * (size_t)slice));
+  SSQ_HIP(d.alloc(&d_work, sl.work_bytes));
   for (size_t i = 0; i < N; ++i)
     if (outs[i].host) SSQ_HIP(d.alloc(&d_outs[i], outs[i].bytes * (size_t)slice));
   if (int rc = bind(slice, d_outs, d_work)) return rc;
@@ -107,7 +123,7 @@ int host_sliced(int64_t batch, const void* x, size_t x_bytes, const HostOut (&ou
 
 // the timing events of one call, released on every path
 struct TimingEvents {
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   TimingEvents() = default;
   TimingEvents(const TimingEvents&) = delete;
   TimingEvents& operator=(const TimingEvents&) = delete;
@@ -123,21 +139,25 @@ struct TimingEvents {
   }
 };
 
-// The launches of a device entry point on the null stream, synchronous.  `run(mid)` issues them and returns the entry
-// point's status (0, or non-zero with the error set).  kernel_ms (may be nullptr) receives their time in n_mid + 1 parts
-// (n_mid: 0, 1 or 2): `run` records the event mid[i], i < n_mid, where part i ends.  Without kernel_ms every mid[i] is
-// nullptr and `run` records nothing.
+// The launches of a device entry point, synchronous.  stream == nullptr: they are on the null stream and the call
+// returns after hipDeviceSynchronize (the STFT entry points); else they are on *stream, the null stream included, and
+// the call is synchronous on that stream (the CWT entry points).  `run(mid)` issues them and returns the entry point's
+// status (0, or non-zero with the error set).  kernel_ms (may be nullptr) receives their time in n_mid + 1 consecutive
+// parts (n_mid: 0 .. 3): `run` records the event mid[i], i < n_mid, on its stream where part i ends.  Without kernel_ms
+// every mid[i] is nullptr and `run` records nothing.  An entry point that documents the time of several parts together
+// reports their sum, which differs from one elapsed-time query across them by float rounding alone.
 template <typename Run>
-int run_timed(float* kernel_ms, int n_mid, Run&& run) {
+int run_timed(float* kernel_ms, int n_mid, const hipStream_t* stream, Run&& run) {
   TimingEvents t;
+  const hipStream_t st = stream ? *stream : nullptr;
   if (!kernel_ms) {
     if (int rc = run((const hipEvent_t*)t.ev)) return rc;
-    SSQ_HIP(hipDeviceSynchronize());
+    SSQ_HIP(stream ? hipStreamSynchronize(st) : hipDeviceSynchronize());
     return 0;
   }
-  SSQ_HIP(t.start(n_mid + 2, nullptr));
+  SSQ_HIP(t.start(n_mid + 2, st));
   if (int rc = run((const hipEvent_t*)t.ev + 1)) return rc;
-  SSQ_HIP(hipEventRecord(t.ev[n_mid + 1], nullptr));
+  SSQ_HIP(hipEventRecord(t.ev[n_mid + 1], st));
   SSQ_HIP(hipEventSynchronize(t.ev[n_mid + 1]));
   for (int i = 0; i <= n_mid; ++i) SSQ_HIP(hipEventElapsedTime(&kernel_ms[i], t.ev[i], t.ev[i + 1]));
   return 0;
@@ -148,24 +168,31 @@ int run_timed(float* kernel_ms, int n_mid, Run&& run) {
 //   bind(cap, outs, work)     outs: the device outputs in the entry point's order (nullptr: not asked for); work: the
 //                             pipeline's workspace of `cap` signals, carved here by its one layout function
 //   run(nb, d_x, mid)         the launches of nb <= cap signals; mid: run_timed's events (Pipe::kMid of them)
-// each returning the entry point's status.  pipe_host: host pointers, in slices; pipe_exec: the caller's device buffers
-// and workspace at cap = batch, timed.
+// each returning the entry point's status.  pipe_host: host pointers, in slices (sized from `work_bytes` a signal, or
+// as the caller's HostSlice says); pipe_exec: the caller's device buffers and workspace at cap = batch, timed, `stream`
+// as run_timed has it (the pipe itself knows where its launches go).
 template <typename Pipe, typename Call, typename Shape, size_t N>
-int pipe_host(const Call& c, const Shape& s, const void* x, size_t x_bytes, const HostOut (&outs)[N], size_t work_bytes) {
+int pipe_host(const Call& c, const Shape& s, const void* x, size_t x_bytes, const HostOut (&outs)[N], HostSlice sl) {
   Pipe pl{c, s};
   if (int rc = pl.tables()) return rc;
-  const hipEvent_t none[2] = {nullptr, nullptr};
+  const hipEvent_t none[3] = {nullptr, nullptr, nullptr};
   return host_sliced(
-      c.batch, x, x_bytes, outs, work_bytes, [&](int64_t cap, void* const* o, void* work) { return pl.bind(cap, o, work); },
+      c.batch, sl, x, x_bytes, outs, [&](int64_t cap, void* const* o, void* work) { return pl.bind(cap, o, work); },
       [&](int64_t nb, const void* d_x) { return pl.run(nb, d_x, none); });
 }
 
+template <typename Pipe, typename Call, typename Shape, size_t N>
+int pipe_host(const Call& c, const Shape& s, const void* x, size_t x_bytes, const HostOut (&outs)[N], size_t work_bytes) {
+  return pipe_host<Pipe>(c, s, x, x_bytes, outs, host_slice(c.batch, x_bytes, outs, work_bytes));
+}
+
 template <typename Pipe, typename Call, typename Shape>
-int pipe_exec(const Call& c, const Shape& s, const void* d_x, void* const* d_outs, void* d_work, float* kernel_ms) {
+int pipe_exec(const Call& c, const Shape& s, const void* d_x, void* const* d_outs, void* d_work, float* kernel_ms,
+              const hipStream_t* stream = nullptr) {
   Pipe pl{c, s};
   if (int rc = pl.tables()) return rc;
   if (int rc = pl.bind(c.batch, d_outs, d_work)) return rc;
-  return run_timed(kernel_ms, Pipe::kMid, [&](const hipEvent_t* mid) { return pl.run(c.batch, d_x, mid); });
+  return run_timed(kernel_ms, Pipe::kMid, stream, [&](const hipEvent_t* mid) { return pl.run(c.batch, d_x, mid); });
 }
 
 }  // namespace ssq

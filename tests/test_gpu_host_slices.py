@@ -15,7 +15,8 @@ import pytest
 
 from ssqueeze_rs_amd import _lib
 from ssqueeze_rs_amd import upstream as up
-from tests.test_gpu_grid_limits import FS, HOP, N_ST, NFFT, STFT_IDS, STFT_RUNS, base_signals, gwin, stft_host
+from tests.test_gpu_grid_limits import (CWT_IDS, CWT_RUNS, FS, GMW, HOP, N_ST, NFFT, STFT_IDS, STFT_RUNS, base_signals,
+                                        cwt_host, cwt_scales, gwin, stft_host)
 
 pytestmark = pytest.mark.gpu
 
@@ -100,8 +101,30 @@ def test_batched_inverses(cdt, monkeypatch):
     assert_slices_change_nothing(lambda: [up.issq_cwt(T, "gmw")], "issq_cwt")
 
 
+@DTYPES
+def test_cwt_map_family_takes_the_batch_whole(rdt):
+    """ssq_cwt2, reassign_cwt, tssq_cwt (orders 1 and 2), mssq_cwt and tmssq_cwt (order 2, n_iter 3), every optional output:
+    their workspace is not linear in the signals and `work_limit_bytes` is defined for the whole batch, so their hosts do
+    not slice and the cap must not touch them.  5 signals of 32 samples, 8 scales at 4 to the octave."""
+    X = signals(rdt)
+    for (name, order), what in zip(CWT_RUNS, CWT_IDS):
+        assert_slices_change_nothing(lambda: cwt_host(name, order, X, 8, 4), what)
+    kw = dict(scales=cwt_scales(8, 4), fs=FS, order=2, n_iter=3)
+
+    def mssq():
+        out = up.mssq_cwt(X, GMW, get_w=True, get_rows=True, get_bins=True, **kw)
+        return [out[0], out[1], out[4], out[5], out[6]]
+
+    def tmssq():
+        out = up.tmssq_cwt(X, GMW, get_tau=True, get_targets=True, **kw)
+        return [out[0], out[1], out[4], out[5]]
+    assert_slices_change_nothing(mssq, "mssq_cwt")
+    assert_slices_change_nothing(tmssq, "tmssq_cwt")
+
+
 def test_walk_hosts():
-    """msst_walk, tmsst_walk, mssq_cwt_walk and tmssq_cwt_walk, which repack every slice on the host: [5, 9, 4] maps."""
+    """msst_walk, tmsst_walk, mssq_cwt_walk and tmssq_cwt_walk on [5, 9, 4] maps.  The two STFT walks repack every slice on
+    the host and keep a loop of their own; the two CWT walks repack nothing and go through `host_sliced`."""
     rng = np.random.default_rng(12)
     R, n = NFFT // 2 + 1, (N_ST - 1) // HOP + 1
     bins = rng.integers(-1, R, size=(B, R, n)).astype(np.int32)
