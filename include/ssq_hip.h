@@ -296,6 +296,41 @@ int ssq_tmsst_walk_host(const int32_t* targets_in, int64_t batch, int64_t n_rows
 /* Target frames of the tile one workgroup of the walk kernel (and of the scatter) owns for one-step targets within `reach`
  * frames walked n_iter steps (1024 .. 4096; host only), -1 where ssq_tmsst_walk_host refuses the pair. */
 int ssq_tmsst_tile_frames(int64_t reach, int n_iter);
+/* Synchroextracting and transient-extracting STFT, `upstream.set_stft` (axis 0; Yu, Yu and Zhang 2017; second order: Bao
+ * et al. 2019) and `upstream.tet_stft` (axis 1; Yu 2019) (csrc/stft_extract.hip; upstream has no such
+ * transform): a coefficient is KEPT where its own estimate says it already sits on the ridge, and zeroed elsewhere;
+ * nothing moves.  window [n_fft] already sized, padtype SSQ_PAD_*, axis 0 (frequency) or 1 (time), order 1 or 2,
+ * gamma < 0: 10 eps of the dtype (NaN is refused), variant: the SSQ_VARIANT_MODULATED bit (the others are ignored).  n_fft
+ * must be a power of two from 16 to 4096.  In fp64 for either dtype, with F = n_fft/2 + 1 and a cell LIVE where
+ * |V| > gamma:
+ *   axis 0: w = the frequency ssq_ssq_stft2_host reports: fs |Re w2| where order = 2, |D| > gamma^2 and Re w2 is finite,
+ *           else fs |Re w1| (order 1: on every cell, from the ONE transform x (g + i g1)); rounded once to `dtype`, +inf
+ *           where the cell is not live;  b = the clamped round-half-even bin of w on np.linspace(0, fs/2, F), taken in
+ *           `dtype` (ssq_ssq_stft2_host's rule, no flipud);  the cell is kept where b == k;
+ *   axis 1: tau = the offset ssq_tssq_stft_host reports, in seconds and `dtype`: d2 with its fallback to d1, clamped to
+ *           +- n_fft/2 (order 1: d1, from the ONE transform x (g + i tg)), +inf where the cell is not live;
+ *           r = rint(tau / (hop/fs)) in `dtype`, BEFORE ssq_tssq_stft_host's clip to the frame range (an edge cell that
+ *           the clip would bring back onto itself is not kept);  the cell is kept where r == 0;
+ *   Te[k][m] = Sx[k][m] where the cell is live and kept, else +0 + 0i.  The rows of Te are the rows of Sx.
+ * Te holds exactly the coefficients that ssq_mssq_stft_host(order, n_iter = 1) leaves on their own row (axis 0) and that
+ * ssq_tssq_stft_host would move by r = 0 (axis 1).  Every cell is written exactly once by ONE kernel; signal b's bits do
+ * not depend on `batch`, the slice or the workspace.  Te: [batch][n_freqs][n_frames] complex of `dtype`; Sx (may be
+ * NULL): the same shape, equal to the STFT; map (may be NULL): [batch][n_freqs][n_frames] REAL of `dtype`, w (axis 0) or
+ * tau (axis 1).  There is no inverse.  Synchronous; the batch goes through the device in slices sized from its free
+ * memory. */
+int ssq_extract_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                          int64_t hop, double fs, int padtype, int axis, int order, double gamma, int variant, void* Te,
+                          void* Sx, void* map);
+/* Device bytes of the workspace ssq_extract_stft_exec needs: for SSQ_F32 the signals widened to fp64 (8 batch n_signal),
+ * for SSQ_F64 none (0); computed on the host; -1 on a shape ssq_extract_stft_host refuses. */
+int64_t ssq_extract_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop);
+/* The same transform on device buffers: d_x [batch][N], d_Te, d_Sx (may be NULL), d_map (may be NULL) as above,
+ * d_workspace of at least ssq_extract_stft_workspace_bytes bytes (where that is 0, d_workspace may be NULL); `window` on
+ * the host.  Synchronous.  kernel_ms (may be NULL): ONE float, the time of the kernel (with the widening of a float32
+ * call), from HIP events around the launches with the tables set up before them. */
+int ssq_extract_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                          int64_t hop, double fs, int padtype, int axis, int order, double gamma, int variant, void* d_Te,
+                          void* d_Sx, void* d_map, void* d_workspace, int64_t workspace_bytes, float* kernel_ms);
 /* Reassigned spectrogram, `upstream.reassign_stft` (csrc/stft_reassign.hip; Kodera et al. 1978; Auger and
  * Flandrin 1995; upstream has no such transform): every bin's energy |Sx|^2 moves along frequency AND time at once, to
  * its instantaneous frequency and its group delay (first order only).  window [n_fft] already sized, padtype SSQ_PAD_*,

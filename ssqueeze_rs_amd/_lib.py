@@ -95,6 +95,11 @@ _SIGNATURES = {
     "ssq_tssq_stft_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64]),
     "ssq_tssq_stft_exec": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_double,
                                      C.c_int, vp, vp, vp, vp, i64, C.POINTER(C.c_float)]),
+    "ssq_extract_stft_host": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_int,
+                                        C.c_double, C.c_int, vp, vp, vp]),
+    "ssq_extract_stft_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64]),
+    "ssq_extract_stft_exec": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_int,
+                                        C.c_double, C.c_int, vp, vp, vp, vp, i64, C.POINTER(C.c_float)]),
     "ssq_tmssq_stft_host": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_double,
                                       C.c_int, C.c_int, vp, vp, vp, vp]),
     "ssq_tmssq_stft_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64, C.c_int]),

@@ -54,6 +54,11 @@ Supported subset (anything else raises ValueError naming the option):
     again at the frame a coefficient landed on, `n_iter` steps in all (1 .. 64, with n_iter ceil(n_fft / (2 hop_len)) <=
     16384), which narrows the ridge of an impulsive or dispersive signal whose group delay is not linear inside the
     window; the conventions of `tssq_stft`; no inverse; `tmsst_walk` runs the walk alone on an int32 map the caller holds;
+  * `set_stft` and `tet_stft`: the synchroextracting (Yu, Yu and Zhang 2017; Bao et al. 2019) and the transient-extracting
+    (Yu 2019) STFT, orders 1 and 2, which upstream does not have (the definition is this project's: DESIGN 4.23,
+    csrc/stft_extract.hip): a coefficient is kept where `ssq_stft2`'s frequency names its own row (`set_stft`) or
+    `tssq_stft`'s group delay its own column (`tet_stft`) and zeroed elsewhere, in ONE kernel that writes every cell once;
+    the conventions of `tssq_stft`; `Te` keeps the rows of `Sx`, a sparse input for `extract_ridges`; no inverse;
   * `reassign_stft`: the reassigned spectrogram (Kodera et al.; Auger and Flandrin 1995), which upstream does not have
     (the definition is this project's: DESIGN 4.14, csrc/stft_reassign.hip): every bin's energy |Sx|^2 moves along
     frequency and time at once, to its instantaneous frequency and group delay (first order); the conventions of
@@ -723,7 +728,87 @@ def tmsst_tile_frames(reach, n_iter):
     return int(c)
 
 
-# csrc/stft_reassign.hip: kReassignQuantumLog2.  `reassign_stft` accumulates |Sx|^2 in 64-bit fixed point with the quantum
+def _extract_stft(name, axis, x, window, n_fft, win_len, hop_len, fs, t, modulated, padtype, order, gamma, get_Sx, get_map):
+    """The body of `set_stft` (axis 0) and `tet_stft` (axis 1) -> (f, Te, Sx | None, map | None), batch axis dropped."""
+    lib = _lib.load()
+    order = _order12(order, f"{name} builds orders 1 and 2")
+    f = _stft_front(x, window, n_fft, win_len, hop_len, fs, t, name)
+    if gamma is not None and math.isnan(float(gamma)):
+        raise ValueError("gamma is NaN")
+    pad = _pad_code(padtype)
+    _lib.require_gpu()
+    shape = _stft_shape(f, hop_len)
+    Te = _lib.pinned_empty(shape, f.cdt)
+    Sx = _lib.pinned_empty(shape, f.cdt) if get_Sx else None
+    mp = _lib.pinned_empty(shape, f.rdt) if get_map else None
+    _call(lib.ssq_extract_stft_host(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs, pad, axis, order,
+                                    _gamma_arg(gamma), _variant(modulated), _ptr(Te), _ptr(Sx), _ptr(mp)))
+    unb = lambda a: None if a is None else (a if f.batched else a[0])                # noqa: E731
+    return f, unb(Te), unb(Sx), unb(mp)
+
+
+def set_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
+             order=2, gamma=None, get_Sx=True, get_w=False):
+    """Synchroextracting STFT -> (Te, Sx | None, Sfs[, w]); not in upstream (Yu, Yu and Zhang 2017; second order: Bao et
+    al. 2019), conventions of `ssq_stft2`.  Where the synchrosqueezed transforms MOVE a coefficient to the frequency it
+    estimates, this KEEPS a coefficient only where its estimated instantaneous frequency is the frequency of its own
+    row, and zeroes the rest: what is left is the ridge itself, unsmeared, with the STFT's own amplitudes and phases.
+
+    With the five windows and STFTs of `ssq_stft2` (in fp64 for either dtype, on the widened signal) and F = n_fft // 2
+    + 1 rows, a cell is live where |V| > gamma (default 10 eps of the dtype) and
+        w = fs |Re w2| where order = 2, |D| > gamma^2 and Re w2 is finite, else fs |Re w1|       (`ssq_stft2`'s `w2`)
+        w = fs |Re w1| on every cell for order = 1              (ONE transform, x (g + i g1), a third of order 2's work)
+    rounded once to the call's dtype, +inf where the cell is not live (`w`, get_w=True).  With b the clamped
+    round-half-even bin of the reported `w` on np.linspace(0, fs / 2, F), taken in the call's dtype (the rule of
+    `ssq_stft2`):
+        Te[k, m] = Sx[k, m]  where the cell is live and b == k,     else +0 + 0i.
+    There is no `squeezing`, `flipud` or `ssq_freqs`: the rows of `Te` are the rows of `Sx`, at `Sfs`.  `Te` holds exactly
+    the coefficients that `mssq_stft(order=order, n_iter=1)` leaves on their own row.  `Sx` (None with get_Sx=False,
+    which saves its store and its copy) equals `stft(x, ...)`.  One kernel writes every cell exactly once, so signal b's
+    bits do not depend on the batch.
+
+    There is no inverse, and SET is not a reconstruction method for strongly modulated components (the ridge cells alone
+    give back a fast chirp with a relative error of 0.5).  What stands in for one is the identity of a tone on a bin
+    centre, (2 / sum(g)) Re sum_k c_k Te[k, m] = x[m] with c = 1/2 on rows 0 and F - 1 and 1 elsewhere, which holds to
+    1e-8.
+
+    `n_fft` must be a power of two from 16 to 4096 and `order` 1 or 2 (ValueError otherwise, before any GPU work).  Every
+    (dtype, n_fft, order) is built without register spills or scratch (profiles/extract_resources.txt)."""
+    f, Te, Sx, w = _extract_stft("set_stft", 0, x, window, n_fft, win_len, hop_len, fs, t, modulated, padtype, order, gamma,
+                                 get_Sx, get_w)
+    return (Te, Sx, _Sfs(f), *((w,) if get_w else ()))
+
+
+def tet_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
+             order=2, gamma=None, get_Sx=True, get_tau=False):
+    """Transient-extracting STFT -> (Te, Sx | None, times, Sfs[, tau]); not in upstream (Yu 2019), conventions of
+    `tssq_stft`.  The dual of `set_stft`: it KEEPS a coefficient only where its estimated group delay is its own column,
+    and zeroes the rest, so an impulse, a click or a dispersive arrival is left on the columns where it happens.
+
+    With the windows and STFTs of `tssq_stft` (in fp64 for either dtype) a cell is live where |V| > gamma (default 10
+    eps of the dtype) and `tau` (get_tau=True) is `tssq_stft`'s reported offset in seconds, in the call's dtype, +inf
+    where the cell is not live: order = 2 uses d2 with its fallback to d1, clamped to +- n_fft / 2 samples; order = 1 uses
+    d1 (ONE transform, x (g + i tg)).  With
+        r = rint(tau / (hop_len / fs))  in the call's dtype,
+        Te[k, m] = Sx[k, m]  where the cell is live and r == 0,     else +0 + 0i.
+    r is the relative target BEFORE `tssq_stft`'s clip to the frame range: an edge cell that the clip would bring back
+    onto itself is not kept.  `Te` holds exactly the coefficients that `tssq_stft` leaves on their own column for that
+    reason (for frequency, the counterpart is `mssq_stft(order=order, n_iter=1)` and `set_stft`).  An isolated unit
+    impulse at sample t0 is kept on column t0 / hop_len only, with |Te[k, t0]| = g[n_fft // 2] in every row.  `Sx` (None
+    with get_Sx=False) equals `stft(x, ...)`; `times` = arange(n_frames) hop_len / fs.  One kernel writes every cell
+    exactly once, so signal b's bits do not depend on the batch.
+
+    There is no inverse (for a tone on a bin centre `set_stft` has an identity that stands in for one; a transient has
+    none).
+
+    `n_fft` must be a power of two from 16 to 4096 and `order` 1 or 2 (ValueError otherwise, before any GPU work).  Every
+    (dtype, n_fft, order) is built without register spills or scratch (profiles/extract_resources.txt)."""
+    f, Te, Sx, tau = _extract_stft("tet_stft", 1, x, window, n_fft, win_len, hop_len, fs, t, modulated, padtype, order,
+                                   gamma, get_Sx, get_tau)
+    return (Te, Sx, _times(f, hop_len), _Sfs(f), *((tau,) if get_tau else ()))
+
+
+# csrc/stft_reassign.hip: kReassignQuantumLog2. `reassign_stft` accumulates |Sx|^2 in 64-bit fixed point with the quantum
 # q = P 2^REASSIGN_QUANTUM_LOG2, P the smallest power of two >= the signal's max |Sx|^2.
 REASSIGN_QUANTUM_LOG2 = -38
 
