@@ -600,6 +600,40 @@ int ssq_tmssq_cwt_walk_host(const int32_t* targets_in, int64_t batch, int64_t n_
 /* Columns of the tile one workgroup of the walk kernel owns; *halo (may be NULL): the columns it stages on either side of
  * the tile.  Host only. */
 int ssq_tmssq_cwt_tile_cols(int* halo);
+/* Synchroextracting and transient-extracting CWT, `upstream.set_cwt` (axis 0) and `upstream.tet_cwt` (axis 1)
+ * (csrc/cwt_extract.hip; the CWT counterpart of ssq_extract_stft_host; upstream has neither): a coefficient
+ * is KEPT where its own estimate says it sits on the ridge and zeroed elsewhere.  Arguments, conventions and limits of
+ * ssq_tssq_cwt_host without its na * n_signal limit (there is no accumulator); axis 0 or 1, order 1 or 2.  With the maps
+ * of ssq_ssq_cwt2_host in fp64 for either dtype, a cell live unless |W| < gamma:
+ *   axis 0: w = ssq_ssq_cwt2_host's w2 (order 2, with its fallback) or |Im(W1/W)| / (2 pi dt) on every cell (order 1, from
+ *           W and W1 alone), rounded once to `dtype`, +inf where the cell is not live;  row_edges [na + 1], Hz, fp64, the
+ *           caller's (`upstream.set_cwt_row_edges`): e[0] = +inf, e[na] = 0, never increasing, no NaN; each is rounded
+ *           once to `dtype`;  keep where e[i+1] <= w < e[i], compared in `dtype` (a NaN w is kept nowhere).
+ *   axis 1: tau = ssq_tssq_cwt_host's reported offset (order 2: d2 with its fallback to d1; order 1: d1, from W and Wt
+ *           alone), +inf where the cell is not live;  keep where rint(tau / dt) == 0 in `dtype`, the relative target
+ *           BEFORE that entry's clip to the signal.
+ *   Te[i][j] = Wx[i][j] where the cell is live and kept, else +0 + 0i.
+ * row_freqs [na] (ssq_tssq_cwt_host's) is required for axis 1 and row_edges for axis 0; the one the axis does not use may
+ * be NULL (it is checked if given).  Te (required), Wx (may be NULL): [batch][na][n_signal] complex of `dtype`, Wx
+ * ssq_ssq_cwt2_host's; map (may be NULL): REAL of `dtype`, w in Hz or tau in seconds.  One operator kernel writes every
+ * cell exactly once.  Workspace: 16 P (batch + 2 M R) bytes for chunks of R rows and nothing else, M = 2 (order 1) or 5
+ * (order 2); a row's result does not depend on R or on the batch.  work_limit_bytes: 0 for the preferred size, else at
+ * least min_bytes. */
+int ssq_extract_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                         const double* scales, const double* row_freqs, const double* row_edges, int64_t na, double dt,
+                         int padtype, int axis, int order, double gamma, int64_t work_limit_bytes, void* Te, void* Wx,
+                         void* map);
+/* Device bytes of the workspace: returns the preferred size (every row in one chunk, capped at 2 GiB) and stores the
+ * least one (one row per chunk) in *min_bytes (may be NULL); computed on the host; -1 on a bad shape. */
+int64_t ssq_extract_cwt_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int order, int64_t* min_bytes);
+/* The same transform on device buffers: d_x [batch][n_signal], d_Te (required), d_Wx, d_map (each may be NULL) as above,
+ * d_workspace of workspace_bytes >= min_bytes (its size sets R; one byte less is refused before any launch); scales,
+ * row_freqs, row_edges on the host.  Synchronous on `stream`.  kernel_ms (may be NULL): ONE float, the time of the kernels
+ * alone, from HIP events around the launches. */
+int ssq_extract_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                         const double* scales, const double* row_freqs, const double* row_edges, int64_t na, double dt,
+                         int padtype, int axis, int order, double gamma, void* d_Te, void* d_Wx, void* d_map,
+                         void* d_workspace, int64_t workspace_bytes, void* stream, float* kernel_ms);
 /* ConceFT, the multitaper synchrosqueezed CWT, `upstream.conceft_cwt` (csrc/cwt_conceft.hip; Daubechies,
  * Wang and Wu 2016; upstream has no such transform).  The wavelets are the GMWs (gmw_gamma, gmw_beta; bandpass norm) of
  * n_orders distinct orders, coeffs [n_orders][n_coeffs] their polynomials as for ssq_cwt_host_gmwk (1 <= n_orders <= 8,

@@ -147,6 +147,12 @@ _SIGNATURES = {
                                      C.POINTER(C.c_float)]),
     "ssq_tmssq_cwt_walk_host": (C.c_int, [vp, i64, i64, i64, C.c_int, vp]),
     "ssq_tmssq_cwt_tile_cols": (C.c_int, [C.POINTER(C.c_int)]),
+    "ssq_extract_cwt_host": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, vp, vp, i64, C.c_double,
+                                       C.c_int, C.c_int, C.c_int, C.c_double, i64, vp, vp, vp]),
+    "ssq_extract_cwt_workspace_bytes": (i64, [C.c_int, i64, i64, i64, C.c_int, C.POINTER(i64)]),
+    "ssq_extract_cwt_exec": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, vp, vp, i64, C.c_double,
+                                       C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, i64, vp,
+                                       C.POINTER(C.c_float)]),
     "ssq_conceft_cwt_host": (C.c_int, [C.c_int, vp, i64, i64, C.c_double, C.c_double, vp, i64, i64, vp, i64, C.c_double,
                                        vp, i64, C.c_double, vp, vp, C.c_int, i64, C.c_int, C.c_double, C.c_int, i64, vp,
                                        vp, vp]),

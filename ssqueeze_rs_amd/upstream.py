@@ -89,6 +89,11 @@ Supported subset (anything else raises ValueError naming the option):
     dispersive signal; a target may lie anywhere in its row, so the walk kernel stages a tile in LDS and reads the far
     steps from device memory; the conventions, the accumulation and the quantum of `tssq_cwt`; no inverse;
     `tmssq_cwt_walk` runs the walk alone on an int32 map the caller holds;
+  * `set_cwt` and `tet_cwt`: the synchroextracting and the transient-extracting CWT (orders 1 and 2), the CWT
+    counterparts of `set_stft` and `tet_stft`, which upstream does not have (the definition is this project's: DESIGN
+    4.24, csrc/cwt_extract.hip): a coefficient is kept where `ssq_cwt2`'s frequency falls in the band of its own row
+    (`set_cwt`, the bands of `set_cwt_row_edges`) or `tssq_cwt`'s group delay names its own column (`tet_cwt`) and zeroed
+    elsewhere, by ONE operator kernel that writes every cell once; the conventions of `tssq_cwt`; no inverse;
   * `conceft_cwt`: ConceFT, the multitaper synchrosqueezed CWT (Daubechies, Wang and Wu 2016), which upstream does not
     have (the definition is this project's: DESIGN 4.18, csrc/cwt_conceft.hip): `ssq_cwt` under M random unit
     combinations of the GMWs of J orders (`conceft_vectors`, gauged by the orders' admittances `gmw_adm_ssq`), averaged,
@@ -1448,6 +1453,106 @@ def tmssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None
     _call(lib.ssq_tmssq_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), _ptr(nu), len(s), f.dt,
                                  f.pad, order, f.gamma, n_iter, limit, _ptr(Tx), _ptr(Wx), _ptr(tau), _ptr(mm)))
     return (*_unbatch(f.batched, Tx, Wx), s.astype(f.rdt), (nu / f.dt).astype(f.rdt), *_unbatch(f.batched, tau, mm))
+
+
+def _row_edges(nu, dt):
+    """e [na + 1] float64, Hz: +inf, the log midpoints sqrt(nu[i-1] nu[i]) / dt of strictly decreasing nu, 0."""
+    if len(nu) < 2 or not (np.diff(nu) < 0).all():
+        raise ValueError("`scales` must give strictly decreasing row frequencies (strictly increasing scales)")
+    e = np.empty(len(nu) + 1, dtype=np.float64)
+    e[0], e[-1] = np.inf, 0.0
+    e[1:-1] = np.sqrt(nu[:-1] * nu[1:]) / dt
+    return e
+
+
+def set_cwt_row_edges(wavelet, scales, fs=None):
+    """e [na + 1] float64, Hz: the edges of `set_cwt`'s rows, the one array the library, the model and the tests read.
+    With nu = `tssq_cwt_row_freqs(wavelet, scales)`, which must be strictly decreasing (ValueError otherwise), and dt =
+    1 / fs (1 without `fs`):
+        e[0] = +inf,    e[i] = sqrt(nu[i-1] nu[i]) / dt  (i = 1 .. na - 1),    e[na] = 0.
+    Row i keeps a frequency w with e[i+1] <= w < e[i]: the outer rows are open-ended, and on an edge the higher-frequency
+    row wins.  Rows are constant-Q, so the midpoint is taken in log frequency on every scale grid (as `mssq_cwt_row_of_bin`
+    takes the nearest row).  Rows and bins are different index sets on the CWT, which is why this is not `ssq_freqs`."""
+    fs = 1.0 if fs is None else float(fs)
+    if not (fs > 0 and math.isfinite(fs)):
+        raise ValueError("`fs` must give a positive sampling period")
+    return _row_edges(tssq_cwt_row_freqs(wavelet, scales), 1.0 / fs)
+
+
+def _extract_cwt(axis, x, wavelet, scales, nv, fs, t, padtype, order, gamma, get_Wx, get_map, work_limit_bytes):
+    """The body of `set_cwt` (axis 0) and `tet_cwt` (axis 1) -> (Te, Wx | None, scales, row_freqs[, map]), batch axis
+    dropped for 1-D `x`."""
+    lib = _lib.load()
+    order, f, s, nu, limit = _tssq_cwt_args(lib.ssq_extract_cwt_workspace_bytes, x, wavelet, scales, nv, fs, t, padtype,
+                                            order, gamma, work_limit_bytes)
+    edges = _row_edges(nu, f.dt) if axis == 0 else None
+    _lib.require_gpu()
+    shape = (f.batch, len(s), f.N)
+    Te = _lib.pinned_empty(shape, f.cdt)
+    Wx = _lib.pinned_empty(shape, f.cdt) if get_Wx else None
+    mp = _lib.pinned_empty(shape, f.rdt) if get_map else None
+    _call(lib.ssq_extract_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), _ptr(nu), _ptr(edges),
+                                   len(s), f.dt, f.pad, axis, order, f.gamma, limit, _ptr(Te), _ptr(Wx), _ptr(mp)))
+    unb = lambda a: None if a is None else (a if f.batched else a[0])                # noqa: E731
+    return (unb(Te), unb(Wx), s.astype(f.rdt), (nu / f.dt).astype(f.rdt), *((unb(mp),) if get_map else ()))
+
+
+def set_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, padtype="reflect", order=2, gamma=None,
+            get_Wx=True, get_w=False, work_limit_bytes=None):
+    """Synchroextracting CWT -> (Te, Wx | None, scales, row_freqs[, w]); not in upstream (the CWT counterpart of
+    `set_stft`: Yu, Yu and Zhang 2017; second order: Bao et al. 2019), conventions of `tssq_cwt`.  Where `ssq_cwt2` and
+    `mssq_cwt` MOVE a coefficient to the frequency it estimates, this KEEPS a coefficient only where its estimated
+    instantaneous frequency falls in the band of its own row, and zeroes the rest: what is left is the ridge itself, with
+    the CWT's own amplitudes and phases.
+
+    Per sample, with the maps of `ssq_cwt2` in fp64 for either dtype, a cell is live unless |W| < gamma (default 10 eps
+    of the dtype; the CWT family's rule) and
+        w = |Im om2| / (2 pi dt) where order = 2, |D| > gamma^2 and Im om2 is finite, else |Im om1| / (2 pi dt)
+                                                                                               (`ssq_cwt2`'s `w2`)
+        w = |Im om1| / (2 pi dt) on every cell for order = 1   (W and W1 alone: TWO inverse transforms a row, not five)
+    rounded once to the call's dtype, +inf where the cell is not live (`w`, get_w=True).  With e = `set_cwt_row_edges`
+    (+inf, the log midpoints of the rows' frequencies in Hz, 0), each edge rounded once to the call's dtype:
+        Te[i, j] = Wx[i, j]  where the cell is live and e[i+1] <= w < e[i],     else +0 + 0i.
+    The comparison is made in the call's dtype on the reported `w`; a NaN is kept nowhere, the outer rows are open-ended
+    and on an edge the higher-frequency row wins.  The rows' own frequencies are used, not `ssq_freqs`: a bin grid is
+    many-to-one onto rows.  There are no `ssq_freqs`, `maprange`, `squeezing`, `flipud` or row weights: `Te` is [na, N]
+    on the rows of `Wx`.  `Wx` (None with get_Wx=False, which saves its store and its copy) equals `ssq_cwt2`'s;
+    `row_freqs` is nu / dt in Hz in the call's real dtype.  One operator kernel writes every cell exactly once, so signal
+    b's bits depend neither on the batch nor on the chunking (`work_limit_bytes`).
+
+    There is no inverse; for a tone on a row's frequency, Re sum_i Te[i, j] gives the tone back (6e-6 at order 2 on the
+    shape of DESIGN 4.24).
+
+    Built: what `tssq_cwt` builds, without its na N limit; `scales` must be strictly increasing, so that the rows'
+    frequencies strictly decrease.  Anything else raises ValueError before any GPU work.  The kernel is built without
+    register spills or scratch (profiles/extract_cwt_resources.txt)."""
+    return _extract_cwt(0, x, wavelet, scales, nv, fs, t, padtype, order, gamma, get_Wx, get_w, work_limit_bytes)
+
+
+def tet_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, padtype="reflect", order=2, gamma=None,
+            get_Wx=True, get_tau=False, work_limit_bytes=None):
+    """Transient-extracting CWT -> (Te, Wx | None, scales, row_freqs[, tau]); not in upstream (the CWT counterpart of
+    `tet_stft`: Yu 2019), conventions of `tssq_cwt`.  The dual of `set_cwt`: it KEEPS a coefficient only where its
+    estimated group delay is its own column, and zeroes the rest, so a click's cone is left as the click's column and a
+    fast sweep as the columns where it crosses each row.
+
+    Per sample, with the maps of `tssq_cwt` in fp64 for either dtype, a cell is live unless |W| < gamma (default 10 eps
+    of the dtype) and `tau` (get_tau=True) is `tssq_cwt`'s reported offset in seconds, in the call's dtype, +inf where the
+    cell is not live: order = 2 uses d2 with its fallback to d1; order = 1 uses d1 (W and Wt alone: TWO inverse
+    transforms a row, not five); both clamped to +- N samples.  With
+        r = rint(tau / dt)  in the call's dtype,
+        Te[i, j] = Wx[i, j]  where the cell is live and r == 0,     else +0 + 0i.
+    r is the relative target BEFORE `tssq_cwt`'s clip to [0, N - 1]: an edge cell that the clip would bring back onto
+    itself is not kept.  A NaN is kept nowhere.  `Te` is [na, N] on the rows of `Wx`; `Wx` (None with get_Wx=False)
+    equals `tssq_cwt`'s and `ssq_cwt2`'s; `row_freqs` is nu / dt in Hz in the call's real dtype.  One operator kernel
+    writes every cell exactly once: none of `tssq_cwt`'s maxima, accumulators, targets or atomic adds, and a workspace
+    without their 20 bytes a cell.
+
+    There is no inverse.
+
+    Built: what `tssq_cwt` builds, without its na N limit.  Anything else raises ValueError before any GPU work.  The
+    kernel is built without register spills or scratch (profiles/extract_cwt_resources.txt)."""
+    return _extract_cwt(1, x, wavelet, scales, nv, fs, t, padtype, order, gamma, get_Wx, get_tau, work_limit_bytes)
 
 
 TMSSQ_CWT_WALK_MAX_N = 1 << 30          # csrc/cwt_tmsst.hip: columns of a map handed to `tmssq_cwt_walk`
