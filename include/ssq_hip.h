@@ -650,7 +650,8 @@ int ssq_extract_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_si
  * Tx: [batch][na][n_signal] complex of `dtype`; Wx (may be NULL): [batch][n_orders][na][n_signal] complex, the planes W_g;
  * w (may be NULL): [batch][n_draws][na][n_signal] REAL of `dtype`, every draw's phase transform, +inf where not kept.
  * Workspace: 32 (fp32: 16) n_orders na n_signal bytes per signal of a slice (to a multiple of 256).  work_limit_bytes:
- * 0 for the preferred size, else at least min_bytes. */
+ * 0 for the preferred size, else at least min_bytes.  Beside that workspace the call holds on the device only as many
+ * signals (x, Tx and the Wx and w asked for) as fit, in slices of the batch (at most ssq_host_slice_cap signals). */
 int ssq_conceft_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, double gmw_gamma, double gmw_beta,
                          const double* coeffs, int64_t n_coeffs, int64_t n_orders, const double* vectors, int64_t n_draws,
                          double scale, const double* scales, int64_t na, double dt, const double* row_const,
@@ -690,7 +691,9 @@ int ssq_conceft_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_si
  * NULL): [batch][n_draws][F][n_frames] REAL of `dtype`, every draw's frequency, +inf where not kept.
  * Workspace: the 2 n_tapers planes of a slice, 32 (fp32: 16) n_tapers F bytes per frame, plus 8 n_signal bytes per
  * signal of a slice for a float32 call; a slice is whole signals, or a run of whole store tiles (4096 / n_fft frames)
- * of one signal.  work_limit_bytes: 0 for the preferred size, else at least min_bytes. */
+ * of one signal.  work_limit_bytes: 0 for the preferred size, else at least min_bytes.  Beside that workspace the call
+ * holds on the device only as many signals (x, Tx and the Sx, dSx and w asked for) as fit, in slices of the batch (at most
+ * ssq_host_slice_cap signals). */
 int ssq_conceft_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* tapers, int64_t n_tapers,
                           int64_t n_fft, int64_t hop, double fs, int padtype, const double* vectors, int64_t n_draws,
                           double scale, double gamma, int variant, int64_t work_limit_bytes, void* Tx, double* ssq_freqs,

@@ -181,12 +181,17 @@ struct ConceftCall {
   int padtype;
   double gamma;
   int variant;
+  hipStream_t st;             // of the launches (the host door: the null stream)
+  float* ms;                  // the exec door's kernel_ms (ConceftPipe), or nullptr
 };
 
 struct ConceftShape {
   int64_t plane;              // na N
   int64_t signal_bytes;       // the 2 J planes of one signal, to a multiple of 256 bytes
   int64_t min_bytes, pref_bytes;
+  int64_t work_bytes = 0;     // of the workspace the call runs in (the doors set it): sets the signals per inner slice
+  ssq_cwt_plan* plan = nullptr;   // conceft_plan's, the door's for the length of the call
+  int64_t plan_bytes = 0;     // the plan's own workspace
 };
 
 constexpr int64_t kConceftPrefBytes = (int64_t)1 << 30;   // the preferred workspace: whole signals up to 1 GiB
@@ -243,110 +248,115 @@ struct PlanHolder {                     // the plan's tables are freed once the 
   }
 };
 
-// The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the signals per slice.  d_Wx, d_w may be
-// nullptr.  Synchronous.  kernel_ms: one float, the stage-2 kernel alone (summed over the slices).
-template <typename T>
-int conceft_run(const ConceftCall& c, const ConceftShape& s, const void* d_x, void* d_Tx, void* d_Wx, void* d_w,
-                void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
-  const int64_t batch = c.batch, N = c.N, na = c.na, J = c.J, M = c.M;
-  PlanHolder ph;
-  ph.st = st;
-  if (int rc = ssq_cwt_plan_create_gmwk(&ph.pl, c.dtype, N, c.gmw_gamma, c.gmw_beta, c.coeffs, c.n_coeffs, J, c.scales, na,
-                                        c.dt, c.padtype, SSQ_VARIANT_UPSTREAM))
+// the plan of `cwt_higher_order` that stage 1 runs through.  The door makes it, behind its argument checks: the host door
+// sizes its slices beside the plan's workspace, which only the plan knows.
+int conceft_plan(const ConceftCall& c, PlanHolder* ph, ConceftShape* s) {
+  ph->st = c.st;
+  if (int rc = ssq_cwt_plan_create_gmwk(&ph->pl, c.dtype, c.N, c.gmw_gamma, c.gmw_beta, c.coeffs, c.n_coeffs, c.J, c.scales,
+                                        c.na, c.dt, c.padtype, SSQ_VARIANT_UPSTREAM))
     return rc;
-  const int64_t plan_bytes = ssq_cwt_plan_workspace_bytes(ph.pl, 1);
+  s->plan = ph->pl;
+  s->plan_bytes = ssq_cwt_plan_workspace_bytes(ph->pl, 1);
+  return 0;
+}
+
+// conceft_cwt on device buffers (pipe_host, pipe_exec).  A call's workspace of s.work_bytes >= s.min_bytes is fixed by the
+// call, not by the signals of a host slice: run() walks its signals in inner slices of work_bytes / signal_bytes whole
+// signals, the plan's transforms and the squeeze kernel alternating.  kernel_ms is therefore the pipe's own (c.ms, one
+// float: the squeeze kernel alone, summed over the inner slices), not run_timed's.
+template <typename T>
+struct ConceftPipe {
+  static constexpr int kMid = 0;
+  const ConceftCall& c;
+  const ConceftShape& s;
   DeviceBufs d;
   TimingEvents t;
-  void *d_plan = nullptr, *d_vec = nullptr, *d_rc = nullptr;
-  SSQ_HIP(d.alloc(&d_plan, (size_t)plan_bytes));
-  std::vector<cpx<T>> vec((size_t)(M * J));
-  for (int64_t i = 0; i < M * J; ++i) vec[(size_t)i] = {(T)c.vectors[2 * i], (T)c.vectors[2 * i + 1]};
-  SSQ_HIP(d.upload(&d_vec, vec.data(), vec.size() * sizeof(cpx<T>)));
-  std::vector<T> rcs((size_t)na);
-  for (int64_t i = 0; i < na; ++i) rcs[(size_t)i] = (T)(c.row_const[i] * c.scale);
-  SSQ_HIP(d.upload(&d_rc, rcs.data(), rcs.size() * sizeof(T)));
-
-  BinRule<T> r;
-  const int flipud = (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0;
-  if (int rc = bin_rule<T>(c.f_asc, na, c.freq_kind, c.freq_transition, flipud, r)) return rc;
   ConceftDev<T> p;
-  std::memset(&p, 0, sizeof(p));
-  p.J = (int)J;
-  p.M = (int)M;
-  p.q.N = N;
-  p.q.na = (int)na;
-  p.q.s_end = (int)na;
-  p.q.is_log = c.freq_kind != SSQ_FREQS_LINEAR ? 1 : 0;
-  p.q.flipud = flipud;
-  p.q.bin_min = r.bin_min;
-  p.q.bin_step = r.bin_step;
-  p.q.inv_bin_step = (T)1 / r.bin_step;
-  p.q.gamma = (T)(c.gamma < 0 ? 10.0 * (sizeof(T) == 8 ? 2.2204460492503131e-16 : 1.1920928955078125e-07) : c.gamma);
-  p.q.variant = 1;
-  p.r.piecewise = c.freq_kind == SSQ_FREQS_LOG_PIECEWISE ? 1 : 0;
-  p.r.idx1 = r.idx1;
-  p.r.vlmin1 = r.vlmin1;
-  p.r.dvl1 = r.dvl1;
-
-  const int64_t slice = std::min<int64_t>(batch, work_bytes / s.signal_bytes);
-  const int64_t planes = J * s.plane;                        // coefficients of one signal's W (or dW)
-  if (kernel_ms) {
-    *kernel_ms = 0.0f;
-    SSQ_HIP(t.start(2, st));
+  const cpx<T>* vec;
+  const T* rcs;               // row_const * scale
+  void* plan_work;
+  int64_t slice;              // signals of an inner slice
+  cpx<T>*Tx, *Wx, *work;
+  T* w;
+  int tables() {
+    const int64_t na = c.na, J = c.J, M = c.M;
+    SSQ_HIP(d.alloc(&plan_work, (size_t)s.plan_bytes));
+    std::vector<cpx<T>> v((size_t)(M * J));
+    for (int64_t i = 0; i < M * J; ++i) v[(size_t)i] = {(T)c.vectors[2 * i], (T)c.vectors[2 * i + 1]};
+    SSQ_HIP(d.upload(&vec, v));
+    std::vector<T> rc((size_t)na);
+    for (int64_t i = 0; i < na; ++i) rc[(size_t)i] = (T)(c.row_const[i] * c.scale);
+    SSQ_HIP(d.upload(&rcs, rc));
+    BinRule<T> r;
+    const int flipud = (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0;
+    if (int e = bin_rule<T>(c.f_asc, na, c.freq_kind, c.freq_transition, flipud, r)) return e;
+    std::memset(&p, 0, sizeof(p));
+    p.J = (int)J;
+    p.M = (int)M;
+    p.q.N = c.N;
+    p.q.na = (int)na;
+    p.q.s_end = (int)na;
+    p.q.is_log = c.freq_kind != SSQ_FREQS_LINEAR ? 1 : 0;
+    p.q.flipud = flipud;
+    p.q.bin_min = r.bin_min;
+    p.q.bin_step = r.bin_step;
+    p.q.inv_bin_step = (T)1 / r.bin_step;
+    p.q.gamma = (T)(c.gamma < 0 ? 10.0 * (sizeof(T) == 8 ? 2.2204460492503131e-16 : 1.1920928955078125e-07) : c.gamma);
+    p.q.variant = 1;
+    p.r.piecewise = c.freq_kind == SSQ_FREQS_LOG_PIECEWISE ? 1 : 0;
+    p.r.idx1 = r.idx1;
+    p.r.vlmin1 = r.vlmin1;
+    p.r.dvl1 = r.dvl1;
+    return 0;
   }
-  SSQ_HIP(hipMemsetAsync(d_Tx, 0, (size_t)(batch * s.plane) * sizeof(cpx<T>), st));
-  for (int64_t b0 = 0; b0 < batch; b0 += slice) {
-    const int64_t nb = std::min(slice, batch - b0);
-    cpx<T>* W = static_cast<cpx<T>*>(d_work);
-    cpx<T>* dW = W + nb * planes;
-    if (int rc = ssq_cwt_plan_exec_cwt(ph.pl, static_cast<const T*>(d_x) + b0 * N, nb, 1, 0, W, dW, d_plan, plan_bytes, st))
-      return rc;
-    if (d_Wx)
-      SSQ_HIP(hipMemcpyAsync(static_cast<cpx<T>*>(d_Wx) + b0 * planes, W, (size_t)(nb * planes) * sizeof(cpx<T>),
-                             hipMemcpyDeviceToDevice, st));
-    p.W = W;
-    p.dW = dW;
-    p.w = d_w ? static_cast<T*>(d_w) + b0 * M * s.plane : nullptr;
-    p.q.Tx = static_cast<cpx<T>*>(d_Tx) + b0 * s.plane;
-    p.signals = nb;
-    const dim3 grid((unsigned)((N + 63) / 64), (unsigned)std::min<int64_t>(nb, 65535));
-    if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[0], st));
-    if (p.r.piecewise)
-      hipLaunchKernelGGL((cwt_conceft_kernel<T, true>), grid, dim3(64), 0, st, p, static_cast<const cpx<T>*>(d_vec),
-                         static_cast<const T*>(d_rc));
-    else
-      hipLaunchKernelGGL((cwt_conceft_kernel<T, false>), grid, dim3(64), 0, st, p, static_cast<const cpx<T>*>(d_vec),
-                         static_cast<const T*>(d_rc));
-    SSQ_HIP(hipGetLastError());
-    if (kernel_ms) {
-      float ms = 0.0f;
-      SSQ_HIP(hipEventRecord(t.ev[1], st));
-      SSQ_HIP(hipEventSynchronize(t.ev[1]));
-      SSQ_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
-      *kernel_ms += ms;
+  int bind(int64_t cap, void* const* outs /* Tx, Wx, w */, void* wk) {
+    Tx = (cpx<T>*)outs[0];
+    Wx = (cpx<T>*)outs[1];
+    w = (T*)outs[2];
+    work = (cpx<T>*)wk;
+    slice = std::min<int64_t>(cap, s.work_bytes / s.signal_bytes);
+    if (c.ms) {
+      *c.ms = 0.0f;
+      SSQ_HIP(t.start(2, c.st));
     }
+    return 0;
   }
-  SSQ_HIP(hipStreamSynchronize(st));                         // (the vectors, weights and tables are freed on return)
-  return 0;
-}
-
-template <typename T>
-int conceft_host_typed(const ConceftCall& c, const ConceftShape& s, const void* x, int64_t work_bytes, void* Tx, void* Wx,
-                       void* w) {
-  DeviceBufs d;
-  const size_t n = (size_t)c.batch * (size_t)s.plane;
-  void *d_x, *d_Tx, *d_work, *d_Wx = nullptr, *d_w = nullptr;
-  SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.batch * (size_t)c.N));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * n));
-  if (Wx) SSQ_HIP(d.alloc(&d_Wx, sizeof(cpx<T>) * n * (size_t)c.J));
-  if (w) SSQ_HIP(d.alloc(&d_w, sizeof(T) * n * (size_t)c.M));
-  SSQ_HIP(d.alloc(&d_work, (size_t)work_bytes));
-  if (int rc = conceft_run<T>(c, s, d_x, d_Tx, d_Wx, d_w, d_work, work_bytes, nullptr, nullptr)) return rc;
-  SSQ_HIP(hipMemcpy(Tx, d_Tx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  if (Wx) SSQ_HIP(hipMemcpy(Wx, d_Wx, sizeof(cpx<T>) * n * (size_t)c.J, hipMemcpyDeviceToHost));
-  if (w) SSQ_HIP(hipMemcpy(w, d_w, sizeof(T) * n * (size_t)c.M, hipMemcpyDeviceToHost));
-  return 0;
-}
+  int run(int64_t nb_run, const void* d_x, const hipEvent_t*) {
+    const int64_t N = c.N, M = c.M;
+    const int64_t planes = c.J * s.plane;                      // coefficients of one signal's W (or dW)
+    const hipStream_t st = c.st;
+    SSQ_HIP(hipMemsetAsync(Tx, 0, (size_t)(nb_run * s.plane) * sizeof(cpx<T>), st));
+    for (int64_t b0 = 0; b0 < nb_run; b0 += slice) {
+      const int64_t nb = std::min(slice, nb_run - b0);
+      cpx<T>* W = work;
+      cpx<T>* dW = W + nb * planes;
+      if (int e = ssq_cwt_plan_exec_cwt(s.plan, static_cast<const T*>(d_x) + b0 * N, nb, 1, 0, W, dW, plan_work, s.plan_bytes, st))
+        return e;
+      if (Wx)
+        SSQ_HIP(hipMemcpyAsync(Wx + b0 * planes, W, (size_t)(nb * planes) * sizeof(cpx<T>), hipMemcpyDeviceToDevice, st));
+      p.W = W;
+      p.dW = dW;
+      p.w = w ? w + b0 * M * s.plane : nullptr;
+      p.q.Tx = Tx + b0 * s.plane;
+      p.signals = nb;
+      const dim3 grid((unsigned)((N + 63) / 64), (unsigned)std::min<int64_t>(nb, 65535));
+      if (c.ms) SSQ_HIP(hipEventRecord(t.ev[0], st));
+      if (p.r.piecewise)
+        hipLaunchKernelGGL((cwt_conceft_kernel<T, true>), grid, dim3(64), 0, st, p, vec, rcs);
+      else
+        hipLaunchKernelGGL((cwt_conceft_kernel<T, false>), grid, dim3(64), 0, st, p, vec, rcs);
+      SSQ_HIP(hipGetLastError());
+      if (c.ms) {
+        float ms = 0.0f;
+        SSQ_HIP(hipEventRecord(t.ev[1], st));
+        SSQ_HIP(hipEventSynchronize(t.ev[1]));
+        SSQ_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+        *c.ms += ms;
+      }
+    }
+    return 0;
+  }
+};
 
 }  // namespace
 
@@ -368,16 +378,20 @@ int ssq_conceft_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_si
                          void* stream, float* kernel_ms) {
   if (!d_x || !d_Tx || !d_workspace) SSQ_FAIL("conceft_cwt: NULL argument");
   const ConceftCall c{dtype, batch, n_signal, gmw_gamma, gmw_beta, coeffs, n_coeffs, n_orders, vectors, n_draws, scale,
-                      scales, na, dt, row_const, ssq_freqs_asc, freq_kind, freq_transition, padtype, gamma, variant};
+                      scales, na, dt, row_const, ssq_freqs_asc, freq_kind, freq_transition, padtype, gamma, variant,
+                      static_cast<hipStream_t>(stream), kernel_ms};
   ConceftShape s;
   if (int rc = conceft_check(c, &s)) return rc;
   if (workspace_bytes < s.min_bytes)
     SSQ_FAIL("conceft_cwt: workspace too small (" + std::to_string(workspace_bytes) + " < " + std::to_string(s.min_bytes) +
              " bytes: ssq_conceft_cwt_workspace_bytes)");
   if (int rc = require_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == SSQ_F32 ? conceft_run<float>(c, s, d_x, d_Tx, d_Wx, d_w, d_workspace, workspace_bytes, st, kernel_ms)
-                          : conceft_run<double>(c, s, d_x, d_Tx, d_Wx, d_w, d_workspace, workspace_bytes, st, kernel_ms);
+  s.work_bytes = workspace_bytes;
+  PlanHolder ph;
+  if (int rc = conceft_plan(c, &ph, &s)) return rc;
+  void* const outs[] = {d_Tx, d_Wx, d_w};
+  return dtype == SSQ_F32 ? pipe_exec<ConceftPipe<float>>(c, s, d_x, outs, d_workspace, nullptr, &c.st)
+                          : pipe_exec<ConceftPipe<double>>(c, s, d_x, outs, d_workspace, nullptr, &c.st);
 }
 
 int ssq_conceft_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, double gmw_gamma, double gmw_beta,
@@ -387,15 +401,25 @@ int ssq_conceft_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_sign
                          int variant, int64_t work_limit_bytes, void* Tx, void* Wx, void* w) {
   if (!x || !Tx) SSQ_FAIL("conceft_cwt: NULL argument");
   const ConceftCall c{dtype, batch, n_signal, gmw_gamma, gmw_beta, coeffs, n_coeffs, n_orders, vectors, n_draws, scale,
-                      scales, na, dt, row_const, ssq_freqs_asc, freq_kind, freq_transition, padtype, gamma, variant};
+                      scales, na, dt, row_const, ssq_freqs_asc, freq_kind, freq_transition, padtype, gamma, variant,
+                      nullptr, nullptr};
   ConceftShape s;
   if (int rc = conceft_check(c, &s)) return rc;
   if (work_limit_bytes < 0 || (work_limit_bytes > 0 && work_limit_bytes < s.min_bytes))
     SSQ_FAIL("conceft_cwt: work_limit_bytes must be 0 or at least " + std::to_string(s.min_bytes) + " bytes");
-  const int64_t work = work_limit_bytes ? std::min(work_limit_bytes, s.pref_bytes) : s.pref_bytes;
+  s.work_bytes = work_limit_bytes ? std::min(work_limit_bytes, s.pref_bytes) : s.pref_bytes;
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? conceft_host_typed<float>(c, s, x, work, Tx, Wx, w)
-                          : conceft_host_typed<double>(c, s, x, work, Tx, Wx, w);
+  PlanHolder ph;
+  if (int rc = conceft_plan(c, &ph, &s)) return rc;
+  const size_t el = dtype == SSQ_F32 ? 4 : 8, map_el = (size_t)s.plane * el;
+  const HostOut outs[] = {{Tx, 2 * map_el}, {Wx, 2 * map_el * (size_t)n_orders}, {w, map_el * (size_t)n_draws}};
+  // the signals that fit beside the call's workspace and the plan's; the workspace holds no more of them than a slice has
+  const int64_t slice = slice_signals(batch, host_signal_bytes(el * (size_t)n_signal, outs),
+                                      (double)s.work_bytes + (double)s.plan_bytes, batch);
+  s.work_bytes = std::min(s.work_bytes, slice * s.signal_bytes);
+  const HostSlice sl{slice, (size_t)s.work_bytes};
+  return dtype == SSQ_F32 ? pipe_host<ConceftPipe<float>>(c, s, x, el * (size_t)n_signal, outs, sl)
+                          : pipe_host<ConceftPipe<double>>(c, s, x, el * (size_t)n_signal, outs, sl);
 }
 
 }  // extern "C"

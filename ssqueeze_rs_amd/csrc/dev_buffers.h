@@ -3,8 +3,10 @@
 // a slice of signals (and the cap on it that lets a test reach the slices after the first), the sliced host call itself
 // (host_slice sizes it, host_sliced runs it: H2D, run, D2H per slice), the timing events of the device entry points
 // (run_timed: up to four parts, on the null stream or a caller's), and the two doors of a pipeline that is written once
-// for both (pipe_host, pipe_exec).  The fp64 STFT pipelines (stft_frames64.h) and the fp64 CWT map pipelines
-// (cwt_maps64.h) go through the same doors.
+// for both (pipe_host, pipe_exec).  The fp64 STFT pipelines (stft_frames64.h), the fp64 CWT map pipelines
+// (cwt_maps64.h) and the two ConceFT transforms (stft_conceft.hip, cwt_conceft.hip) go through the same doors.  A host
+// door sizes its slices with host_slice (a workspace linear in the signals), builds its own HostSlice from slice_signals
+// (ConceFT: a workspace fixed by the call, beside which the signals are sliced), or takes the batch whole (cwt_pipe_host).
 #pragma once
 #include <atomic>
 #include <vector>
@@ -82,14 +84,20 @@ struct HostSlice {
   size_t work_bytes;
 };
 
-// the slice of a workspace that is linear in the signals (`work_bytes` each): slice_signals' of everything a signal
-// needs on the device, x, the outputs that were asked for and its workspace
+// what a signal of a host call holds on the device outside its workspace: x and the outputs that were asked for
 template <size_t N>
-HostSlice host_slice(int64_t batch, size_t x_bytes, const HostOut (&outs)[N], size_t work_bytes) {
-  double per = (double)x_bytes + (double)work_bytes;
+double host_signal_bytes(size_t x_bytes, const HostOut (&outs)[N]) {
+  double per = (double)x_bytes;
   for (const HostOut& o : outs)
     if (o.host) per += (double)o.bytes;
-  const int64_t slice = slice_signals(batch, per, 0.0, batch);
+  return per;
+}
+
+// the slice of a workspace that is linear in the signals (`work_bytes` each): slice_signals' of everything a signal
+// needs on the device, host_signal_bytes and its workspace
+template <size_t N>
+HostSlice host_slice(int64_t batch, size_t x_bytes, const HostOut (&outs)[N], size_t work_bytes) {
+  const int64_t slice = slice_signals(batch, host_signal_bytes(x_bytes, outs) + (double)work_bytes, 0.0, batch);
   return {slice, work_bytes * (size_t)slice};
 }
 
@@ -168,9 +176,11 @@ int run_timed(float* kernel_ms, int n_mid, const hipStream_t* stream, Run&& run)
 //   bind(cap, outs, work)     outs: the device outputs in the entry point's order (nullptr: not asked for); work: the
 //                             pipeline's workspace of `cap` signals, carved here by its one layout function
 //   run(nb, d_x, mid)         the launches of nb <= cap signals; mid: run_timed's events (Pipe::kMid of them)
-// each returning the entry point's status.  pipe_host: host pointers, in slices (sized from `work_bytes` a signal, or
-// as the caller's HostSlice says); pipe_exec: the caller's device buffers and workspace at cap = batch, timed, `stream`
-// as run_timed has it (the pipe itself knows where its launches go).
+// each returning the entry point's status.  The mid events mark one boundary per call: a pipe whose timed stages
+// alternate per inner slice (ConceFT) has kMid = 0, is handed a null kernel_ms and sums its own event pairs into a
+// float* of its call struct, which the host door leaves null.  pipe_host: host pointers, in slices (sized from
+// `work_bytes` a signal, or as the caller's HostSlice says); pipe_exec: the caller's device buffers and workspace at
+// cap = batch, timed, `stream` as run_timed has it (the pipe itself knows where its launches go).
 template <typename Pipe, typename Call, typename Shape, size_t N>
 int pipe_host(const Call& c, const Shape& s, const void* x, size_t x_bytes, const HostOut (&outs)[N], HostSlice sl) {
   Pipe pl{c, s};

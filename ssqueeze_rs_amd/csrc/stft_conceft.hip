@@ -282,6 +282,8 @@ struct CfStftCall {
   int64_t M;
   double scale, gamma;
   int variant;
+  hipStream_t st;             // of the launches (the host door: the null stream)
+  float* ms;                  // the exec door's kernel_ms (CfStftPipe), or nullptr
 };
 
 struct CfStftShape : FrameShape {
@@ -289,6 +291,7 @@ struct CfStftShape : FrameShape {
   int64_t frame_bytes;        // the 2 J coefficients of every bin of one frame
   int64_t widen_bytes;        // the fp64 copy of one signal (float32 calls)
   int64_t min_bytes, pref_bytes;
+  int64_t work_bytes = 0;     // of the workspace the call runs in (the doors set it): sets the inner slices
   double dw;
   std::vector<double> sfs;
 };
@@ -359,132 +362,118 @@ hipError_t cf_planes_launch(CfPlanesDev<T> p, int logn, long long frames, long l
   });
 }
 
-// The whole transform on device buffers; `work_bytes` >= s.min_bytes sets the slices.  d_Sx, d_dSx, d_w may be nullptr.
-// Synchronous.  kernel_ms: two floats, the stage-2 kernel alone and the stage-1 kernel alone (each summed over the slices).
+// conceft_stft on device buffers (pipe_host, pipe_exec).  A call's workspace of s.work_bytes >= s.min_bytes is fixed by
+// the call, not by the signals of a host slice: run() walks its signals in inner slices of that workspace (cf_stft_slice),
+// the plane kernel and the squeeze kernel alternating.  kernel_ms is therefore the pipe's own (c.ms, two floats: the
+// squeeze kernel alone, then the plane kernel alone, each summed over the inner slices), not run_timed's.
 template <typename T>
-int cf_stft_run(const CfStftCall& c, const CfStftShape& s, const void* d_x, void* d_Tx, void* d_Sx, void* d_dSx, void* d_w,
-                void* d_work, int64_t work_bytes, hipStream_t st, float* kernel_ms) {
-  const int64_t batch = c.batch, N = c.N, n = c.n_fft, J = c.J, M = c.M, F = s.n_freqs, nfr = s.n_frames;
+struct CfStftPipe {
+  static constexpr int kMid = 0;
+  const CfStftCall& c;
+  const CfStftShape& s;
   DeviceBufs d;
   TimingEvents t;
-  std::vector<double> wa((size_t)(2 * J * n)), h1((size_t)J);
-  for (int64_t j = 0; j < J; ++j) {
-    const host::SstTables tb = host::sst_level_tables(c.tapers + j * n, n, host::kSstFirst);   // fp64 for either dtype
-    std::copy(tb.wa.begin(), tb.wa.end(), wa.begin() + 2 * j * n);
-    h1[(size_t)j] = tb.h1;
-  }
-  const std::vector<double> tw = host::pass_twiddles(s.logn);
-  std::vector<cpx<T>> vec((size_t)(M * J));
-  for (int64_t i = 0; i < M * J; ++i) vec[(size_t)i] = {(T)c.vectors[2 * i], (T)c.vectors[2 * i + 1]};
-  void *d_tw, *d_wa, *d_h1, *d_vec;
-  SSQ_HIP(d.upload(&d_tw, tw.data(), sizeof(double) * tw.size()));
-  SSQ_HIP(d.upload(&d_wa, wa.data(), sizeof(double) * wa.size()));
-  SSQ_HIP(d.upload(&d_h1, h1.data(), sizeof(double) * h1.size()));
-  SSQ_HIP(d.upload(&d_vec, vec.data(), sizeof(cpx<T>) * vec.size()));
-
-  int64_t nb_slice, sf;
-  cf_stft_slice(s, batch, work_bytes, &nb_slice, &sf);
-  double* d_xd = static_cast<double*>(d_work);                                // float32 calls: [nb_slice][N]
-  cpx<T>* planes = reinterpret_cast<cpx<T>*>(static_cast<char*>(d_work) + s.widen_bytes * nb_slice);
-
-  CfPlanesDev<T> p1{};
-  p1.tw = (const cpx<double>*)d_tw;
-  p1.wa = (const cpx<double>*)d_wa;
-  p1.h1 = (const double*)d_h1;
-  p1.planes = planes;
-  p1.n_signal = N;
-  p1.n_frames = nfr;
-  p1.pitch = sf;
-  p1.J = (int)J;
-  p1.hop = (int)c.hop;
-  p1.pad_left = (int)(n / 2);                                  // the larger half of the n - 1 pad samples on the left
-  p1.padtype = c.padtype;
-  p1.rot = (c.variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
-
-  CfSqueezeDev<T> p2{};
-  p2.planes = planes;
-  p2.pitch = sf;
-  p2.n_frames = nfr;
-  p2.J = (int)J;
-  p2.M = (int)M;
-  p2.F = (int)F;
-  p2.flip = (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0;
-  p2.gamma = (T)s.gamma;
-  p2.dw = (T)s.dw;
-  p2.fs = (T)s.fs;
-  p2.inv_n = (T)(1.0 / (double)n);
-  p2.fac = (T)(s.dw * c.scale);
-
-  const size_t map_sig = (size_t)F * (size_t)nfr;
-  if (kernel_ms) {
-    kernel_ms[0] = kernel_ms[1] = 0.0f;
-    SSQ_HIP(t.start(3, st));
-  }
-  SSQ_HIP(hipMemsetAsync(d_Tx, 0, (size_t)batch * map_sig * sizeof(cpx<T>), st));
-  for (int64_t b0 = 0; b0 < batch; b0 += nb_slice) {
-    const int64_t nb = std::min(nb_slice, batch - b0);
-    const double* xd;
-    if constexpr (sizeof(T) == 4) {
-      SSQ_HIP(widen_f64(static_cast<const float*>(d_x) + b0 * N, d_xd, (long long)nb * N, st));
-      xd = d_xd;
-    } else {
-      xd = static_cast<const double*>(d_x) + b0 * N;
+  CfPlanesDev<T> p1;
+  CfSqueezeDev<T> p2;
+  const cpx<T>* vec;
+  cpx<T>*Tx, *Sx, *dSx, *planes;
+  T* w;
+  double* xd;                 // float32 calls: [nb_slice][N]
+  int64_t nb_slice, sf;       // signals and frames of an inner slice
+  int tables() {
+    const int64_t n = c.n_fft, J = c.J, M = c.M;
+    std::vector<double> wa((size_t)(2 * J * n)), h1((size_t)J);
+    for (int64_t j = 0; j < J; ++j) {
+      const host::SstTables tb = host::sst_level_tables(c.tapers + j * n, n, host::kSstFirst);   // fp64 for either dtype
+      std::copy(tb.wa.begin(), tb.wa.end(), wa.begin() + 2 * j * n);
+      h1[(size_t)j] = tb.h1;
     }
-    for (int64_t f0 = 0; f0 < nfr; f0 += sf) {
-      const int64_t cols = std::min(sf, nfr - f0);
-      if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[0], st));
-      for (int64_t b1 = 0; b1 < nb; b1 += 65535) {               // stage 1: at most 65535 signals a launch
-        const int64_t n1 = std::min<int64_t>(nb - b1, 65535);
-        p1.x = xd + b1 * N;
-        p1.planes = planes + b1 * 2 * J * F * sf;
-        p1.Sx = d_Sx ? static_cast<cpx<T>*>(d_Sx) + (size_t)(b0 + b1) * J * map_sig : nullptr;
-        p1.dSx = d_dSx ? static_cast<cpx<T>*>(d_dSx) + (size_t)(b0 + b1) * J * map_sig : nullptr;
+    std::vector<cpx<T>> v((size_t)(M * J));
+    for (int64_t i = 0; i < M * J; ++i) v[(size_t)i] = {(T)c.vectors[2 * i], (T)c.vectors[2 * i + 1]};
+    p1 = CfPlanesDev<T>{};
+    SSQ_HIP(d.upload(&p1.tw, host::pass_twiddles(s.logn)));
+    SSQ_HIP(d.upload(&p1.wa, wa));
+    SSQ_HIP(d.upload(&p1.h1, h1));
+    SSQ_HIP(d.upload(&vec, v));
+    p1.n_signal = c.N;
+    p1.n_frames = s.n_frames;
+    p1.J = (int)J;
+    p1.hop = (int)c.hop;
+    p1.pad_left = (int)(n / 2);                                // the larger half of the n - 1 pad samples on the left
+    p1.padtype = c.padtype;
+    p1.rot = (c.variant & SSQ_VARIANT_MODULATED) ? (int)(n / 2) : 0;
+    p2 = CfSqueezeDev<T>{};
+    p2.n_frames = s.n_frames;
+    p2.J = (int)J;
+    p2.M = (int)M;
+    p2.F = (int)s.n_freqs;
+    p2.flip = (c.variant & SSQ_VARIANT_FLIPUD) ? 1 : 0;
+    p2.gamma = (T)s.gamma;
+    p2.dw = (T)s.dw;
+    p2.fs = (T)s.fs;
+    p2.inv_n = (T)(1.0 / (double)n);
+    p2.fac = (T)(s.dw * c.scale);
+    return 0;
+  }
+  int bind(int64_t cap, void* const* outs /* Tx, Sx, dSx, w */, void* work) {
+    Tx = (cpx<T>*)outs[0];
+    Sx = (cpx<T>*)outs[1];
+    dSx = (cpx<T>*)outs[2];
+    w = (T*)outs[3];
+    cf_stft_slice(s, cap, s.work_bytes, &nb_slice, &sf);
+    xd = (double*)work;
+    planes = (cpx<T>*)((char*)work + s.widen_bytes * nb_slice);
+    p1.pitch = p2.pitch = sf;
+    p2.planes = planes;
+    if (c.ms) {
+      c.ms[0] = c.ms[1] = 0.0f;
+      SSQ_HIP(t.start(3, c.st));
+    }
+    return 0;
+  }
+  int run(int64_t nb_run, const void* d_x, const hipEvent_t*) {
+    const int64_t N = c.N, J = c.J, M = c.M, F = s.n_freqs, nfr = s.n_frames;
+    const size_t map_sig = (size_t)F * (size_t)nfr;
+    const hipStream_t st = c.st;
+    SSQ_HIP(hipMemsetAsync(Tx, 0, (size_t)nb_run * map_sig * sizeof(cpx<T>), st));
+    for (int64_t b0 = 0; b0 < nb_run; b0 += nb_slice) {
+      const int64_t nb = std::min(nb_slice, nb_run - b0);
+      const double* x64;
+      SSQ_HIP(frame_signals64((const T*)d_x + b0 * N, xd, (long long)nb * N, st, &x64));
+      for (int64_t f0 = 0; f0 < nfr; f0 += sf) {
+        const int64_t cols = std::min(sf, nfr - f0);
+        if (c.ms) SSQ_HIP(hipEventRecord(t.ev[0], st));
         p1.f_begin = f0;
         p1.f_stop = f0 + cols;
-        SSQ_HIP(cf_planes_launch<T>(p1, s.logn, cols, n1, st));
-      }
-      if (kernel_ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
-      p2.Tx = static_cast<cpx<T>*>(d_Tx) + (size_t)b0 * map_sig + f0;
-      p2.w = d_w ? static_cast<T*>(d_w) + (size_t)b0 * M * map_sig + f0 : nullptr;
-      p2.signals = nb;
-      p2.cols = cols;
-      const dim3 grid((unsigned)((cols + 63) / 64), (unsigned)std::min<int64_t>(nb, 65535));
-      hipLaunchKernelGGL((conceft_stft_squeeze_kernel<T>), grid, dim3(64), 0, st, p2, static_cast<const cpx<T>*>(d_vec));
-      SSQ_HIP(hipGetLastError());
-      if (kernel_ms) {
-        float ms1 = 0.0f, ms2 = 0.0f;
-        SSQ_HIP(hipEventRecord(t.ev[2], st));
-        SSQ_HIP(hipEventSynchronize(t.ev[2]));
-        SSQ_HIP(hipEventElapsedTime(&ms1, t.ev[0], t.ev[1]));
-        SSQ_HIP(hipEventElapsedTime(&ms2, t.ev[1], t.ev[2]));
-        kernel_ms[0] += ms2;
-        kernel_ms[1] += ms1;
+        SSQ_HIP(for_signal_runs(nb, [&](int64_t b1, int64_t n1) {
+          p1.x = x64 + b1 * N;
+          p1.planes = planes + b1 * 2 * J * F * sf;
+          p1.Sx = Sx ? Sx + (size_t)(b0 + b1) * J * map_sig : nullptr;
+          p1.dSx = dSx ? dSx + (size_t)(b0 + b1) * J * map_sig : nullptr;
+          return cf_planes_launch<T>(p1, s.logn, cols, n1, st);
+        }));
+        if (c.ms) SSQ_HIP(hipEventRecord(t.ev[1], st));
+        p2.Tx = Tx + (size_t)b0 * map_sig + f0;
+        p2.w = w ? w + (size_t)b0 * M * map_sig + f0 : nullptr;
+        p2.signals = nb;
+        p2.cols = cols;
+        const dim3 grid((unsigned)((cols + 63) / 64), (unsigned)std::min<int64_t>(nb, 65535));
+        hipLaunchKernelGGL((conceft_stft_squeeze_kernel<T>), grid, dim3(64), 0, st, p2, vec);
+        SSQ_HIP(hipGetLastError());
+        if (c.ms) {
+          float ms1 = 0.0f, ms2 = 0.0f;
+          SSQ_HIP(hipEventRecord(t.ev[2], st));
+          SSQ_HIP(hipEventSynchronize(t.ev[2]));
+          SSQ_HIP(hipEventElapsedTime(&ms1, t.ev[0], t.ev[1]));
+          SSQ_HIP(hipEventElapsedTime(&ms2, t.ev[1], t.ev[2]));
+          c.ms[0] += ms2;
+          c.ms[1] += ms1;
+        }
       }
     }
+    return 0;
   }
-  SSQ_HIP(hipStreamSynchronize(st));                         // (the vectors and tables are freed on return)
-  return 0;
-}
-
-template <typename T>
-int cf_stft_host_typed(const CfStftCall& c, const CfStftShape& s, const void* x, int64_t work_bytes, void* Tx, void* Sx,
-                       void* dSx, void* w) {
-  DeviceBufs d;
-  const size_t n = (size_t)c.batch * (size_t)s.n_freqs * (size_t)s.n_frames;
-  void *d_x, *d_Tx, *d_work, *d_Sx = nullptr, *d_dSx = nullptr, *d_w = nullptr;
-  SSQ_HIP(d.upload(&d_x, x, sizeof(T) * (size_t)c.batch * (size_t)c.N));
-  SSQ_HIP(d.alloc(&d_Tx, sizeof(cpx<T>) * n));
-  if (Sx) SSQ_HIP(d.alloc(&d_Sx, sizeof(cpx<T>) * n * (size_t)c.J));
-  if (dSx) SSQ_HIP(d.alloc(&d_dSx, sizeof(cpx<T>) * n * (size_t)c.J));
-  if (w) SSQ_HIP(d.alloc(&d_w, sizeof(T) * n * (size_t)c.M));
-  SSQ_HIP(d.alloc(&d_work, (size_t)work_bytes));
-  if (int rc = cf_stft_run<T>(c, s, d_x, d_Tx, d_Sx, d_dSx, d_w, d_work, work_bytes, nullptr, nullptr)) return rc;
-  SSQ_HIP(hipMemcpy(Tx, d_Tx, sizeof(cpx<T>) * n, hipMemcpyDeviceToHost));
-  if (Sx) SSQ_HIP(hipMemcpy(Sx, d_Sx, sizeof(cpx<T>) * n * (size_t)c.J, hipMemcpyDeviceToHost));
-  if (dSx) SSQ_HIP(hipMemcpy(dSx, d_dSx, sizeof(cpx<T>) * n * (size_t)c.J, hipMemcpyDeviceToHost));
-  if (w) SSQ_HIP(hipMemcpy(w, d_w, sizeof(T) * n * (size_t)c.M, hipMemcpyDeviceToHost));
-  return 0;
-}
+};
 
 }  // namespace
 
@@ -503,17 +492,18 @@ int ssq_conceft_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_s
                           int64_t n_draws, double scale, double gamma, int variant, void* d_Tx, void* d_Sx, void* d_dSx,
                           void* d_w, void* d_workspace, int64_t workspace_bytes, void* stream, float* kernel_ms) {
   if (!d_x || !d_Tx || !d_workspace) SSQ_FAIL("conceft_stft: NULL argument");
-  const CfStftCall c{dtype, batch, n_signal, tapers, n_tapers, n_fft, hop, fs, padtype, vectors, n_draws, scale, gamma, variant};
+  const CfStftCall c{dtype, batch, n_signal, tapers, n_tapers, n_fft, hop, fs, padtype, vectors, n_draws, scale, gamma, variant,
+                     static_cast<hipStream_t>(stream), kernel_ms};
   CfStftShape s;
   if (int rc = cf_stft_check(c, &s)) return rc;
   if (workspace_bytes < s.min_bytes)
     SSQ_FAIL("conceft_stft: workspace too small (" + std::to_string(workspace_bytes) + " < " + std::to_string(s.min_bytes) +
              " bytes: ssq_conceft_stft_workspace_bytes)");
   if (int rc = require_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == SSQ_F32
-             ? cf_stft_run<float>(c, s, d_x, d_Tx, d_Sx, d_dSx, d_w, d_workspace, workspace_bytes, st, kernel_ms)
-             : cf_stft_run<double>(c, s, d_x, d_Tx, d_Sx, d_dSx, d_w, d_workspace, workspace_bytes, st, kernel_ms);
+  s.work_bytes = workspace_bytes;
+  void* const outs[] = {d_Tx, d_Sx, d_dSx, d_w};
+  return dtype == SSQ_F32 ? pipe_exec<CfStftPipe<float>>(c, s, d_x, outs, d_workspace, nullptr, &c.st)
+                          : pipe_exec<CfStftPipe<double>>(c, s, d_x, outs, d_workspace, nullptr, &c.st);
 }
 
 int ssq_conceft_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* tapers, int64_t n_tapers,
@@ -521,16 +511,24 @@ int ssq_conceft_stft_host(int dtype, const void* x, int64_t batch, int64_t n_sig
                           double scale, double gamma, int variant, int64_t work_limit_bytes, void* Tx, double* ssq_freqs,
                           void* Sx, void* dSx, void* w) {
   if (!x || !Tx) SSQ_FAIL("conceft_stft: NULL argument");
-  const CfStftCall c{dtype, batch, n_signal, tapers, n_tapers, n_fft, hop, fs, padtype, vectors, n_draws, scale, gamma, variant};
+  const CfStftCall c{dtype, batch, n_signal, tapers, n_tapers, n_fft, hop, fs, padtype, vectors, n_draws, scale, gamma, variant,
+                     nullptr, nullptr};
   CfStftShape s;
   if (int rc = cf_stft_check(c, &s)) return rc;
   if (work_limit_bytes < 0 || (work_limit_bytes > 0 && work_limit_bytes < s.min_bytes))
     SSQ_FAIL("conceft_stft: work_limit_bytes must be 0 or at least " + std::to_string(s.min_bytes) + " bytes");
-  const int64_t work = work_limit_bytes ? std::min(work_limit_bytes, s.pref_bytes) : s.pref_bytes;
+  s.work_bytes = work_limit_bytes ? std::min(work_limit_bytes, s.pref_bytes) : s.pref_bytes;
   fill_ssq_freqs(ssq_freqs, s.sfs, variant);
   if (int rc = require_device()) return rc;
-  return dtype == SSQ_F32 ? cf_stft_host_typed<float>(c, s, x, work, Tx, Sx, dSx, w)
-                          : cf_stft_host_typed<double>(c, s, x, work, Tx, Sx, dSx, w);
+  const size_t el = dtype == SSQ_F32 ? 4 : 8, map_el = (size_t)s.n_freqs * (size_t)s.n_frames * el;
+  const HostOut outs[] = {{Tx, 2 * map_el}, {Sx, 2 * map_el * (size_t)n_tapers}, {dSx, 2 * map_el * (size_t)n_tapers},
+                          {w, map_el * (size_t)n_draws}};
+  // the signals that fit beside the call's workspace; a workspace of whole signals holds no more of them than a slice has
+  const int64_t slice = slice_signals(batch, host_signal_bytes(el * (size_t)n_signal, outs), (double)s.work_bytes, batch);
+  s.work_bytes = std::min(s.work_bytes, std::max(s.min_bytes, slice * (s.widen_bytes + s.frame_bytes * s.n_frames)));
+  const HostSlice sl{slice, (size_t)s.work_bytes};
+  return dtype == SSQ_F32 ? pipe_host<CfStftPipe<float>>(c, s, x, el * (size_t)n_signal, outs, sl)
+                          : pipe_host<CfStftPipe<double>>(c, s, x, el * (size_t)n_signal, outs, sl);
 }
 
 }  // extern "C"

@@ -391,19 +391,11 @@ struct ExtractPipe {
     return 0;
   }
   int run(int64_t nb, const void* d_x, const hipEvent_t*) {
-    const double* x64;
-    if constexpr (sizeof(T) == 4) {
-      SSQ_HIP(widen_f64((const float*)d_x, xd, (long long)nb * p.n_signal, nullptr));
-      x64 = xd;
-    } else {
-      x64 = (const double*)d_x;
-    }
-    for (int64_t b0 = 0; b0 < nb; b0 += 65535) {            // at most 65535 signals a launch
-      const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
-      p.x = x64;
+    SSQ_HIP(frame_signals64((const T*)d_x, xd, (long long)nb * p.n_signal, nullptr, &p.x));
+    SSQ_HIP(for_signal_runs(nb, [&](int64_t b0, int64_t n1) {
       p.b0 = (int)b0;
-      SSQ_HIP(extract_launch<T>(p, s.logn, s.order, n1, nullptr));
-    }
+      return extract_launch<T>(p, s.logn, s.order, n1, nullptr);
+    }));
     return 0;
   }
 };

@@ -2,9 +2,10 @@
 // stft_reassign.hip share: a workgroup of 256 lanes owns a tile of consecutive frames of one signal, a
 // frame is held by n/16 lanes, 256/(n/16) frames side by side (fft_core.h; frames of 2048 points and more span several
 // waves).  Here: the per-length configuration, the sample loader, the split of a packed pair of real-input spectra, the
-// float32 -> fp64 widening of the signals, the dispatch on the transform length, and the call struct, argument checks and
-// shape the entry points have in common.  The kernels' own bodies (their transforms in order, operators and read-outs) stay
-// in their files: what is here compiles to the same machine code in each of them.
+// float32 -> fp64 widening of the signals (frame_signals64: the fp64 signals of a slice of either dtype), the dispatch on
+// the transform length, the loop over runs of at most 65535 signals a launch (for_signal_runs), and the call struct,
+// argument checks and shape the entry points have in common.  The kernels' own bodies (their transforms in order,
+// operators and read-outs) stay in their files: what is here compiles to the same machine code in each of them.
 #pragma once
 #include <cmath>
 #include <string>
@@ -87,6 +88,28 @@ __global__ void widen_f64_kernel(const I* __restrict__ in, double* __restrict__ 
 inline hipError_t widen_f64(const float* d_in, double* d_out, long long n, hipStream_t stream) {
   hipLaunchKernelGGL(widen_f64_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_in, d_out, n);
   return hipGetLastError();
+}
+
+// *x64: the `count` samples at d_x in fp64 for the operator kernels: a float32 slice widened into d_xd on `stream`, a
+// float64 slice as it is (d_xd is not read)
+template <typename T>
+hipError_t frame_signals64(const T* d_x, double* d_xd, long long count, hipStream_t stream, const double** x64) {
+  if constexpr (sizeof(T) == 4) {
+    *x64 = d_xd;
+    return widen_f64(d_x, d_xd, count, stream);
+  } else {
+    *x64 = d_x;
+    return hipSuccess;
+  }
+}
+
+// f(b0, n1) on the runs of at most 65535 signals that make up `nb` (a grid's y and z end there: DESIGN 4.10.1), up to the
+// first error
+template <typename F>
+hipError_t for_signal_runs(int64_t nb, F&& f) {
+  for (int64_t b0 = 0; b0 < nb; b0 += 65535)
+    if (hipError_t e = f(b0, nb - b0 < 65535 ? nb - b0 : (int64_t)65535); e != hipSuccess) return e;
+  return hipSuccess;
 }
 
 // f(std::integral_constant<int, LOGN>) for the transform length 2^logn, 16 to 4096 points

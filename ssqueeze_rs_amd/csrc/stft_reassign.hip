@@ -393,36 +393,27 @@ hipError_t reassign_run(ReassignDev<T> p, ReassignScat<T> sc, const ReassignShap
   const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
   hipError_t e = hipMemsetAsync(d_emax, 0, sizeof(unsigned long long) * (size_t)nb, nullptr);
   if (e != hipSuccess) return e;
-  const double* xd;
-  if constexpr (sizeof(T) == 4) {
-    if ((e = widen_f64((const float*)d_x, d_xd, (long long)nb * p.n_signal, nullptr)) != hipSuccess) return e;
-    xd = d_xd;
-  } else {
-    xd = (const double*)d_x;
-  }
-  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
-    const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
-    p.x = xd;
+  if ((e = frame_signals64(d_x, d_xd, (long long)nb * p.n_signal, nullptr, &p.x)) != hipSuccess) return e;
+  e = for_signal_runs(nb, [&](int64_t b0, int64_t n1) {
     p.b0 = (int)b0;
-    if ((e = reassign_launch<T>(p, s.logn, n1, nullptr)) != hipSuccess) return e;
-  }
+    return reassign_launch<T>(p, s.logn, n1, nullptr);
+  });
+  if (e != hipSuccess) return e;
   if (ev && (e = hipEventRecord(ev, nullptr)) != hipSuccess) return e;
   const long long tiles = (s.n_frames + s.tile - 1) / s.tile;
   const size_t lds = sizeof(unsigned long long) * (size_t)s.n_freqs * (size_t)s.tile;    // <= 8 kReassignCells
   if ((e = hipFuncSetAttribute((const void*)reassign_scatter_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds)) != hipSuccess)
     return e;
-  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
-    const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
+  return for_signal_runs(nb, [&](int64_t b0, int64_t n1) {
     sc.Sx = d_Sx + map_sig * b0;
     sc.tgt = d_tgt + map_sig * b0;
     sc.emax = d_emax + b0;
     sc.Rx = d_Rx + map_sig * b0;
     hipLaunchKernelGGL(reassign_scatter_kernel<T>, dim3((unsigned)tiles, (unsigned)n1), dim3(kReassignScatterThreads), lds,
                        nullptr, sc);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return hipGetLastError();
+  });
 }
 
 // reassign_stft on device buffers (pipe_host, pipe_exec).  kernel_ms: two parts, the event recorded between the operator

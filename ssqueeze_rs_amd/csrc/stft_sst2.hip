@@ -260,23 +260,14 @@ template <typename T>
 hipError_t sst2_operator_run(Sst2Dev<T> p, const Sst2Shape& s, const T* d_x, int64_t nb, cpx<T>* d_Sx, cpx<T>* d_map,
                              double* d_xd /* float32 calls: [nb][n_signal] */) {
   const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  hipError_t e;
   const double* xd;
-  if constexpr (sizeof(T) == 4) {
-    if ((e = widen_f64((const float*)d_x, d_xd, (long long)nb * p.n_signal, nullptr)) != hipSuccess) return e;
-    xd = d_xd;
-  } else {
-    xd = (const double*)d_x;
-  }
-  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
-    const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
+  if (hipError_t e = frame_signals64(d_x, d_xd, (long long)nb * p.n_signal, nullptr, &xd); e != hipSuccess) return e;
+  return for_signal_runs(nb, [&](int64_t b0, int64_t n1) {
     p.x = xd + b0 * p.n_signal;
     p.Sx = d_Sx + map_sig * b0;
     p.map = d_map + map_sig * b0;
-    e = sst2_launch<T>(p, s.logn, n1, nullptr);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return sst2_launch<T>(p, s.logn, n1, nullptr);
+  });
 }
 
 // Tx zeroed, then the scatter of `nb` signals on device buffers
@@ -284,17 +275,13 @@ template <typename T>
 hipError_t sst2_scatter_run(const Sst2Shape& s, int squeezing, T dw, int64_t nb, const cpx<T>* d_Sx, const cpx<T>* d_map,
                             cpx<T>* d_Tx, T* d_w) {
   const size_t map_sig = (size_t)s.n_freqs * (size_t)s.n_frames;
-  hipError_t e = hipMemsetAsync(d_Tx, 0, sizeof(cpx<T>) * map_sig * (size_t)nb, nullptr);
-  if (e != hipSuccess) return e;
-  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
-    const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
+  if (hipError_t e = hipMemsetAsync(d_Tx, 0, sizeof(cpx<T>) * map_sig * (size_t)nb, nullptr); e != hipSuccess) return e;
+  return for_signal_runs(nb, [&](int64_t b0, int64_t n1) {
     hipLaunchKernelGGL(sst2_scatter_kernel<T>, dim3((unsigned)((s.n_frames + 255) / 256), (unsigned)n1), dim3(256), 0, nullptr,
                        d_Sx + map_sig * b0, d_map + map_sig * b0, d_Tx + map_sig * b0, d_w ? d_w + map_sig * b0 : (T*)nullptr,
                        (int)s.n_freqs, (long long)s.n_frames, squeezing, dw, (T)((T)s.dw / (T)s.n_freqs));
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return hipGetLastError();
+  });
 }
 
 #define SSQ_SST2_INSTANTIATE(T)                                                                                          \

@@ -398,21 +398,11 @@ int tsst_out_block(DeviceBufs& d, const TsstShape& s, int64_t hop, void* d_Sx, v
 template <typename T>
 hipError_t tsst_operator_run(TsstDev<T> p, const TsstShape& s, const T* d_x, int64_t nb,
                              double* d_xd /* float32 calls: [nb][n_signal] */) {
-  hipError_t e;
-  const double* xd;
-  if constexpr (sizeof(T) == 4) {
-    if ((e = widen_f64((const float*)d_x, d_xd, (long long)nb * p.n_signal, nullptr)) != hipSuccess) return e;
-    xd = d_xd;
-  } else {
-    xd = (const double*)d_x;
-  }
-  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
-    const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
-    p.x = xd;
+  if (hipError_t e = frame_signals64(d_x, d_xd, (long long)nb * p.n_signal, nullptr, &p.x); e != hipSuccess) return e;
+  return for_signal_runs(nb, [&](int64_t b0, int64_t n1) {
     p.b0 = (int)b0;
-    if ((e = tsst_launch<T>(p, s.logn, s.order, n1, nullptr)) != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return tsst_launch<T>(p, s.logn, s.order, n1, nullptr);
+  });
 }
 
 template <typename T>
@@ -424,8 +414,7 @@ hipError_t tsst_scatter_run(TsstScat<T> sc, const TsstShape& s, int64_t nb, cons
   if (sc.reach < 1 || sc.tile < 256 || sc.tile % 256 || sc.tile > kTsstMaxTile || stage > kTsstWideStage ||
       (!trim && stage > kTsstStage))
     return hipErrorInvalidValue;
-  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {
-    const int64_t n1 = nb - b0 < 65535 ? nb - b0 : 65535;
+  return for_signal_runs(nb, [&](int64_t b0, int64_t n1) {
     sc.Sx = d_Sx + map_sig * b0;
     sc.rel = d_rel + map_sig * b0;
     sc.Tx = d_Tx + map_sig * b0;
@@ -436,9 +425,8 @@ hipError_t tsst_scatter_run(TsstScat<T> sc, const TsstShape& s, int64_t nb, cons
       hipLaunchKernelGGL((tsst_scatter_kernel<T, kTsstStage, true>), grid, dim3(kTsstThreads), 0, nullptr, sc);
     else
       hipLaunchKernelGGL((tsst_scatter_kernel<T, kTsstWideStage, true>), grid, dim3(kTsstThreads), 0, nullptr, sc);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return hipGetLastError();
+  });
 }
 
 #define SSQ_TSST_INSTANTIATE(T)                                                                                          \

@@ -351,30 +351,36 @@ def test_workspace_size_does_not_change_a_bit(rdt):
     pref = int(lib.ssq_conceft_cwt_workspace_bytes(code, B, N, na, J, C.byref(mn)))
     assert 0 < mn.value < pref == 3 * mn.value
     cdt = np.complex64 if rdt == np.float32 else np.complex128
+    M = r.shape[0]
+    shapes = [((B, na, N), cdt), ((B, J, na, N), cdt), ((B, M, na, N), rdt)]
+    sizes = [int(np.prod(sh)) * np.dtype(dt).itemsize for sh, dt in shapes]       # Tx, Wx, w
     res = []
     for ws in (mn.value, pref):
-        bufs = [C.c_void_p() for _ in range(3)]
+        bufs = [C.c_void_p() for _ in range(5)]
         try:
-            for d, n in zip(bufs, (X.nbytes, B * na * N * np.dtype(cdt).itemsize, ws)):
+            for d, n in zip(bufs, (X.nbytes, ws, *sizes)):
                 _lib.check(lib.ssq_dev_malloc(C.byref(d), n))
             _lib.check(lib.ssq_memcpy_h2d(bufs[0], _vp(X), X.nbytes, None))
             ms = C.c_float(-1.0)
-            _lib.check(lib.ssq_conceft_cwt_exec(code, bufs[0], B, N, p0, p1, _vp(polys), polys.shape[1], J, _vp(r), r.shape[0],
+            _lib.check(lib.ssq_conceft_cwt_exec(code, bufs[0], B, N, p0, p1, _vp(polys), polys.shape[1], J, _vp(r), M,
                                                 float(adm(J)[0] / c.sum()), _vp(s), na, 1 / FS, _vp(rc), _vp(f),
-                                                up.FREQS[kind], f_idx or 0, 0, -1.0, up.VARIANT_FLIPUD, bufs[1], None, None,
-                                                bufs[2], ws, None, C.byref(ms)))
+                                                up.FREQS[kind], f_idx or 0, 0, -1.0, up.VARIANT_FLIPUD, bufs[2], bufs[3], bufs[4],
+                                                bufs[1], ws, None, C.byref(ms)))
             assert ms.value > 0
-            Tx = np.empty((B, na, N), dtype=cdt)
-            _lib.check(lib.ssq_memcpy_d2h(_vp(Tx), bufs[1], Tx.nbytes, None))
+            got = [np.empty(sh, dtype=dt) for sh, dt in shapes]
+            for a, d in zip(got, bufs[2:]):
+                _lib.check(lib.ssq_memcpy_d2h(_vp(a), d, a.nbytes, None))
             _lib.check(lib.ssq_device_sync())
-            res.append(Tx)
+            res.append(got)
         finally:
             for d in bufs:
                 if d:
                     lib.ssq_dev_free(d)
-    assert np.array_equal(res[0], res[1])
-    ref = up.conceft_cwt(X, GMW, scales=sc, orders=J, vectors=case_vectors(0)[0], fs=FS)[0]
-    assert np.array_equal(res[0], ref)
+    # every output of the device door, the optional ones included, is the host call's bit for bit at either workspace
+    ref = up.conceft_cwt(X, GMW, scales=sc, orders=J, vectors=case_vectors(0)[0], fs=FS, get_Wx=True, get_w=True)
+    for got in res:
+        for k, a in zip((0, 3, 4), got):
+            assert np.array_equal(a, ref[k]), k
     # bad arguments are refused before any launch
     assert lib.ssq_conceft_cwt_exec(code, None, B, N, p0, p1, _vp(polys), polys.shape[1], J, _vp(r), r.shape[0], 1.0, _vp(s),
                                     na, 1 / FS, _vp(rc), _vp(f), up.FREQS[kind], f_idx or 0, 0, -1.0, 0, None, None, None, None,

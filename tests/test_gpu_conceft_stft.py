@@ -373,29 +373,35 @@ def test_workspace_size_does_not_change_a_bit(rdt):
     csz = np.dtype(_cdt(rdt)).itemsize
     wid = 8 * N if rdt == np.float32 else 0
     assert mn.value == wid + 2 * J * F * 16 * csz and pref == 3 * (wid + 2 * J * F * nfr * csz)
+    M = r.shape[0]
+    shapes = [((B, F, nfr), _cdt(rdt)), ((B, J, F, nfr), _cdt(rdt)), ((B, J, F, nfr), _cdt(rdt)), ((B, M, F, nfr), rdt)]
+    sizes = [int(np.prod(sh)) * np.dtype(dt).itemsize for sh, dt in shapes]       # Tx, Sx, dSx, w
     res = []
     for ws in (mn.value, pref, pref // 2):
-        bufs = [C.c_void_p() for _ in range(3)]
+        bufs = [C.c_void_p() for _ in range(6)]
         try:
-            for d, nbytes in zip(bufs, (X.nbytes, B * F * nfr * csz, ws)):
+            for d, nbytes in zip(bufs, (X.nbytes, ws, *sizes)):
                 _lib.check(lib.ssq_dev_malloc(C.byref(d), nbytes))
             _lib.check(lib.ssq_memcpy_h2d(bufs[0], _vp(X), X.nbytes, None))
             ms = (C.c_float * 2)(-1.0, -1.0)
             _lib.check(lib.ssq_conceft_stft_exec(code, bufs[0], B, N, _vp(wins), J, n, hop, FS, up.PAD_MODES[pad], _vp(r),
-                                                 r.shape[0], scale, -1.0, up._variant(True), bufs[1], None, None, None,
-                                                 bufs[2], ws, None, ms))
+                                                 M, scale, -1.0, up._variant(True), bufs[2], bufs[3], bufs[4], bufs[5],
+                                                 bufs[1], ws, None, ms))
             assert ms[0] > 0 and ms[1] > 0
-            Tx = np.empty((B, F, nfr), dtype=_cdt(rdt))
-            _lib.check(lib.ssq_memcpy_d2h(_vp(Tx), bufs[1], Tx.nbytes, None))
+            got = [np.empty(sh, dtype=dt) for sh, dt in shapes]
+            for a, d in zip(got, bufs[2:]):
+                _lib.check(lib.ssq_memcpy_d2h(_vp(a), d, a.nbytes, None))
             _lib.check(lib.ssq_device_sync())
-            res.append(Tx)
+            res.append(got)
         finally:
             for d in bufs:
                 if d:
                     lib.ssq_dev_free(d)
-    assert np.array_equal(res[0], res[1]) and np.array_equal(res[0], res[2])
-    ref = up.conceft_stft(X, tapers(i), vectors=case_vectors(i)[0], **call_kw(i))[0]
-    assert np.array_equal(res[0], ref)
+    # every output of the device door, the optional ones included, is the host call's bit for bit at every workspace
+    ref = up.conceft_stft(X, tapers(i), vectors=case_vectors(i)[0], get_planes=True, get_w=True, **call_kw(i))
+    for got in res:
+        for k, a in zip((0, 3, 4, 5), got):
+            assert np.array_equal(a, ref[k]), k
     # bad arguments are refused before any launch
     assert lib.ssq_conceft_stft_exec(code, None, B, N, _vp(wins), J, n, hop, FS, 0, _vp(r), r.shape[0], scale, -1.0, 0, None,
                                      None, None, None, None, 0, None, None) != 0
