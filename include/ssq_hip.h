@@ -634,6 +634,62 @@ int ssq_extract_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_si
                          const double* scales, const double* row_freqs, const double* row_edges, int64_t na, double dt,
                          int padtype, int axis, int order, double gamma, void* d_Te, void* d_Wx, void* d_map,
                          void* d_workspace, int64_t workspace_bytes, void* stream, float* kernel_ms);
+/* Local maximum synchrosqueezed STFT, `upstream.lmssq_stft` (csrc/stft_lmsst.hip; Yu, Wang, Zhao and Liu
+ * 2019; upstream has no such transform).  Arguments as ssq_mssq_stft_host (n_fft a power of two from 16 to 4096, squeezing
+ * SUM or LEBESGUE, the MODULATED and FLIPUD bits of `variant`, gamma < 0: 10 eps of the dtype), with `delta` from 1 to
+ * min(n_fft / 2, 256) in place of order and n_iter.  No derivative of the window is formed: ONE fp64 transform x g per
+ * frame.  Per column, F = n_fft / 2 + 1 rows:
+ *   A[k] = re^2 + im^2 of Sx[k] as reported (rounded to `dtype`), in fp64, the products and the sum rounded one by one;
+ *   m[k] = the row of the maximum of A over max(0, k - delta) .. min(F - 1, k + delta), scanned ascending and taken only
+ *          where strictly greater (the lowest row wins a tie; rows that are not kept take part);
+ *   Tx[r(m[k])] += Sx[k] dw (SUM) or dw / F (LEBESGUE) for the kept k (|V| > gamma in fp64), rows ascending, in `dtype`,
+ *          no atomics;  r(b) = F - 1 - b under FLIPUD, else b.
+ * ONE kernel decides a column in LDS and writes every cell of Tx exactly once: nothing is cleared and there is no map in
+ * device memory.  Tx, Sx (both required): [batch][n_freqs][n_frames] complex of `dtype`; ssq_freqs (may be NULL):
+ * [n_freqs] fp64; bins (may be NULL): int32, the row of Tx a coefficient went to, -1 where it was not kept.
+ * Synchronous; the batch goes through the device in slices sized from its free memory. */
+int ssq_lmssq_stft_host(int dtype, const void* x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                        int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, int delta, void* Tx,
+                        double* ssq_freqs, void* Sx, int32_t* bins);
+/* Device bytes of the workspace ssq_lmssq_stft_exec needs: for SSQ_F32 the signals widened to fp64 (8 batch n_signal),
+ * for SSQ_F64 none (0); computed on the host; -1 on a shape ssq_lmssq_stft_host refuses. */
+int64_t ssq_lmssq_stft_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t n_fft, int64_t hop);
+/* The same transform on device buffers: d_x [batch][n_signal], d_Tx, d_Sx (required), d_bins (may be NULL) as above,
+ * d_workspace of at least ssq_lmssq_stft_workspace_bytes (NULL with 0 bytes for SSQ_F64); window on the host.
+ * Synchronous.  kernel_ms (may be NULL): ONE float, the time of the kernels alone, from HIP events around the launches. */
+int ssq_lmssq_stft_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, const double* window, int64_t n_fft,
+                        int64_t hop, double fs, int padtype, int squeezing, double gamma, int variant, int delta, void* d_Tx,
+                        void* d_Sx, int32_t* d_bins, void* d_workspace, int64_t workspace_bytes, float* kernel_ms);
+/* Local maximum synchrosqueezed CWT, `upstream.lmssq_cwt` (csrc/cwt_lmsst.hip; the CWT counterpart of
+ * ssq_lmssq_stft_host).  Arguments as ssq_ssq_cwt2_host, for 2 .. 2049 scales, with `delta` from 1 to min(na - 1, 256) and
+ * row_freqs_hz [na], the rows' own frequencies in Hz (positive, finite; `upstream.tssq_cwt_row_freqs` / dt), each rounded
+ * once to `dtype`.  A map set of W alone: ONE inverse transform a row.  Per column, with A and m as above over the na
+ * rows of Wx as reported: w[i] = row_freqs_hz[m[i]], +inf where |W| < gamma on the fp64 coefficient; rows[i] = m[i], -1
+ * there; Tx = ssqueeze(Wx, w) by ssq_ssqueeze_w_exec, so a coefficient keeps its own row weight and phase.  Tx, Wx
+ * (required), w (REAL of `dtype`), rows (int32) (each may be NULL): [batch][na][n_signal]; Wx is ssq_ssq_cwt2_host's bit
+ * for bit.  Workspace: 16 P (batch + 2 R) bytes for chunks of R rows; a row's result depends neither on R nor on the
+ * batch.  work_limit_bytes: 0 for the preferred size, else at least min_bytes. */
+int ssq_lmssq_cwt_host(int dtype, const void* x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                       const double* scales, int64_t na, double dt, const double* row_const, const double* ssq_freqs_asc,
+                       int freq_kind, int64_t freq_transition, int padtype, int squeezing, double gamma, int variant,
+                       int64_t work_limit_bytes, int delta, const double* row_freqs_hz, void* Tx, void* Wx, void* w,
+                       int32_t* rows);
+/* Device bytes of the workspace: returns the preferred size (every row in one chunk, capped at 2 GiB) and stores the
+ * least one (one row per chunk) in *min_bytes (may be NULL); computed on the host; -1 on a bad shape. */
+int64_t ssq_lmssq_cwt_workspace_bytes(int dtype, int64_t batch, int64_t n_signal, int64_t na, int64_t* min_bytes);
+/* The same transform on device buffers: d_Tx, d_Wx, d_w (required), d_rows (may be NULL) as above, d_workspace of
+ * workspace_bytes >= min_bytes; the tables on the host.  Synchronous on `stream`.  kernel_ms (may be NULL): THREE floats,
+ * the time of the transforms with the Wx kernel, of the plane kernel (the window maximum), and of the squeeze. */
+int ssq_lmssq_cwt_exec(int dtype, const void* d_x, int64_t batch, int64_t n_signal, int wavelet, double p0, double p1,
+                       const double* scales, int64_t na, double dt, const double* row_const, const double* ssq_freqs_asc,
+                       int freq_kind, int64_t freq_transition, int padtype, int squeezing, double gamma, int variant, int delta,
+                       const double* row_freqs_hz, void* d_Tx, void* d_Wx, void* d_w, int32_t* d_rows, void* d_workspace,
+                       int64_t workspace_bytes, void* stream, float* kernel_ms);
+/* The plane kernel of ssq_lmssq_cwt_host alone, `upstream.lmsst_rows`: A [batch][n_rows][n_cols] REAL of `dtype` on the
+ * host (a float32 map is widened on load, which is exact), rows [same shape] int32: m as above, with no keep rule.
+ * n_rows 2 .. 2049, n_cols 1 .. 2^30, delta 1 .. min(n_rows - 1, 256).  Synchronous, the batch sliced to the device's
+ * free memory. */
+int ssq_lmsst_rows_host(int dtype, const void* A, int64_t batch, int64_t n_rows, int64_t n_cols, int delta, int32_t* rows);
 /* ConceFT, the multitaper synchrosqueezed CWT, `upstream.conceft_cwt` (csrc/cwt_conceft.hip; Daubechies,
  * Wang and Wu 2016; upstream has no such transform).  The wavelets are the GMWs (gmw_gamma, gmw_beta; bandpass norm) of
  * n_orders distinct orders, coeffs [n_orders][n_coeffs] their polynomials as for ssq_cwt_host_gmwk (1 <= n_orders <= 8,

@@ -100,6 +100,19 @@ _SIGNATURES = {
     "ssq_extract_stft_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64]),
     "ssq_extract_stft_exec": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_int,
                                         C.c_double, C.c_int, vp, vp, vp, vp, i64, C.POINTER(C.c_float)]),
+    "ssq_lmssq_stft_host": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_double,
+                                      C.c_int, C.c_int, vp, vp, vp, vp]),
+    "ssq_lmssq_stft_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64]),
+    "ssq_lmssq_stft_exec": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_double,
+                                      C.c_int, C.c_int, vp, vp, vp, vp, i64, C.POINTER(C.c_float)]),
+    "ssq_lmssq_cwt_host": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, C.c_double, vp, vp,
+                                     C.c_int, i64, C.c_int, C.c_int, C.c_double, C.c_int, i64, C.c_int, vp, vp, vp, vp,
+                                     vp]),
+    "ssq_lmssq_cwt_workspace_bytes": (i64, [C.c_int, i64, i64, i64, C.POINTER(i64)]),
+    "ssq_lmssq_cwt_exec": (C.c_int, [C.c_int, vp, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, C.c_double, vp, vp,
+                                     C.c_int, i64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,
+                                     i64, vp, C.POINTER(C.c_float)]),
+    "ssq_lmsst_rows_host": (C.c_int, [C.c_int, vp, i64, i64, i64, C.c_int, vp]),
     "ssq_tmssq_stft_host": (C.c_int, [C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, C.c_int, C.c_double,
                                       C.c_int, C.c_int, vp, vp, vp, vp]),
     "ssq_tmssq_stft_workspace_bytes": (i64, [C.c_int, i64, i64, i64, i64, C.c_int]),

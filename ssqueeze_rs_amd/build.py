@@ -22,7 +22,7 @@ SOURCES = ["api_common.hip", "api_stft.hip", "stft_fused.hip", "stft_anylen.hip"
            "ridge.hip", "issq_components.hip", "ssqueeze.hip", "istft_fused.hip", "stft_sst2.hip", "cwt_sst2.hip", "stft_tsst.hip",
            "stft_reassign.hip", "cwt_reassign.hip", "cwt_tsst.hip", "stft_msst.hip", "cwt_conceft.hip",
            "stft_conceft.hip", "cwt_msst.hip", "stft_tmsst.hip", "cwt_tmsst.hip", "stft_extract.hip",
-           "cwt_extract.hip"]
+           "cwt_extract.hip", "stft_lmsst.hip", "cwt_lmsst.hip"]
 CXXFLAGS = ["-std=c++17", "-O3", "-fno-slp-vectorize", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
             "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-Wno-unused-value"]
 

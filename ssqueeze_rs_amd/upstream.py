@@ -94,6 +94,16 @@ Supported subset (anything else raises ValueError naming the option):
     4.24, csrc/cwt_extract.hip): a coefficient is kept where `ssq_cwt2`'s frequency falls in the band of its own row
     (`set_cwt`, the bands of `set_cwt_row_edges`) or `tssq_cwt`'s group delay names its own column (`tet_cwt`) and zeroed
     elsewhere, by ONE operator kernel that writes every cell once; the conventions of `tssq_cwt`; no inverse;
+  * `lmssq_stft`: the local maximum synchrosqueezed STFT (Yu, Wang, Zhao and Liu 2019), which upstream does not have (the
+    definition is this project's: DESIGN 4.25, csrc/stft_lmsst.hip): a coefficient moves to the row where |Sx| has its
+    maximum inside a window of +- `delta` rows (default `lmsst_default_delta`, the window's main lobe); no derivative of
+    the window, ONE transform per frame, decided in LDS by ONE kernel that writes every cell of `Tx` once; the
+    conventions of `mssq_stft`; every column keeps its sum, so `Tx` inverts through `issq_stft`;
+  * `lmssq_cwt`: the local maximum synchrosqueezed CWT, the CWT counterpart of `lmssq_stft`, which upstream does not have
+    (the definition is this project's: DESIGN 4.26, csrc/cwt_lmsst.hip): a coefficient moves to the frequency of the row
+    where |Wx| has its maximum inside +- `delta` rows (default `lmssq_cwt_default_delta`), with its own row weight; ONE
+    inverse transform per row, for 2 .. 2049 scales; the conventions of `mssq_cwt`; `Tx` inverts through `issq_cwt`;
+    `lmsst_rows` runs the window maximum alone on a real map the caller holds;
   * `conceft_cwt`: ConceFT, the multitaper synchrosqueezed CWT (Daubechies, Wang and Wu 2016), which upstream does not
     have (the definition is this project's: DESIGN 4.18, csrc/cwt_conceft.hip): `ssq_cwt` under M random unit
     combinations of the GMWs of J orders (`conceft_vectors`, gauged by the orders' admittances `gmw_adm_ssq`), averaged,
@@ -592,6 +602,89 @@ def msst_tile_cols(n_rows):
     if c < 0:
         raise ValueError(f"n_rows {n_rows!r}: 1 .. {MSST_MAX_ROWS}")
     return int(c)
+
+
+LMSST_MAX_DELTA = 256                   # csrc/stft_lmsst.hip: kLmsstMaxDelta, a bound on work (not a measured number)
+LMSST_LOBE_LEVEL = 1e-3                 # where a main lobe counts as over: 60 dB down -- part of the definition, not measured
+
+
+def _delta(delta, n_rows, default):
+    """`delta` checked: None asks `default()`; an int from 1 to min(n_rows - 1, 256)."""
+    if delta is None:
+        delta = default()
+    top = min(n_rows - 1, LMSST_MAX_DELTA)
+    if not isinstance(delta, (int, np.integer)) or isinstance(delta, (bool, np.bool_)) or not 1 <= delta <= top:
+        raise ValueError(f"delta {delta!r}: an int from 1 to min(rows - 1, {LMSST_MAX_DELTA}) = {top}")
+    return int(delta)
+
+
+def lmsst_default_delta(window, n_fft):
+    """The default `delta` of `lmssq_stft`: the half-width in rows of the window's main lobe.  With G = |rfft(g)| of the
+    window sized to `n_fft` (`get_window`) and F = n_fft // 2 + 1, the smallest d >= 1 with G[d] <= 1e-3 G[0] (the lobe has
+    fallen 60 dB) or G[d + 1] >= G[d] (the lobe has ended); F - 1 if there is none; at most 256.  The 1e-3 is part of the
+    definition, not a measurement.  numpy on the host, no GPU."""
+    if not isinstance(window, np.ndarray):
+        raise ValueError("`window` must be an ndarray")
+    g = get_window(window, len(window), int(n_fft))
+    G = np.abs(np.fft.rfft(g, int(n_fft)))
+    F = len(G)
+    d = F - 1
+    for k in range(1, F - 1):
+        if G[k] <= LMSST_LOBE_LEVEL * G[0] or G[k + 1] >= G[k]:
+            d = k
+            break
+    return int(max(1, min(d, F - 1, LMSST_MAX_DELTA)))
+
+
+def lmssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
+               squeezing="sum", gamma=None, flipud=False, delta=None, get_bins=False):
+    """Local maximum synchrosqueezed STFT -> (Tx, Sx, ssq_freqs, Sfs[, bins]); not in upstream (Yu, Wang, Zhao and Liu
+    2019), conventions of `mssq_stft`.  Where the rest of the family moves a coefficient to the frequency that a quotient
+    of STFTs estimates, this moves it to the row where |Sx| has its maximum inside a window of +- `delta` rows.  It needs
+    no derivative of the window (no g', t g or g''): ONE transform per frame against the three of `ssq_stft2`, any window,
+    and a target that is an argmax, not a ratio, which degrades slowest under noise.
+
+    Per column, with F = n_fft // 2 + 1 rows and an int `delta` >= 1:
+        A[k] = re^2 + im^2 of Sx[k] as the call reports it (rounded to the call's dtype), evaluated in fp64 with the two
+               products and the sum rounded one by one (numpy's re*re + im*im on float64, bit for bit)
+        m[k] = the row of the maximum of A over rows max(0, k - delta) .. min(F - 1, k + delta), scanned ascending and
+               taken only where strictly greater, so the lowest row wins a tie; rows that are not kept take part
+    A cell is kept where |V| > gamma on the fp64 coefficient (default 10 eps of the dtype; `ssq_stft2`'s rule).  Then, for
+    every kept k, rows ascending inside a column, in the call's dtype and without atomics (`mssq_stft`'s accumulation):
+        Tx[r(m[k]), j] += Sx[k, j] dw  ('sum')    or    dw / F  ('lebesgue');        r(b) = F - 1 - b under `flipud`, else b
+    A kept k always has a kept target (A[m[k]] >= A[k]).  Coefficients move along frequency only and keep their phase, so
+    every column keeps its sum: `issq_stft`, `extract_ridges` and the component inversion take `Tx` unchanged.
+
+    `Sx` equals `stft(x, ...)` up to the rounding of another FFT arrangement (a real-input transform, not `ssq_stft2`'s
+    packed pair); `bins` (get_bins=True) is int32: the row of `Tx` each coefficient went to, -1 where it was not kept.
+    float32 in gives complex64 out; the transform runs in fp64 for either dtype.
+
+    `delta=None` asks for `lmsst_default_delta(window, n_fft)`, the half-width of the window's main lobe (its 1e-3 level is
+    part of the definition, not a measurement); else an int from 1 to min(F - 1, 256) -- 256 is a bound on work, not a
+    measured number.  `delta = F - 1` sends every kept cell of a column to the column's largest row.
+
+    The limit: LMSST puts energy on the SPECTROGRAM's ridge, which on a fast FM is not the instantaneous frequency (on the
+    FM model of DESIGN 4.25, 56 % of the energy lies within one bin of the true frequency where `ssq_stft2` has 85 %).  It
+    complements the second-order transforms and does not replace them.
+
+    `n_fft` must be a power of two from 16 to 4096 and `squeezing` 'sum' or 'lebesgue'; a bool, a float or an
+    out-of-range `delta` is refused (ValueError, before any GPU work).  One kernel decides a column in LDS and writes every
+    cell of `Tx` once (csrc/stft_lmsst.hip); every (dtype, n_fft) is built without register spills or scratch
+    (profiles/lmsst_resources.txt)."""
+    lib = _lib.load()
+    squeeze = _squeeze_code(squeezing)
+    f = _stft_front(x, window, n_fft, win_len, hop_len, fs, t, "lmssq_stft")
+    pad = _pad_code(padtype)
+    delta = _delta(delta, f.n_freqs, lambda: lmsst_default_delta(f.win, f.n_fft))
+    _lib.require_gpu()
+    shape = _stft_shape(f, hop_len)
+    Tx, Sx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    bins = _lib.pinned_empty(shape, np.int32) if get_bins else None
+    freqs = np.empty(f.n_freqs, dtype=np.float64)
+    _call(lib.ssq_lmssq_stft_host(f.code, _ptr(f.xa), f.batch, f.N, _ptr(f.win), f.n_fft, hop_len, f.fs, pad, squeeze,
+                                  _gamma_arg(gamma), _variant(modulated, flipud), delta, _ptr(Tx), _ptr(freqs), _ptr(Sx),
+                                  _ptr(bins)))
+    return (*_unbatch(f.batched, Tx, Sx), freqs.astype(f.rdt), _Sfs(f), *_unbatch(f.batched, bins))
 
 
 def tssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None, modulated=True, padtype="reflect",
@@ -1711,6 +1804,107 @@ def mssq_cwt_tile_cols(na):
     if c < 0:
         raise ValueError(f"na {na!r}: 2 .. {MSST_MAX_ROWS}")
     return int(c)
+
+
+def lmssq_cwt_default_delta(wavelet, scales):
+    """The default `delta` of `lmssq_cwt`: the half-width in rows of the wavelet's response across the scales.  With the
+    wavelet evaluated by the library (`ssq_upstream_psih`, as `upstream_scales` does), wc its peak frequency, i0 = na // 2
+    and R[i] = psih(scales[i] wc / scales[i0]) the response of the rows to a tone on the peak frequency of row i0, the
+    smallest d >= 1 at which both neighbours i0 - d and i0 + d that exist are <= 1e-3 R[i0]; at most min(na - 1, 256).  The
+    1e-3 is part of the definition, not a measurement.  numpy on the host, no GPU."""
+    from .upstream_scales import _psih_fn
+    wcode, p0, p1 = _wavelet(wavelet)
+    s = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
+    na = len(s)
+    if na < 2 or not (np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError("`scales` must hold at least 2 positive, finite scales")
+    wc = (p1 / p0) ** (1 / p0) if wcode == WAVELET["gmw"] else p0
+    i0 = na // 2
+    R = _psih_fn(wavelet)(s * (wc / s[i0]))
+    d = 1
+    while d < na - 1:
+        near = [R[i] for i in (i0 - d, i0 + d) if 0 <= i < na]
+        if all(r <= LMSST_LOBE_LEVEL * R[i0] for r in near):
+            break
+        d += 1
+    return int(max(1, min(d, na - 1, LMSST_MAX_DELTA)))
+
+
+def lmssq_cwt(x, wavelet="gmw", scales="log-piecewise", nv=None, fs=None, t=None, ssq_freqs=None, padtype="reflect",
+              squeezing="sum", maprange="peak", gamma=None, flipud=True, delta=None, get_w=False, get_rows=False):
+    """Local maximum synchrosqueezed CWT -> (Tx, Wx, ssq_freqs, scales[, w][, rows]); not in upstream (the CWT counterpart
+    of `lmssq_stft`; Yu, Wang, Zhao and Liu 2019), conventions of `mssq_cwt`.  A coefficient moves to the frequency of the
+    row where |Wx| has its maximum inside a window of +- `delta` rows.  No derivative of the wavelet is formed: ONE
+    inverse transform per row against the five of `ssq_cwt2`.
+
+    Per column, with na rows (scales ascending) and an int `delta` >= 1:
+        A[i] = re^2 + im^2 of Wx[i] as the call reports it (rounded to the call's dtype), evaluated in fp64 with the two
+               products and the sum rounded one by one
+        m[i] = the row of the maximum of A over rows max(0, i - delta) .. min(na - 1, i + delta), scanned ascending and
+               taken only where strictly greater, so the lowest row wins a tie; rows that are not kept take part
+        w[i] = nu_hz[m[i]], nu_hz = `tssq_cwt_row_freqs(wavelet, scales)` fs rounded once to the call's dtype; +inf where
+               the cell is not kept: |W| < gamma on the fp64 coefficient (default 10 eps of the dtype; `ssq_cwt2`'s rule)
+    and `Tx` = `ssqueeze(Wx, w, ...)`: rows ascending inside a column, no atomics, `flipud` applied there.  A coefficient
+    keeps its OWN row weight and phase, so every column keeps its weighted sum: `issq_cwt`, `extract_ridges` and the
+    component inversion take `Tx` unchanged.  On a 'peak' log grid over log scales a coefficient lands on bin
+    na - 1 - m[i].
+
+    `Wx` is `ssq_cwt2`'s bit for bit; `w` (get_w=True) is real; `rows` (get_rows=True) is int32 m, -1 where a cell is not
+    kept.  `lmsst_rows` runs the window maximum alone on a map the caller holds.
+
+    `delta=None` asks for `lmssq_cwt_default_delta(wavelet, scales)`, the half-width of the wavelet's response across the
+    rows (its 1e-3 level is part of the definition, not a measurement); else an int from 1 to min(na - 1, 256) -- 256 is a
+    bound on work, not a measured number.  The limit is `lmssq_stft`'s: the energy goes to the SCALOGRAM's ridge, which on
+    a fast FM is not the instantaneous frequency.
+
+    Built: what `ssq_cwt2` builds (order-0 'gmw' and 'morlet', an ndarray `scales` of the three grids), for 2 .. 2049
+    scales and `squeezing` 'sum' or 'lebesgue'.  Anything else, a bool, a float or an out-of-range `delta` raises
+    ValueError before any GPU work.  The kernels are built without register spills or scratch
+    (profiles/lmsst_cwt_resources.txt)."""
+    lib = _lib.load()
+    squeeze = _squeeze_code(squeezing)
+    f = _cwt_front(x, wavelet, scales, fs, t, gamma, padtype)
+    s, row_const, f_asc, scaletype, f_idx = _finite_freq_grid(f, scales, nv, ssq_freqs, maprange)
+    na = len(s)
+    if not 2 <= na <= MSST_MAX_ROWS:
+        raise ValueError(f"na = {na} scales: lmssq_cwt builds 2 .. {MSST_MAX_ROWS}")
+    delta = _delta(delta, na, lambda: lmssq_cwt_default_delta(wavelet, s))
+    nu_hz = np.ascontiguousarray(tssq_cwt_row_freqs(wavelet, s) / f.dt)
+    if not (np.isfinite(nu_hz).all() and (nu_hz > 0).all()):
+        raise ValueError("`scales` give row frequencies that are not positive and finite")
+    _lib.require_gpu()
+    shape = (f.batch, na, f.N)
+    Tx, Wx = _lib.pinned_empty(shape, f.cdt), _lib.pinned_empty(shape, f.cdt)
+    w = _lib.pinned_empty(shape, f.rdt) if get_w else None
+    rows = _lib.pinned_empty(shape, np.int32) if get_rows else None
+    _call(lib.ssq_lmssq_cwt_host(f.code, _ptr(f.xa), f.batch, f.N, f.wcode, f.p0, f.p1, _ptr(s), na, f.dt,
+                                 _ptr(row_const), _ptr(f_asc), FREQS[scaletype], f_idx or 0, f.pad, squeeze, f.gamma,
+                                 VARIANT_FLIPUD if flipud else 0, 0, delta, _ptr(nu_hz), _ptr(Tx), _ptr(Wx), _ptr(w),
+                                 _ptr(rows)))
+    return (*_unbatch(f.batched, Tx, Wx), f_asc[::-1].astype(f.rdt), s.astype(f.rdt), *_unbatch(f.batched, w, rows))
+
+
+def lmsst_rows(A, delta):
+    """The window maximum of `lmssq_cwt` alone, on a map the caller holds -> int32 m, same shape.  `A`: float32 or float64
+    [R, n] or [B, R, n] (2 <= R <= 2049; a float32 map is widened, which is exact); per column
+        m[k] = the row of the maximum of A over rows max(0, k - delta) .. min(R - 1, k + delta), scanned ascending and
+               taken only where strictly greater (the lowest row wins a tie)
+    with no keep rule.  Runs the plane kernel of `lmssq_cwt` (csrc/cwt_lmsst.hip); a `delta` that is not an int from 1 to
+    min(R - 1, 256) and every other refusal is a ValueError before any GPU work."""
+    lib = _lib.load()
+    if not isinstance(A, np.ndarray) or A.dtype not in (np.float32, np.float64) or A.ndim not in (2, 3):
+        raise ValueError("`A` must be a float32 or float64 ndarray [R, n] or [B, R, n]")
+    a3 = np.ascontiguousarray(A if A.ndim == 3 else A[None])
+    B, R, n = a3.shape
+    if not 2 <= R <= MSST_MAX_ROWS or B < 1 or n < 1:
+        raise ValueError(f"`A` of shape {A.shape}: 2 .. {MSST_MAX_ROWS} rows, and no empty axis")
+    if delta is None:
+        raise ValueError("delta None: `lmsst_rows` has no default")
+    delta = _delta(delta, R, None)
+    _lib.require_gpu()
+    out = np.empty(a3.shape, np.int32)
+    _call(lib.ssq_lmsst_rows_host(SSQ_F32 if a3.dtype == np.float32 else SSQ_F64, _ptr(a3), B, R, n, delta, _ptr(out)))
+    return _unbatch(A.ndim == 3, out)[0]
 
 
 CONCEFT_MAX_ORDERS = 8                  # csrc/cwt_conceft.hip: kConceftMaxOrders
